@@ -15,6 +15,13 @@ samples per pixel grow as 256*N so every GPU traces the same 530.8 M samples as 
 
 (HRT_BENCH_SHARE_GPU=1 rehearses the N > 1 path on a one-GPU box: all ranks share GPU 0, collectives over gloo.)
 
+A plain run sets up, warms up, times the --steps steps and prints the line; ms_per_step is the wall time of one timed step.
+--dump-outputs DIR writes what the last timed step computed -- the float32 (1080, 1920, 3) frame rank 0 receives -- to
+DIR/frame.npy (24.9 MB); the inputs (scene, camera, seed) are fixed, so two builds can be compared output for output.
+--full adds everything below that needs work of its own: the timed frame checked (finite, mean equal to
+tests/golden/bench_frame_means.json), value_host_to_host, without_pruning, other_configs and cpu_baseline (--no-extras and
+--no-cpu-baseline leave parts of it out).
+
 Rank 0 prints ONE JSON line.  What its evidence keys mean:
   roofline      memory side of the dominant kernel.  `traffic` = bytes per launch that crossed the L2 <-> fabric boundary, from
                 the committed rocprofv3 PMC passes (profiles/r03_<cfg>_pmc.json; separate --pmc runs): read and write requests
@@ -27,12 +34,13 @@ Rank 0 prints ONE JSON line.  What its evidence keys mean:
   valu          the compute side: vector wave instructions per second (SQ_INSTS_VALU of the committed PMC run / the live kernel
                 time) over the MEASURED issue peak of the part (tools/micro/valu_rate.hip: 1024 SIMDs x one simple instruction
                 per 1.30 ns at this occupancy), with the lane utilisation of that work beside it (same PMC runs).
-  value_host_to_host   the same frame through hrt_render: gamma, tile assemble and the D2H copy of the frame included.
-  without_pruning      the kernel rate of the same frame on a scene created with HRT_PRUNE=0 (no exact path pruning), and the
+  frame_mean    (--full) float64 mean of the timed frame, checked against the committed one (tolerance 0).
+  value_host_to_host   (--full) the same frame through hrt_render: gamma, tile assemble and the D2H copy of the frame included.
+  without_pruning      (--full) the kernel rate of the same frame on a scene created with HRT_PRUNE=0 (no exact path pruning), and the
                        check that the two frames are bit-identical: `value` includes an optimisation that skips provably
                        irrelevant work, this is the rate without it.
-  other_configs        kernel time of BASELINE's other configurations at their true sizes (one launch each).
-  cpu_baseline  the CPU oracle (a port of the reference algorithm, reference-shaped KD-tree) timed on this host on a
+  other_configs        (--full) kernel time of BASELINE's other configurations at their true sizes (one launch each).
+  cpu_baseline  (--full) the CPU oracle (a port of the reference algorithm, reference-shaped KD-tree) timed on this host on a
                 bounded sample of the same workload, threaded three ways -- a reported baseline, not the target.
 """
 import argparse
@@ -223,9 +231,14 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--spp", type=int, default=SPP, help="samples per pixel per GPU (default: the metric's 256)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip value_host_to_host and other_configs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the timed frame and measure value_host_to_host, without_pruning, other_configs and cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip value_host_to_host, without_pruning and other_configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frame of the last timed step to DIR/frame.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -331,7 +344,11 @@ def main():
             "roofline": roofline, "valu": valu,
         }
         out["source_sha16"] = source_sha16()
-        if frame is not None:
+        if args.dump_outputs:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "frame.npy"), frame.cpu().numpy().astype(np.float32, copy=False))
+        if args.full:
             import numpy as np
             host_frame = frame.cpu().numpy()
             if not np.isfinite(host_frame).all():
@@ -342,7 +359,7 @@ def main():
             if key in means and means[key] != out["frame_mean"]:
                 raise SystemExit(f"bench.py: frame mean {out['frame_mean']!r} differs from the committed {means[key]!r} ({key})")
             out["frame_mean_checked"] = key in means
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             import numpy as np
             host_img, st = scene.render(cam, W, H, spp, SEED, flags=hrt.FLAG_GAMMA)  # once to size the library's buffers
             t1 = time.perf_counter()
@@ -368,7 +385,7 @@ def main():
                                       "frame": "bit-identical to the pruned frame (checked in this run)"}
             plain.close()
             out["other_configs"] = other_configs(hrt)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(hrt, desc, cam)
         print(json.dumps(out), flush=True)
     if world > 1:

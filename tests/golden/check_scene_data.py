@@ -1,6 +1,10 @@
 """Scene DATA of the host layer against the reference's own set-up code, read WHERE IT LIES (build container only).
 
-    python tests/golden/check_scene_data.py            # pass / fail per scene, nothing of the reference is stored
+    python tests/golden/check_scene_data.py            # pass / fail per scene
+    python tests/golden/check_scene_data.py --write    # and record the reference's objects in tests/golden/ref_scene_data.npz
+
+Only the resulting DATA is recorded (object positions, sizes, materials, transformed mesh vertices), none of the reference's
+text; tests/test_scene_data_against_reference.py checks the host layer against that record.
 
 Why: host/scene*.cpp was transcribed by hand from Scene.h's setup_* functions, and both the oracle and the GPU path are fed
 by it -- a slip in a literal would be invisible to every parity test.  This script reads
@@ -18,6 +22,7 @@ from the host layer's own seeded generator (N13) and are not compared.
 """
 import ctypes as C
 import importlib
+import json
 import math
 import os
 import re
@@ -234,12 +239,95 @@ class Lgt(C.Structure):
     _fields_ = [("pos", C.c_float * 3), ("radius", C.c_float), ("color", C.c_float * 3)]
 
 
-def check(name, ref_fn, setup_name, aspect, hrt):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from test_host_layer import MeshDesc, SceneDesc
+def reference_scene(ref_fn, aspect):
+    """The objects the reference's set-up function `ref_fn` creates, interpreted from its Scene.h (needs the reference)."""
     src = open(os.path.join(REF, "src", "Scene.h")).read()
     sc = Scene(os.path.join(ROOT, "assets"))
     run(function_body(src, ref_fn), sc, {"aspect_ratio": aspect})
+    return sc
+
+
+# ---------------------------------------------------------------- the same objects as a committed fixture (GOLDEN)
+# GOLDEN holds, per (set-up function, aspect ratio), what reference_scene() produced: every sphere, square, mesh and light with
+# the Material fields listed above (float64, exact), mesh vertices after their transforms as arrays, the texture and normal-map
+# lists and dark_sky.  Written by `python tests/golden/check_scene_data.py --write` where the reference is present; read by
+# tests/test_scene_data_against_reference.py, which therefore needs nothing outside the repository.
+GOLDEN = os.path.join(HERE, "ref_scene_data.npz")
+
+
+def golden_key(ref_fn, aspect):
+    return f"{ref_fn} {aspect:.9g}"
+
+
+def _plain(x):
+    return x.tolist() if isinstance(x, np.ndarray) else x
+
+
+def _material_data(m):
+    return {k: _plain(v) for k, v in m.__dict__.items()}
+
+
+def scene_data(sc, key):
+    """(json-able description, {array name: array}) of a Scene."""
+    meshes, arrays = [], {}
+    for i, m in enumerate(sc.meshes):
+        arrays[f"{key}/mesh{i}"] = np.asarray(m.v, np.float64)
+        meshes.append({"off": m.off, "material": _material_data(m.material)})
+    d = {"spheres": [{"m_center": _plain(s.m_center), "m_radius": s.m_radius, "material": _material_data(s.material)} for s in sc.spheres],
+         "squares": [{"v": _plain(np.asarray(q.v, np.float64)), "m_right_vector": _plain(q.m_right_vector), "m_up_vector": _plain(q.m_up_vector),
+                      "material": _material_data(q.material)} for q in sc.squares],
+         "meshes": meshes,
+         "lights": [{"pos": _plain(l.pos), "radius": l.radius, "material": _plain(l.material)} for l in sc.lights],
+         "textures": list(sc.textures), "normals": list(sc.normals), "dark_sky": sc.dark_sky}
+    return d, arrays
+
+
+def write_golden(scenes):
+    meta, arrays = {}, {}
+    for ref_fn, aspect in scenes:
+        key = golden_key(ref_fn, aspect)
+        meta[key], a = scene_data(reference_scene(ref_fn, aspect), key)
+        arrays.update(a)
+    np.savez_compressed(GOLDEN, meta=np.array(json.dumps(meta, sort_keys=True)), **arrays)
+
+
+def golden_scene(ref_fn, aspect):
+    """The Scene of `ref_fn` at `aspect` as GOLDEN recorded it."""
+    key = golden_key(ref_fn, aspect)
+    with np.load(GOLDEN, allow_pickle=False) as g:
+        d = json.loads(str(g["meta"]))[key]
+        verts = {k: g[k] for k in g.files if k.startswith(key + "/")}
+
+    def material(md):
+        m = Material()
+        for k, v in md.items():
+            setattr(m, k, np.array(v, np.float64) if isinstance(v, list) else v)
+        return m
+    sc = Scene(os.path.join(ROOT, "assets"))
+    for s in d["spheres"]:
+        o = Sphere(); o.m_center = np.array(s["m_center"], np.float64); o.m_radius = s["m_radius"]; o.material = material(s["material"])
+        sc.spheres.append(o)
+    for q in d["squares"]:
+        o = Square(); o.v = np.array(q["v"], np.float64); o.m_right_vector = np.array(q["m_right_vector"], np.float64)
+        o.m_up_vector = np.array(q["m_up_vector"], np.float64); o.material = material(q["material"])
+        sc.squares.append(o)
+    for i, md in enumerate(d["meshes"]):
+        o = Mesh(); o.off = md["off"]; o.v = verts[f"{key}/mesh{i}"]; o.material = material(md["material"])
+        sc.meshes.append(o)
+    for l in d["lights"]:
+        o = Light(); o.pos = np.array(l["pos"], np.float64); o.radius = l["radius"]; o.material = np.array(l["material"], np.float64)
+        sc.lights.append(o)
+    sc.textures, sc.normals, sc.dark_sky = list(d["textures"]), list(d["normals"]), d["dark_sky"]
+    return sc
+
+
+def check(name, ref_fn, setup_name, aspect, hrt, sc=None):
+    """Compares the host layer's flattened `setup_name` scene with the reference's objects: `sc` when given (golden_scene()),
+    otherwise interpreted from the reference's Scene.h."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_host_layer import MeshDesc, SceneDesc
+    if sc is None:
+        sc = reference_scene(ref_fn, aspect)
     host = hrt.HostScene().setup(setup_name, aspect, 1); desc = host.flatten()
     d = C.cast(desc, C.POINTER(SceneDesc)).contents
     mats = C.cast(d.materials, C.POINTER(hrt.Material))
@@ -281,14 +369,22 @@ def check(name, ref_fn, setup_name, aspect, hrt):
     return compared, fails
 
 
+SCENES = (("cornell_box", "setup_cornell_box", "cornell_box", 16 / 9), ("cornell_box (1:1)", "setup_cornell_box", "cornell_box", 1.0),
+          ("backrooms_pool", "setup_backrooms_pool", "backrooms_pool", 16 / 9), ("random_spheres", "setup_random_spheres", "random_spheres", 16 / 9))
+
+
 def main():
-    if not os.path.isdir(os.path.join(REF, "src")):
-        print("reference absent: nothing to check"); return 0
+    """Checks against the reference's Scene.h where it is present (`--write`: and records GOLDEN from it), else against GOLDEN."""
+    live = os.path.isdir(os.path.join(REF, "src"))
+    if "--write" in sys.argv:
+        if not live:
+            print("reference absent: cannot write " + os.path.relpath(GOLDEN, ROOT)); return 1
+        write_golden([(ref_fn, aspect) for _, ref_fn, _, aspect in SCENES])
     hrt = importlib.import_module("hai719-raytracing_amd")
     bad = 0
-    for name, ref_fn, setup, aspect in (("cornell_box", "setup_cornell_box", "cornell_box", 16 / 9), ("cornell_box (1:1)", "setup_cornell_box", "cornell_box", 1.0),
-                                        ("backrooms_pool", "setup_backrooms_pool", "backrooms_pool", 16 / 9), ("random_spheres", "setup_random_spheres", "random_spheres", 16 / 9)):
-        compared, fails = check(name.split(" ")[0], ref_fn, setup, aspect, hrt)
+    print("against " + ("the reference's set-up code" if live else os.path.relpath(GOLDEN, ROOT)))
+    for name, ref_fn, setup, aspect in SCENES:
+        compared, fails = check(name.split(" ")[0], ref_fn, setup, aspect, hrt, None if live else golden_scene(ref_fn, aspect))
         print(f"{name}: {'PASS' if not fails else 'FAIL'} ({compared})")
         for f in fails[:20]: print("   " + f)
         bad += bool(fails)

@@ -16,6 +16,9 @@ oracle_converged.npz  oracle means of 16 x 64 spp at 96x54 with the standard err
                   the counter-based RNG streams (any seed must estimate the same image).
 oracle_images.npz oracle renders + AOVs of the config scenes at test size (fixed seed), so the GPU
                   box checks the HIP path against committed pixels as well as the live oracle.
+ref_live.npz      random triangles, boxes, rays, optics inputs and camera poses with what the reference's own code
+                  returns for them (tests/test_oracle_pins.py::test_live_reference_parts_when_present); written alone by
+                  `python tests/golden/make_golden.py ref_live`.
 """
 import importlib, json, os, sys
 import numpy as np
@@ -136,5 +139,40 @@ def main():
     np.savez_compressed(os.path.join(HERE, "oracle_converged.npz"), **st)
     print("golden vectors written")
 
+def ref_live():
+    """Inputs of test_live_reference_parts_when_present (seed 99) and the reference's outputs on them."""
+    assert O.ref_parts() is not None, "oracle/_ref is not built: run `make -C oracle` where the reference exists"
+    rng = np.random.default_rng(99)
+    n = 3000
+    g = {}
+    g["rays"] = np.concatenate([rng.uniform(-1, 2, (n, 2)), np.full((n, 1), 2.0), rng.normal(0, 0.4, (n, 2)),
+                                np.full((n, 1), -1.0), rng.uniform(0, 1, (n, 1))], 1).astype(np.float32)
+    tris, boxes = [], []
+    for _ in range(5):
+        tris.append(rng.uniform(-1, 1, 9).astype(np.float32))
+        boxes.append(np.sort(rng.uniform(-1, 1, (2, 3)), axis=0).astype(np.float32).ravel())
+    g["tris"], g["boxes"] = np.stack(tris), np.stack(boxes)
+    g["tri_out"] = np.stack([O.kat("triangle", t, g["rays"], use_ref=True) for t in tris])
+    g["aabb_out"] = np.stack([O.kat("aabb", b, g["rays"], use_ref=True) for b in boxes])
+    d = rng.normal(size=(n, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
+    nn = rng.normal(size=(n, 3)); nn /= np.linalg.norm(nn, axis=1, keepdims=True)
+    g["optics_in"] = np.concatenate([d, nn, rng.uniform(0.4, 2.5, (n, 1)), rng.uniform(0, 1, (n, 1))], 1).astype(np.float32)
+    g["optics_out"] = O.kat_optics(g["optics_in"], use_ref=True)
+    g["uv"] = rng.uniform(0, 1, (n, 2)).astype(np.float32)
+    cams, rays_out = [], []
+    for aspect in (1.0, 16 / 9, 0.7):
+        cam = hrt.default_camera(aspect)
+        cam.eye[:] = rng.uniform(-5, 5, 3).astype(np.float32)
+        q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
+        cam.right[:], cam.up[:], cam.forward[:] = q[0].astype(np.float32), q[1].astype(np.float32), q[2].astype(np.float32)
+        cams.append(O.camera_to_row(cam))
+        rays_out.append(O.ref_camera_rays(cam, g["uv"]))
+    g["cameras"], g["camera_rays_out"] = np.stack(cams), np.stack(rays_out)
+    np.savez_compressed(os.path.join(HERE, "ref_live.npz"), **g)
+    print("ref_live.npz written")
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["ref_live"]:
+        ref_live()
+    else:
+        main()

@@ -93,29 +93,27 @@ def test_ppm_loader_matches_reference_golden(hrt):
 
 
 def test_live_reference_parts_when_present(hrt, oracle):
-    """In the build container oracle/_ref exists: fresh random inputs, still bit-exact."""
-    if oracle.ref_parts() is None:
-        pytest.skip("oracle/_ref not built here (the reference does not travel to the GPU box)")
-    rng = np.random.default_rng(99)
-    n = 3000
-    rays = np.concatenate([rng.uniform(-1, 2, (n, 2)), np.full((n, 1), 2.0), rng.normal(0, 0.4, (n, 2)),
-                           np.full((n, 1), -1.0), rng.uniform(0, 1, (n, 1))], 1).astype(np.float32)
-    for _ in range(5):
-        tri = rng.uniform(-1, 1, 9).astype(np.float32)
-        assert np.array_equal(oracle.kat("triangle", tri, rays), oracle.kat("triangle", tri, rays, use_ref=True))
-        box = np.sort(rng.uniform(-1, 1, (2, 3)), axis=0).astype(np.float32).ravel()
-        assert np.array_equal(oracle.kat("aabb", box, rays), oracle.kat("aabb", box, rays, use_ref=True))
-    d = rng.normal(size=(n, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
-    nn = rng.normal(size=(n, 3)); nn /= np.linalg.norm(nn, axis=1, keepdims=True)
-    inp = np.concatenate([d, nn, rng.uniform(0.4, 2.5, (n, 1)), rng.uniform(0, 1, (n, 1))], 1).astype(np.float32)
-    assert np.array_equal(oracle.kat_optics(inp), oracle.kat_optics(inp, use_ref=True))
-    uv = rng.uniform(0, 1, (n, 2)).astype(np.float32)
-    for aspect in (1.0, 16 / 9, 0.7):
-        cam = hrt.default_camera(aspect)
-        cam.eye[:] = rng.uniform(-5, 5, 3).astype(np.float32)
-        q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
-        cam.right[:], cam.up[:], cam.forward[:] = q[0].astype(np.float32), q[1].astype(np.float32), q[2].astype(np.float32)
-        assert np.array_equal(oracle.camera_rays(cam, uv), oracle.ref_camera_rays(cam, uv))
+    """Random triangles, boxes, optics inputs and camera poses (tests/golden/ref_live.npz), bit-exact against what the
+    reference's own code returns for them: the recorded outputs, and live where oracle/_ref is built."""
+    g = np.load(os.path.join(GOLDEN, "ref_live.npz"))
+    live = oracle.ref_parts() is not None
+    rays = g["rays"]
+    for tri, want in zip(g["tris"], g["tri_out"]):
+        got = oracle.kat("triangle", tri, rays)
+        assert np.array_equal(got, want)
+        assert not live or np.array_equal(got, oracle.kat("triangle", tri, rays, use_ref=True))
+    for box, want in zip(g["boxes"], g["aabb_out"]):
+        got = oracle.kat("aabb", box, rays)
+        assert np.array_equal(got, want)
+        assert not live or np.array_equal(got, oracle.kat("aabb", box, rays, use_ref=True))
+    inp = g["optics_in"]
+    assert np.array_equal(oracle.kat_optics(inp), g["optics_out"])
+    assert not live or np.array_equal(oracle.kat_optics(inp), oracle.kat_optics(inp, use_ref=True))
+    uv = g["uv"]
+    for row, want in zip(g["cameras"], g["camera_rays_out"]):
+        cam = oracle.camera_from_row(hrt, row)
+        assert np.array_equal(oracle.camera_rays(cam, uv), want)
+        assert not live or np.array_equal(oracle.camera_rays(cam, uv), oracle.ref_camera_rays(cam, uv))
 
 
 def test_oracle_renders_match_committed_images(hrt, oracle):
