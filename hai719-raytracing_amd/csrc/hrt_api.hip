@@ -11,6 +11,7 @@
 #include <rccl/rccl.h>  // types and prototypes only: librccl.so is opened with dlopen by hrt_multi_create (hrt_multi.hip)
 
 #include <array>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -236,6 +237,7 @@ struct hrt_scene {
     DScene d{};                  // host copy of the device scene header
     DScene *d_scene = nullptr;   // the header in HBM (read by the kernels through a constant-space pointer)
     DCamera *d_cam = nullptr;    // camera block in HBM, re-uploaded only when the camera changes
+    DCamera *d_cam_aov = nullptr;  // hrt_render_aov's own camera block (it takes no part in the trace launches' ordering)
     DCamera h_cam{};
     bool cam_valid = false;
     uint32_t lds_units = 0;
@@ -337,6 +339,7 @@ void hrt_scene_destroy(hrt_scene *s) {
     if (s->sp_pool) (void)hipFree(s->sp_pool);
     if (s->d_scene) (void)hipFree(s->d_scene);
     if (s->d_cam) (void)hipFree(s->d_cam);
+    if (s->d_cam_aov) (void)hipFree(s->d_cam_aov);
     if (s->d_tiles) (void)hipFree(s->d_tiles);
     if (s->d_frame) (void)hipFree(s->d_frame);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -803,17 +806,29 @@ static int scene_create_impl(const hrt_scene_desc *desc, hrt_scene *s) {
     d.n_kd_units = (uint32_t)units.size();
     s->lds_units = std::min<uint32_t>(d.n_kd_units, g_rt.lds_budget / 16u) & ~3u;  // whole 64-byte lines: no treelet or leaf straddles
     d.dark_sky = D.dark_sky;
-    {   // exact path pruning needs 0 x value == 0: no colour of the scene may be infinite or NaN (hrt_device.h DScene::prune_ok)
+    {   // exact path pruning needs 0 x value == 0 for every value a zero throughput meets, and a finite throughput wherever a
+        // pruned term is dropped (hrt_device.h DScene::prune_ok).  Bounded in fp64: the throughput is a product of at most
+        // HRT_MAXBOUNCES albedo-like colours (albedos, checkers, mesh colours; texels are bytes <= 1), and what it multiplies is
+        // an emission (light colour or checker x intensity), the direct-light sum (lights x light colour x albedo x |1 - t|)
+        // or the sky (<= HRT_MAXBOUNCES + 1).  Below FLT_MAX / 2 (room for fp32 rounding) no term of a path can overflow.
         bool finite = true;
-        auto fin3 = [&](const float *v) { finite = finite && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); };
+        auto mag = [&](float v) { finite = finite && std::isfinite(v); return std::fabs((double)v); };
+        auto mag3 = [&](const float *v) { return std::max(mag(v[0]), std::max(mag(v[1]), mag(v[2]))); };
+        double albedo = 1.0, emit = 0.0, transmit = 1.0, light = 0.0;
         for (uint32_t i = 0; i < D.n_materials; ++i) {
             const hrt_material &m = D.materials[i];
-            fin3(m.albedo); fin3(m.checker1); fin3(m.checker2); fin3(m.light_color);
-            finite = finite && std::isfinite(m.light_intensity);
+            const double checker = std::max(mag3(m.checker1), mag3(m.checker2));
+            albedo = std::max(albedo, std::max(mag3(m.albedo), checker));
+            const double e = std::max(1.0, std::max(mag3(m.light_color), checker)) * mag(m.light_intensity);
+            if (m.emissive) emit = std::max(emit, e);
+            transmit = std::max(transmit, std::fabs(1.0 - (double)m.transparency));
+            finite = finite && std::isfinite(m.transparency);
         }
-        for (uint32_t i = 0; i < D.n_lights; ++i) fin3(D.lights[i].color);
-        for (const float4 &c : colors) finite = finite && std::isfinite(c.x) && std::isfinite(c.y) && std::isfinite(c.z);
-        d.prune_ok = finite ? 1u : 0u;
+        for (uint32_t i = 0; i < D.n_lights; ++i) light = std::max(light, mag3(D.lights[i].color));
+        for (const float4 &c : colors) albedo = std::max(albedo, std::max(mag(c.x), std::max(mag(c.y), mag(c.z))));
+        const double term = std::max(std::max(emit, (double)HRT_MAXBOUNCES + 1.0), (double)D.n_lights * light * albedo * transmit);
+        const double bound = std::pow(albedo, (double)HRT_MAXBOUNCES) * term;
+        d.prune_ok = (finite && bound < 0.5 * (double)FLT_MAX) ? 1u : 0u;
         if (const char *e = std::getenv("HRT_PRUNE")) if (e[0] == '0') d.prune_ok = 0u;  // measurement aid: the same kernels without the pruning (bench.py reports both rates)
     }
     d.any_motion = 0u;  // (time x 0 == 0 whatever the time: with no motion anywhere a ray's time is never looked at)
@@ -828,6 +843,7 @@ static int scene_create_impl(const hrt_scene_desc *desc, hrt_scene *s) {
     HIP_TRY(hipMalloc((void **)&s->d_scene, sizeof(DScene)));
     HIP_TRY(hipMemcpy(s->d_scene, &s->d, sizeof(DScene), hipMemcpyHostToDevice));
     HIP_TRY(hipMalloc((void **)&s->d_cam, sizeof(DCamera)));
+    HIP_TRY(hipMalloc((void **)&s->d_cam_aov, sizeof(DCamera)));
     return HRT_OK;
 }
 
@@ -916,7 +932,7 @@ static int make_camera(const hrt_camera *cam, DCamera &C) {
 }
 
 static int fill_render(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
-                       uint32_t flags, uint32_t rank, uint32_t world, DRender &R, hipStream_t stream) {
+                       uint32_t flags, uint32_t rank, uint32_t world, DRender &R, DCamera &C) {
     if (!s || !cam) return fail(HRT_ERR_INVALID, "render: NULL argument");
     if (!g_rt.ready) return fail(HRT_ERR_STATE, "render: call hrt_init first");
     { const int drc = use_device(s->device); if (drc != HRT_OK) return drc; }  // a scene lives on its device.  Unconditional: HIP's current
@@ -926,19 +942,11 @@ static int fill_render(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t
     if (w > 65535u || h > 65535u) return fail(HRT_ERR_INVALID, "render: w and h must be below 65536 (tile origins are packed in 16 + 16 bits)");
     if (!world || rank >= world) return fail(HRT_ERR_INVALID, "render: bad rank/world");
     R.scene = s->d_scene;
-    R.cam = s->d_cam;
     R.lds_units = (flags & HRT_FLAG_NO_LDS_TREE) ? 0u : s->lds_units;
     R.err_abs = 2e-6f * (s->bound + std::sqrt(cam->eye[0] * cam->eye[0] + cam->eye[1] * cam->eye[1] + cam->eye[2] * cam->eye[2]) + 1.f);
-    DCamera C;
     {
         const int crc = make_camera(cam, C);
         if (crc != HRT_OK) return crc;
-    }
-    if (!s->cam_valid || std::memcmp(&C, &s->h_cam, sizeof(C)) != 0) {
-        // the previous launch may still be reading the old block: stream order makes the copy wait for it
-        s->h_cam = C;
-        HIP_TRY(hipMemcpyAsync(s->d_cam, &s->h_cam, sizeof(C), hipMemcpyHostToDevice, stream));
-        s->cam_valid = true;
     }
     R.w = w; R.h = h; R.spp = spp;
     R.seed_lo = (uint32_t)seed; R.seed_hi = (uint32_t)(seed >> 32);
@@ -958,8 +966,10 @@ static int fill_render(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t
 static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t s0, uint32_t spp, uint64_t seed,
                         uint32_t flags, uint32_t rank, uint32_t world, float *d_tiles, void *stream_, bool accumulate) {
     DRender R;
-    int rc = fill_render(s, cam, w, h, spp, seed, flags, rank, world, R, (hipStream_t)stream_);
+    DCamera C;
+    int rc = fill_render(s, cam, w, h, spp, seed, flags, rank, world, R, C);
     if (rc != HRT_OK) return rc;
+    R.cam = s->d_cam;
     if (!d_tiles) return fail(HRT_ERR_INVALID, "render: NULL tile buffer");
     if ((uint64_t)s0 + spp > 0xffffffffull) return fail(HRT_ERR_INVALID, "render: sample index overflows 32 bits");
     R.out_tiles = d_tiles;
@@ -1059,9 +1069,15 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
     s->last_lds = lds_bytes;
     s->last_waves = stream_kernel ? grid * (HRT_SP_WG / 64) : grid * (HRT_WG / 64u);
     // One hrt_scene carries ONE launch at a time (work-queue head, stamps, path pool, camera block).  Launches on one
-    // stream are ordered by the stream; a launch on another stream first waits for the previous one.
+    // stream are ordered by the stream; a launch on another stream first waits for the previous one -- before anything of
+    // its own is enqueued, the copy of a new camera block included (the previous launch may still be reading the old one).
     if (s->timed && s->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->ev1, 0));
     s->last_stream = stream;
+    if (!s->cam_valid || std::memcmp(&C, &s->h_cam, sizeof(C)) != 0) {
+        s->h_cam = C;
+        HIP_TRY(hipMemcpyAsync(s->d_cam, &s->h_cam, sizeof(C), hipMemcpyHostToDevice, stream));
+        s->cam_valid = true;
+    }
     HIP_TRY(hipMemsetAsync(s->tile_counter, 0, sizeof(uint32_t), stream));
     HIP_TRY(hipMemsetAsync(s->stamps, 0, 16 * sizeof(unsigned long long), stream));  // [15] = give-up code of the streaming kernel
     HIP_TRY(hipEventRecord(s->ev0, stream));
@@ -1273,8 +1289,13 @@ int hrt_render(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint
 int hrt_render_aov(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t which, float *out_rgb) {
     if (!out_rgb || which > 3u) return fail(HRT_ERR_INVALID, "hrt_render_aov: bad argument");
     DRender R;
-    int rc = fill_render(s, cam, w, h, 1, 0, 0, 0, 1, R, nullptr);
+    DCamera C;
+    int rc = fill_render(s, cam, w, h, 1, 0, 0, 0, 1, R, C);
     if (rc != HRT_OK) return rc;
+    // A camera block of its own: a trace launch on another stream may still be reading s->d_cam.  The AOV kernel runs on the
+    // null stream and hipMemcpy below waits for it, so the block is free again when this returns.
+    HIP_TRY(hipMemcpy(s->d_cam_aov, &C, sizeof(C), hipMemcpyHostToDevice));
+    R.cam = s->d_cam_aov;
     float *d = nullptr;
     const size_t bytes = (size_t)w * h * 3 * sizeof(float);
     HIP_TRY(hipMalloc((void **)&d, bytes));

@@ -89,9 +89,9 @@ struct DScene {
     uint32_t n_kd_units;
     int32_t dark_sky, skybox_image;
     uint32_t any_motion;       // some material has a motion vector != 0: only then does a ray's time matter (hrt_stream.hip recomputes it per hit visit)
-    uint32_t prune_ok;         // every colour a path's throughput or radiance is multiplied by or added to is finite (materials, lights, mesh
-                               // colours; texels are bytes): then throughput x value == 0 whenever the throughput is 0, which the streaming
-                               // kernel's exact path pruning (hrt_stream.hip HRT_SP_PRUNE) relies on
+    uint32_t prune_ok;         // no product a path can form overflows fp32 (hrt_scene_create bounds albedo-like colours ^ HRT_MAXBOUNCES x
+                               // the largest emission / light / sky term in fp64): then every throughput is finite and throughput x value == 0
+                               // whenever the throughput is 0, which the exact path pruning (hrt_stream.hip HRT_SP_PRUNE) relies on
 };
 
 struct DCamera {

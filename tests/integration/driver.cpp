@@ -2,9 +2,16 @@
 // normal-mapped square that is ROTATED after setQuad, a moving sphere, a vertex-coloured mesh, a light -- and runs the
 // binding code of INTEGRATION.md path A on it.
 //   driver flatten        toHrt() + hrt_host_scene_flatten, prints what arrived in the hrt_scene_desc (no GPU needed)
-//   driver render out.bin ray_trace_from_camera() as INTEGRATION.md writes it (needs a GPU); dumps the image
+//   driver render out.bin [m0 .. m15]
+//                         ray_trace_from_camera() as INTEGRATION.md writes it (needs a GPU); dumps the image.  The optional 16
+//                         numbers replace the mocked modelviewInverse (column-major, as GL returns it): a trackball pose
+//   driver direct out.bin ex ey ez rx ry rz ux uy uz fx fy fz
+//                         the same mock scene through hrt_render directly, with the hrt_camera given (eye, right, up, forward;
+//                         Camera's perspective constants), HRT_FLAG_GAMMA and the pinned seed: the frame the binding must give
+// The binding seeds a frame with time(nullptr); the mock pins it (HRT_TEST_SEED) so that the two modes can be compared.
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <ctime>
 #include <iostream>
@@ -71,7 +78,34 @@ static unsigned int selected_scene = 0;
 static unsigned int nsamples = 4;
 static std::vector<Vec3> g_last_image;
 
+static const uint64_t HRT_TEST_SEED = 20261015;
+#define time(x) ((time_t)HRT_TEST_SEED)  // pins the binding's seed: time(nullptr) inside the extracted body only
 #include "ray_trace_from_camera.inc"   // <- the new body of main.cpp:200-263, extracted verbatim from INTEGRATION.md
+#undef time
+
+static void dump(const char *path, const std::vector<Vec3> &image) {
+    FILE *f = std::fopen(path, "wb");
+    std::fwrite(&image[0], sizeof(Vec3), image.size(), f);
+    std::fclose(f);
+}
+
+// hrt_render on the same mock scene, without the binding: the reference frame of `driver direct`
+static int render_direct(const hrt_camera &cam, const char *path) {
+    if (hrt_init(0) != HRT_OK) { std::printf("hrt: %s\n", hrt_last_error()); return 1; }
+    hrt_host_scene *hs = scenes[0].toHrt();
+    const hrt_scene_desc *desc = nullptr;
+    hrt_scene *dev = nullptr;
+    std::vector<Vec3> image((size_t)g_w * g_h);
+    int rc = hs ? hrt_host_scene_flatten(hs, &desc) : HRT_ERR_STATE;
+    if (rc == HRT_OK) rc = hrt_scene_create(desc, &dev);
+    if (rc == HRT_OK) rc = hrt_render(dev, &cam, (uint32_t)g_w, (uint32_t)g_h, nsamples, HRT_TEST_SEED, HRT_FLAG_GAMMA, &image[0][0], nullptr);
+    if (rc != HRT_OK) std::printf("hrt: %s\n", hrt_last_error());
+    hrt_scene_destroy(dev);
+    hrt_host_scene_free(hs);
+    if (rc != HRT_OK) return 1;
+    dump(path, image);
+    return 0;
+}
 
 int main(int argc, char **argv) {
     MockBuilder::fill(scenes[0]);
@@ -97,12 +131,26 @@ int main(int argc, char **argv) {
         hrt_host_scene_free(hs);
         return 0;
     }
+    if (mode == "direct") {
+        if (argc != 15) { std::printf("direct: out.bin and 12 camera numbers\n"); return 1; }
+        hrt_camera cam = {};
+        for (int k = 0; k < 3; ++k) {
+            cam.eye[k] = std::strtof(argv[3 + k], nullptr);
+            cam.right[k] = std::strtof(argv[6 + k], nullptr);
+            cam.up[k] = std::strtof(argv[9 + k], nullptr);
+            cam.forward[k] = std::strtof(argv[12 + k], nullptr);
+        }
+        cam.fovy_deg = 45.f;
+        cam.aspect = float(g_w) / float(g_h);
+        cam.znear = 4.1f;
+        cam.zfar = 10000.f;
+        return render_direct(cam, argv[2]);
+    }
+    if (argc == 19)
+        for (int k = 0; k < 16; ++k) matrixUtilities.modelviewInverse[k] = std::strtod(argv[3 + k], nullptr);
+    else if (argc > 3) { std::printf("render: out.bin and optionally 16 matrix numbers\n"); return 1; }
     ray_trace_from_camera();
     if (g_last_image.empty()) return 2;
-    if (argc > 2) {
-        FILE *f = std::fopen(argv[2], "wb");
-        std::fwrite(&g_last_image[0], sizeof(Vec3), g_last_image.size(), f);
-        std::fclose(f);
-    }
+    if (argc > 2) dump(argv[2], g_last_image);
     return 0;
 }

@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from scene_util import describe_difference, many_squares
+from scene_util import describe_difference, many_squares, same_nonfinite
 
 pytestmark = pytest.mark.gpu
 
@@ -33,12 +33,18 @@ LIBM_TIES = {}  # (scene, w, h, spp, seed) -> [(y, x), ...]: pixels excused beca
 
 
 def assert_pixels_agree(img, ref, what, rel=1e-6, excused=()):
-    """Every pixel within rel * max(1, |ref|) on all channels (minus explicitly excused ones)."""
-    bad = (np.abs(img.astype(np.float64) - ref) > rel * np.maximum(1.0, np.abs(ref))).any(axis=2)
+    """Every pixel within rel * max(1, |ref|) on all channels (minus explicitly excused ones).  A value that is non-finite on
+    exactly one side, or non-finite on both sides in different ways (NaN against inf, +inf against -inf), is a bad pixel:
+    a plain |img - ref| > tol is False for a NaN and would let it through."""
+    a, r = img.astype(np.float64), ref.astype(np.float64)
+    both = np.isfinite(a) & np.isfinite(r)
+    diff = np.abs(np.where(both, a, 0.0) - np.where(both, r, 0.0))
+    bad = np.where(both, diff > rel * np.maximum(1.0, np.abs(np.where(both, r, 0.0))), ~same_nonfinite(a, r)).any(axis=2)
     for y, x in excused:
         bad[y, x] = False
-    assert not bad.any(), (f"{what}: {int(bad.sum())} of {bad.size} pixels beyond {rel:g}, worst |diff| "
-                           f"{np.abs(img - ref).max():.3g}, first at (y, x) {np.argwhere(bad)[:5].tolist()}")
+    assert not bad.any(), (f"{what}: {int(bad.sum())} of {bad.size} pixels beyond {rel:g} "
+                           f"({int((~both & ~same_nonfinite(a, r)).any(axis=2).sum())} of them non-finite on one side only or differently), "
+                           f"worst finite |diff| {diff.max():.3g}, first at (y, x) {np.argwhere(bad)[:5].tolist()}")
 
 
 def aov(gpu, dev, cam, w, h, which):

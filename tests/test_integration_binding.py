@@ -54,3 +54,35 @@ def test_binding_code_of_integration_md_renders(gpu, tmp_path):
     assert r.returncode == 0 and "Done in" in r.stdout, r.stdout + r.stderr
     img = np.fromfile(img_path, np.float32).reshape(54, 96, 3)
     assert np.isfinite(img).all() and img.max() > 0.2 and (img > 0).mean() > 0.5   # gradient sky + lit objects, gamma applied
+
+
+@pytest.mark.gpu
+def test_binding_code_of_integration_md_renders_a_trackball_pose_as_hrt_render(gpu, tmp_path):
+    """The hrt_camera fill of INTEGRATION.md off the default pose: the mocked inverse modelview is an fp64 trackball pose (the
+    default pose orbited about the origin), the binding casts it to floats itself, and its frame must be -- bit for bit -- the
+    frame of hrt_render on the same mock scene with the camera built here the same way, HRT_FLAG_GAMMA and the pinned seed."""
+    exe = _build(str(tmp_path))
+    yaw, pitch, roll = np.radians([30.0, 15.0, 5.0])
+    rz = np.array([[np.cos(roll), -np.sin(roll), 0], [np.sin(roll), np.cos(roll), 0], [0, 0, 1]])
+    rx = np.array([[1, 0, 0], [0, np.cos(pitch), -np.sin(pitch)], [0, np.sin(pitch), np.cos(pitch)]])
+    ry = np.array([[np.cos(yaw), 0, np.sin(yaw)], [0, 1, 0], [-np.sin(yaw), 0, np.cos(yaw)]])
+    r = rz @ rx @ ry
+    mi = np.eye(4)
+    mi[:3, :3] = r.T
+    mi[:3, 3] = r.T @ np.array([0.0, 0.0, 6.1])
+    column_major = mi.T.reshape(-1)
+    eye, right, up, fwd = (np.float32(mi[:3, 3]), np.float32(mi[:3, 0]), np.float32(mi[:3, 1]), np.float32(-mi[:3, 2]))
+    assert float(np.dot(right.astype(np.float64), up.astype(np.float64))) != 0.0   # the float basis is not exactly orthonormal
+    via_binding = os.path.join(str(tmp_path), "binding.bin")
+    direct = os.path.join(str(tmp_path), "direct.bin")
+    r1 = subprocess.run([exe, "render", via_binding] + [repr(float(x)) for x in column_major], capture_output=True, text=True)
+    assert r1.returncode == 0 and "Done in" in r1.stdout, r1.stdout + r1.stderr
+    r2 = subprocess.run([exe, "direct", direct] + [repr(float(x)) for v in (eye, right, up, fwd) for x in v], capture_output=True, text=True)
+    assert r2.returncode == 0, r2.stdout + r2.stderr
+    a = np.fromfile(via_binding, np.float32).reshape(54, 96, 3)
+    b = np.fromfile(direct, np.float32).reshape(54, 96, 3)
+    assert np.isfinite(a).all() and a.max() > 0.2
+    assert np.array_equal(a, b), f"binding vs hrt_render: {int((a != b).any(axis=2).sum())} pixels differ"
+    default = os.path.join(str(tmp_path), "default.bin")
+    assert subprocess.run([exe, "render", default], capture_output=True, text=True).returncode == 0
+    assert not np.array_equal(np.fromfile(default, np.float32).reshape(54, 96, 3), a)   # the pose did arrive
