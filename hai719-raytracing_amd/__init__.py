@@ -91,6 +91,11 @@ class Stats(C.Structure):
     ]
 
 
+class Adaptive(C.Structure):
+    """``hrt_adaptive``: parameters of adaptive sampling (include/hrt.h)."""
+    _fields_ = [("min_spp", C.c_uint32), ("max_spp", C.c_uint32), ("threshold", C.c_float)]
+
+
 def _load(name: str) -> C.CDLL:
     path = os.path.join(_HERE, name)
     if not os.path.exists(path):
@@ -173,6 +178,10 @@ def device_lib() -> C.CDLL:
         lib.hrt_multi_gather.restype = C.c_char_p
         lib.hrt_render_multi.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                          C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.POINTER(Adaptive), C.c_uint64,
+                                            C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_render_adaptive_tiles.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.POINTER(Adaptive),
+                                                  C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.hrt_debug_kat.argtypes = [C.c_uint32, C.POINTER(Camera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         _dev = lib
     return _dev
@@ -358,6 +367,24 @@ class DeviceScene:
         """hrt_render_accumulate: add samples [first_sample, first_sample + n_samples) to the running sums (asynchronous)."""
         self._check(self._lib.hrt_render_accumulate(self._h, C.byref(cam), w, h, first_sample, n_samples, seed, flags, rank,
                                                     world, C.c_void_p(d_sum_tiles_ptr), C.c_void_p(stream_ptr)))
+
+    def render_adaptive(self, cam: Camera, w: int, h: int, min_spp: int, max_spp: int, threshold: float, seed: int = 1,
+                        flags: int = 0, stats: Optional[Stats] = None):
+        """hrt_render_adaptive: whole frame -> (frame (h, w, 3) float32, tile_spp (tiles_y, tiles_x) uint32).  Every tile of the
+        frame is bit-identical to the same tile of ``render`` at that tile's count.  ``stats``: a Stats to fill, if wanted."""
+        out = np.empty((h, w, 3), dtype=np.float32)
+        spp = np.empty(((h + TILE - 1) // TILE, (w + TILE - 1) // TILE), dtype=np.uint32)
+        p = Adaptive(min_spp, max_spp, threshold)
+        self._check(self._lib.hrt_render_adaptive(self._h, C.byref(cam), w, h, C.byref(p), seed, flags, out.ctypes.data,
+                                                   spp.ctypes.data, None if stats is None else C.byref(stats)))
+        return out, spp
+
+    def render_adaptive_tiles(self, cam: Camera, w: int, h: int, min_spp: int, max_spp: int, threshold: float, seed: int,
+                              flags: int, rank: int, world: int, d_tiles_ptr: int, d_tile_spp_ptr: int, stream_ptr: int = 0):
+        """hrt_render_adaptive_tiles: this rank's tiles (means) and their counts (uint32 per owned tile) into device buffers."""
+        p = Adaptive(min_spp, max_spp, threshold)
+        self._check(self._lib.hrt_render_adaptive_tiles(self._h, C.byref(cam), w, h, C.byref(p), seed, flags, rank, world,
+                                                        C.c_void_p(d_tiles_ptr), C.c_void_p(d_tile_spp_ptr), C.c_void_p(stream_ptr)))
 
     def check_last_launch(self):
         """hrt_check_last_launch: waits for the last launch; raises if the trace kernel gave up (incomplete tiles)."""

@@ -1,0 +1,251 @@
+// Adaptive sampling (include/hrt.h hrt_render_adaptive*): per-tile sample counts set by a noise estimate.  Included by hrt_api.hip
+// inside its extern "C" block, after everything it builds on.
+//
+// The scheme, per 8x8 tile of the rank:
+//   round 0   samples [0, min/2) of every tile                                     (trace kernel, accumulating into the sums)
+//   round 1   samples [min/2, min) of every tile, then every tile is JUDGED
+//   round k   the tiles still active get min(n, max - n) more (the count doubles, clipped at max), then are judged again
+// Judging a tile compares its sums before the round (S_old, n_old samples) with those after it (S_new, n_new), per in-image pixel
+// in fp32:  A = S_old / n_old,  B = S_new / n_new,  e = (|B.r - A.r| + |B.g - A.g| + |B.b - A.b|) / sqrtf(1e-4 + |B.r| + |B.g| + |B.b|)
+// (the two-buffer estimate: the old sums are the first half of the new ones).  The tile stays active while max e >= threshold and
+// n_new < max.  Active tiles all share one count (they have been active in every round), so a round is one launch of samples
+// [n_old, n_new) over the list of active tiles.  A tile's decision reads only its own pixels, and a sample's random numbers depend
+// only on (seed, pixel, sample): every tile ends with the bits of a plain render at its count, whatever the rank partition.
+//
+// Per round, all on the caller's stream:  gather (active tiles' sums -> compact buffer)  ->  trace kernel over the list, samples
+// [n_old, n_new) added in sample order  ->  hrt_check_last_launch  ->  judge (one wave per tile)  ->  compact (next list, ascending)
+// -> read back the 4-byte length of the next list, which sizes the next launch and ends the loop at 0.  Then the sums become means
+// by each tile's own count (and gamma).
+
+#define HRT_AD_WG 256u  // gather / judge / finalize: 4 waves, one tile each
+
+// Active tile k (rank slot list[k], or k itself when list is NULL: every tile) -> slot k of the compact buffer.
+extern "C" __global__ void __launch_bounds__(HRT_AD_WG) hrt_ad_gather_kernel(const float *__restrict__ full, const uint32_t *__restrict__ list,
+                                                                              uint32_t n, float *__restrict__ compact) {
+    const uint32_t k = blockIdx.x * (HRT_AD_WG / 64u) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (k >= n) return;
+    const uint32_t slot = list ? list[k] : k;
+    const float *src = full + ((size_t)slot * 64u + lane) * 3u;
+    float *dst = compact + ((size_t)k * 64u + lane) * 3u;
+    dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
+}
+
+// One wave per active tile, one lane per pixel: the tile's error (wave max of e over its in-image pixels), S_new back into the
+// full buffer, the tile's count, and keep[k] = whether it takes part in the next round.
+extern "C" __global__ void __launch_bounds__(HRT_AD_WG) hrt_ad_judge_kernel(const float *__restrict__ compact, float *__restrict__ full,
+                                                                             const uint32_t *__restrict__ list, uint32_t n, uint32_t n_old,
+                                                                             uint32_t n_new, float threshold, uint32_t max_spp, uint32_t w,
+                                                                             uint32_t h, uint32_t rank, uint32_t world, uint32_t tiles_x,
+                                                                             uint32_t *__restrict__ counts, uint32_t *__restrict__ keep) {
+    const uint32_t k = blockIdx.x * (HRT_AD_WG / 64u) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (k >= n) return;  // wave-uniform
+    const uint32_t slot = list ? list[k] : k;
+    const uint32_t tile = rank + slot * world;
+    const uint32_t px = (tile % tiles_x) * 8u + (lane & 7u), py = (tile / tiles_x) * 8u + (lane >> 3);
+    const float *b = compact + ((size_t)k * 64u + lane) * 3u;
+    float *a = full + ((size_t)slot * 64u + lane) * 3u;
+    const float b0 = b[0], b1 = b[1], b2 = b[2];
+    float e = 0.f;  // every e is >= 0 (or NaN, which v_max_f32 drops): lanes outside the image leave the max alone
+    if (px < w && py < h) {
+#pragma clang fp contract(off)
+        const float fo = (float)n_old, fn = (float)n_new;
+        const float A0 = a[0] / fo, A1 = a[1] / fo, A2 = a[2] / fo;
+        const float B0 = b0 / fn, B1 = b1 / fn, B2 = b2 / fn;
+        e = (fabsf(B0 - A0) + fabsf(B1 - A1) + fabsf(B2 - A2)) / sqrtf(1e-4f + fabsf(B0) + fabsf(B1) + fabsf(B2));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) e = fmaxf(e, __shfl_xor(e, off));
+    a[0] = b0; a[1] = b1; a[2] = b2;
+    if (lane == 0) {
+        counts[slot] = n_new;
+        keep[k] = (e >= threshold && n_new < max_spp) ? 1u : 0u;
+    }
+}
+
+// The next list: the rank slots of the kept tiles in ASCENDING order (neighbouring tiles stay together in a streaming-kernel unit;
+// the order changes no pixel).  ONE workgroup walks the flags 1024 at a time: ballot + popcount give each kept tile its place
+// within its wave, a scan of the 16 wave totals places the waves, and the running base carries over to the next 1024.  *count
+// receives the list's length.  (One flag per active tile -- 32 400 at 1080p, 32 passes -- against a trace launch of milliseconds.)
+extern "C" __global__ void __launch_bounds__(1024) hrt_ad_compact_kernel(const uint32_t *__restrict__ keep, const uint32_t *__restrict__ list,
+                                                                          uint32_t n, uint32_t *__restrict__ next, uint32_t *__restrict__ count) {
+    __shared__ uint32_t wave_total[16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t base = 0;
+    for (uint32_t b0 = 0; b0 < n; b0 += 1024u) {
+        const uint32_t k = b0 + tid;
+        const bool on = k < n && keep[k] != 0u;
+        const uint64_t m = __ballot(on);
+        if (lane == 0) wave_total[wave] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t off = base, total = 0;
+        for (uint32_t v = 0; v < 16u; ++v) {
+            const uint32_t t = wave_total[v];
+            if (v < wave) off += t;
+            total += t;
+        }
+        if (on) next[off + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = list ? list[k] : k;
+        base += total;
+        __syncthreads();  // wave_total is rewritten by the next 1024
+    }
+    if (tid == 0) *count = base;
+}
+
+// sums -> means by each tile's own count, then gamma: the arithmetic of hrt_finalize_kernel (bit-identical when all counts are equal).
+// In place (out may alias sums).
+extern "C" __global__ void __launch_bounds__(HRT_AD_WG) hrt_ad_finalize_kernel(const float *sums, float *out, uint32_t n_tiles,
+                                                                                const uint32_t *__restrict__ counts, uint32_t gamma) {
+    const uint32_t k = blockIdx.x * (HRT_AD_WG / 64u) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (k >= n_tiles) return;
+    const float nspp = (float)counts[k];
+    const size_t i = ((size_t)k * 64u + lane) * 3u;
+    for (uint32_t c = 0; c < 3u; ++c) {
+        float v = sums[i + c] / nspp;
+        if (gamma) v = (float)pow((double)v, 1.0 / 2.2);
+        out[i + c] = v;
+    }
+}
+
+// Checked BEFORE the scene and the library state, so that a machine without a GPU can test it.
+static int adaptive_check(const char *who, const hrt_adaptive *p, const hrt_camera *cam) {
+    const std::string w = who;
+    if (!p) return fail(HRT_ERR_INVALID, w + ": params is NULL");
+    if (p->min_spp < 2u || (p->min_spp & 1u)) return fail(HRT_ERR_INVALID, w + ": min_spp must be even and at least 2 (got " + std::to_string(p->min_spp) + ")");
+    if (p->max_spp < p->min_spp) return fail(HRT_ERR_INVALID, w + ": max_spp must be at least min_spp (got " + std::to_string(p->max_spp) + " < " + std::to_string(p->min_spp) + ")");
+    if (std::isnan(p->threshold) || p->threshold < 0.f) return fail(HRT_ERR_INVALID, w + ": threshold must be a non-negative number (+inf allowed)");
+    if (!cam) return fail(HRT_ERR_INVALID, w + ": camera is NULL");
+    return HRT_OK;
+}
+
+// Waits for the trace launch just made, refuses it if the kernel gave up, and adds its event time.
+static int adaptive_trace_done(hrt_scene *s, double *kernel_ms) {
+    const int rc = hrt_check_last_launch(s);
+    if (rc != HRT_OK) return rc;
+    float f = 0.f;
+    HIP_TRY(hipEventElapsedTime(&f, s->ev0, s->ev1));
+    *kernel_ms += (double)f;
+    return HRT_OK;
+}
+
+// The rounds over this rank's tiles: d_sums (tiles_owned tiles, tile-major) ends with the means, d_counts with each tile's count
+// (NULL: the scene's own count map, ad_words + 3 x tiles_owned).
+static int adaptive_run(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, const hrt_adaptive *p, uint64_t seed, uint32_t flags,
+                        uint32_t rank, uint32_t world, float *d_sums, uint32_t *d_counts, hipStream_t stream, double *kernel_ms) {
+    *kernel_ms = 0.0;
+    DRender R;
+    DCamera C;
+    int rc = fill_render(s, cam, w, h, p->min_spp, seed, flags, rank, world, R, C);  // the frame, the partition; the scene's device
+    if (rc != HRT_OK) return rc;
+    const uint32_t n_tiles = R.tiles_owned;
+    if (n_tiles == 0u) return HRT_OK;
+    const size_t compact_floats = (size_t)n_tiles * 192u, words = 4u * (size_t)n_tiles + 1u;
+    if (s->ad_compact_cap < compact_floats) {
+        if (s->ad_compact) (void)hipFree(s->ad_compact);
+        s->ad_compact = nullptr; s->ad_compact_cap = 0;
+        HIP_TRY(hipMalloc((void **)&s->ad_compact, compact_floats * sizeof(float)));
+        s->ad_compact_cap = compact_floats;
+    }
+    if (s->ad_words_cap < words) {
+        if (s->ad_words) (void)hipFree(s->ad_words);
+        s->ad_words = nullptr; s->ad_words_cap = 0;
+        HIP_TRY(hipMalloc((void **)&s->ad_words, words * sizeof(uint32_t)));
+        s->ad_words_cap = words;
+    }
+    uint32_t *const lists[2] = {s->ad_words, s->ad_words + n_tiles};
+    uint32_t *const keep = s->ad_words + 2u * (size_t)n_tiles;
+    uint32_t *const counter = s->ad_words + 4u * (size_t)n_tiles;
+    if (!d_counts) d_counts = s->ad_words + 3u * (size_t)n_tiles;
+    const uint32_t half = p->min_spp / 2u;
+
+    HIP_TRY(hipMemsetAsync(d_sums, 0, compact_floats * sizeof(float), stream));
+    rc = launch_trace(s, cam, w, h, 0u, half, seed, flags, rank, world, d_sums, stream, true);  // round 0
+    if (rc == HRT_OK) rc = adaptive_trace_done(s, kernel_ms);
+    if (rc != HRT_OK) return rc;
+    uint32_t done = half, n = n_tiles, next = 0;
+    const uint32_t *active = nullptr;  // round 1: every tile
+    for (uint32_t round = 1; n != 0u; ++round) {
+        const uint32_t add = round == 1u ? half : std::min(done, p->max_spp - done);
+        const dim3 grid((n + HRT_AD_WG / 64u - 1u) / (HRT_AD_WG / 64u));
+        hipLaunchKernelGGL(hrt_ad_gather_kernel, grid, dim3(HRT_AD_WG), 0, stream, d_sums, active, n, s->ad_compact);
+        HIP_TRY(hipGetLastError());
+        rc = launch_trace(s, cam, w, h, done, add, seed, flags, rank, world, s->ad_compact, stream, true, active, n);
+        if (rc == HRT_OK) rc = adaptive_trace_done(s, kernel_ms);
+        if (rc != HRT_OK) return rc;
+        hipLaunchKernelGGL(hrt_ad_judge_kernel, grid, dim3(HRT_AD_WG), 0, stream, s->ad_compact, d_sums, active, n, done, done + add,
+                           p->threshold, p->max_spp, w, h, rank, world, R.tiles_x, d_counts, keep);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(hrt_ad_compact_kernel, dim3(1), dim3(1024), 0, stream, keep, active, n, lists[round & 1u], counter);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&next, counter, sizeof(next), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        done += add;
+        active = lists[round & 1u];
+        n = next;
+    }
+    hipLaunchKernelGGL(hrt_ad_finalize_kernel, dim3((n_tiles + HRT_AD_WG / 64u - 1u) / (HRT_AD_WG / 64u)), dim3(HRT_AD_WG), 0, stream, d_sums, d_sums,
+                       n_tiles, d_counts, (flags & HRT_FLAG_GAMMA) ? 1u : 0u);
+    HIP_TRY(hipGetLastError());
+    return HRT_OK;
+}
+
+int hrt_render_adaptive_tiles(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, const hrt_adaptive *params, uint64_t seed,
+                              uint32_t flags, uint32_t rank, uint32_t world, float *d_tiles, uint32_t *d_tile_spp, void *stream) {
+    int rc = adaptive_check("hrt_render_adaptive_tiles", params, cam);
+    if (rc != HRT_OK) return rc;
+    if (!d_tiles) return fail(HRT_ERR_INVALID, "hrt_render_adaptive_tiles: d_tiles is NULL");
+    if (!d_tile_spp) return fail(HRT_ERR_INVALID, "hrt_render_adaptive_tiles: d_tile_spp is NULL");
+    if (!s) return fail(HRT_ERR_INVALID, "hrt_render_adaptive_tiles: scene is NULL");
+    double ms = 0.0;
+    return adaptive_run(s, cam, w, h, params, seed, flags, rank, world, d_tiles, d_tile_spp, (hipStream_t)stream, &ms);
+}
+
+int hrt_render_adaptive(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, const hrt_adaptive *params, uint64_t seed,
+                        uint32_t flags, float *out_rgb, uint32_t *out_tile_spp, hrt_stats *stats) {
+    int rc = adaptive_check("hrt_render_adaptive", params, cam);
+    if (rc != HRT_OK) return rc;
+    if (!out_rgb) return fail(HRT_ERR_INVALID, "hrt_render_adaptive: out_rgb is NULL");
+    if (!s) return fail(HRT_ERR_INVALID, "hrt_render_adaptive: scene is NULL");
+    if (!g_rt.ready) return fail(HRT_ERR_STATE, "render: call hrt_init first");
+    { const int drc = use_device(s->device); if (drc != HRT_OK) return drc; }
+    if (!w || !h || (uint64_t)w * h > 0x7fffffffull) return fail(HRT_ERR_INVALID, "hrt_render_adaptive: bad frame size");
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t tiles = hrt_tiles_total(w, h);
+    const size_t tile_floats = (size_t)tiles * 64 * 3, frame_floats = (size_t)w * h * 3;
+    if (s->tiles_cap < tile_floats) {
+        if (s->d_tiles) (void)hipFree(s->d_tiles);
+        s->d_tiles = nullptr; s->tiles_cap = 0;
+        HIP_TRY(hipMalloc((void **)&s->d_tiles, tile_floats * sizeof(float)));
+        s->tiles_cap = tile_floats;
+    }
+    if (s->frame_cap < frame_floats) {
+        if (s->d_frame) (void)hipFree(s->d_frame);
+        s->d_frame = nullptr; s->frame_cap = 0;
+        HIP_TRY(hipMalloc((void **)&s->d_frame, frame_floats * sizeof(float)));
+        s->frame_cap = frame_floats;
+    }
+    double ms = 0.0;
+    rc = adaptive_run(s, cam, w, h, params, seed, flags, 0, 1, s->d_tiles, nullptr, nullptr, &ms);  // the count map: the scene's
+    if (rc == HRT_OK) rc = hrt_assemble_frame(s->d_tiles, tiles, w, h, 1, s->d_frame, nullptr);
+    std::vector<uint32_t> counts(tiles);
+    hipError_t e = hipSuccess;
+    if (rc == HRT_OK) e = hipMemcpy(out_rgb, s->d_frame, frame_floats * sizeof(float), hipMemcpyDeviceToHost);
+    if (rc == HRT_OK && e == hipSuccess) e = hipMemcpy(counts.data(), s->ad_words + 3u * (size_t)tiles, (size_t)tiles * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (rc != HRT_OK) return rc;
+    if (e != hipSuccess) return fail(HRT_ERR_DEVICE, std::string("hrt_render_adaptive: ") + hipGetErrorString(e));
+    if (out_tile_spp) std::memcpy(out_tile_spp, counts.data(), (size_t)tiles * sizeof(uint32_t));
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        const uint32_t tx = (w + HRT_TILE - 1) / HRT_TILE;
+        uint64_t samples = 0;
+        for (uint32_t t = 0; t < tiles; ++t) {
+            const uint32_t x0 = (t % tx) * HRT_TILE, y0 = (t / tx) * HRT_TILE;
+            samples += (uint64_t)std::min<uint32_t>(HRT_TILE, w - x0) * std::min<uint32_t>(HRT_TILE, h - y0) * counts[t];
+        }
+        stats->kernel_ms = ms;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->samples = samples;
+        stats->vgprs = (uint32_t)g_rt.attr.numRegs;
+        stats->lds_bytes = s->last_lds;
+        stats->waves_launched = s->last_waves;
+    }
+    return HRT_OK;
+}

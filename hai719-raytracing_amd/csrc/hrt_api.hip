@@ -258,6 +258,12 @@ struct hrt_scene {
     uint32_t last_grid = 0, last_waves = 0, last_lds = 0;
     hipStream_t last_stream = nullptr;  // stream of the previous launch on this scene
     int device = 0;                     // the device that holds this scene (current when it was created)
+    // scratch of the adaptive entry points (hrt_adaptive.hip), grown on demand: the active tiles' sums, compact; and in ad_words
+    // the two tile lists, the judge's keep flags and the count map of hrt_render_adaptive (tiles each), then the list counter
+    float *ad_compact = nullptr;
+    size_t ad_compact_cap = 0;
+    uint32_t *ad_words = nullptr;
+    size_t ad_words_cap = 0;
 };
 
 #include "hrt_kdbuild.hip"
@@ -294,15 +300,21 @@ int hrt_init(int device_ordinal) {
     if (g_rt.lds_budget > 64u * 1024u) {
         HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)g_rt.lds_budget));
+        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_list, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_rt.lds_budget));
         HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_lights, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)g_rt.lds_budget));
+        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_lights_list, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_rt.lds_budget));
         HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_rt.lds_budget));
+        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_exact_list, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_rt.lds_budget));
         HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_lights_exact, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)g_rt.lds_budget));
+        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_lights_exact_list, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_rt.lds_budget));
     }
     if (HRT_WG > 256) {  // one big workgroup per CU: backed-up streams + nodelets go past the 64 KiB default
         HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace2_kernel_lights, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace2_kernel_list, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace2_kernel_lights_list, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
     {   // u8 -> float tables in double, as the reference evaluates c/255. and c/127.5 - 1. (Material.cpp:87,124)
         float lut[512];
@@ -317,6 +329,9 @@ int hrt_init(int device_ordinal) {
         HIP_TRY(hipFuncSetAttribute((const void *)hrt_wgstream_kernel_lights_exact, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
         HIP_TRY(hipFuncSetAttribute((const void *)hrt_wgstream_kernel_sph, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
         HIP_TRY(hipFuncSetAttribute((const void *)hrt_wgstream_kernel_lights_sph, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+        for (const void *k : {(const void *)hrt_wgstream_kernel_list, (const void *)hrt_wgstream_kernel_lights_list, (const void *)hrt_wgstream_kernel_exact_list,
+                              (const void *)hrt_wgstream_kernel_lights_exact_list, (const void *)hrt_wgstream_kernel_sph_list, (const void *)hrt_wgstream_kernel_lights_sph_list})
+            HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
         const char *k = std::getenv("HRT_KERNEL");
         const std::string ks = k ? k : "";
         g_rt.use_dual = ks != "single";
@@ -342,6 +357,8 @@ void hrt_scene_destroy(hrt_scene *s) {
     if (s->d_cam_aov) (void)hipFree(s->d_cam_aov);
     if (s->d_tiles) (void)hipFree(s->d_tiles);
     if (s->d_frame) (void)hipFree(s->d_frame);
+    if (s->ad_compact) (void)hipFree(s->ad_compact);
+    if (s->ad_words) (void)hipFree(s->ad_words);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     delete s;
@@ -957,18 +974,30 @@ static int fill_render(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t
     R.tiles_owned = hrt_tiles_owned(w, h, rank, world);
     R.tile_counter = s->tile_counter;
     R.stamps = s->stamps;
+    R.tile_list = nullptr;
     return HRT_OK;
 }
+
+// The kernel of that name, or its build over a tile list (DRender::tile_list) when the launch has one.
+#define HRT_PICK(k) (R.tile_list ? k##_list : k)
 
 // One launch of the trace kernel over this rank's tiles: samples [s0, s0 + spp) of every pixel.
 // accumulate = false: d_tiles receives the pixel means (s0 must be 0).
 // accumulate = true : d_tiles holds the running sums of samples [0, s0) and receives the sums of [0, s0 + spp).
+// list (device, list_n rank slots; adaptive sampling): only those tiles, into a COMPACT d_tiles (entry j of the list at slot j).
+// The kernel-form and grid choices below then see list_n tiles.
 static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t s0, uint32_t spp, uint64_t seed,
-                        uint32_t flags, uint32_t rank, uint32_t world, float *d_tiles, void *stream_, bool accumulate) {
+                        uint32_t flags, uint32_t rank, uint32_t world, float *d_tiles, void *stream_, bool accumulate,
+                        const uint32_t *list = nullptr, uint32_t list_n = 0) {
     DRender R;
     DCamera C;
     int rc = fill_render(s, cam, w, h, spp, seed, flags, rank, world, R, C);
     if (rc != HRT_OK) return rc;
+    if (list) {
+        if (list_n > R.tiles_owned) return fail(HRT_ERR_INVALID, "render: tile list longer than the rank's tiles");
+        R.tile_list = list;
+        R.tiles_owned = list_n;
+    }
     R.cam = s->d_cam;
     if (!d_tiles) return fail(HRT_ERR_INVALID, "render: NULL tile buffer");
     if ((uint64_t)s0 + spp > 0xffffffffull) return fail(HRT_ERR_INVALID, "render: sample index overflows 32 bits");
@@ -1043,8 +1072,8 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
         }
         R.sp_pool = s->sp_pool;
     } else {
-        const void *kfn = exact ? (s->d.n_lights ? (const void *)hrt_trace_kernel_lights_exact : (const void *)hrt_trace_kernel_exact)
-                                : (s->d.n_lights ? (const void *)hrt_trace_kernel_lights : (const void *)hrt_trace_kernel);
+        const void *kfn = exact ? (s->d.n_lights ? (const void *)HRT_PICK(hrt_trace_kernel_lights_exact) : (const void *)HRT_PICK(hrt_trace_kernel_exact))
+                                : (s->d.n_lights ? (const void *)HRT_PICK(hrt_trace_kernel_lights) : (const void *)HRT_PICK(hrt_trace_kernel));
         lds_bytes = R.lds_units * 16u;
         if (dual_kernel) {
             // 4 workgroups per CU: 160 KiB = 4 x (27 KiB of backed-up streams + 12 KiB of nodelets)
@@ -1052,7 +1081,7 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
             const uint32_t room = (156u * 1024u / wgs - backup) / 16u;
             if (R.lds_units > room) R.lds_units = room & ~3u;
             lds_bytes = R.lds_units * 16u + backup;
-            kfn = s->d.n_lights ? (const void *)hrt_trace2_kernel_lights : (const void *)hrt_trace2_kernel;
+            kfn = s->d.n_lights ? (const void *)HRT_PICK(hrt_trace2_kernel_lights) : (const void *)HRT_PICK(hrt_trace2_kernel);
         }
         int per_cu = 0;
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, HRT_WG, lds_bytes));
@@ -1082,23 +1111,23 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
     HIP_TRY(hipMemsetAsync(s->stamps, 0, 16 * sizeof(unsigned long long), stream));  // [15] = give-up code of the streaming kernel
     HIP_TRY(hipEventRecord(s->ev0, stream));
     if (stream_kernel && exact) {
-        if (s->d.n_lights) hipLaunchKernelGGL(hrt_wgstream_kernel_lights_exact, dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
-        else hipLaunchKernelGGL(hrt_wgstream_kernel_exact, dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
+        if (s->d.n_lights) hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel_lights_exact), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
+        else hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel_exact), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
     } else if (stream_kernel && s->d.n_spheres >= HRT_SPHERE_FILTER_MIN && s->d.n_spheres <= 128u) {  // a crowd of spheres: the builds with the pair filter
-        if (s->d.n_lights) hipLaunchKernelGGL(hrt_wgstream_kernel_lights_sph, dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
-        else hipLaunchKernelGGL(hrt_wgstream_kernel_sph, dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
+        if (s->d.n_lights) hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel_lights_sph), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
+        else hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel_sph), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
     } else if (stream_kernel) {
-        if (s->d.n_lights) hipLaunchKernelGGL(hrt_wgstream_kernel_lights, dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
-        else hipLaunchKernelGGL(hrt_wgstream_kernel, dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
+        if (s->d.n_lights) hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel_lights), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
+        else hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
     } else if (exact) {
-        if (s->d.n_lights) hipLaunchKernelGGL(hrt_trace_kernel_lights_exact, dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
-        else hipLaunchKernelGGL(hrt_trace_kernel_exact, dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
+        if (s->d.n_lights) hipLaunchKernelGGL(HRT_PICK(hrt_trace_kernel_lights_exact), dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
+        else hipLaunchKernelGGL(HRT_PICK(hrt_trace_kernel_exact), dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
     } else {
         if (dual_kernel) {
-            if (s->d.n_lights) hipLaunchKernelGGL(hrt_trace2_kernel_lights, dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
-            else hipLaunchKernelGGL(hrt_trace2_kernel, dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
-        } else if (s->d.n_lights) hipLaunchKernelGGL(hrt_trace_kernel_lights, dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
-        else hipLaunchKernelGGL(hrt_trace_kernel, dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
+            if (s->d.n_lights) hipLaunchKernelGGL(HRT_PICK(hrt_trace2_kernel_lights), dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
+            else hipLaunchKernelGGL(HRT_PICK(hrt_trace2_kernel), dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
+        } else if (s->d.n_lights) hipLaunchKernelGGL(HRT_PICK(hrt_trace_kernel_lights), dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
+        else hipLaunchKernelGGL(HRT_PICK(hrt_trace_kernel), dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(s->ev1, stream));
@@ -1421,6 +1450,7 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 }
 
 #include "hrt_multi.hip"
+#include "hrt_adaptive.hip"
 
 int hrt_kd_build_gpu(const hrt_kd_build_input *in, hrt_kd_build_output *out, void *user) {
     (void)user;

@@ -133,4 +133,14 @@ struct DRender {
     uint32_t sp_band_log2;       // streaming kernel: a work unit is one ROW BAND of a tile, 8 x (8 >> this) pixels (then one tile per unit): finer
                                  // items on the tile queue when tiles are few and heavy (many samples per pixel)
     uint32_t *sp_pool;           // streaming kernel built with HRT_SP_GLOBAL: per-workgroup path records
+    const uint32_t *tile_list;   // the *_list kernels (adaptive sampling, hrt_adaptive.hip): work-queue item j is rank slot tile_list[j],
+                                 // tiles_owned is the list's length and out_tiles a COMPACT buffer (slot j of the list at j).  Read only by
+                                 // the LIST instantiations: the other kernels compile as if the field did not exist
 };
+
+// Rank slot of work-queue item j: the item itself, or -- in the LIST builds -- the item-th entry of R.tile_list.
+template <bool LIST>
+__device__ __forceinline__ uint32_t rank_slot(const DRender &R, uint32_t j) {
+    if (LIST) return R.tile_list[j];
+    return j;
+}

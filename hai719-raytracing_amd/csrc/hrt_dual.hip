@@ -401,7 +401,7 @@ __device__ __forceinline__ void walk_visit(const CX &cx, PathState &p) {
     if (walk_some(cx, p.ray, p.parked, p.w, p.h, HRT_DS_TRIPS)) p.stage = 2u;
 }
 
-template <bool LIGHTS>
+template <bool LIGHTS, bool LIST = false>
 __device__ __forceinline__ void trace_body_dual(const DRender &R) {
     extern __shared__ uint4 s_units[];
     Ctx cx;
@@ -438,7 +438,7 @@ __device__ __forceinline__ void trace_body_dual(const DRender &R) {
     };
     auto locate = [&](uint32_t j, uint32_t &xy) -> bool {  // pixel of this lane in tile slot j; false = outside the image
         if (j == HRT_DS_NONE) { xy = 0; return false; }
-        const uint32_t tile = R.rank + j * R.world;
+        const uint32_t tile = R.rank + rank_slot<LIST>(R, j) * R.world;
         const uint32_t px = (tile % R.tiles_x) * 8u + (lane & 7u), py = (tile / R.tiles_x) * 8u + (lane >> 3);
         xy = px | (py << 16);
         return px < R.w && py < R.h && R.spp > 0u;
@@ -600,3 +600,6 @@ __device__ __forceinline__ void trace_body_dual(const DRender &R) {
 
 extern "C" __global__ void __launch_bounds__(HRT_WG, HRT_MIN_WAVES) hrt_trace2_kernel(const DRender R) { hrtk::trace_body_dual<false>(R); }
 extern "C" __global__ void __launch_bounds__(HRT_WG, HRT_MIN_WAVES) hrt_trace2_kernel_lights(const DRender R) { hrtk::trace_body_dual<true>(R); }
+// over a tile list (DRender::tile_list; adaptive sampling, hrt_adaptive.hip)
+extern "C" __global__ void __launch_bounds__(HRT_WG, HRT_MIN_WAVES) hrt_trace2_kernel_list(const DRender R) { hrtk::trace_body_dual<false, true>(R); }
+extern "C" __global__ void __launch_bounds__(HRT_WG, HRT_MIN_WAVES) hrt_trace2_kernel_lights_list(const DRender R) { hrtk::trace_body_dual<true, true>(R); }

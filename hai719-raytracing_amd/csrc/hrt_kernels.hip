@@ -1291,7 +1291,7 @@ __device__ __forceinline__ Ray camera_ray(ccam C, float u, float v, float time) 
 // The megakernel body.  LIGHTS = the scene has point lights (soft-shadow fan-out, Scene.h:305-334,
 // compiled in); scenes without lights run the variant that carries none of that code or its registers.
 // ---------------------------------------------------------------------------
-template <bool LIGHTS, bool EXACT = false>
+template <bool LIGHTS, bool EXACT = false, bool LIST = false>
 __device__ __forceinline__ void trace_body(const DRender &R) {
     extern __shared__ uint4 s_units[];
     CtxT<EXACT> cx;
@@ -1324,7 +1324,7 @@ __device__ __forceinline__ void trace_body(const DRender &R) {
         if (lane == 0) j = atomicAdd(R.tile_counter, 1u);
         j = __builtin_amdgcn_readfirstlane(j);
         if (j >= R.tiles_owned) break;  // the queue is finite: every wave gets here
-        const uint32_t tile = R.rank + j * R.world;
+        const uint32_t tile = R.rank + rank_slot<LIST>(R, j) * R.world;
         const uint32_t px = (tile % R.tiles_x) * 8u + (lane & 7u);
         const uint32_t py = (tile / R.tiles_x) * 8u + (lane >> 3);
         const bool inside = px < R.w && py < R.h;
@@ -1450,6 +1450,11 @@ extern "C" __global__ void __launch_bounds__(HRT_WG, HRT_MIN_WAVES_SINGLE_LIGHTS
 // HRT_FLAG_EXACT_ONLY: the proof builds (no filters, no v_rcp_f32; see CtxT).  Not tuned: 2 waves per SIMD.
 extern "C" __global__ void __launch_bounds__(HRT_WG, 2) hrt_trace_kernel_exact(const DRender R) { trace_body<false, true>(R); }
 extern "C" __global__ void __launch_bounds__(HRT_WG, 2) hrt_trace_kernel_lights_exact(const DRender R) { trace_body<true, true>(R); }
+// The same four over a tile list (DRender::tile_list; adaptive sampling, hrt_adaptive.hip)
+extern "C" __global__ void __launch_bounds__(HRT_WG, HRT_MIN_WAVES_SINGLE) hrt_trace_kernel_list(const DRender R) { trace_body<false, false, true>(R); }
+extern "C" __global__ void __launch_bounds__(HRT_WG, HRT_MIN_WAVES_SINGLE_LIGHTS) hrt_trace_kernel_lights_list(const DRender R) { trace_body<true, false, true>(R); }
+extern "C" __global__ void __launch_bounds__(HRT_WG, 2) hrt_trace_kernel_exact_list(const DRender R) { trace_body<false, true, true>(R); }
+extern "C" __global__ void __launch_bounds__(HRT_WG, 2) hrt_trace_kernel_lights_exact_list(const DRender R) { trace_body<true, true, true>(R); }
 
 // gamma_correct (Functions.cpp:56-60): pow(c, 1/2.2) in double, over this rank's tile buffer.  Kept out of
 // the megakernel: fp64 pow is register-hungry and runs once per pixel.

@@ -281,7 +281,7 @@ __device__ __forceinline__ void sp_push_all(const SpLds &L, SpCtl &C, uint32_t o
     }
 }
 
-template <bool LIGHTS, bool EXACT = false, bool SPHF = false>
+template <bool LIGHTS, bool EXACT = false, bool SPHF = false, bool LIST = false>
 __device__ __forceinline__ void stream_body(const DRender &R) {
     extern __shared__ uint4 s_raw[];
     SpLds L;
@@ -446,7 +446,7 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                                 for (uint32_t t = 0; t < G; ++t) {
                                     uint32_t xy = 0xFFFFFFFFu;
                                     if (j + t < items) {
-                                        const uint32_t tile = R.rank + ((j + t) >> blog) * R.world, band = (j + t) & ((1u << blog) - 1u);
+                                        const uint32_t tile = R.rank + rank_slot<LIST>(R, (j + t) >> blog) * R.world, band = (j + t) & ((1u << blog) - 1u);
                                         xy = ((tile % R.tiles_x) * 8u) | (((tile / R.tiles_x) * 8u + band * (8u >> blog)) << 16);  // the band's first row
                                     }
                                     tile_xy[k * HRT_SP_MAXG + t] = xy;
@@ -989,3 +989,11 @@ extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstrea
 // HRT_FLAG_EXACT_ONLY proof builds (no filters, no v_rcp_f32; CtxT in hrt_kernels.hip)
 extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstream_kernel_exact(const DRender R) { hrtk::stream_body<false, true>(R); }
 extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstream_kernel_lights_exact(const DRender R) { hrtk::stream_body<true, true>(R); }
+// The same six over a tile list (DRender::tile_list; adaptive sampling, hrt_adaptive.hip).  Outputs go to the list's compact buffer, so
+// the reductions' out_tiles indexing (rj * (192 >> blog) + i) is the same as above.
+extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstream_kernel_list(const DRender R) { hrtk::stream_body<false, false, false, true>(R); }
+extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstream_kernel_lights_list(const DRender R) { hrtk::stream_body<true, false, false, true>(R); }
+extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstream_kernel_sph_list(const DRender R) { hrtk::stream_body<false, false, true, true>(R); }
+extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstream_kernel_lights_sph_list(const DRender R) { hrtk::stream_body<true, false, true, true>(R); }
+extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstream_kernel_exact_list(const DRender R) { hrtk::stream_body<false, true, false, true>(R); }
+extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstream_kernel_lights_exact_list(const DRender R) { hrtk::stream_body<true, true, false, true>(R); }

@@ -7,6 +7,8 @@
 //             [--w 850] [--h 480] [--spp 20] [--seed 1] [--out ./rendu.ppm] [--assets DIR] [--gpu 0]
 //             [--kd gpu]                         build the KD-trees' split search on the GPU (hrt_kd_build_gpu; the same trees)
 //             [--gpus N | --devices 0,1,2,...]   image tiles across several GPUs of this node (hrt_multi_*; an ordinal may repeat)
+//             [--adaptive THRESHOLD [--spp-min 8]] adaptive sampling (hrt_render_adaptive): per 8x8 tile from --spp-min up to --spp
+//                                                  samples per pixel, until the tile's noise estimate is below THRESHOLD (one GPU)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -26,6 +28,8 @@ static Scene scene;
 static hrt_scene *device_scene = nullptr;
 static uint64_t seed = 1;
 static std::string out_path = "./rendu.ppm";
+static bool adaptive = false;  // --adaptive: hrt_render_adaptive from min_spp up to nsamples
+static hrt_adaptive adaptive_params = {8u, 0u, 0.f};
 
 // Drop-in for ray_trace_from_camera(): same inputs (current scene, nsamples, window size, camera),
 // same output file and quantisation; returns non-zero instead of printing-and-returning on failure.
@@ -35,17 +39,25 @@ static int ray_trace_from_camera() {
     const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
     std::vector<float> image((size_t)w * h * 3, 0.f);
     const hrt_camera cam = default_camera((float)w / (float)h);
-    std::cout << "Ray tracing a " << w << " x " << h << " image on the GPU using " << nsamples
-              << " samples per pixel" << std::endl;
+    if (adaptive)
+        std::cout << "Ray tracing a " << w << " x " << h << " image on the GPU using " << adaptive_params.min_spp << " to " << nsamples
+                  << " samples per pixel (adaptive, threshold " << adaptive_params.threshold << ")" << std::endl;
+    else
+        std::cout << "Ray tracing a " << w << " x " << h << " image on the GPU using " << nsamples
+                  << " samples per pixel" << std::endl;
     hrt_stats st;
+    adaptive_params.max_spp = nsamples;
     int rc = multi ? hrt_multi_render(multi, &cam, w, h, nsamples, seed, HRT_FLAG_GAMMA, image.data(), &st)
-                   : hrt_render(device_scene, &cam, w, h, nsamples, seed, HRT_FLAG_GAMMA, image.data(), &st);
+             : adaptive ? hrt_render_adaptive(device_scene, &cam, w, h, &adaptive_params, seed, HRT_FLAG_GAMMA, image.data(), nullptr, &st)
+                        : hrt_render(device_scene, &cam, w, h, nsamples, seed, HRT_FLAG_GAMMA, image.data(), &st);
     if (rc != HRT_OK) {
-        std::cout << "hrt_render failed: " << hrt_last_error() << std::endl;
+        std::cout << (adaptive ? "hrt_render_adaptive" : "hrt_render") << " failed: " << hrt_last_error() << std::endl;
         return rc;
     }
     std::cout << "  Done in " << st.total_ms / 1000.0 << " seconds (kernel " << st.kernel_ms << " ms, "
-              << (double)st.samples / st.kernel_ms / 1e3 << " Msamples/s)" << std::endl;
+              << (double)st.samples / st.kernel_ms / 1e3 << " Msamples/s";
+    if (adaptive) std::cout << ", mean " << (double)st.samples / ((double)w * h) << " spp";
+    std::cout << ")" << std::endl;
     rc = hrt_write_ppm(out_path.c_str(), image.data(), w, h);
     if (rc != HRT_OK) std::cout << hrt_last_error() << std::endl;
     return rc;
@@ -67,12 +79,18 @@ int main(int argc, char **argv) {
         else if (k == "--assets") assets = v;
         else if (k == "--gpu") gpu = atoi(v.c_str());
         else if (k == "--kd") kd_on_gpu = v == "gpu";
+        else if (k == "--adaptive") { adaptive = true; adaptive_params.threshold = strtof(v.c_str(), nullptr); }
+        else if (k == "--spp-min") adaptive_params.min_spp = (unsigned)atoi(v.c_str());
         else if (k == "--gpus") { devices.clear(); for (int d = 0; d < atoi(v.c_str()); ++d) devices.push_back(d); }
         else if (k == "--devices") {
             devices.clear();
             for (size_t a = 0; a < v.size();) { size_t b = v.find(',', a); if (b == std::string::npos) b = v.size(); devices.push_back(atoi(v.substr(a, b - a).c_str())); a = b + 1; }
         }
         else { std::cerr << "unknown option " << k << std::endl; return 2; }
+    }
+    if (adaptive && !devices.empty()) {
+        std::cerr << "--adaptive renders on one GPU: it cannot be combined with --gpus / --devices" << std::endl;
+        return 2;
     }
     scene.asset_root = assets;
     if (!scene.setup_by_name(name, (float)SCREENWIDTH / (float)SCREENHEIGHT, seed)) {

@@ -369,6 +369,40 @@ HRT_API int hrt_render_accumulate(hrt_scene *scene, const hrt_camera *cam, uint3
  * (main.cpp:196).  d_tiles may alias d_sum_tiles.  The result is what hrt_render_tiles(total_samples) writes. */
 HRT_API int hrt_finalize_tiles(const float *d_sum_tiles, uint32_t n_tiles, uint32_t total_samples, uint32_t flags,
                        float *d_tiles, void *stream);
+/* ---- adaptive sampling: per-tile sample counts set by a noise estimate ("render until clean")
+ * Work is per HRT_TILE x HRT_TILE tile.  Round 0 adds samples [0, min_spp/2) to every tile, round 1 adds [min_spp/2, min_spp).
+ * After every round from round 1 on, each tile rendered in it is judged: with S_old the sums over its n_old samples before the
+ * round and S_new those over n_new samples after it, per in-image pixel in fp32
+ *     A = S_old / (float)n_old,  B = S_new / (float)n_new,
+ *     e = (|B.r - A.r| + |B.g - A.g| + |B.b - A.b|) / sqrtf(1e-4f + |B.r| + |B.g| + |B.b|)     (sums left to right)
+ * and tile_err = max e over the tile's in-image pixels.  The tile stays active while tile_err >= threshold and n_new < max_spp;
+ * the next round adds min(n, max_spp - n) samples to every active tile (the count doubles, clipped at max_spp).  Rounds end when
+ * no tile is active.  So every count lies in {min_spp * 2^k} u {max_spp}; threshold 0 gives every tile max_spp, +inf every
+ * tile min_spp, and min_spp == max_spp is a uniform render.
+ * CONTRACT: every tile of the result is bit-identical to the same tile of hrt_render at the count that tile was given (a
+ * sample's random numbers depend only on (seed, pixel, sample), and the sums continue in sample order).  A tile's decision
+ * reads only its own pixels, so counts and pixels are the same for any rank / world partition.
+ * Parameters: min_spp even and >= 2, max_spp >= min_spp, threshold not NaN and not negative (+inf allowed).  They, the camera
+ * and the output pointers are checked before the scene and the library state: a bad one returns HRT_ERR_INVALID and
+ * hrt_last_error() names it. */
+typedef struct hrt_adaptive {
+    uint32_t min_spp, max_spp;
+    float threshold;
+} hrt_adaptive;
+/* This rank's tiles (rank r of world: tiles r, r + world, ...), layout of hrt_render_tiles, into DEVICE memory: d_tiles receives
+ * the pixel means (gamma-corrected with HRT_FLAG_GAMMA), d_tile_spp one uint32 count per owned tile.  Runs on `stream` (a
+ * hipStream_t, NULL = the default stream) and synchronises it once per round: one 4-byte read-back (how many tiles are still
+ * active) sizes the next launch.  Every trace launch is checked (hrt_check_last_launch); a kernel that gave up ends the call
+ * with HRT_ERR_DEVICE.  The rounds' scratch (compact sums, tile lists, counter) lives in the hrt_scene. */
+HRT_API int hrt_render_adaptive_tiles(hrt_scene *scene, const hrt_camera *cam, uint32_t w, uint32_t h, const hrt_adaptive *params,
+                                      uint64_t seed, uint32_t flags, uint32_t rank, uint32_t world, float *d_tiles,
+                                      uint32_t *d_tile_spp, void *stream);
+/* The whole frame on the scene's device into a HOST buffer out_rgb[h*w*3], as hrt_render.  out_tile_spp (host, may be NULL):
+ * tiles_y * tiles_x counts, row-major.  stats (may be NULL): kernel_ms = the trace kernels' time summed over all rounds,
+ * samples = sum over in-image pixels of their tile's count. */
+HRT_API int hrt_render_adaptive(hrt_scene *scene, const hrt_camera *cam, uint32_t w, uint32_t h, const hrt_adaptive *params,
+                                uint64_t seed, uint32_t flags, float *out_rgb, uint32_t *out_tile_spp, hrt_stats *stats);
+
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
  * format 6: the same integers as bytes (binary PPM; negative values, which P3 prints with a sign, clamp to 0).
