@@ -7,8 +7,8 @@
 //   round k   the tiles still active get min(n, max - n) more (the count doubles, clipped at max), then are judged again
 // Judging a tile compares its sums before the round (S_old, n_old samples) with those after it (S_new, n_new), per in-image pixel
 // in fp32:  A = S_old / n_old,  B = S_new / n_new,  e = (|B.r - A.r| + |B.g - A.g| + |B.b - A.b|) / sqrtf(1e-4 + |B.r| + |B.g| + |B.b|)
-// (the two-buffer estimate: the old sums are the first half of the new ones).  The tile stays active while max e >= threshold and
-// n_new < max.  Active tiles all share one count (they have been active in every round), so a round is one launch of samples
+// (the two-buffer estimate: the old sums are the first half of the new ones); a pixel whose e is NaN counts as 0.  The tile stays
+// active while max e >= threshold and n_new < max.  Active tiles all share one count (they have been active in every round), so a round is one launch of samples
 // [n_old, n_new) over the list of active tiles.  A tile's decision reads only its own pixels, and a sample's random numbers depend
 // only on (seed, pixel, sample): every tile ends with the bits of a plain render at its count, whatever the rank partition.
 //
@@ -45,13 +45,14 @@ extern "C" __global__ void __launch_bounds__(HRT_AD_WG) hrt_ad_judge_kernel(cons
     const float *b = compact + ((size_t)k * 64u + lane) * 3u;
     float *a = full + ((size_t)slot * 64u + lane) * 3u;
     const float b0 = b[0], b1 = b[1], b2 = b[2];
-    float e = 0.f;  // every e is >= 0 (or NaN, which v_max_f32 drops): lanes outside the image leave the max alone
+    float e = 0.f;  // every e is >= 0: lanes outside the image leave the max alone
     if (px < w && py < h) {
 #pragma clang fp contract(off)
         const float fo = (float)n_old, fn = (float)n_new;
         const float A0 = a[0] / fo, A1 = a[1] / fo, A2 = a[2] / fo;
         const float B0 = b0 / fn, B1 = b1 / fn, B2 = b2 / fn;
         e = (fabsf(B0 - A0) + fabsf(B1 - A1) + fabsf(B2 - A2)) / sqrtf(1e-4f + fabsf(B0) + fabsf(B1) + fabsf(B2));
+        e = e >= 0.f ? e : 0.f;  // a mean that is inf or NaN gives e = NaN: such a pixel counts as 0 (include/hrt.h)
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) e = fmaxf(e, __shfl_xor(e, off));

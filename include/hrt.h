@@ -375,8 +375,9 @@ HRT_API int hrt_finalize_tiles(const float *d_sum_tiles, uint32_t n_tiles, uint3
  * round and S_new those over n_new samples after it, per in-image pixel in fp32
  *     A = S_old / (float)n_old,  B = S_new / (float)n_new,
  *     e = (|B.r - A.r| + |B.g - A.g| + |B.b - A.b|) / sqrtf(1e-4f + |B.r| + |B.g| + |B.b|)     (sums left to right)
- * and tile_err = max e over the tile's in-image pixels.  The tile stays active while tile_err >= threshold and n_new < max_spp;
- * the next round adds min(n, max_spp - n) samples to every active tile (the count doubles, clipped at max_spp).  Rounds end when
+ * and tile_err = max e over the tile's in-image pixels, where a pixel whose e is NaN (a mean that is inf or NaN) counts as 0: a
+ * tile whose in-image pixels are all non-finite has tile_err 0.  The tile stays active while tile_err >= threshold and
+ * n_new < max_spp; the next round adds min(n, max_spp - n) samples to every active tile (the count doubles, clipped at max_spp).  Rounds end when
  * no tile is active.  So every count lies in {min_spp * 2^k} u {max_spp}; threshold 0 gives every tile max_spp, +inf every
  * tile min_spp, and min_spp == max_spp is a uniform render.
  * CONTRACT: every tile of the result is bit-identical to the same tile of hrt_render at the count that tile was given (a

@@ -116,3 +116,34 @@ def describe_difference(a, b):
     if same_nan:   # np.array_equal counts a NaN as unequal to itself: say so, a caller deciding with it fails on these alone
         text += f"; {same_nan} more pixels hold the same NaN / inf on both sides (not counted above; unequal to np.array_equal)"
     return text
+
+
+def open_box(gpu, albedo, lamp, light=None, floor_albedo=None):
+    """An open-fronted box of five diffuse walls, an emissive lamp square under its ceiling, an optional point light."""
+    M = gpu.Material.make
+    s = gpu.HostScene()
+    s.set_sky(True)
+    if light is not None:
+        s.add_light((0.5, 1.2, 0.5), 0.4, light)
+    fl = albedo if floor_albedo is None else floor_albedo
+    s.add_quad((-2, -1.5, -4), (1, 0, 0), (0, 0, 1), 4, 6, M(albedo=fl))                     # floor
+    s.add_quad((-2, 1.8, 2), (1, 0, 0), (0, 0, -1), 4, 6, M(albedo=albedo))                  # ceiling
+    s.add_quad((-2, -1.5, -4), (1, 0, 0), (0, 1, 0), 4, 3.3, M(albedo=albedo))               # back
+    s.add_quad((-2, -1.5, 2), (0, 0, -1), (0, 1, 0), 6, 3.3, M(albedo=albedo))               # left
+    s.add_quad((2, -1.5, -4), (0, 0, 1), (0, 1, 0), 6, 3.3, M(albedo=albedo))                # right
+    s.add_quad((-1.5, 1.75, -3.0), (1, 0, 0), (0, 0, 1), 3.0, 3.0, lamp)                     # lamp, facing down
+    return s
+
+
+def overflow_scene(gpu, mechanism, lit):
+    """A box whose colour products overflow fp32 (tests/test_gpu_views.py): mechanism "emission" (an infinite lamp over a black
+    floor; `lit` adds a point light) or "throughput" (albedos of 1e8)."""
+    M = gpu.Material.make
+    if mechanism == "emission":
+        # (a) a black floor below a lamp whose light_color x light_intensity overflows fp32: a path off the floor has throughput
+        # 0 and then meets an infinite emission -- 0 x inf = NaN unless the path ends where its throughput became 0
+        return open_box(gpu, (0.7, 0.7, 0.7), M(albedo=(0, 0, 0), emissive=True, light_color=(1e30, 1e30, 1e30), light_intensity=1e10),
+                        light=(1.0, 1.0, 1.0) if lit else None, floor_albedo=(0, 0, 0))
+    # (b) albedos of 1e8: after five bounces the throughput is 1e40 = inf, and a last segment that ends on a non-emitting wall or
+    # in the dark sky adds inf x 0 = NaN unless it is pruned
+    return open_box(gpu, (1e8, 1e8, 1e8), M(albedo=(0, 0, 0), emissive=True, light_color=(1, 1, 1), light_intensity=5.0))

@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from adaptive_ref import errors_from, expected_counts, samples, sequence, tile_err, tiles_differing
+
 pytestmark = pytest.mark.gpu
 
 W, H, SEED = 120, 67, 11  # 15 x 9 tiles; the last column and row are partly outside the image
@@ -19,53 +21,20 @@ def build(gpu, name, w=W, h=H):
     return desc, gpu.DeviceScene(desc), gpu.default_camera(w / h)
 
 
-def sequence(min_spp, max_spp):
-    """The counts a tile passes through: min/2 (round 0), min (round 1), then doubling, clipped at max."""
-    seq = [min_spp // 2, min_spp]
-    while seq[-1] < max_spp:
-        seq.append(min(2 * seq[-1], max_spp))
-    return seq
-
-
-def tile_err(a, b, w=W, h=H):
-    """include/hrt.h: per pixel e = sum|B - A| / sqrtf(1e-4 + sum|B|) in fp32, left to right; max over the tile's in-image pixels.
-    a, b: the means of uniform renders at n_old and n_new samples (no gamma): exactly S_old / n_old and S_new / n_new."""
-    d = np.abs(b - a)
-    num = (d[..., 0] + d[..., 1]) + d[..., 2]
-    den = np.sqrt(((np.float32(1e-4) + np.abs(b[..., 0])) + np.abs(b[..., 1])) + np.abs(b[..., 2]))
-    e = (num / den).astype(np.float32)
-    ty, tx = (h + 7) // 8, (w + 7) // 8
-    pad = np.zeros((ty * 8, tx * 8), dtype=np.float32)
-    pad[:h, :w] = e
-    return pad.reshape(ty, 8, tx, 8).max(axis=(1, 3))
-
-
 def uniform(dev, cam, counts, flags=0, w=W, h=H):
     return {int(c): dev.render(cam, w, h, int(c), seed=SEED, flags=flags)[0] for c in np.unique(np.asarray(counts))}
 
 
 def errors_at(dev, cam, min_spp, max_spp, w=W, h=H):
     """tile_err of every judged count n (the error computed in the round that brought the tile to n)."""
-    seq = sequence(min_spp, max_spp)
-    ref = uniform(dev, cam, seq, 0, w, h)
-    return {n: tile_err(ref[p], ref[n], w, h) for p, n in zip(seq, seq[1:])}
-
-
-def expected_counts(err, min_spp, max_spp, thr):
-    seq = sequence(min_spp, max_spp)[1:]
-    counts = np.full(err[seq[0]].shape, seq[0], dtype=np.uint32)
-    for cur, nxt in zip(seq, seq[1:]):
-        go = (counts == cur) & (err[cur] >= np.float32(thr))
-        counts[go] = nxt
-    return counts
+    return errors_from(uniform(dev, cam, sequence(min_spp, max_spp), 0, w, h), min_spp, max_spp)
 
 
 def assert_tiles_match(frame, counts, refs, w=W, h=H):
-    """Every tile equals the same tile of the uniform render at its count."""
-    per_pixel = np.repeat(np.repeat(counts, 8, axis=0), 8, axis=1)[:h, :w]
-    for c in np.unique(counts):
-        m = per_pixel == c
-        assert np.array_equal(frame[m], refs[int(c)][m]), f"tiles at {c} spp differ from hrt_render({c})"
+    """Every tile has the bits of the same tile of the uniform render at its count."""
+    assert frame.shape == (h, w, 3)
+    bad = tiles_differing(frame, counts, refs)
+    assert not bad, f"{len(bad)} tiles differ from hrt_render at their count, first (tile y, tile x, count): {bad[:5]}"
 
 
 @pytest.mark.parametrize("name", ["cornell_mesh", "random_spheres", "cornell_box", "backrooms_pool"])
@@ -80,8 +49,7 @@ def test_every_tile_is_the_uniform_render_at_its_count(gpu, name):
         assert counts.shape == ((H + 7) // 8, (W + 7) // 8)
         assert counts.min() == mn and counts.max() > mn, f"threshold {thr} gave no spread of counts {np.unique(counts)}"
         assert_tiles_match(frame, counts, uniform(dev, cam, counts, gamma))
-        per_pixel = np.repeat(np.repeat(counts, 8, axis=0), 8, axis=1)[:H, :W]
-        assert st.samples == int(per_pixel.astype(np.uint64).sum())
+        assert st.samples == samples(counts, W, H)
         assert st.kernel_ms > 0
 
 

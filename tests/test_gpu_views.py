@@ -17,7 +17,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from scene_util import describe_difference, many_spheres, many_squares, overlapping_soup, placed_camera
+from scene_util import describe_difference, many_spheres, many_squares, open_box, overflow_scene, overlapping_soup, placed_camera
 from test_gpu_parity import aov, assert_pixels_agree
 
 pytestmark = pytest.mark.gpu
@@ -363,26 +363,9 @@ def test_camera_switch_on_a_multi_scene(gpu):
 
 
 # ------------------------------------------------------------------------------------------- colour range and pruning
-def _box(gpu, albedo, lamp, light=None, floor_albedo=None):
-    """An open-fronted box of five diffuse walls, an emissive lamp square under its ceiling, an optional point light."""
-    M = gpu.Material.make
-    s = gpu.HostScene()
-    s.set_sky(True)
-    if light is not None:
-        s.add_light((0.5, 1.2, 0.5), 0.4, light)
-    fl = albedo if floor_albedo is None else floor_albedo
-    s.add_quad((-2, -1.5, -4), (1, 0, 0), (0, 0, 1), 4, 6, M(albedo=fl))                     # floor
-    s.add_quad((-2, 1.8, 2), (1, 0, 0), (0, 0, -1), 4, 6, M(albedo=albedo))                  # ceiling
-    s.add_quad((-2, -1.5, -4), (1, 0, 0), (0, 1, 0), 4, 3.3, M(albedo=albedo))               # back
-    s.add_quad((-2, -1.5, 2), (0, 0, -1), (0, 1, 0), 6, 3.3, M(albedo=albedo))               # left
-    s.add_quad((2, -1.5, -4), (0, 0, 1), (0, 1, 0), 6, 3.3, M(albedo=albedo))                # right
-    s.add_quad((-1.5, 1.75, -3.0), (1, 0, 0), (0, 0, 1), 3.0, 3.0, lamp)                     # lamp, facing down
-    return s
-
-
 def _in_range_scene(gpu, lit):
     M = gpu.Material.make
-    s = _box(gpu, (3.5, 2.0, 4.0), M(albedo=(0, 0, 0), emissive=True, light_color=(20, 18, 12), light_intensity=500.0),
+    s = open_box(gpu, (3.5, 2.0, 4.0), M(albedo=(0, 0, 0), emissive=True, light_color=(20, 18, 12), light_intensity=500.0),
              light=(20.0, 15.0, 10.0) if lit else None)
     rng = np.random.default_rng(31)
     s.add_quad((-1.5, -1.4, -3), (1, 0, 0.2), (0, 1, 0.1), 1.2, 1.0,
@@ -407,18 +390,6 @@ def test_colours_above_one_keep_parity_and_exactness(gpu, oracle, lit):
     assert np.isfinite(frame).all() and frame.max() > 10.0
 
 
-def _overflow_scene(gpu, mechanism, lit):
-    M = gpu.Material.make
-    if mechanism == "emission":
-        # (a) a black floor below a lamp whose light_color x light_intensity overflows fp32: a path off the floor has throughput
-        # 0 and then meets an infinite emission -- 0 x inf = NaN unless the path ends where its throughput became 0
-        return _box(gpu, (0.7, 0.7, 0.7), M(albedo=(0, 0, 0), emissive=True, light_color=(1e30, 1e30, 1e30), light_intensity=1e10),
-                    light=(1.0, 1.0, 1.0) if lit else None, floor_albedo=(0, 0, 0))
-    # (b) albedos of 1e8: after five bounces the throughput is 1e40 = inf, and a last segment that ends on a non-emitting wall or
-    # in the dark sky adds inf x 0 = NaN unless it is pruned
-    return _box(gpu, (1e8, 1e8, 1e8), M(albedo=(0, 0, 0), emissive=True, light_color=(1, 1, 1), light_intensity=5.0))
-
-
 @pytest.mark.parametrize("mechanism,lit", [("emission", False), ("emission", True), ("throughput", False)],
                          ids=["emission_overflow-unlit", "emission_overflow-lit", "throughput_overflow-unlit"])
 def test_overflowing_colours_switch_the_pruning_off(gpu, monkeypatch, mechanism, lit):
@@ -426,7 +397,7 @@ def test_overflowing_colours_switch_the_pruning_off(gpu, monkeypatch, mechanism,
     0 x inf.  Where a colour product can overflow fp32 the pruned kernels must give the frame of the unpruned proof builds bit
     for bit, NaNs included, and the frame of a scene created with HRT_PRUNE=0.  No oracle comparison here: the recursion of the
     reference and the throughput form of the kernels overflow in different places, so NaN / inf land on different pixels."""
-    host = _overflow_scene(gpu, mechanism, lit)
+    host = overflow_scene(gpu, mechanism, lit)
     desc = host.flatten()
     dev = gpu.DeviceScene(desc)
     monkeypatch.setenv("HRT_PRUNE", "0")
