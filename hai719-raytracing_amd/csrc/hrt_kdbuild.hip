@@ -182,7 +182,10 @@ static int kd_build_gpu_impl(const hrt_kd_build_input *in, hrt_kd_build_output *
         for (int pass = 0; pass < 2; ++pass) {
             const float *src = pass ? in->hi : in->lo;
             for (uint32_t i = 0; i < n0; ++i)
-                for (int a = 0; a < 3; ++a) soa[(size_t)a * cap[0] + i] = src[3 * (size_t)i + a];
+                for (int a = 0; a < 3; ++a) {
+                    const float v = src[3 * (size_t)i + a];
+                    soa[(size_t)a * cap[0] + i] = v == 0.f ? 0.f : v;  // -0.0 is +0.0 (include/hrt.h hrt_kd_builder_fn)
+                }
             HIP_TRY(hipMemcpy(pass ? hi[0].p : lo[0].p, soa.data(), 3 * cap[0] * sizeof(float), hipMemcpyHostToDevice));
         }
     }

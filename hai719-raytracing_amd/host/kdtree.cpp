@@ -328,6 +328,12 @@ FlatKDTree build_flat_kdtree(const float *positions, uint32_t nv, const uint32_t
                 r.b.hi[a] = std::max(r.b.hi[a], p[a]);
             }
         }
+        // -0.0 becomes +0.0 (include/hrt.h hrt_kd_builder_fn): the two compare equal, so a split at zero would otherwise keep
+        // whichever sign the sort of the bounds put first -- an order no other builder reproduces.
+        for (int a = 0; a < 3; ++a) {
+            if (r.b.lo[a] == 0.f) r.b.lo[a] = 0.f;
+            if (r.b.hi[a] == 0.f) r.b.hi[a] = 0.f;
+        }
         for (int a = 0; a < 3; ++a) {
             root.lo[a] = std::min(root.lo[a], r.b.lo[a]);
             root.hi[a] = std::max(root.hi[a], r.b.hi[a]);

@@ -117,7 +117,10 @@ typedef struct hrt_kdunit {
  * SAH", replacing KDTree::buildTree, KDTree.cpp:87-151).  The host layer prepares the triangle references of a mesh
  * (id + bounds, the padded root cell, the heuristic's constants), hands them to a builder, and turns the builder's nodes
  * into the rope tree of hrt_kdunit above.  Two builders exist and give the SAME nodes: the host's own (threaded, the
- * default) and hrt_kd_build_gpu in libhrt.so (level by level on the device); hrt_host_scene_set_kd_builder selects. */
+ * default) and hrt_kd_build_gpu in libhrt.so (level by level on the device); hrt_host_scene_set_kd_builder selects.
+ * The host layer hands a builder no -0.0 in lo / hi (it becomes +0.0), and a builder treats a -0.0 it is given as +0.0: the
+ * two compare equal, so otherwise the sign of a split at zero would depend on the order of the references.  tests/kd_ref.py
+ * states the whole rule in numpy. */
 typedef struct hrt_kd_build_input {
     uint32_t n_refs;
     const uint32_t *ids;   /* triangle id of each reference                                                  */
