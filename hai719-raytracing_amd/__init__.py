@@ -96,6 +96,19 @@ class Adaptive(C.Structure):
     _fields_ = [("min_spp", C.c_uint32), ("max_spp", C.c_uint32), ("threshold", C.c_float)]
 
 
+FEATURE_FLOATS = 12  # HRT_FEATURE_FLOATS: albedo rgb, normal xyz, emission rgb, depth, coverage, 0
+
+
+class DenoiseParams(C.Structure):
+    """``hrt_denoise_params``: the a-trous filter's iteration count and edge-stopping widths (include/hrt.h).  The defaults were
+    chosen by tools/denoise_report.py's sweep ("Denoising")."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float),
+                ("sigma_depth", C.c_float)]
+
+    def __init__(self, iterations=4, sigma_color=8.0, sigma_normal=0.05, sigma_albedo=0.4, sigma_depth=0.05):
+        super().__init__(iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth)
+
+
 def _load(name: str) -> C.CDLL:
     path = os.path.join(_HERE, name)
     if not os.path.exists(path):
@@ -182,6 +195,14 @@ def device_lib() -> C.CDLL:
                                             C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         lib.hrt_render_adaptive_tiles.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.POINTER(Adaptive),
                                                   C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.hrt_render_features.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                            C.c_void_p, C.c_void_p]
+        lib.hrt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+        lib.hrt_denoise_scratch_bytes.restype = C.c_size_t
+        lib.hrt_denoise.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), C.c_uint32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]
+        lib.hrt_render_denoised.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                            C.c_uint32, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Stats)]
         lib.hrt_debug_kat.argtypes = [C.c_uint32, C.POINTER(Camera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         _dev = lib
     return _dev
@@ -386,6 +407,27 @@ class DeviceScene:
         self._check(self._lib.hrt_render_adaptive_tiles(self._h, C.byref(cam), w, h, C.byref(p), seed, flags, rank, world,
                                                         C.c_void_p(d_tiles_ptr), C.c_void_p(d_tile_spp_ptr), C.c_void_p(stream_ptr)))
 
+    def render_features(self, cam: Camera, w: int, h: int, first_sample: int, n_samples: int, seed: int = 1) -> np.ndarray:
+        """hrt_render_features: first-hit features of samples [first_sample, first_sample + n_samples) (n_samples 0: pixel centres)
+        -> (h, w, FEATURE_FLOATS) float32.  The device buffer is a torch tensor on the scene's device; the call waits for it."""
+        import torch
+        d = torch.empty((h, w, FEATURE_FLOATS), dtype=torch.float32, device="cuda")
+        s = torch.cuda.current_stream()
+        self._check(self._lib.hrt_render_features(self._h, C.byref(cam), w, h, first_sample, n_samples, seed, C.c_void_p(d.data_ptr()),
+                                                  C.c_void_p(s.cuda_stream)))
+        s.synchronize()
+        return d.cpu().numpy()
+
+    def render_denoised(self, cam: Camera, w: int, h: int, spp: int, feature_spp: int, seed: int = 1, flags: int = 0,
+                        params: Optional[DenoiseParams] = None, stats: Optional[Stats] = None) -> np.ndarray:
+        """hrt_render_denoised: render, features over samples [0, feature_spp), denoise -> (h, w, 3) float32.  ``params``: a
+        DenoiseParams (default values when None); ``stats``: a Stats to fill, if wanted."""
+        out = np.empty((h, w, 3), dtype=np.float32)
+        p = DenoiseParams() if params is None else params
+        self._check(self._lib.hrt_render_denoised(self._h, C.byref(cam), w, h, spp, feature_spp, seed, flags, C.byref(p), out.ctypes.data,
+                                                  None if stats is None else C.byref(stats)))
+        return out
+
     def check_last_launch(self):
         """hrt_check_last_launch: waits for the last launch; raises if the trace kernel gave up (incomplete tiles)."""
         self._check(self._lib.hrt_check_last_launch(self._h))
@@ -505,6 +547,23 @@ def finalize_tiles(d_sum_tiles_ptr: int, n_tiles: int, total_samples: int, flags
                                 C.c_void_p(stream_ptr))
     if rc < 0:
         raise HrtError(f"hrt_finalize_tiles failed ({rc}): {lib.hrt_last_error().decode()}")
+
+
+def denoise_scratch_bytes(w: int, h: int) -> int:
+    """hrt_denoise_scratch_bytes: size of the scratch buffer hrt_denoise needs for a w x h frame."""
+    return int(device_lib().hrt_denoise_scratch_bytes(w, h))
+
+
+def denoise(d_color_ptr: int, d_features_ptr: int, w: int, h: int, params: Optional[DenoiseParams], flags: int, d_scratch_ptr: int,
+            d_out_ptr: int, stream_ptr: int = 0):
+    """hrt_denoise on device pointers (asynchronous on the stream): linear colour (h, w, 3) and features (h, w, FEATURE_FLOATS)
+    -> d_out (h, w, 3).  ``params`` None: the default DenoiseParams; ``flags``: FLAG_GAMMA or 0."""
+    lib = device_lib()
+    p = DenoiseParams() if params is None else params
+    rc = lib.hrt_denoise(C.c_void_p(d_color_ptr), C.c_void_p(d_features_ptr), w, h, C.byref(p), flags, C.c_void_p(d_scratch_ptr),
+                         C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr))
+    if rc < 0:
+        raise HrtError(f"hrt_denoise failed ({rc}): {lib.hrt_last_error().decode()}")
 
 
 def encode_ppm(d_frame_ptr: int, w: int, h: int, fmt: int, d_out_ptr: int, capacity: int, stream_ptr: int = 0) -> int:

@@ -264,6 +264,16 @@ struct hrt_scene {
     size_t ad_compact_cap = 0;
     uint32_t *ad_words = nullptr;
     size_t ad_words_cap = 0;
+    // hrt_render_features' own camera block (with its host copy and the event that orders feature launches across streams), and the
+    // scratch of hrt_render_denoised (hrt_denoise.hip), grown on demand: the linear frame, the features, the filter's scratch, the result
+    DCamera *d_cam_feat = nullptr;
+    DCamera h_cam_feat{};
+    hipEvent_t ev_feat = nullptr;
+    bool feat_used = false;
+    hipStream_t feat_stream = nullptr;
+    float *dn_frame = nullptr, *dn_feat = nullptr, *dn_out = nullptr;
+    void *dn_scratch = nullptr;
+    size_t dn_frame_cap = 0, dn_feat_cap = 0, dn_out_cap = 0, dn_scratch_cap = 0;
 };
 
 #include "hrt_kdbuild.hip"
@@ -359,6 +369,9 @@ void hrt_scene_destroy(hrt_scene *s) {
     if (s->d_frame) (void)hipFree(s->d_frame);
     if (s->ad_compact) (void)hipFree(s->ad_compact);
     if (s->ad_words) (void)hipFree(s->ad_words);
+    if (s->d_cam_feat) (void)hipFree(s->d_cam_feat);
+    if (s->ev_feat) (void)hipEventDestroy(s->ev_feat);
+    for (void *p : {(void *)s->dn_frame, (void *)s->dn_feat, (void *)s->dn_out, s->dn_scratch}) if (p) (void)hipFree(p);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     delete s;
@@ -1451,6 +1464,7 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 
 #include "hrt_multi.hip"
 #include "hrt_adaptive.hip"
+#include "hrt_denoise.hip"
 
 int hrt_kd_build_gpu(const hrt_kd_build_input *in, hrt_kd_build_output *out, void *user) {
     (void)user;

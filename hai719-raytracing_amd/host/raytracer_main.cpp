@@ -9,6 +9,9 @@
 //             [--gpus N | --devices 0,1,2,...]   image tiles across several GPUs of this node (hrt_multi_*; an ordinal may repeat)
 //             [--adaptive THRESHOLD [--spp-min 8]] adaptive sampling (hrt_render_adaptive): per 8x8 tile from --spp-min up to --spp
 //                                                  samples per pixel, until the tile's noise estimate is below THRESHOLD (one GPU)
+//             [--denoise FEATURE_SPP [--denoise-iters N]] denoised frame (hrt_render_denoised): --spp samples, first-hit features of the
+//                                                  first FEATURE_SPP of them (0 = pixel centres), the a-trous filter with its default
+//                                                  parameters and N iterations (one GPU)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -30,6 +33,9 @@ static uint64_t seed = 1;
 static std::string out_path = "./rendu.ppm";
 static bool adaptive = false;  // --adaptive: hrt_render_adaptive from min_spp up to nsamples
 static hrt_adaptive adaptive_params = {8u, 0u, 0.f};
+static bool denoise = false;  // --denoise: hrt_render_denoised with the default parameters (the same as the Python DenoiseParams())
+static uint32_t feature_spp = 0;
+static hrt_denoise_params denoise_params = {4u, 8.0f, 0.05f, 0.4f, 0.05f};
 
 // Drop-in for ray_trace_from_camera(): same inputs (current scene, nsamples, window size, camera),
 // same output file and quantisation; returns non-zero instead of printing-and-returning on failure.
@@ -43,15 +49,17 @@ static int ray_trace_from_camera() {
         std::cout << "Ray tracing a " << w << " x " << h << " image on the GPU using " << adaptive_params.min_spp << " to " << nsamples
                   << " samples per pixel (adaptive, threshold " << adaptive_params.threshold << ")" << std::endl;
     else
-        std::cout << "Ray tracing a " << w << " x " << h << " image on the GPU using " << nsamples
-                  << " samples per pixel" << std::endl;
+        std::cout << "Ray tracing a " << w << " x " << h << " image on the GPU using " << nsamples << " samples per pixel"
+                  << (denoise ? ", denoised (features of " + std::to_string(feature_spp) + " samples, " + std::to_string(denoise_params.iterations) + " iterations)" : std::string())
+                  << std::endl;
     hrt_stats st;
     adaptive_params.max_spp = nsamples;
     int rc = multi ? hrt_multi_render(multi, &cam, w, h, nsamples, seed, HRT_FLAG_GAMMA, image.data(), &st)
              : adaptive ? hrt_render_adaptive(device_scene, &cam, w, h, &adaptive_params, seed, HRT_FLAG_GAMMA, image.data(), nullptr, &st)
+             : denoise  ? hrt_render_denoised(device_scene, &cam, w, h, nsamples, feature_spp, seed, HRT_FLAG_GAMMA, &denoise_params, image.data(), &st)
                         : hrt_render(device_scene, &cam, w, h, nsamples, seed, HRT_FLAG_GAMMA, image.data(), &st);
     if (rc != HRT_OK) {
-        std::cout << (adaptive ? "hrt_render_adaptive" : "hrt_render") << " failed: " << hrt_last_error() << std::endl;
+        std::cout << (adaptive ? "hrt_render_adaptive" : denoise ? "hrt_render_denoised" : "hrt_render") << " failed: " << hrt_last_error() << std::endl;
         return rc;
     }
     std::cout << "  Done in " << st.total_ms / 1000.0 << " seconds (kernel " << st.kernel_ms << " ms, "
@@ -81,6 +89,8 @@ int main(int argc, char **argv) {
         else if (k == "--kd") kd_on_gpu = v == "gpu";
         else if (k == "--adaptive") { adaptive = true; adaptive_params.threshold = strtof(v.c_str(), nullptr); }
         else if (k == "--spp-min") adaptive_params.min_spp = (unsigned)atoi(v.c_str());
+        else if (k == "--denoise") { denoise = true; feature_spp = (uint32_t)strtoul(v.c_str(), nullptr, 10); }
+        else if (k == "--denoise-iters") denoise_params.iterations = (uint32_t)strtoul(v.c_str(), nullptr, 10);
         else if (k == "--gpus") { devices.clear(); for (int d = 0; d < atoi(v.c_str()); ++d) devices.push_back(d); }
         else if (k == "--devices") {
             devices.clear();
@@ -90,6 +100,14 @@ int main(int argc, char **argv) {
     }
     if (adaptive && !devices.empty()) {
         std::cerr << "--adaptive renders on one GPU: it cannot be combined with --gpus / --devices" << std::endl;
+        return 2;
+    }
+    if (denoise && adaptive) {
+        std::cerr << "--denoise filters a uniform render: it cannot be combined with --adaptive" << std::endl;
+        return 2;
+    }
+    if (denoise && !devices.empty()) {
+        std::cerr << "--denoise renders on one GPU: it cannot be combined with --gpus / --devices" << std::endl;
         return 2;
     }
     scene.asset_root = assets;

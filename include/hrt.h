@@ -407,6 +407,53 @@ HRT_API int hrt_render_adaptive_tiles(hrt_scene *scene, const hrt_camera *cam, u
 HRT_API int hrt_render_adaptive(hrt_scene *scene, const hrt_camera *cam, uint32_t w, uint32_t h, const hrt_adaptive *params,
                                 uint64_t seed, uint32_t flags, float *out_rgb, uint32_t *out_tile_spp, hrt_stats *stats);
 
+/* ---- denoising: first-hit feature buffers and an edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010)
+ * FEATURES, per pixel (x, y) (pixel index y*w + x) and per sample s in [first_sample, first_sample + n_samples): the camera ray of
+ * that sample exactly as the trace kernels draw it (the RNG stream (seed, pixel, s): u, v, time, then the camera), its closest hit
+ * and the shading of that hit -- the device functions hrt_render_aov uses.  So pixel, sample and seed give the ray and first hit of
+ * that sample in hrt_render.  n_samples == 0: one ray through the pixel centre at time 0 (hrt_render_aov's rays: albedo, normal,
+ * emission and depth are then its outputs bit for bit).  HRT_FEATURE_FLOATS floats per pixel, row-major:
+ *     albedo rgb, shading normal xyz, emission rgb, depth (the hit's t), coverage (fraction of samples that hit), 0
+ * each = (sum over the samples in sample order, in fp32, starting from +0) / (float)n (n = 1 for n_samples == 0); a miss adds 0. */
+#define HRT_FEATURE_FLOATS 12
+/* d_features: device, h*w*HRT_FEATURE_FLOATS floats.  Runs on `stream`, asynchronously, with a camera block of its own (a trace
+ * launch on another stream cannot see it); feature launches of one scene on different streams are ordered. */
+HRT_API int hrt_render_features(hrt_scene *scene, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples, uint64_t seed, float *d_features, void *stream);
+/* THE FILTER.  Input: c = linear pixel means (h*w*3) and the features above (a = albedo, n = normal, e = emission, z = depth).
+ * All arithmetic is fp32 without fused multiply-add, in the order written; tests/denoise_ref.py states the same rule in numpy.
+ * 1. Demodulate: d_k = a_k if a_k > 0 else 1,  x_k = (c_k - e_k / 6) / d_k.  A first hit contributes (direct + E + a * incoming) / 6
+ *    to a sample and `direct` carries the albedo as a factor for every material type (diffuse, glass, mirror: shade() sets one
+ *    albedo, direct_light multiplies each light term by it, the throughput is multiplied by it), so x is exact for a pixel covered
+ *    by one surface.  Misses (a = 0, e = 0) and albedo-0 emitters are filtered in colour space (d = 1).
+ *    A pixel is INVALID when a component of x or of its albedo, normal, emission or depth is not finite; its x becomes NaN.
+ * 2. Iterate, i = 0 .. iterations-1, step s = 2^i:  y_p = (sum_q w_pq x_q) / (sum_q w_pq)  over the 5x5 taps q = p + s*(j, k),
+ *    rows k = -2..2 outer, columns j = -2..2 inner; taps outside the image and taps whose x is not finite are skipped.  An invalid
+ *    pixel keeps y_p = x_p (NaN).  The centre tap has w = h_0 h_0; any other tap
+ *        w_pq = (h_j h_k) * expf(-E),  E = ((T(|x_p - x_q|^2, (sc_i)^2) + T(|n_p - n_q|^2, sn^2)) + T(|a_p - a_q|^2, sa^2)) + T((z_p - z_q)^2, (sz * max(max(z_p, z_q), 1e-3))^2)
+ *    with h = (1, 4, 6, 4, 1) / 16, sc_i = sigma_color * 2^-i (the colour term tightens every iteration), |v|^2 = (v0 v0 + v1 v1) + v2 v2,
+ *    and T(num, den) = 0 if num == 0 or den == +inf, else num / den (so sigma = +inf switches a term off).  The sums run in tap order:
+ *    sum_w += w, sum_x += w * x_q per channel.
+ * 3. Remodulate: r_k = d_k * y_k + e_k / 6.  A pixel with a non-finite component of r is written as its input c instead (invalid
+ *    pixels therefore pass through unchanged).  With HRT_FLAG_GAMMA every value v then becomes (float)pow((double)v, 1/2.2), the
+ *    arithmetic of hrt_finalize_tiles.  A finite input never gives a non-finite linear output.
+ * Parameters: iterations 1..8, every sigma > 0 and not NaN (+inf allowed), w and h positive, flags HRT_FLAG_GAMMA or 0, no NULL
+ * pointer.  They are checked before any device call: a bad one returns HRT_ERR_INVALID and hrt_last_error() names it. */
+typedef struct hrt_denoise_params {
+    uint32_t iterations;                                          /* 1..8; step of iteration i = 2^i pixels */
+    float sigma_color, sigma_normal, sigma_albedo, sigma_depth;   /* > 0; +inf switches a term off       */
+} hrt_denoise_params;
+/* Bytes of d_scratch hrt_denoise needs for a w x h frame (the packed guides and two ping-pong colour buffers, 64 per pixel). */
+HRT_API size_t hrt_denoise_scratch_bytes(uint32_t w, uint32_t h);
+/* Device pointers, asynchronous on `stream`.  d_color: h*w*3 linear means; d_features: as hrt_render_features writes them;
+ * d_out: h*w*3 (must not alias the inputs or the scratch). */
+HRT_API int hrt_denoise(const float *d_color, const float *d_features, uint32_t w, uint32_t h, const hrt_denoise_params *p, uint32_t flags, void *d_scratch, float *d_out, void *stream);
+/* The whole frame on the scene's device into a HOST buffer out_rgb[h*w*3]: hrt_render's frame at spp samples, linear (by the kernel
+ * form hrt_render picks; the kernel-form flags apply), checked with hrt_check_last_launch, the features of samples [0, feature_spp)
+ * (feature_spp <= spp; 0 = pixel centres), then hrt_denoise with HRT_FLAG_GAMMA as given in flags.  The frame never leaves the
+ * device; the scratch lives in the hrt_scene, grown on demand.  The result is bit-identical to hrt_denoise(hrt_render(...) without
+ * gamma, hrt_render_features(0, feature_spp)).  stats (may be NULL): kernel_ms = the trace kernel's time, as hrt_render. */
+HRT_API int hrt_render_denoised(hrt_scene *scene, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp, uint64_t seed, uint32_t flags, const hrt_denoise_params *p, float *out_rgb, hrt_stats *stats);
+
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
  * format 6: the same integers as bytes (binary PPM; negative values, which P3 prints with a sign, clamp to 0).
