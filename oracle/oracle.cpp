@@ -1079,6 +1079,54 @@ uint32_t oracle_trace_path(const oracle_scene *o, const hrt_camera *cam, uint32_
     return g_trace_n;
 }
 
+// First-hit features of include/hrt.h (hrt_render_features) for a list of pixel indices (y*w + x): per sample s in
+// [first_sample, first_sample + n_samples) the camera sample of render_pixel (PathRng(seed, pixel, s): u, v, time), its closest
+// hit and shade_hit; ordered fp32 sums from +0 divided by (float)n.  n_samples == 0: the pixel centre at time 0 (oracle_aov's ray),
+// n = 1.  out: n_pixels x HRT_FEATURE_FLOATS = albedo, normal, emission, depth, coverage, 0.
+int oracle_features(const oracle_scene *o, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples,
+                    uint64_t seed, const uint32_t *pixels, uint32_t n_pixels, float *out) {
+    if (!o || !cam || !pixels || !out || !w || !h) return -1;
+    const OScene &S = o->S;
+    const CameraMats cm = camera_matrices(*cam);
+    const uint32_t count = n_samples ? n_samples : 1u;
+    for (uint32_t i = 0; i < n_pixels; ++i) {
+        const uint32_t pixel = pixels[i];
+        if ((uint64_t)pixel >= (uint64_t)w * h) return -1;
+        const uint32_t x = pixel % w, y = pixel / w;
+        V3 alb = v3(0.f, 0.f, 0.f), nrm = v3(0.f, 0.f, 0.f), emi = v3(0.f, 0.f, 0.f);
+        float depth = 0.f, hits = 0.f;
+        for (uint32_t k = 0; k < count; ++k) {
+            V3 pos, dir;
+            float time = 0.f;
+            if (n_samples == 0) {
+                camera_ray(cm, ((float)x + 0.5f) / w, ((float)y + 0.5f) / h, pos, dir);
+            } else {
+                PathRng rng(seed, pixel, first_sample + k, nullptr);
+                float u = ((float)x + rng.next()) / w;
+                float v = ((float)y + rng.next()) / h;
+                camera_ray(cm, u, v, pos, dir);
+                time = rng.next();
+            }
+            SceneHit sh = compute_intersection(S, make_ray(pos, dir, time), nullptr);
+            if (sh.kind) {
+                Shading s = shade_hit(S, sh, nullptr);
+                alb = alb + s.albedo;
+                nrm = nrm + s.normal;
+                emi = emi + s.emission;
+                depth = depth + sh.t;
+                hits = hits + 1.f;
+            }
+        }
+        const float c = (float)count;
+        float *f = out + (size_t)HRT_FEATURE_FLOATS * i;
+        f[0] = alb.x / c; f[1] = alb.y / c; f[2] = alb.z / c;
+        f[3] = nrm.x / c; f[4] = nrm.y / c; f[5] = nrm.z / c;
+        f[6] = emi.x / c; f[7] = emi.y / c; f[8] = emi.z / c;
+        f[9] = depth / c; f[10] = hits / c; f[11] = 0.f;
+    }
+    return 0;
+}
+
 // out: 64 doubles = modelview, projection (what the reference's GL read-back would hold), their inverses
 void oracle_camera_matrices(const hrt_camera *cam, double *out) {
     camera_forward_matrices(*cam, out, out + 16);

@@ -60,6 +60,7 @@ def lib() -> C.CDLL:
         L.oracle_kat_normalize.restype = None
         L.oracle_trace_path.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 5 + [C.c_uint64, C.c_void_p, C.c_uint32]
         L.oracle_trace_path.restype = C.c_uint32
+        L.oracle_features.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
         _lib = L
     return _lib
 
@@ -128,6 +129,17 @@ class OracleScene:
         rc = self._L.oracle_aov(self._h, C.byref(cam), w, h, *[b.ctypes.data for b in bufs])
         assert rc == 0
         return dict(zip(["hit", "normal", "albedo", "emission"], bufs))
+
+    def features(self, cam, w, h, first_sample, n_samples, seed, pixels=None):
+        """First-hit features (include/hrt.h hrt_render_features) of the pixel indices `pixels` (y*w + x; None: every pixel)
+        -> (len(pixels), 12) float32, or (h, w, 12) for the whole frame."""
+        whole = pixels is None
+        px = np.arange(w * h, dtype=np.uint32) if whole else np.ascontiguousarray(pixels, dtype=np.uint32).ravel()
+        out = np.empty((px.size, 12), dtype=np.float32)
+        rc = self._L.oracle_features(self._h, C.byref(cam), w, h, first_sample, n_samples, seed, px.ctypes.data, px.size,
+                                     out.ctypes.data)
+        assert rc == 0
+        return out.reshape(h, w, 12) if whole else out
 
     def ref_tree_stats(self, mesh=0):
         out = (C.c_uint32 * 4)()
