@@ -99,6 +99,24 @@ class Adaptive(C.Structure):
 FEATURE_FLOATS = 12  # HRT_FEATURE_FLOATS: albedo rgb, normal xyz, emission rgb, depth, coverage, 0
 
 
+# Ray queries (include/hrt.h hrt_trace_rays).  A ray is RAY_FLOATS float32: origin, time, direction, tmax.
+RAY_FLOATS = 8
+RAY_O, RAY_TIME, RAY_D, RAY_TMAX = slice(0, 3), 3, slice(4, 7), 7
+QUERY_CLOSEST, QUERY_SHADE, QUERY_OCCLUDED = 0, 1, 2
+RAYS_NORMALIZE = 256  # HRT_RAYS_NORMALIZE: the Ray constructor's normalisation of d first
+_QUERY_MODES = {"closest": QUERY_CLOSEST, "shade": QUERY_SHADE, "occluded": QUERY_OCCLUDED}
+# Columns of a CLOSEST / SHADE record.  Records come back as float32; the integer columns (kind, index, prim, material type) hold
+# u32 bits: read them with .view(np.uint32) (numpy) or .view(torch.int32) (torch).
+HIT_T, HIT_KIND, HIT_INDEX, HIT_PRIM = 0, 1, 2, 3
+CLOSEST_FLOATS = 4
+SHADE_NORMAL, SHADE_TRANSPARENCY = slice(4, 7), 7
+SHADE_ALBEDO, SHADE_INDEX_MEDIUM = slice(8, 11), 11
+SHADE_EMISSION, SHADE_MATERIAL_TYPE = slice(12, 15), 15
+SHADE_FLOATS = 16
+KIND_MISS, KIND_SPHERE, KIND_SQUARE, KIND_MESH = 0, 1, 2, 3
+NO_PRIM = 0xFFFFFFFF  # index and prim of a miss, prim of a sphere or square hit
+
+
 class DenoiseParams(C.Structure):
     """``hrt_denoise_params``: the a-trous filter's iteration count and edge-stopping widths (include/hrt.h).  The defaults were
     chosen by tools/denoise_report.py's sweep ("Denoising")."""
@@ -204,6 +222,7 @@ def device_lib() -> C.CDLL:
         lib.hrt_render_denoised.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                             C.c_uint32, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Stats)]
         lib.hrt_debug_kat.argtypes = [C.c_uint32, C.POINTER(Camera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.hrt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         _dev = lib
     return _dev
 
@@ -427,6 +446,45 @@ class DeviceScene:
         self._check(self._lib.hrt_render_denoised(self._h, C.byref(cam), w, h, spp, feature_spp, seed, flags, C.byref(p), out.ctypes.data,
                                                   None if stats is None else C.byref(stats)))
         return out
+
+    def trace_rays(self, rays, mode: str = "closest", flags: int = 0, normalize: bool = False):
+        """hrt_trace_rays: the scene traced with caller rays, (n, RAY_FLOATS) float32 rows {o, time, d, tmax}.
+
+        mode "closest" -> (n, CLOSEST_FLOATS) float32 records, "shade" -> (n, SHADE_FLOATS), "occluded" -> (n,) 0 / 1 (uint32 in
+        numpy, int32 in torch); the columns are HIT_* and SHADE_* above.  A contiguous float32 torch tensor on the GPU runs on the
+        current torch stream of its device and gives a torch tensor there, without synchronising.  Anything else is taken as a
+        NumPy array: copied to the device, traced, copied back as a NumPy array.  ``flags``: FLAG_EXACT_ONLY, FLAG_MESH_BRUTE,
+        FLAG_NO_LDS_TREE; ``normalize`` adds RAYS_NORMALIZE."""
+        import torch
+        if mode not in _QUERY_MODES:
+            raise ValueError(f"trace_rays: mode must be one of {sorted(_QUERY_MODES)} (got {mode!r})")
+        q = _QUERY_MODES[mode]
+        flags = int(flags) | (RAYS_NORMALIZE if normalize else 0)
+        is_torch = isinstance(rays, torch.Tensor)
+        if is_torch:
+            if (rays.device.type != "cuda" or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != RAY_FLOATS
+                    or not rays.is_contiguous()):
+                raise ValueError("trace_rays: a torch tensor must be a contiguous (n, 8) float32 tensor on the GPU")
+            d_rays = rays
+        else:
+            a = np.ascontiguousarray(rays, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != RAY_FLOATS:
+                raise ValueError(f"trace_rays: rays must have shape (n, {RAY_FLOATS}) (got {a.shape})")
+            d_rays = torch.from_numpy(a).to("cuda")
+        n, dev = d_rays.shape[0], d_rays.device
+        if n > 0x7FFFFFFF:
+            raise ValueError(f"trace_rays: at most 2^31 - 1 rays per call (got {n})")
+        if q == QUERY_OCCLUDED:
+            out = torch.empty((n,), dtype=torch.int32, device=dev)
+        else:
+            out = torch.empty((n, SHADE_FLOATS if q == QUERY_SHADE else CLOSEST_FLOATS), dtype=torch.float32, device=dev)
+        s = torch.cuda.current_stream(dev)
+        self._check(self._lib.hrt_trace_rays(self._h, C.c_void_p(d_rays.data_ptr()), n, q, flags, C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(s.cuda_stream)))
+        if is_torch:
+            return out
+        r = out.cpu().numpy()
+        return r.view(np.uint32) if q == QUERY_OCCLUDED else r
 
     def check_last_launch(self):
         """hrt_check_last_launch: waits for the last launch; raises if the trace kernel gave up (incomplete tiles)."""

@@ -172,9 +172,12 @@ template <> struct TabPtr<true> { typedef lf4 f4; typedef lmesh mesh; typedef lf
 // SPHF: the kernel carries the spheres' pair filter (sphere_filter; scenes with HRT_SPHERE_FILTER_MIN..128 spheres run such a
 // build).  It is a build of its own because its code in prims_hit and shadow_blocked costs the register allocator room that
 // the scenes without a crowd of spheres -- every wall-and-mesh scene -- then pay for in spills (measured: Cornell+mesh -17 %).
-template <bool EXACT, bool LTAB = false, bool SPHF = false>
+// FARB: HRT_FLAG_MESH_BRUTE is honoured in a build that is not EXACT too (the ray queries, hrt_rays.hip, set it per ray for origins
+// far outside the scene, where the walk's entry point o + t d is off the line by more than a cell can absorb).
+template <bool EXACT, bool LTAB = false, bool SPHF = false, bool FARB = false>
 struct CtxT {
     static constexpr bool exact = EXACT;
+    static constexpr bool far_brute = FARB;
     static constexpr bool sphf = SPHF && !EXACT;
     typedef typename TabPtr<LTAB>::f4 tab4;
     typedef typename TabPtr<LTAB>::mesh tabmesh;
@@ -491,7 +494,7 @@ __device__ __forceinline__ bool mesh_brute(const CX &cx, cmesh M, const Ray &ray
 template <class CX>
 __device__ __forceinline__ bool mesh_traverse(const CX &cx, cmesh M, const Ray &ray, f3 inv, float &best_t,
                                               uint32_t &best_tri, float &bu, float &bv) {
-    if (CX::exact && (cx.flags & HRT_FLAG_MESH_BRUTE)) return mesh_brute(cx, M, ray, best_t, best_tri, bu, bv);
+    if ((CX::exact || CX::far_brute) && (cx.flags & HRT_FLAG_MESH_BRUTE)) return mesh_brute(cx, M, ray, best_t, best_tri, bu, bv);
     float t_entry = 0.f, t_scene_exit = HRT_FLT_MAX;
     {
         float t0 = (M->kd_lo[0] - ray.o.x) * inv.x, t1 = (M->kd_hi[0] - ray.o.x) * inv.x;

@@ -454,6 +454,37 @@ HRT_API int hrt_denoise(const float *d_color, const float *d_features, uint32_t 
  * gamma, hrt_render_features(0, feature_spp)).  stats (may be NULL): kernel_ms = the trace kernel's time, as hrt_render. */
 HRT_API int hrt_render_denoised(hrt_scene *scene, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp, uint64_t seed, uint32_t flags, const hrt_denoise_params *p, float *out_rgb, hrt_stats *stats);
 
+/* ---- ray queries: the scene traced with the caller's own rays (picking, visibility, baking, hit buffers for other code)
+ * RAYS: n records of 8 floats (32 bytes, the array 16-byte aligned) {o.x, o.y, o.z, time, d.x, d.y, d.z, tmax}, device memory.
+ * CLOSEST: Scene::computeIntersection (Scene.h:202-230) on the ray exactly as given -- no normalisation unless HRT_RAYS_NORMALIZE,
+ * `time` places the moving objects (motion blur) -- and the hit is reported only if t < tmax (tmax = +inf: the reference's
+ * unbounded query).  Output, 4 x 32 bits per ray: {t (float), kind (u32: 0 miss, 1 sphere, 2 square, 3 mesh), index (u32: the
+ * object), prim (u32: the reference triangle id of a mesh hit, the id hrt_render_aov reports; 0xFFFFFFFF otherwise)}.  A miss is
+ * {0, 0, 0xFFFFFFFF, 0xFFFFFFFF}.
+ * SHADE: 16 x 32 bits per ray: the CLOSEST record, {n.xyz, transparency}, {albedo.rgb, index_medium}, {emission.rgb, material type
+ * (u32)} -- the values shade() gives, hence those of hrt_render_aov and hrt_render_features for the same ray.  On a miss every field
+ * after the CLOSEST record is 0.
+ * OCCLUDED: one u32 per ray, 1 if some object's own hit (the value CLOSEST compares for it) has EPSILON <= t < tmax, else 0:
+ * Scene::computeShadow (Scene.h:235-255) with every transparency taken as 0, so deterministic, no random numbers.  It equals
+ * (CLOSEST.kind != 0).  An object ends the query only as a whole: a mesh whose nearest triangle has 0 <= t < EPSILON hides its
+ * farther triangles from that ray, as in the closest hit.
+ * DEGENERATE rays -- a component of o, d or time not finite, d == 0, tmax NaN or <= 0, or with HRT_RAYS_NORMALIZE a normalised d
+ * that is not finite or is 0 -- are not traced: the miss record, 0 for OCCLUDED.
+ * Flags: HRT_FLAG_EXACT_ONLY (proof build), HRT_FLAG_MESH_BRUTE (with EXACT_ONLY), HRT_FLAG_NO_LDS_TREE (accepted; queries read the
+ * tree from global memory anyway, DESIGN.md section 5 "Ray queries"), HRT_RAYS_NORMALIZE (apply
+ * the Ray constructor's normalisation, Line.h:13-16, to d first: then the records equal those of the normalised rays).  All give
+ * the same records.  Any other bit is refused.
+ * Checked before the scene and the library state, HRT_ERR_INVALID with hrt_last_error() naming the culprit: mode, flags, NULL or
+ * misaligned pointers when n > 0 (d_rays 16 bytes; d_out 16 bytes, 4 for OCCLUDED), n > 2^31 - 1; then a NULL scene.  n == 0
+ * returns HRT_OK and launches nothing.
+ * CONCURRENCY: asynchronous on `stream` (a hipStream_t, NULL = the default stream).  The call touches none of the per-launch
+ * state of the scene (work-queue head, path pool, camera blocks): a query may run on another stream at the same time as a render
+ * of the same scene, and queries of one scene on several streams may overlap. */
+enum { HRT_QUERY_CLOSEST = 0, HRT_QUERY_SHADE = 1, HRT_QUERY_OCCLUDED = 2 };
+#define HRT_RAYS_NORMALIZE 256u
+#define HRT_RAY_FLOATS 8
+HRT_API int hrt_trace_rays(hrt_scene *scene, const float *d_rays, uint32_t n, uint32_t mode, uint32_t flags, void *d_out, void *stream);
+
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
  * format 6: the same integers as bytes (binary PPM; negative values, which P3 prints with a sign, clamp to 0).
