@@ -115,6 +115,7 @@ SHADE_EMISSION, SHADE_MATERIAL_TYPE = slice(12, 15), 15
 SHADE_FLOATS = 16
 KIND_MISS, KIND_SPHERE, KIND_SQUARE, KIND_MESH = 0, 1, 2, 3
 NO_PRIM = 0xFFFFFFFF  # index and prim of a miss, prim of a sphere or square hit
+RADIANCE_ACCUMULATE = 512  # HRT_RADIANCE_ACCUMULATE: add to the running sums in the output instead of storing means
 
 
 class DenoiseParams(C.Structure):
@@ -223,6 +224,9 @@ def device_lib() -> C.CDLL:
                                             C.c_uint32, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Stats)]
         lib.hrt_debug_kat.argtypes = [C.c_uint32, C.POINTER(Camera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.hrt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.hrt_trace_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                           C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.hrt_camera_rays.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
         _dev = lib
     return _dev
 
@@ -486,6 +490,72 @@ class DeviceScene:
         r = out.cpu().numpy()
         return r.view(np.uint32) if q == QUERY_OCCLUDED else r
 
+    def trace_radiance(self, rays, spp: int = 1, first_sample: int = 0, seed: int = 1, keys=None, out=None, accumulate: bool = False,
+                       flags: int = 0, normalize: bool = False):
+        """hrt_trace_radiance: the path-traced colour of caller rays, (n, RAY_FLOATS) float32 rows {o, time, d, tmax} (tmax unused),
+        samples [first_sample, first_sample + spp) of RNG stream (seed, key, sample); key i unless ``keys`` (n uint32 / int32) is given.
+
+        Returns (n, 3) float32: the mean of the samples, or with ``accumulate`` the running sums (``out`` then holds the sums of the
+        earlier samples and is updated in place).  A contiguous float32 torch tensor on the GPU runs on the current torch stream of its
+        device and gives a torch tensor there, without synchronising; anything else is taken as NumPy and comes back as NumPy.
+        ``flags``: FLAG_EXACT_ONLY, FLAG_MESH_BRUTE, FLAG_NO_LDS_TREE; ``normalize`` adds RAYS_NORMALIZE."""
+        import torch
+        flags = int(flags) | (RAYS_NORMALIZE if normalize else 0) | (RADIANCE_ACCUMULATE if accumulate else 0)
+        is_torch = isinstance(rays, torch.Tensor)
+        if is_torch:
+            if (rays.device.type != "cuda" or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != RAY_FLOATS
+                    or not rays.is_contiguous()):
+                raise ValueError("trace_radiance: a torch tensor must be a contiguous (n, 8) float32 tensor on the GPU")
+            d_rays = rays
+        else:
+            a = np.ascontiguousarray(rays, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != RAY_FLOATS:
+                raise ValueError(f"trace_radiance: rays must have shape (n, {RAY_FLOATS}) (got {a.shape})")
+        n = rays.shape[0] if is_torch else a.shape[0]
+        if n > 0x7FFFFFFF:
+            raise ValueError(f"trace_radiance: at most 2^31 - 1 rays per call (got {n})")
+        if keys is not None and not is_torch:
+            k = np.ascontiguousarray(keys)
+            if k.shape != (n,) or k.dtype not in (np.uint32, np.int32):
+                raise ValueError(f"trace_radiance: keys must be (n,) uint32 (got {k.shape} {k.dtype})")
+        if not is_torch:
+            d_rays = torch.from_numpy(a).to("cuda")
+        dev = d_rays.device
+        d_keys = None
+        if keys is not None:
+            if is_torch:
+                if (not isinstance(keys, torch.Tensor) or keys.device != dev or keys.dtype not in (torch.int32, torch.uint32)
+                        or keys.shape != (n,) or not keys.is_contiguous()):
+                    raise ValueError("trace_radiance: keys must be a contiguous (n,) int32 tensor on the rays' device")
+                d_keys = keys
+            else:
+                d_keys = torch.from_numpy(k.view(np.int32)).to(dev)
+        if out is None:
+            if accumulate and first_sample != 0:
+                raise ValueError("trace_radiance: accumulate after sample 0 needs the running sums in `out`")
+            d_out = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+        elif is_torch:
+            if (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float32 or out.shape != (n, 3)
+                    or not out.is_contiguous()):
+                raise ValueError("trace_radiance: out must be a contiguous (n, 3) float32 tensor on the rays' device")
+            d_out = out
+        else:
+            o = np.asarray(out)
+            if o.shape != (n, 3) or o.dtype != np.float32:
+                raise ValueError(f"trace_radiance: out must be (n, 3) float32 (got {o.shape} {o.dtype})")
+            d_out = torch.from_numpy(np.ascontiguousarray(o)).to(dev)
+        s = torch.cuda.current_stream(dev)
+        self._check(self._lib.hrt_trace_radiance(self._h, C.c_void_p(d_rays.data_ptr()),
+                                                 None if d_keys is None else C.c_void_p(d_keys.data_ptr()), n, first_sample, spp,
+                                                 seed, flags, C.c_void_p(d_out.data_ptr()), C.c_void_p(s.cuda_stream)))
+        if is_torch:
+            return d_out
+        r = d_out.cpu().numpy()
+        if out is not None:
+            out[...] = r
+            return out
+        return r
+
     def check_last_launch(self):
         """hrt_check_last_launch: waits for the last launch; raises if the trace kernel gave up (incomplete tiles)."""
         self._check(self._lib.hrt_check_last_launch(self._h))
@@ -563,6 +633,20 @@ def render_multi(desc, cam: Camera, w: int, h: int, spp: int, seed: int, flags: 
     if rc < 0:
         raise HrtError(f"hrt error {rc}: {lib.hrt_last_error().decode()}")
     return out, st
+
+
+def camera_rays(cam: Camera, w: int, h: int, sample: int = 0, seed: int = 1):
+    """hrt_camera_rays: the render's camera rays of sample ``sample`` of a w x h frame as a (w*h, RAY_FLOATS) float32 torch tensor
+    on the current device (pixel y*w + x), written on the current torch stream.  Traced with trace_radiance(first_sample=sample)
+    they give the render's samples."""
+    import torch
+    lib = device_lib()
+    out = torch.empty((w * h, RAY_FLOATS), dtype=torch.float32, device="cuda")
+    rc = lib.hrt_camera_rays(C.byref(cam), w, h, sample, seed, C.c_void_p(out.data_ptr()),
+                             C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc < 0:
+        raise HrtError(f"hrt_camera_rays failed ({rc}): {lib.hrt_last_error().decode()}")
+    return out
 
 
 def tiles_total(w: int, h: int) -> int:

@@ -1466,6 +1466,7 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 #include "hrt_adaptive.hip"
 #include "hrt_denoise.hip"
 #include "hrt_rays.hip"
+#include "hrt_radiance.hip"
 
 int hrt_kd_build_gpu(const hrt_kd_build_input *in, hrt_kd_build_output *out, void *user) {
     (void)user;

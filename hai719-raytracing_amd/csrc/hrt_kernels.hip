@@ -1271,8 +1271,10 @@ __device__ __forceinline__ float div_narrow(double r, double d, double inv_d) {
     const float lo = (float)(q * (1.0 - 8.881784197001252e-16)), hi = (float)(q * (1.0 + 8.881784197001252e-16));  // 1 -+ 2^-50
     return (lo == hi) ? lo : (float)(r / d);
 }
-template <bool EXACT = false>
-__device__ __forceinline__ Ray camera_ray(ccam C, float u, float v, float time) {
+// CP: where the camera block is read from -- ccam (scalar loads of the scene's block in device memory) for the trace kernels, a
+// kernel argument for hrt_camera_rays_kernel (hrt_radiance.hip).
+template <bool EXACT = false, class CP = ccam>
+__device__ __forceinline__ Ray camera_ray(CP C, float u, float v, float time) {
     const double ri0 = C->pi0 * (2.0 * (double)u - 1.0);
     const double ri1 = C->pi5 * -(2.0 * (double)v - 1.0);
     const double d = C->pi15, inv_d = C->inv15;

@@ -485,6 +485,40 @@ enum { HRT_QUERY_CLOSEST = 0, HRT_QUERY_SHADE = 1, HRT_QUERY_OCCLUDED = 2 };
 #define HRT_RAY_FLOATS 8
 HRT_API int hrt_trace_rays(hrt_scene *scene, const float *d_rays, uint32_t n, uint32_t mode, uint32_t flags, void *d_out, void *stream);
 
+/* ---- radiance queries: the path-traced colour of the caller's own rays (baking, light probes, panoramas, other camera models)
+ * RAYS: the records of hrt_trace_rays ({o, time, d, tmax}, device memory, 16-byte aligned); tmax is not read.  Ray i has the key
+ * k = d_keys ? d_keys[i] : i.  For each sample s in [first_sample, first_sample + n_samples), in that order, one path runs: RNG
+ * stream (seed, k, s) from draw 3 on (draws 0..2 are the camera's u, v, time), first segment the caller's ray as given (`time`,
+ * the same for every sample, places the moving objects), then exactly the render's integrator: HRT_MAXBOUNCES bounces, the sky
+ * (Scene::skyboxTexture with the bounces left), direct light with soft shadows, scatter, the exact pruning of the render, and
+ * sum += radiance / 6.
+ * OUTPUT: 3 floats per ray at d_out[3i .. 3i+2]: sum / (float)n_samples; with HRT_RADIANCE_ACCUMULATE d_out holds the running
+ * sums of samples [0, first_sample) on entry, the call adds its samples in order and stores the raw sums (as
+ * hrt_render_accumulate).
+ * DEGENERATE rays (the rule of hrt_trace_rays without tmax: a component of o, d or time not finite, d == 0, or with
+ * HRT_RAYS_NORMALIZE a normalised d that is not finite or is 0) add nothing: 0 in mean mode, their sums left as they are under
+ * HRT_RADIANCE_ACCUMULATE.
+ * CONTRACT: take the records hrt_camera_rays(cam, w, h, s, seed) writes and trace them with first_sample = s, n_samples = 1,
+ * d_keys = NULL for s = 0..S-1; the outputs summed in sample order in fp32 and divided by (float)S are hrt_render(cam, w, h, S,
+ * seed) without HRT_FLAG_GAMMA, bit for bit, for every scene and every kernel form.
+ * Flags: HRT_FLAG_EXACT_ONLY (proof build), HRT_FLAG_MESH_BRUTE (with EXACT_ONLY), HRT_FLAG_NO_LDS_TREE (accepted; radiance queries
+ * read the tree from global memory anyway, DESIGN.md section 5 "Radiance queries"), HRT_RAYS_NORMALIZE, HRT_RADIANCE_ACCUMULATE.  The
+ * first three give the same values.  Any other bit is refused.
+ * Checked before the scene and the library state, HRT_ERR_INVALID with hrt_last_error() naming the culprit: flags, NULL or
+ * misaligned pointers when n > 0 (d_rays 16 bytes; d_keys, if given, and d_out 4 bytes), n > 2^31 - 1, n_samples == 0,
+ * first_sample + n_samples > 2^32 (sample indices do not wrap); then a NULL scene.  n == 0 returns HRT_OK and launches nothing.
+ * CONCURRENCY: as hrt_trace_rays -- asynchronous on `stream`, no per-launch state of the scene is touched, so radiance queries may
+ * overlap a render of the same scene on another stream. */
+#define HRT_RADIANCE_ACCUMULATE 512u
+HRT_API int hrt_trace_radiance(hrt_scene *scene, const float *d_rays, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
+                               uint32_t n_samples, uint64_t seed, uint32_t flags, float *d_out, void *stream);
+/* The camera rays of sample `sample` of a w x h frame as ray records (device, 16-byte aligned, w*h records, pixel y*w + x):
+ * u = (x + draw0) / w, v = (y + draw1) / h, time = draw2 of stream (seed, y*w + x, sample); o and d are the render's camera ray
+ * (d normalised twice, as the reference); tmax = +inf.  No scene: it runs on the calling thread's current device, asynchronously
+ * on `stream`, and the camera block travels as a kernel argument.  Refused (HRT_ERR_INVALID): a NULL cam, a camera hrt_render
+ * refuses, w or h zero, w*h > 2^31 - 1, d_rays NULL or misaligned (checked in that order, before the library state). */
+HRT_API int hrt_camera_rays(const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t sample, uint64_t seed, float *d_rays, void *stream);
+
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
  * format 6: the same integers as bytes (binary PPM; negative values, which P3 prints with a sign, clamp to 0).
