@@ -128,6 +128,18 @@ class DenoiseParams(C.Structure):
         super().__init__(iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth)
 
 
+class DenoiseVarParams(C.Structure):
+    """``hrt_denoise_var_params``: the variance-guided filter's iteration and prefilter counts, the colour width in standard
+    deviations of the difference of a pair of pixels' own means, the guide widths and the variance floor (include/hrt.h).  The defaults were chosen by
+    tools/denoise_report.py --var ("Variance-guided denoising")."""
+    _fields_ = [("iterations", C.c_uint32), ("prefilter", C.c_uint32), ("sigma_variance", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float), ("variance_floor", C.c_float)]
+
+    def __init__(self, iterations=4, prefilter=2, sigma_variance=8.0, sigma_normal=0.05, sigma_albedo=0.4, sigma_depth=0.05,
+                 variance_floor=1e-8):
+        super().__init__(iterations, prefilter, sigma_variance, sigma_normal, sigma_albedo, sigma_depth, variance_floor)
+
+
 def _load(name: str) -> C.CDLL:
     path = os.path.join(_HERE, name)
     if not os.path.exists(path):
@@ -222,6 +234,12 @@ def device_lib() -> C.CDLL:
                                     C.c_void_p, C.c_void_p]
         lib.hrt_render_denoised.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                             C.c_uint32, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_denoise_var_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+        lib.hrt_denoise_var_scratch_bytes.restype = C.c_size_t
+        lib.hrt_denoise_var.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DenoiseVarParams), C.c_uint32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.hrt_render_denoised_var.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                                C.c_uint32, C.POINTER(DenoiseVarParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         lib.hrt_debug_kat.argtypes = [C.c_uint32, C.POINTER(Camera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.hrt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.hrt_trace_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
@@ -450,6 +468,19 @@ class DeviceScene:
         self._check(self._lib.hrt_render_denoised(self._h, C.byref(cam), w, h, spp, feature_spp, seed, flags, C.byref(p), out.ctypes.data,
                                                   None if stats is None else C.byref(stats)))
         return out
+
+    def render_denoised_var(self, cam: Camera, w: int, h: int, spp: int, feature_spp: int, seed: int = 1, flags: int = 0,
+                            params: Optional[DenoiseVarParams] = None, stats: Optional[Stats] = None, variance: bool = False):
+        """hrt_render_denoised_var: render ``spp`` samples (even) keeping the first half's means, features over samples
+        [0, feature_spp), the variance-guided filter -> (h, w, 3) float32; with ``variance`` the pair (frame, (h, w) float32 map of
+        the result's estimated variance, in demodulated units).  ``params``: a DenoiseVarParams (default values when None)."""
+        out = np.empty((h, w, 3), dtype=np.float32)
+        var = np.empty((h, w), dtype=np.float32) if variance else None
+        p = DenoiseVarParams() if params is None else params
+        self._check(self._lib.hrt_render_denoised_var(self._h, C.byref(cam), w, h, spp, feature_spp, seed, flags, C.byref(p),
+                                                      out.ctypes.data, None if var is None else var.ctypes.data,
+                                                      None if stats is None else C.byref(stats)))
+        return (out, var) if variance else out
 
     def trace_rays(self, rays, mode: str = "closest", flags: int = 0, normalize: bool = False):
         """hrt_trace_rays: the scene traced with caller rays, (n, RAY_FLOATS) float32 rows {o, time, d, tmax}.
@@ -706,6 +737,24 @@ def denoise(d_color_ptr: int, d_features_ptr: int, w: int, h: int, params: Optio
                          C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr))
     if rc < 0:
         raise HrtError(f"hrt_denoise failed ({rc}): {lib.hrt_last_error().decode()}")
+
+
+def denoise_var_scratch_bytes(w: int, h: int) -> int:
+    """hrt_denoise_var_scratch_bytes: size of the scratch buffer hrt_denoise_var needs for a w x h frame."""
+    return int(device_lib().hrt_denoise_var_scratch_bytes(w, h))
+
+
+def denoise_var(d_color_ptr: int, d_color_half_ptr: int, d_features_ptr: int, w: int, h: int, params: Optional[DenoiseVarParams],
+                flags: int, d_scratch_ptr: int, d_out_ptr: int, d_variance_out_ptr: int = 0, stream_ptr: int = 0):
+    """hrt_denoise_var on device pointers (asynchronous on the stream): linear means of all samples and of their first half
+    (h, w, 3) and features (h, w, FEATURE_FLOATS) -> d_out (h, w, 3) and, if its pointer is not 0, the variance map (h, w).
+    ``params`` None: the default DenoiseVarParams; ``flags``: FLAG_GAMMA or 0."""
+    lib = device_lib()
+    p = DenoiseVarParams() if params is None else params
+    rc = lib.hrt_denoise_var(C.c_void_p(d_color_ptr), C.c_void_p(d_color_half_ptr), C.c_void_p(d_features_ptr), w, h, C.byref(p), flags,
+                             C.c_void_p(d_scratch_ptr), C.c_void_p(d_out_ptr), C.c_void_p(d_variance_out_ptr), C.c_void_p(stream_ptr))
+    if rc < 0:
+        raise HrtError(f"hrt_denoise_var failed ({rc}): {lib.hrt_last_error().decode()}")
 
 
 def encode_ppm(d_frame_ptr: int, w: int, h: int, fmt: int, d_out_ptr: int, capacity: int, stream_ptr: int = 0) -> int:

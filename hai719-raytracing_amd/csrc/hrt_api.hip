@@ -274,6 +274,9 @@ struct hrt_scene {
     float *dn_frame = nullptr, *dn_feat = nullptr, *dn_out = nullptr;
     void *dn_scratch = nullptr;
     size_t dn_frame_cap = 0, dn_feat_cap = 0, dn_out_cap = 0, dn_scratch_cap = 0;
+    // more of hrt_render_denoised_var (hrt_denoise_var.hip): the first half's sums and frame, the variance map (capacities in bytes)
+    float *dnv_half_tiles = nullptr, *dnv_frame_half = nullptr, *dnv_var = nullptr;
+    size_t dnv_half_tiles_cap = 0, dnv_frame_half_cap = 0, dnv_var_cap = 0;
 };
 
 #include "hrt_kdbuild.hip"
@@ -371,7 +374,8 @@ void hrt_scene_destroy(hrt_scene *s) {
     if (s->ad_words) (void)hipFree(s->ad_words);
     if (s->d_cam_feat) (void)hipFree(s->d_cam_feat);
     if (s->ev_feat) (void)hipEventDestroy(s->ev_feat);
-    for (void *p : {(void *)s->dn_frame, (void *)s->dn_feat, (void *)s->dn_out, s->dn_scratch}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)s->dn_frame, (void *)s->dn_feat, (void *)s->dn_out, s->dn_scratch, (void *)s->dnv_half_tiles,
+                    (void *)s->dnv_frame_half, (void *)s->dnv_var}) if (p) (void)hipFree(p);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     delete s;
@@ -1465,6 +1469,7 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 #include "hrt_multi.hip"
 #include "hrt_adaptive.hip"
 #include "hrt_denoise.hip"
+#include "hrt_denoise_var.hip"
 #include "hrt_rays.hip"
 #include "hrt_radiance.hip"
 

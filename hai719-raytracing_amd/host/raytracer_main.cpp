@@ -12,6 +12,8 @@
 //             [--denoise FEATURE_SPP [--denoise-iters N]] denoised frame (hrt_render_denoised): --spp samples, first-hit features of the
 //                                                  first FEATURE_SPP of them (0 = pixel centres), the a-trous filter with its default
 //                                                  parameters and N iterations (one GPU)
+//             [--denoise-var FEATURE_SPP [--denoise-iters N]] variance-guided denoised frame (hrt_render_denoised_var): --spp samples
+//                                                  (even), the colour width of every pair of pixels set by the noise of their own means (one GPU)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -36,6 +38,8 @@ static hrt_adaptive adaptive_params = {8u, 0u, 0.f};
 static bool denoise = false;  // --denoise: hrt_render_denoised with the default parameters (the same as the Python DenoiseParams())
 static uint32_t feature_spp = 0;
 static hrt_denoise_params denoise_params = {4u, 8.0f, 0.05f, 0.4f, 0.05f};
+static bool denoise_var = false;  // --denoise-var: hrt_render_denoised_var with the default parameters (the Python DenoiseVarParams())
+static hrt_denoise_var_params denoise_var_params = {4u, 2u, 8.0f, 0.05f, 0.4f, 0.05f, 1e-8f};
 
 // Drop-in for ray_trace_from_camera(): same inputs (current scene, nsamples, window size, camera),
 // same output file and quantisation; returns non-zero instead of printing-and-returning on failure.
@@ -51,15 +55,17 @@ static int ray_trace_from_camera() {
     else
         std::cout << "Ray tracing a " << w << " x " << h << " image on the GPU using " << nsamples << " samples per pixel"
                   << (denoise ? ", denoised (features of " + std::to_string(feature_spp) + " samples, " + std::to_string(denoise_params.iterations) + " iterations)" : std::string())
+                  << (denoise_var ? ", denoised by variance (features of " + std::to_string(feature_spp) + " samples, " + std::to_string(denoise_var_params.iterations) + " iterations)" : std::string())
                   << std::endl;
     hrt_stats st;
     adaptive_params.max_spp = nsamples;
     int rc = multi ? hrt_multi_render(multi, &cam, w, h, nsamples, seed, HRT_FLAG_GAMMA, image.data(), &st)
              : adaptive ? hrt_render_adaptive(device_scene, &cam, w, h, &adaptive_params, seed, HRT_FLAG_GAMMA, image.data(), nullptr, &st)
+             : denoise_var ? hrt_render_denoised_var(device_scene, &cam, w, h, nsamples, feature_spp, seed, HRT_FLAG_GAMMA, &denoise_var_params, image.data(), nullptr, &st)
              : denoise  ? hrt_render_denoised(device_scene, &cam, w, h, nsamples, feature_spp, seed, HRT_FLAG_GAMMA, &denoise_params, image.data(), &st)
                         : hrt_render(device_scene, &cam, w, h, nsamples, seed, HRT_FLAG_GAMMA, image.data(), &st);
     if (rc != HRT_OK) {
-        std::cout << (adaptive ? "hrt_render_adaptive" : denoise ? "hrt_render_denoised" : "hrt_render") << " failed: " << hrt_last_error() << std::endl;
+        std::cout << (adaptive ? "hrt_render_adaptive" : denoise_var ? "hrt_render_denoised_var" : denoise ? "hrt_render_denoised" : "hrt_render") << " failed: " << hrt_last_error() << std::endl;
         return rc;
     }
     std::cout << "  Done in " << st.total_ms / 1000.0 << " seconds (kernel " << st.kernel_ms << " ms, "
@@ -90,7 +96,8 @@ int main(int argc, char **argv) {
         else if (k == "--adaptive") { adaptive = true; adaptive_params.threshold = strtof(v.c_str(), nullptr); }
         else if (k == "--spp-min") adaptive_params.min_spp = (unsigned)atoi(v.c_str());
         else if (k == "--denoise") { denoise = true; feature_spp = (uint32_t)strtoul(v.c_str(), nullptr, 10); }
-        else if (k == "--denoise-iters") denoise_params.iterations = (uint32_t)strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--denoise-var") { denoise_var = true; feature_spp = (uint32_t)strtoul(v.c_str(), nullptr, 10); }
+        else if (k == "--denoise-iters") denoise_params.iterations = denoise_var_params.iterations = (uint32_t)strtoul(v.c_str(), nullptr, 10);
         else if (k == "--gpus") { devices.clear(); for (int d = 0; d < atoi(v.c_str()); ++d) devices.push_back(d); }
         else if (k == "--devices") {
             devices.clear();
@@ -108,6 +115,22 @@ int main(int argc, char **argv) {
     }
     if (denoise && !devices.empty()) {
         std::cerr << "--denoise renders on one GPU: it cannot be combined with --gpus / --devices" << std::endl;
+        return 2;
+    }
+    if (denoise_var && adaptive) {
+        std::cerr << "--denoise-var filters a uniform render: it cannot be combined with --adaptive" << std::endl;
+        return 2;
+    }
+    if (denoise_var && !devices.empty()) {
+        std::cerr << "--denoise-var renders on one GPU: it cannot be combined with --gpus / --devices" << std::endl;
+        return 2;
+    }
+    if (denoise_var && denoise) {
+        std::cerr << "--denoise-var and --denoise are two filters: give one of them" << std::endl;
+        return 2;
+    }
+    if (denoise_var && (nsamples < 2u || (nsamples & 1u))) {
+        std::cerr << "--denoise-var compares the two halves of the samples: --spp must be even and at least 2" << std::endl;
         return 2;
     }
     scene.asset_root = assets;

@@ -454,6 +454,51 @@ HRT_API int hrt_denoise(const float *d_color, const float *d_features, uint32_t 
  * gamma, hrt_render_features(0, feature_spp)).  stats (may be NULL): kernel_ms = the trace kernel's time, as hrt_render. */
 HRT_API int hrt_render_denoised(hrt_scene *scene, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp, uint64_t seed, uint32_t flags, const hrt_denoise_params *p, float *out_rgb, hrt_stats *stats);
 
+/* ---- variance-guided denoising: the filter above with a colour width PER PAIR OF PIXELS, the estimated variance of the
+ * difference of the two pixels' own means (the spatial half of SVGF, Schied et al., HPG 2017).  Where the frame is still noisy the colour term is wide, where it has
+ * converged it is narrow and the detail survives.  hrt_denoise and hrt_render_denoised are unchanged.
+ * Input: c = linear means over all N samples, c_half = linear means over the first N/2 samples of the same render (N even), and the
+ * features of hrt_render_features.  All arithmetic is fp32 without fused multiply-add, in the order written;
+ * tests/denoise_var_ref.py states the same rule in numpy.  T, h, |v|^2, d, the tap order and the skipping of taps are those of THE
+ * FILTER above; G_pq = (T(|n_p - n_q|^2, sn^2) + T(|a_p - a_q|^2, sa^2)) + T((z_p - z_q)^2, (sz * max(max(z_p, z_q), 1e-3))^2) are its
+ * guide terms.
+ * 1. Demodulate both frames with step 1 above (e_k / 6 is computed once per channel): x from c, x_half from c_half.  A pixel is
+ *    INVALID when it is invalid for either frame; its x becomes NaN.  Variance of the mean, summed over the channels:
+ *    delta = x - x_half (half the difference of the two half means), v = (delta_0 delta_0 + delta_1 delta_1) + delta_2 delta_2;
+ *    v = 0 on an invalid pixel and where that sum is not finite.
+ * 2. Prefilter v alone, passes i = 0 .. prefilter-1 at step 2^i:  v_p <- (sum_q w_pq v_q) / (sum_q w_pq)  with w = h_0 h_0 at the
+ *    centre and w_pq = (h_j h_k) * expf(-G_pq) elsewhere; sum_w += w, sum_v += w * v_q.  An invalid pixel keeps its v.
+ * 3. Iterate, i = 0 .. iterations-1, step 2^i, as step 2 above with
+ *        w_pq = (h_j h_k) * expf(-E),  E = T(|x_p - x_q|^2, D_pq) + G_pq,
+ *        D_pq = +inf if sigma_variance == +inf, else (sigma_variance * sigma_variance) * ((v_p + v_q) + variance_floor)
+ *    (the width is the variance of the difference of the two means, the same for both pixels of a pair, so a bright outlier hands
+ *    on what it loses; it is not tightened over the iterations: the variance shrinks by itself), and the
+ *    variance carried along:  v_p <- (sum_q (w_pq w_pq) v_q) / (sum_w sum_w), the centre tap included with w = h_0 h_0;
+ *    sum_v += (w * w) * v_q in tap order beside sum_w and sum_x.  An invalid pixel keeps x (NaN) and v (0).
+ * 4. Remodulate, fall back to the input pixel c, gamma: step 3 above, unchanged.  d_variance_out, if wanted, receives the final v
+ *    (h*w floats, in demodulated units): an error map of the result.
+ * Parameters: iterations 1..8, prefilter 0..4, every sigma > 0 and not NaN (+inf switches its term off), variance_floor finite and
+ * >= 0, w and h positive, flags HRT_FLAG_GAMMA or 0; spp even and >= 2, feature_spp <= spp.  They are checked before any device call:
+ * a bad one returns HRT_ERR_INVALID and hrt_last_error() names it. */
+typedef struct hrt_denoise_var_params {
+    uint32_t iterations;                                           /* 1..8; step of iteration i = 2^i pixels            */
+    uint32_t prefilter;                                            /* 0..4 passes over the variance before the iterations */
+    float sigma_variance, sigma_normal, sigma_albedo, sigma_depth; /* > 0; +inf switches a term off                       */
+    float variance_floor;                                          /* >= 0, added to v_p + v_q in the colour width      */
+} hrt_denoise_var_params;
+/* Bytes of d_scratch hrt_denoise_var needs for a w x h frame (the packed guides and two ping-pong {x, v} buffers, 64 per pixel). */
+HRT_API size_t hrt_denoise_var_scratch_bytes(uint32_t w, uint32_t h);
+/* Device pointers, asynchronous on `stream`.  d_color, d_color_half: h*w*3 linear means; d_features: as hrt_render_features writes
+ * them; d_out: h*w*3; d_variance_out: h*w, may be NULL (neither may alias the inputs or the scratch). */
+HRT_API int hrt_denoise_var(const float *d_color, const float *d_color_half, const float *d_features, uint32_t w, uint32_t h, const hrt_denoise_var_params *p, uint32_t flags, void *d_scratch, float *d_out, float *d_variance_out, void *stream);
+/* The whole frame on the scene's device into HOST buffers out_rgb[h*w*3] and out_variance[h*w] (may be NULL): samples [0, spp/2)
+ * with hrt_render_accumulate, a copy of those sums, samples [spp/2, spp) on top, both finalised without gamma (every launch checked
+ * with hrt_check_last_launch), the features of samples [0, feature_spp), then hrt_denoise_var with HRT_FLAG_GAMMA as given in flags
+ * (the kernel-form flags apply).  Nothing but the result leaves the device.  The result is bit-identical to hrt_denoise_var(
+ * hrt_render(spp), hrt_render(spp/2), hrt_render_features(0, feature_spp)), both renders without gamma.  stats (may be NULL):
+ * kernel_ms = the two trace launches' time. */
+HRT_API int hrt_render_denoised_var(hrt_scene *scene, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp, uint64_t seed, uint32_t flags, const hrt_denoise_var_params *p, float *out_rgb, float *out_variance, hrt_stats *stats);
+
 /* ---- ray queries: the scene traced with the caller's own rays (picking, visibility, baking, hit buffers for other code)
  * RAYS: n records of 8 floats (32 bytes, the array 16-byte aligned) {o.x, o.y, o.z, time, d.x, d.y, d.z, tmax}, device memory.
  * CLOSEST: Scene::computeIntersection (Scene.h:202-230) on the ray exactly as given -- no normalisation unless HRT_RAYS_NORMALIZE,
