@@ -138,26 +138,17 @@ static int adaptive_run(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
     if (rc != HRT_OK) return rc;
     const uint32_t n_tiles = R.tiles_owned;
     if (n_tiles == 0u) return HRT_OK;
-    const size_t compact_floats = (size_t)n_tiles * 192u, words = 4u * (size_t)n_tiles + 1u;
-    if (s->ad_compact_cap < compact_floats) {
-        if (s->ad_compact) (void)hipFree(s->ad_compact);
-        s->ad_compact = nullptr; s->ad_compact_cap = 0;
-        HIP_TRY(hipMalloc((void **)&s->ad_compact, compact_floats * sizeof(float)));
-        s->ad_compact_cap = compact_floats;
-    }
-    if (s->ad_words_cap < words) {
-        if (s->ad_words) (void)hipFree(s->ad_words);
-        s->ad_words = nullptr; s->ad_words_cap = 0;
-        HIP_TRY(hipMalloc((void **)&s->ad_words, words * sizeof(uint32_t)));
-        s->ad_words_cap = words;
-    }
-    uint32_t *const lists[2] = {s->ad_words, s->ad_words + n_tiles};
-    uint32_t *const keep = s->ad_words + 2u * (size_t)n_tiles;
-    uint32_t *const counter = s->ad_words + 4u * (size_t)n_tiles;
-    if (!d_counts) d_counts = s->ad_words + 3u * (size_t)n_tiles;
+    const size_t sum_bytes = (size_t)n_tiles * 192u * sizeof(float);
+    if ((rc = s->ad_compact.grow(sum_bytes)) != HRT_OK || (rc = s->ad_words.grow((4u * (size_t)n_tiles + 1u) * sizeof(uint32_t))) != HRT_OK) return rc;
+    float *const compact = s->ad_compact.as<float>();
+    uint32_t *const words = s->ad_words.as<uint32_t>();
+    uint32_t *const lists[2] = {words, words + n_tiles};
+    uint32_t *const keep = words + 2u * (size_t)n_tiles;
+    uint32_t *const counter = words + 4u * (size_t)n_tiles;
+    if (!d_counts) d_counts = words + 3u * (size_t)n_tiles;
     const uint32_t half = p->min_spp / 2u;
 
-    HIP_TRY(hipMemsetAsync(d_sums, 0, compact_floats * sizeof(float), stream));
+    HIP_TRY(hipMemsetAsync(d_sums, 0, sum_bytes, stream));
     rc = launch_trace(s, cam, w, h, 0u, half, seed, flags, rank, world, d_sums, stream, true);  // round 0
     if (rc == HRT_OK) rc = adaptive_trace_done(s, kernel_ms);
     if (rc != HRT_OK) return rc;
@@ -166,12 +157,12 @@ static int adaptive_run(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
     for (uint32_t round = 1; n != 0u; ++round) {
         const uint32_t add = round == 1u ? half : std::min(done, p->max_spp - done);
         const dim3 grid((n + HRT_AD_WG / 64u - 1u) / (HRT_AD_WG / 64u));
-        hipLaunchKernelGGL(hrt_ad_gather_kernel, grid, dim3(HRT_AD_WG), 0, stream, d_sums, active, n, s->ad_compact);
+        hipLaunchKernelGGL(hrt_ad_gather_kernel, grid, dim3(HRT_AD_WG), 0, stream, d_sums, active, n, compact);
         HIP_TRY(hipGetLastError());
-        rc = launch_trace(s, cam, w, h, done, add, seed, flags, rank, world, s->ad_compact, stream, true, active, n);
+        rc = launch_trace(s, cam, w, h, done, add, seed, flags, rank, world, compact, stream, true, active, n);
         if (rc == HRT_OK) rc = adaptive_trace_done(s, kernel_ms);
         if (rc != HRT_OK) return rc;
-        hipLaunchKernelGGL(hrt_ad_judge_kernel, grid, dim3(HRT_AD_WG), 0, stream, s->ad_compact, d_sums, active, n, done, done + add,
+        hipLaunchKernelGGL(hrt_ad_judge_kernel, grid, dim3(HRT_AD_WG), 0, stream, compact, d_sums, active, n, done, done + add,
                            p->threshold, p->max_spp, w, h, rank, world, R.tiles_x, d_counts, keep);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(hrt_ad_compact_kernel, dim3(1), dim3(1024), 0, stream, keep, active, n, lists[round & 1u], counter);
@@ -194,7 +185,7 @@ int hrt_render_adaptive_tiles(hrt_scene *s, const hrt_camera *cam, uint32_t w, u
     if (rc != HRT_OK) return rc;
     if (!d_tiles) return fail(HRT_ERR_INVALID, "hrt_render_adaptive_tiles: d_tiles is NULL");
     if (!d_tile_spp) return fail(HRT_ERR_INVALID, "hrt_render_adaptive_tiles: d_tile_spp is NULL");
-    if (!s) return fail(HRT_ERR_INVALID, "hrt_render_adaptive_tiles: scene is NULL");
+    if ((rc = enter_scene("hrt_render_adaptive_tiles", s)) != HRT_OK) return rc;
     double ms = 0.0;
     return adaptive_run(s, cam, w, h, params, seed, flags, rank, world, d_tiles, d_tile_spp, (hipStream_t)stream, &ms);
 }
@@ -204,49 +195,30 @@ int hrt_render_adaptive(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
     int rc = adaptive_check("hrt_render_adaptive", params, cam);
     if (rc != HRT_OK) return rc;
     if (!out_rgb) return fail(HRT_ERR_INVALID, "hrt_render_adaptive: out_rgb is NULL");
-    if (!s) return fail(HRT_ERR_INVALID, "hrt_render_adaptive: scene is NULL");
-    if (!g_rt.ready) return fail(HRT_ERR_STATE, "render: call hrt_init first");
-    { const int drc = use_device(s->device); if (drc != HRT_OK) return drc; }
-    if (!w || !h || (uint64_t)w * h > 0x7fffffffull) return fail(HRT_ERR_INVALID, "hrt_render_adaptive: bad frame size");
+    if ((rc = enter_scene("hrt_render_adaptive", s)) != HRT_OK) return rc;
+    if ((rc = check_frame("hrt_render_adaptive", w, h, k_max_pixels)) != HRT_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t tiles = hrt_tiles_total(w, h);
-    const size_t tile_floats = (size_t)tiles * 64 * 3, frame_floats = (size_t)w * h * 3;
-    if (s->tiles_cap < tile_floats) {
-        if (s->d_tiles) (void)hipFree(s->d_tiles);
-        s->d_tiles = nullptr; s->tiles_cap = 0;
-        HIP_TRY(hipMalloc((void **)&s->d_tiles, tile_floats * sizeof(float)));
-        s->tiles_cap = tile_floats;
-    }
-    if (s->frame_cap < frame_floats) {
-        if (s->d_frame) (void)hipFree(s->d_frame);
-        s->d_frame = nullptr; s->frame_cap = 0;
-        HIP_TRY(hipMalloc((void **)&s->d_frame, frame_floats * sizeof(float)));
-        s->frame_cap = frame_floats;
-    }
+    const size_t frame_bytes = (size_t)w * h * 3 * sizeof(float);
+    if ((rc = s->tiles.grow((size_t)tiles * 64 * 3 * sizeof(float))) != HRT_OK || (rc = s->frame.grow(frame_bytes)) != HRT_OK) return rc;
     double ms = 0.0;
-    rc = adaptive_run(s, cam, w, h, params, seed, flags, 0, 1, s->d_tiles, nullptr, nullptr, &ms);  // the count map: the scene's
-    if (rc == HRT_OK) rc = hrt_assemble_frame(s->d_tiles, tiles, w, h, 1, s->d_frame, nullptr);
+    rc = adaptive_run(s, cam, w, h, params, seed, flags, 0, 1, s->tiles.as<float>(), nullptr, nullptr, &ms);  // the count map: the scene's
+    if (rc == HRT_OK) rc = hrt_assemble_frame(s->tiles.as<float>(), tiles, w, h, 1, s->frame.as<float>(), nullptr);
     std::vector<uint32_t> counts(tiles);
     hipError_t e = hipSuccess;
-    if (rc == HRT_OK) e = hipMemcpy(out_rgb, s->d_frame, frame_floats * sizeof(float), hipMemcpyDeviceToHost);
-    if (rc == HRT_OK && e == hipSuccess) e = hipMemcpy(counts.data(), s->ad_words + 3u * (size_t)tiles, (size_t)tiles * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (rc == HRT_OK) e = hipMemcpy(out_rgb, s->frame.p, frame_bytes, hipMemcpyDeviceToHost);
+    if (rc == HRT_OK && e == hipSuccess) e = hipMemcpy(counts.data(), s->ad_words.as<uint32_t>() + 3u * (size_t)tiles, (size_t)tiles * sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (rc != HRT_OK) return rc;
     if (e != hipSuccess) return fail(HRT_ERR_DEVICE, std::string("hrt_render_adaptive: ") + hipGetErrorString(e));
     if (out_tile_spp) std::memcpy(out_tile_spp, counts.data(), (size_t)tiles * sizeof(uint32_t));
     if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
         const uint32_t tx = (w + HRT_TILE - 1) / HRT_TILE;
         uint64_t samples = 0;
         for (uint32_t t = 0; t < tiles; ++t) {
             const uint32_t x0 = (t % tx) * HRT_TILE, y0 = (t / tx) * HRT_TILE;
             samples += (uint64_t)std::min<uint32_t>(HRT_TILE, w - x0) * std::min<uint32_t>(HRT_TILE, h - y0) * counts[t];
         }
-        stats->kernel_ms = ms;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        stats->samples = samples;
-        stats->vgprs = (uint32_t)g_rt.attr.numRegs;
-        stats->lds_bytes = s->last_lds;
-        stats->waves_launched = s->last_waves;
+        fill_stats(s, stats, t0, ms, samples);
     }
     return HRT_OK;
 }

@@ -231,6 +231,43 @@ int upload(const std::vector<T> &v, T **dptr) {
     return HRT_OK;
 }
 
+// A device scratch buffer that grows on demand and never shrinks; the capacity is in bytes.  The old block is freed before the
+// larger one is asked for (its contents are never wanted), so a frame size that only just fits does not need both at once.
+struct Scratch {
+    void *p = nullptr;
+    size_t cap = 0;
+    template <class T> T *as() const { return (T *)p; }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+    }
+    int grow(size_t bytes) {
+        if (cap >= bytes) return HRT_OK;
+        release();
+        HIP_TRY(hipMalloc(&p, bytes));
+        cap = bytes;
+        return HRT_OK;
+    }
+};
+
+// w x h is a frame of at most max_pixels pixels (2^31 - 1 where pixels are indexed, 2^31 / 16 where 16-byte records of them are).
+int check_frame(const std::string &who, uint32_t w, uint32_t h, uint64_t max_pixels) {
+    if (!w || !h) return fail(HRT_ERR_INVALID, who + ": w and h must be positive (got " + std::to_string(w) + " x " + std::to_string(h) + ")");
+    if ((uint64_t)w * h > max_pixels) return fail(HRT_ERR_INVALID, who + ": image too large: w * h must be at most " + std::to_string(max_pixels));
+    return HRT_OK;
+}
+const uint64_t k_max_pixels = 0x7fffffffull, k_max_records = 0x7fffffffull / 16u;
+
+// The margin scale of the filters (CtxT::err_abs) for rays of unit direction that start |o| from the world origin in a scene whose
+// points lie within `bound` of it.
+__host__ __device__ __forceinline__ float margin_scale(float bound, float olen) { return 2e-6f * (bound + olen + 1.f); }
+
+// HRT_FLAG_MESH_BRUTE exists in the proof builds only.
+int check_mesh_brute(const std::string &who, uint32_t flags) {
+    if ((flags & HRT_FLAG_MESH_BRUTE) && !(flags & HRT_FLAG_EXACT_ONLY)) return fail(HRT_ERR_INVALID, who + ": flags: HRT_FLAG_MESH_BRUTE needs HRT_FLAG_EXACT_ONLY");
+    return HRT_OK;
+}
+
 }  // namespace
 
 struct hrt_scene {
@@ -245,39 +282,54 @@ struct hrt_scene {
     std::vector<void *> allocations;
     uint32_t *tile_counter = nullptr;
     unsigned long long *stamps = nullptr;  // diagnostic cycle counters (HRT_STAMPS builds)
-    float *sp_scratch = nullptr;           // per-workgroup sample scratch of the streaming kernel
-    size_t sp_scratch_cap = 0;
-    uint32_t *sp_pool = nullptr;           // path records of the streaming kernel when they live in global memory
-    size_t sp_pool_cap = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     float bound = 0.f;  // largest distance of any scene point from the origin (filter margins)
-    // scratch of hrt_render (whole frame on one GPU)
-    float *d_tiles = nullptr, *d_frame = nullptr;
-    size_t tiles_cap = 0, frame_cap = 0;
+    // Scratch, grown on demand.  The streaming kernel's: per-workgroup samples (floats), and its path records (words) when they
+    // live in global memory.  hrt_render's: the frame in tiles and in rows.  The adaptive entry points' (hrt_adaptive.hip): the
+    // active tiles' sums, compact; and in ad_words the two tile lists, the judge's keep flags and the count map of
+    // hrt_render_adaptive (tiles each), then the list counter.  The denoisers' (hrt_denoise.hip): the linear frame, the features,
+    // the filter's scratch, the result; and for the variance-guided one the first half's sums and frame, and the variance map.
+    Scratch sp_scratch, sp_pool, tiles, frame, ad_compact, ad_words, dn_frame, dn_feat, dn_scratch, dn_out, dnv_half_tiles, dnv_frame_half, dnv_var;
+    std::array<Scratch *, 13> scratch() { return {&sp_scratch, &sp_pool, &tiles, &frame, &ad_compact, &ad_words, &dn_frame, &dn_feat, &dn_scratch, &dn_out, &dnv_half_tiles, &dnv_frame_half, &dnv_var}; }
     uint32_t last_grid = 0, last_waves = 0, last_lds = 0;
     hipStream_t last_stream = nullptr;  // stream of the previous launch on this scene
     int device = 0;                     // the device that holds this scene (current when it was created)
-    // scratch of the adaptive entry points (hrt_adaptive.hip), grown on demand: the active tiles' sums, compact; and in ad_words
-    // the two tile lists, the judge's keep flags and the count map of hrt_render_adaptive (tiles each), then the list counter
-    float *ad_compact = nullptr;
-    size_t ad_compact_cap = 0;
-    uint32_t *ad_words = nullptr;
-    size_t ad_words_cap = 0;
-    // hrt_render_features' own camera block (with its host copy and the event that orders feature launches across streams), and the
-    // scratch of hrt_render_denoised (hrt_denoise.hip), grown on demand: the linear frame, the features, the filter's scratch, the result
+    // hrt_render_features' own camera block, with its host copy and the event that orders feature launches across streams
     DCamera *d_cam_feat = nullptr;
     DCamera h_cam_feat{};
     hipEvent_t ev_feat = nullptr;
     bool feat_used = false;
     hipStream_t feat_stream = nullptr;
-    float *dn_frame = nullptr, *dn_feat = nullptr, *dn_out = nullptr;
-    void *dn_scratch = nullptr;
-    size_t dn_frame_cap = 0, dn_feat_cap = 0, dn_out_cap = 0, dn_scratch_cap = 0;
-    // more of hrt_render_denoised_var (hrt_denoise_var.hip): the first half's sums and frame, the variance map (capacities in bytes)
-    float *dnv_half_tiles = nullptr, *dnv_frame_half = nullptr, *dnv_var = nullptr;
-    size_t dnv_half_tiles_cap = 0, dnv_frame_half_cap = 0, dnv_var_cap = 0;
 };
+
+namespace {
+
+// What every entry point that works on a scene does after its own argument checks: the scene is there, the library is
+// initialised, and the scene's device is current (a scene lives on its device; HIP's current device is per thread, g_rt's copy of
+// it per process, so this is unconditional -- but for a call that then has nothing to do on the device: switch_device = false).
+int enter_scene(const std::string &who, hrt_scene *s, bool switch_device = true) {
+    if (!s) return fail(HRT_ERR_INVALID, who + ": scene is NULL");
+    if (!g_rt.ready) return fail(HRT_ERR_STATE, who + ": call hrt_init first");
+    return switch_device ? use_device(s->device) : HRT_OK;
+}
+int enter_render(const std::string &who, hrt_scene *s, const hrt_camera *cam) {
+    if (!cam) return fail(HRT_ERR_INVALID, who + ": camera is NULL");
+    return enter_scene(who, s);
+}
+
+// The stats block of a render that took kernel_ms on the device and `samples` samples, started at t0.
+void fill_stats(const hrt_scene *s, hrt_stats *stats, std::chrono::steady_clock::time_point t0, double kernel_ms, uint64_t samples) {
+    std::memset(stats, 0, sizeof(*stats));
+    stats->kernel_ms = kernel_ms;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stats->samples = samples;
+    stats->vgprs = (uint32_t)g_rt.attr.numRegs;
+    stats->lds_bytes = s->last_lds;
+    stats->waves_launched = s->last_waves;
+}
+
+}  // namespace
 
 #include "hrt_kdbuild.hip"
 
@@ -363,19 +415,12 @@ void hrt_scene_destroy(hrt_scene *s) {
     for (void *p : s->allocations) (void)hipFree(p);
     if (s->tile_counter) (void)hipFree(s->tile_counter);
     if (s->stamps) (void)hipFree(s->stamps);
-    if (s->sp_scratch) (void)hipFree(s->sp_scratch);
-    if (s->sp_pool) (void)hipFree(s->sp_pool);
     if (s->d_scene) (void)hipFree(s->d_scene);
     if (s->d_cam) (void)hipFree(s->d_cam);
     if (s->d_cam_aov) (void)hipFree(s->d_cam_aov);
-    if (s->d_tiles) (void)hipFree(s->d_tiles);
-    if (s->d_frame) (void)hipFree(s->d_frame);
-    if (s->ad_compact) (void)hipFree(s->ad_compact);
-    if (s->ad_words) (void)hipFree(s->ad_words);
+    for (Scratch *b : s->scratch()) b->release();
     if (s->d_cam_feat) (void)hipFree(s->d_cam_feat);
     if (s->ev_feat) (void)hipEventDestroy(s->ev_feat);
-    for (void *p : {(void *)s->dn_frame, (void *)s->dn_feat, (void *)s->dn_out, s->dn_scratch, (void *)s->dnv_half_tiles,
-                    (void *)s->dnv_frame_half, (void *)s->dnv_var}) if (p) (void)hipFree(p);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     delete s;
@@ -967,17 +1012,14 @@ static int make_camera(const hrt_camera *cam, DCamera &C) {
 
 static int fill_render(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
                        uint32_t flags, uint32_t rank, uint32_t world, DRender &R, DCamera &C) {
-    if (!s || !cam) return fail(HRT_ERR_INVALID, "render: NULL argument");
-    if (!g_rt.ready) return fail(HRT_ERR_STATE, "render: call hrt_init first");
-    { const int drc = use_device(s->device); if (drc != HRT_OK) return drc; }  // a scene lives on its device.  Unconditional: HIP's current
-                                                                               // device is per thread, g_rt's copy of it per process
-    if (!w || !h || !spp) return fail(HRT_ERR_INVALID, "render: w, h and spp must be positive");
-    if ((uint64_t)w * h > 0x7fffffffull) return fail(HRT_ERR_INVALID, "render: image too large");
+    const int frc = check_frame("render", w, h, k_max_pixels);  // the scene is the caller's to enter (enter_scene)
+    if (frc != HRT_OK) return frc;
+    if (!spp) return fail(HRT_ERR_INVALID, "render: spp must be positive");
     if (w > 65535u || h > 65535u) return fail(HRT_ERR_INVALID, "render: w and h must be below 65536 (tile origins are packed in 16 + 16 bits)");
     if (!world || rank >= world) return fail(HRT_ERR_INVALID, "render: bad rank/world");
     R.scene = s->d_scene;
     R.lds_units = (flags & HRT_FLAG_NO_LDS_TREE) ? 0u : s->lds_units;
-    R.err_abs = 2e-6f * (s->bound + std::sqrt(cam->eye[0] * cam->eye[0] + cam->eye[1] * cam->eye[1] + cam->eye[2] * cam->eye[2]) + 1.f);
+    R.err_abs = margin_scale(s->bound, std::sqrt(cam->eye[0] * cam->eye[0] + cam->eye[1] * cam->eye[1] + cam->eye[2] * cam->eye[2]));
     {
         const int crc = make_camera(cam, C);
         if (crc != HRT_OK) return crc;
@@ -1040,7 +1082,7 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
     const bool stream_kernel = stream_fits && !(flags & (HRT_FLAG_WAVE_KERNEL | HRT_FLAG_DUAL_KERNEL)) &&
                                (g_rt.use_stream == 1 || (flags & HRT_FLAG_STREAM_KERNEL) || (g_rt.use_stream < 0 && stream_pays));
     const bool exact = (flags & HRT_FLAG_EXACT_ONLY) != 0u;  // proof builds exist for the lane-per-pixel and streaming forms
-    if ((flags & HRT_FLAG_MESH_BRUTE) && !exact) return fail(HRT_ERR_INVALID, "render: HRT_FLAG_MESH_BRUTE needs HRT_FLAG_EXACT_ONLY");
+    if ((rc = check_mesh_brute("render", flags)) != HRT_OK) return rc;
     if (exact && (flags & HRT_FLAG_DUAL_KERNEL)) return fail(HRT_ERR_INVALID, "render: no exact-only build of the two-stream kernel");
     const bool dual_kernel = !exact && !stream_kernel && (g_rt.use_dual || (flags & HRT_FLAG_DUAL_KERNEL)) && s->d.n_meshes > 0u &&
                              !(flags & HRT_FLAG_WAVE_KERNEL);
@@ -1070,24 +1112,11 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
             while (glog == 0u && band < 2u && ((uint64_t)R.tiles_owned << band) < 64ull * grid && (64u >> (band + 1u)) * (uint64_t)std::min<uint32_t>(spp, HRT_SP_SCHUNK) >= 4096u) ++band;
             R.sp_band_log2 = band;
         }
-        const size_t need_floats = (size_t)grid * HRT_SP_UNITS * HRT_SP_UNIT * 3u;  // HRT_SP_UNITS units in flight per workgroup
-        if (s->sp_scratch_cap < need_floats) {
-            if (s->sp_scratch) (void)hipFree(s->sp_scratch);
-            s->sp_scratch = nullptr; s->sp_scratch_cap = 0;
-            HIP_TRY(hipMalloc((void **)&s->sp_scratch, need_floats * sizeof(float)));
-            s->sp_scratch_cap = need_floats;
-        }
-        R.sp_scratch = s->sp_scratch;
-        if (HRT_SP_GLOBAL) {
-            const size_t need_words = (size_t)grid * SP_FIELDS * HRT_SP_POOL;
-            if (s->sp_pool_cap < need_words) {
-                if (s->sp_pool) (void)hipFree(s->sp_pool);
-                s->sp_pool = nullptr; s->sp_pool_cap = 0;
-                HIP_TRY(hipMalloc((void **)&s->sp_pool, need_words * sizeof(uint32_t)));
-                s->sp_pool_cap = need_words;
-            }
-        }
-        R.sp_pool = s->sp_pool;
+        rc = s->sp_scratch.grow((size_t)grid * HRT_SP_UNITS * HRT_SP_UNIT * 3u * sizeof(float));  // HRT_SP_UNITS units in flight per workgroup
+        if (rc == HRT_OK && HRT_SP_GLOBAL) rc = s->sp_pool.grow((size_t)grid * SP_FIELDS * HRT_SP_POOL * sizeof(uint32_t));
+        if (rc != HRT_OK) return rc;
+        R.sp_scratch = s->sp_scratch.as<float>();
+        R.sp_pool = s->sp_pool.as<uint32_t>();
     } else {
         const void *kfn = exact ? (s->d.n_lights ? (const void *)HRT_PICK(hrt_trace_kernel_lights_exact) : (const void *)HRT_PICK(hrt_trace_kernel_exact))
                                 : (s->d.n_lights ? (const void *)HRT_PICK(hrt_trace_kernel_lights) : (const void *)HRT_PICK(hrt_trace_kernel));
@@ -1159,11 +1188,15 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
 
 int hrt_render_tiles(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
                      uint32_t flags, uint32_t rank, uint32_t world, float *d_tiles, void *stream) {
+    const int rc = enter_render("hrt_render_tiles", s, cam);
+    if (rc != HRT_OK) return rc;
     return launch_trace(s, cam, w, h, 0u, spp, seed, flags, rank, world, d_tiles, stream, false);
 }
 
 int hrt_render_accumulate(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples,
                           uint64_t seed, uint32_t flags, uint32_t rank, uint32_t world, float *d_sum_tiles, void *stream) {
+    const int rc = enter_render("hrt_render_accumulate", s, cam);
+    if (rc != HRT_OK) return rc;
     return launch_trace(s, cam, w, h, first_sample, n_samples, seed, flags, rank, world, d_sum_tiles, stream, true);
 }
 
@@ -1184,7 +1217,7 @@ int hrt_encode_ppm(const float *d_frame, uint32_t w, uint32_t h, int format, uns
     if (!d_frame || !d_out || !bytes || !w || !h) return fail(HRT_ERR_INVALID, "hrt_encode_ppm: bad argument");
     if (format != 3 && format != 6) return fail(HRT_ERR_INVALID, "hrt_encode_ppm: format must be 3 (ASCII) or 6 (binary)");
     if (!g_rt.ready) return fail(HRT_ERR_STATE, "hrt_encode_ppm: call hrt_init first");
-    if ((uint64_t)w * h > 0x7fffffffull / 16u) return fail(HRT_ERR_INVALID, "hrt_encode_ppm: image too large");
+    { const int frc = check_frame("hrt_encode_ppm", w, h, k_max_records); if (frc != HRT_OK) return frc; }
     hipStream_t stream = (hipStream_t)stream_;
     char head[64];
     // main.cpp:258: "P3" endl w " " h endl 255 endl
@@ -1292,42 +1325,23 @@ int hrt_kernel_info(hrt_stats *out) {
 int hrt_render(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed, uint32_t flags,
                float *out_rgb, hrt_stats *stats) {
     if (!out_rgb) return fail(HRT_ERR_INVALID, "hrt_render: NULL output");
-    if (!s) return fail(HRT_ERR_INVALID, "hrt_render: NULL scene");
-    if (!g_rt.ready) return fail(HRT_ERR_STATE, "render: call hrt_init first");
-    { const int drc = use_device(s->device); if (drc != HRT_OK) return drc; }  // the frame and tile buffers below belong on the scene's device
+    int rc = enter_render("hrt_render", s, cam);  // the frame and tile buffers below belong on the scene's device
+    if (rc != HRT_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
-    const size_t tiles = hrt_tiles_total(w, h);
-    const size_t tile_floats = tiles * 64 * 3, frame_floats = (size_t)w * h * 3;
-    if (s->tiles_cap < tile_floats) {
-        if (s->d_tiles) (void)hipFree(s->d_tiles);
-        s->d_tiles = nullptr; s->tiles_cap = 0;
-        HIP_TRY(hipMalloc((void **)&s->d_tiles, tile_floats * sizeof(float)));
-        s->tiles_cap = tile_floats;
-    }
-    if (s->frame_cap < frame_floats) {
-        if (s->d_frame) (void)hipFree(s->d_frame);
-        s->d_frame = nullptr; s->frame_cap = 0;
-        HIP_TRY(hipMalloc((void **)&s->d_frame, frame_floats * sizeof(float)));
-        s->frame_cap = frame_floats;
-    }
-    int rc = hrt_render_tiles(s, cam, w, h, spp, seed, flags, 0, 1, s->d_tiles, nullptr);
+    const size_t tiles = hrt_tiles_total(w, h), frame_bytes = (size_t)w * h * 3 * sizeof(float);
+    if ((rc = s->tiles.grow(tiles * 64 * 3 * sizeof(float))) != HRT_OK || (rc = s->frame.grow(frame_bytes)) != HRT_OK) return rc;
+    rc = hrt_render_tiles(s, cam, w, h, spp, seed, flags, 0, 1, s->tiles.as<float>(), nullptr);
     if (rc != HRT_OK) return rc;
-    rc = hrt_assemble_frame(s->d_tiles, (uint32_t)tiles, w, h, 1, s->d_frame, nullptr);
+    rc = hrt_assemble_frame(s->tiles.as<float>(), (uint32_t)tiles, w, h, 1, s->frame.as<float>(), nullptr);
     if (rc != HRT_OK) return rc;
-    HIP_TRY(hipMemcpy(out_rgb, s->d_frame, frame_floats * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_rgb, s->frame.p, frame_bytes, hipMemcpyDeviceToHost));
     rc = hrt_check_last_launch(s);  // never hand back a frame the kernel did not finish
     if (rc != HRT_OK) return rc;
     if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
         double ms = 0.0;
         rc = hrt_last_kernel_ms(s, &ms);
         if (rc != HRT_OK) return rc;
-        stats->kernel_ms = ms;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        stats->samples = (uint64_t)w * h * spp;
-        stats->vgprs = (uint32_t)g_rt.attr.numRegs;
-        stats->lds_bytes = s->last_lds;
-        stats->waves_launched = s->last_waves;
+        fill_stats(s, stats, t0, ms, (uint64_t)w * h * spp);
     }
     return HRT_OK;
 }
@@ -1336,7 +1350,8 @@ int hrt_render_aov(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, 
     if (!out_rgb || which > 3u) return fail(HRT_ERR_INVALID, "hrt_render_aov: bad argument");
     DRender R;
     DCamera C;
-    int rc = fill_render(s, cam, w, h, 1, 0, 0, 0, 1, R, C);
+    int rc = enter_render("hrt_render_aov", s, cam);
+    if (rc == HRT_OK) rc = fill_render(s, cam, w, h, 1, 0, 0, 0, 1, R, C);
     if (rc != HRT_OK) return rc;
     // A camera block of its own: a trace launch on another stream may still be reading s->d_cam.  The AOV kernel runs on the
     // null stream and hipMemcpy below waits for it, so the block is free again when this returns.
@@ -1406,7 +1421,7 @@ int hrt_debug_kat(uint32_t which, const hrt_camera *cam, const float *prim, cons
         double b = 0.0;
         for (int k = 0; k < 13; ++k) b = std::max(b, (double)std::fabs(prim[k]));
         for (size_t k = 0; k < (size_t)n * 7; ++k) if (k % 7 < 3) b = std::max(b, (double)std::fabs(in[k]));
-        err_abs = 2e-6f * ((float)(b * 4.0) + 1.f);  // the margin scale fill_render derives from the scene extent
+        err_abs = margin_scale((float)(b * 4.0), 0.f);  // as fill_render derives it from the scene extent (x + 0.f is x)
     }
     void *d_prim = nullptr;
     float *d_in = nullptr, *d_out = nullptr;
@@ -1469,7 +1484,6 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 #include "hrt_multi.hip"
 #include "hrt_adaptive.hip"
 #include "hrt_denoise.hip"
-#include "hrt_denoise_var.hip"
 #include "hrt_rays.hip"
 #include "hrt_radiance.hip"
 

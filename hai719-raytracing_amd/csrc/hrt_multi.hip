@@ -64,14 +64,11 @@ struct hrt_multi {
     std::vector<hipStream_t> stream;
     std::vector<hipEvent_t> done;
     std::vector<bool> busy;            // `done` of the slot has been recorded by a render (and may still be pending)
-    std::vector<float *> d_tiles;      // slots 1..n-1: this slot's tiles on its own device
+    std::vector<Scratch> tiles;         // slots 1..n-1: this slot's tiles on its own device
     std::vector<ncclComm_t> comm;      // gather == rccl: one communicator per slot
     bool use_rccl = false;
     std::string note;                  // what creation fell back from, if anything (also left in hrt_last_error())
-    size_t tiles_cap = 0;              // floats per slot buffer
-    float *d_gathered = nullptr;       // slot 0's device: n blocks of tiles_cap floats
-    float *d_frame = nullptr;
-    size_t frame_cap = 0;
+    Scratch gathered, frame;            // slot 0's device: n blocks of tiles, one per slot; the frame in rows
 };
 
 // Nothing of an earlier render may still be running when its buffers go away: slots on other devices run asynchronously.
@@ -84,12 +81,11 @@ static void multi_free_buffers(hrt_multi *m) {
     if (!m->n || !m->replica[0]) return;  // creation failed before any buffer existed
     multi_quiesce(m);
     for (uint32_t i = 0; i < m->n; ++i)
-        if (i < m->d_tiles.size() && m->d_tiles[i] && use_device(m->ordinal[i]) == HRT_OK) { (void)hipFree(m->d_tiles[i]); m->d_tiles[i] = nullptr; }
+        if (i < m->tiles.size() && m->tiles[i].p && use_device(m->ordinal[i]) == HRT_OK) m->tiles[i].release();
     if (use_device(m->ordinal[0]) == HRT_OK) {
-        if (m->d_gathered) (void)hipFree(m->d_gathered);
-        if (m->d_frame) (void)hipFree(m->d_frame);
+        m->gathered.release();
+        m->frame.release();
     }
-    m->d_gathered = nullptr; m->d_frame = nullptr; m->tiles_cap = 0; m->frame_cap = 0;
 }
 
 void hrt_multi_destroy(hrt_multi *m) {
@@ -127,7 +123,7 @@ int hrt_multi_create(const hrt_scene_desc *desc, uint32_t n_devices, const int *
     m->stream.assign(n_devices, nullptr);
     m->done.assign(n_devices, nullptr);
     m->busy.assign(n_devices, false);
-    m->d_tiles.assign(n_devices, nullptr);
+    m->tiles.assign(n_devices, Scratch());
     m->comm.assign(n_devices, nullptr);
     int rc = HRT_OK;
     for (uint32_t i = 0; i < n_devices && rc == HRT_OK; ++i) {
@@ -191,24 +187,23 @@ int hrt_multi_render(hrt_multi *m, const hrt_camera *cam, uint32_t w, uint32_t h
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t n = m->n;
     const size_t per = std::max<size_t>((size_t)hrt_tiles_owned(w, h, 0, n) * 64u * 3u, 1);  // floats per slot block: slot 0's share is the largest
-    const size_t frame_floats = (size_t)w * h * 3u;
+    const size_t frame_bytes = (size_t)w * h * 3u * sizeof(float);
     int rc;
-    if (m->tiles_cap < per || m->frame_cap < frame_floats) {
-        multi_free_buffers(m);  // waits for every slot's previous launch and copy first
-        if ((rc = use_device(m->ordinal[0])) != HRT_OK) return rc;
-        HIP_TRY(hipMalloc((void **)&m->d_gathered, per * n * sizeof(float)));
-        HIP_TRY(hipMalloc((void **)&m->d_frame, frame_floats * sizeof(float)));
+    // n is fixed for a handle and no buffer shrinks, and `gathered` (n blocks of `per`) grows only after every slot's `per` did:
+    // so a `gathered` that is large enough says the slots' buffers are too, also after a call that failed half way.
+    if (m->gathered.cap < per * n * sizeof(float) || m->frame.cap < frame_bytes) {
+        multi_quiesce(m);  // a buffer is freed when it grows: every slot's previous launch and copy end first
         for (uint32_t i = 1; i < n; ++i) {
             if ((rc = use_device(m->ordinal[i])) != HRT_OK) return rc;
-            HIP_TRY(hipMalloc((void **)&m->d_tiles[i], per * sizeof(float)));
+            if ((rc = m->tiles[i].grow(per * sizeof(float))) != HRT_OK) return rc;
         }
-        m->tiles_cap = per;
-        m->frame_cap = frame_floats;
         if ((rc = use_device(m->ordinal[0])) != HRT_OK) return rc;
+        if ((rc = m->frame.grow(frame_bytes)) != HRT_OK || (rc = m->gathered.grow(per * n * sizeof(float))) != HRT_OK) return rc;  // gathered last: its size stands for the slots'
     }
+    float *const d_gathered = m->gathered.as<float>();
     // render: every slot at once, blocks of `per` floats in the gather buffer
     for (uint32_t i = 0; i < n; ++i) {
-        float *tiles = i == 0 ? m->d_gathered : m->d_tiles[i];
+        float *tiles = i == 0 ? d_gathered : m->tiles[i].as<float>();
         rc = hrt_render_tiles(m->replica[i], cam, w, h, spp, seed, flags, i, n, tiles, (void *)m->stream[i]);  // switches to the slot's device
         if (rc != HRT_OK) return rc;
     }
@@ -217,8 +212,8 @@ int hrt_multi_render(hrt_multi *m, const hrt_camera *cam, uint32_t w, uint32_t h
         RcclApi &api = rccl_api();
         RCCL_TRY(api.GroupStart());
         for (uint32_t i = 0; i < n; ++i) {
-            const float *src = i == 0 ? m->d_gathered : m->d_tiles[i];  // slot 0 in place: sendbuff == recvbuff + 0 * per
-            const ncclResult_t r = api.Gather(src, i == 0 ? m->d_gathered : nullptr, per, ncclFloat, 0, m->comm[i], m->stream[i]);
+            const float *src = i == 0 ? d_gathered : m->tiles[i].as<float>();  // slot 0 in place: sendbuff == recvbuff + 0 * per
+            const ncclResult_t r = api.Gather(src, i == 0 ? d_gathered : nullptr, per, ncclFloat, 0, m->comm[i], m->stream[i]);
             if (r != ncclSuccess) { (void)api.GroupEnd(); return fail(HRT_ERR_DEVICE, std::string("ncclGather: ") + api.GetErrorString(r)); }
         }
         RCCL_TRY(api.GroupEnd());
@@ -227,7 +222,7 @@ int hrt_multi_render(hrt_multi *m, const hrt_camera *cam, uint32_t w, uint32_t h
             const uint32_t owned = hrt_tiles_owned(w, h, i, n);
             if (!owned) continue;
             if ((rc = use_device(m->ordinal[i])) != HRT_OK) return rc;
-            HIP_TRY(hipMemcpyPeerAsync(m->d_gathered + (size_t)i * per, m->ordinal[0], m->d_tiles[i], m->ordinal[i], (size_t)owned * 64u * 3u * sizeof(float), m->stream[i]));
+            HIP_TRY(hipMemcpyPeerAsync(d_gathered + (size_t)i * per, m->ordinal[0], m->tiles[i].p, m->ordinal[i], (size_t)owned * 64u * 3u * sizeof(float), m->stream[i]));
         }
     }
     for (uint32_t i = 0; i < n; ++i) {
@@ -237,9 +232,9 @@ int hrt_multi_render(hrt_multi *m, const hrt_camera *cam, uint32_t w, uint32_t h
     }
     if ((rc = use_device(m->ordinal[0])) != HRT_OK) return rc;
     for (uint32_t i = 1; i < n; ++i) HIP_TRY(hipStreamWaitEvent(m->stream[0], m->done[i], 0));
-    rc = hrt_assemble_frame(m->d_gathered, (uint32_t)(per / 192u), w, h, n, m->d_frame, (void *)m->stream[0]);
+    rc = hrt_assemble_frame(d_gathered, (uint32_t)(per / 192u), w, h, n, m->frame.as<float>(), (void *)m->stream[0]);
     if (rc != HRT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out_rgb, m->d_frame, frame_floats * sizeof(float), hipMemcpyDeviceToHost, m->stream[0]));
+    HIP_TRY(hipMemcpyAsync(out_rgb, m->frame.p, frame_bytes, hipMemcpyDeviceToHost, m->stream[0]));
     HIP_TRY(hipStreamSynchronize(m->stream[0]));
     for (uint32_t i = 0; i < n; ++i) m->busy[i] = false;  // stream 0 waited for every slot's `done`
     double kernel_ms = 0.0;
@@ -251,13 +246,8 @@ int hrt_multi_render(hrt_multi *m, const hrt_camera *cam, uint32_t w, uint32_t h
     }
     if ((rc = use_device(m->ordinal[0])) != HRT_OK) return rc;
     if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->kernel_ms = kernel_ms;  // the slowest slot
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        stats->samples = (uint64_t)w * h * spp;
-        stats->vgprs = (uint32_t)g_rt.attr.numRegs;
-        stats->lds_bytes = m->replica[0]->last_lds;
-        for (uint32_t i = 0; i < n; ++i) stats->waves_launched += m->replica[i]->last_waves;
+        fill_stats(m->replica[0], stats, t0, kernel_ms, (uint64_t)w * h * spp);  // the slowest slot's time; slot 0's waves, then the others'
+        for (uint32_t i = 1; i < n; ++i) stats->waves_launched += m->replica[i]->last_waves;
     }
     return HRT_OK;
 }

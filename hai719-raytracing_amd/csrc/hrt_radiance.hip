@@ -1,5 +1,5 @@
 // Radiance queries on caller rays (include/hrt.h hrt_trace_radiance) and the camera rays of a frame (hrt_camera_rays).
-// Included by hrt_api.hip inside its extern "C" block, after hrt_rays.hip (DRays' constants and rays_finite).
+// Included by hrt_api.hip inside its extern "C" block, after hrt_rays.hip (the query helpers) and hrt_denoise.hip (camera_sample).
 //
 // hrt_radiance_kernel is trace_body (hrt_kernels.hip) with the camera taken out: one lane per ray, and per sample one path whose
 // first segment is the caller's ray, then the same stages -- A (spheres, squares, mesh gates), B (mesh walks, deferred until
@@ -9,15 +9,17 @@
 // call may overlap a render of the same scene).  The ray record is read again at the start of every sample (two 16-byte loads)
 // instead of being kept in registers across the path.
 //
-// Filter margin and far origins as in rays_body (hrt_rays.hip, DESIGN.md section 5 "Ray queries"): err_abs = 2e-6 (bound + |o| + 1)
-// for a unit direction, +inf otherwise, for the whole path (bounce origins lie within `bound`); a first segment from farther than
-// HRT_RAYS_FAR (bound + 1) tests every triangle of a gated mesh (mesh_brute), bounce segments are walked.
+// Filter margin and far origins are query_margin's (hrt_rays.hip, DESIGN.md section 5 "Ray queries"): the margin holds for the
+// whole path (bounce origins lie within `bound`); the far-origin flag for its first segment only, bounce segments are walked.
 
 #define HRT_RADIANCE_WG 256u
 #ifndef HRT_RADIANCE_MIN_WAVES
 #define HRT_RADIANCE_MIN_WAVES 5  // waves per SIMD the register allocator leaves room for; A/B on MI355X, 1080p x 16 samples, tree from
                                   // global memory: 4 -> 5 is +20 % on Cornell+mesh, +14 % on the pool, +15 % on random_spheres (DESIGN.md
                                   // section 5 "Radiance queries")
+#endif
+#ifndef HRT_RADIANCE_STAGE_TREE
+#define HRT_RADIANCE_STAGE_TREE 0  // -DHRT_RADIANCE_STAGE_TREE: the A/B build that stages the tree prefix (see hrt_trace_radiance)
 #endif
 
 struct DRadiance {
@@ -36,45 +38,17 @@ struct DRadiance {
 extern "C++" {
 namespace hrtk {
 
-// The record of ray i as the first segment of a path: false if it is degenerate (include/hrt.h hrt_trace_radiance).
-__device__ __forceinline__ bool radiance_ray(const DRadiance &Q, uint32_t i, Ray &ray) {
-    const gf4 rays = (gf4)Q.rays;
-    const float4 a = ld(rays, 2u * i), b = ld(rays, 2u * i + 1u);
-    ray.o = mk(a.x, a.y, a.z);
-    ray.time = a.w;
-    ray.d = mk(b.x, b.y, b.z);
-    bool ok = rays_finite(a.x) && rays_finite(a.y) && rays_finite(a.z) && rays_finite(a.w) && rays_finite(b.x) &&
-              rays_finite(b.y) && rays_finite(b.z) && !(b.x == 0.f && b.y == 0.f && b.z == 0.f);
-    if (ok && (Q.flags & HRT_RAYS_NORMALIZE)) {  // the Ray constructor (Line.h:13-16); a length that under- or overflows is degenerate
-        ray.d = normalize(ray.d);
-        ok = rays_finite(ray.d.x) && rays_finite(ray.d.y) && rays_finite(ray.d.z) && !(ray.d.x == 0.f && ray.d.y == 0.f && ray.d.z == 0.f);
-    }
-    return ok;
-}
-
 template <bool LIGHTS, bool EXACT>
 __device__ __forceinline__ void radiance_body(const DRadiance &Q) {
-    extern __shared__ uint4 s_units[];
     CtxT<EXACT, false, false, true> cx;
-    cx.S = (cscene)Q.scene;
-    cx.set_tables((gf4)cx.S->tabs, (gf1)c_u8_lut, cx.S);
-    cx.lds = (lu4)s_units;
-    cx.lds_n = Q.lds_units;
-    cx.flags = Q.flags;
-    cx.err_abs = 0.f;
     unsigned long long stamps_local[17] = {0};
-    cx.st = stamps_local;
-    {
-        gu4 g_units = (gu4)cx.S->kd_units;
-        for (uint32_t i = threadIdx.x; i < cx.lds_n; i += blockDim.x) s_units[i] = ld(g_units, i);
-    }
-    __syncthreads();
+    query_context(cx, Q.scene, Q.lds_units, Q.flags, stamps_local);
     const bool has_mesh = cx.S->n_meshes != 0u;
     const bool prune = !EXACT && cx.S->prune_ok != 0u;  // as trace_body
     const bool sky_is_zero = cx.S->skybox_image < 0 && cx.S->dark_sky != 0;
     const bool accumulate = (Q.flags & HRT_RADIANCE_ACCUMULATE) != 0u;
     const uint32_t stride = gridDim.x * blockDim.x;
-    const float far2 = HRT_RAYS_FAR * (Q.bound + 1.f);
+    const float far = query_far(Q.bound);
 
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;  // this lane's ray
     uint32_t key = 0;        // its RNG key
@@ -87,6 +61,7 @@ __device__ __forceinline__ void radiance_body(const DRadiance &Q) {
     f3 thr = mk(1.f, 1.f, 1.f), rad = mk(0.f, 0.f, 0.f);
     Rng rng;
     rng.k0 = rng.k1 = rng.i = 0;
+    float tmax;              // of the record: a path's first segment has no far end
     Hit h;
     h.kind = 0; h.index = 0; h.t = HRT_FLT_MAX; h.tri = 0; h.a0 = 0.f; h.a1 = 0.f;
     uint32_t parked = 0;     // meshes whose box this lane's ray enters and that are still to be walked
@@ -98,7 +73,7 @@ __device__ __forceinline__ void radiance_body(const DRadiance &Q) {
     auto next_ray = [&]() {
         live = false;
         for (; i < Q.n; i += stride) {
-            if (radiance_ray(Q, i, ray)) {
+            if (query_ray(Q, i, ray, tmax)) {
                 live = true;
                 break;
             }
@@ -106,9 +81,7 @@ __device__ __forceinline__ void radiance_body(const DRadiance &Q) {
         }
         if (live) {
             key = Q.keys ? Q.keys[i] : i;
-            const float olen = length(ray.o);
-            cx.err_abs = fabsf(dot(ray.d, ray.d) - 1.f) <= 1e-5f ? 2e-6f * (Q.bound + olen + 1.f) : __builtin_inff();
-            first_flags = olen > far2 ? (Q.flags | HRT_FLAG_MESH_BRUTE) : Q.flags;
+            query_margin(ray, Q.bound, far, Q.flags, cx.err_abs, first_flags);
             sum = mk(0.f, 0.f, 0.f);
             if (accumulate) { const float *a_ = Q.out + (size_t)i * 3u; sum = mk(a_[0], a_[1], a_[2]); }
             s = 0;
@@ -120,7 +93,7 @@ __device__ __forceinline__ void radiance_body(const DRadiance &Q) {
         // ---- stage A: (re)start a path, spheres + squares, mesh gates
         if (live && stage == 0u) {
             if (remaining == 0) {  // sample first_sample + s of ray i: the caller's ray, RNG stream (seed, key, sample) from draw 3
-                (void)radiance_ray(Q, i, ray);
+                (void)query_ray(Q, i, ray, tmax);
                 rng.start(Q.seed_lo, Q.seed_hi, key, Q.first_sample + s);
                 rng.i = 3u;  // draws 0..2 are the camera's u, v, time
                 cx.flags = first_flags;
@@ -198,13 +171,7 @@ extern "C" __global__ void __launch_bounds__(256) hrt_camera_rays_kernel(const D
                                                                          uint32_t seed_lo, uint32_t seed_hi, float4 *__restrict__ out) {
     const uint32_t pixel = blockIdx.x * blockDim.x + threadIdx.x;
     if (pixel >= w * h) return;
-    const uint32_t px = pixel % w, py = pixel / w;
-    Rng rng;
-    rng.start(seed_lo, seed_hi, pixel, sample);
-    const float u = ((float)px + rng.next()) / (float)w;
-    const float v = ((float)py + rng.next()) / (float)h;
-    const float tm = rng.next();
-    const Ray r = camera_ray<false>(&C, u, v, tm);
+    const Ray r = camera_sample(&C, seed_lo, seed_hi, w, h, pixel, sample);
     out[2u * pixel] = make_float4(r.o.x, r.o.y, r.o.z, r.time);
     out[2u * pixel + 1u] = make_float4(r.d.x, r.d.y, r.d.z, __builtin_inff());
 }
@@ -218,26 +185,14 @@ extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_radiance_ke
 int hrt_trace_radiance(hrt_scene *s, const float *d_rays, const uint32_t *d_keys, uint32_t n, uint32_t first_sample, uint32_t n_samples,
                        uint64_t seed, uint32_t flags, float *d_out, void *stream) {
     const std::string who = "hrt_trace_radiance";
-    const uint32_t known = HRT_FLAG_EXACT_ONLY | HRT_FLAG_MESH_BRUTE | HRT_FLAG_NO_LDS_TREE | HRT_RAYS_NORMALIZE | HRT_RADIANCE_ACCUMULATE;
-    if (flags & ~known) return fail(HRT_ERR_INVALID, who + ": unknown flags bits " + std::to_string(flags & ~known));
-    if ((flags & HRT_FLAG_MESH_BRUTE) && !(flags & HRT_FLAG_EXACT_ONLY)) return fail(HRT_ERR_INVALID, who + ": flags: HRT_FLAG_MESH_BRUTE needs HRT_FLAG_EXACT_ONLY");
-    if (n > 0u) {
-        if (!d_rays) return fail(HRT_ERR_INVALID, who + ": d_rays is NULL");
-        if ((uintptr_t)d_rays % 16u) return fail(HRT_ERR_INVALID, who + ": d_rays is not 16-byte aligned");
-        if (d_keys && (uintptr_t)d_keys % 4u) return fail(HRT_ERR_INVALID, who + ": d_keys is not 4-byte aligned");
-        if (!d_out) return fail(HRT_ERR_INVALID, who + ": d_out is NULL");
-        if ((uintptr_t)d_out % 4u) return fail(HRT_ERR_INVALID, who + ": d_out is not 4-byte aligned");
-    }
-    if (n > 0x7fffffffu) return fail(HRT_ERR_INVALID, who + ": n must be at most 2^31 - 1 (got " + std::to_string(n) + ")");
+    int rc = query_check(who, flags, HRT_RADIANCE_ACCUMULATE, d_rays, d_keys, d_out, 4u, n);
+    if (rc != HRT_OK) return rc;
     if (n_samples == 0u) return fail(HRT_ERR_INVALID, who + ": n_samples must be positive");
     if ((uint64_t)first_sample + n_samples > 0x100000000ull)
         return fail(HRT_ERR_INVALID, who + ": first_sample + n_samples must be at most 2^32 (sample indices do not wrap)");
-    if (!s) return fail(HRT_ERR_INVALID, who + ": scene is NULL");
-    if (!g_rt.ready) return fail(HRT_ERR_STATE, who + ": call hrt_init first");
-    if (n == 0u) return HRT_OK;
-    { const int drc = use_device(s->device); if (drc != HRT_OK) return drc; }
+    rc = enter_scene(who, s, n != 0u);  // also checked for an empty batch, which leaves the current device alone
+    if (rc != HRT_OK || n == 0u) return rc;
     DRadiance Q;
-    Q.scene = s->d_scene;
     Q.rays = (const float4 *)d_rays;
     Q.keys = d_keys;
     Q.out = d_out;
@@ -247,28 +202,14 @@ int hrt_trace_radiance(hrt_scene *s, const float *d_rays, const uint32_t *d_keys
     Q.n_samples = n_samples;
     Q.seed_lo = (uint32_t)seed;
     Q.seed_hi = (uint32_t)(seed >> 32);
-    // The tree prefix is NOT staged by default: measured on MI355X (DESIGN.md section 5 "Radiance queries"), its 36 KiB per workgroup
-    // cost a fifth of the resident waves at 5 waves per SIMD and -12..-16 % on the mesh scenes.  HRT_RADIANCE_STAGE_TREE builds keep
-    // the staged form for A/B runs (HRT_FLAG_NO_LDS_TREE turns it off there).  <= 64 KiB: no attribute to raise.
-#ifdef HRT_RADIANCE_STAGE_TREE
-    Q.lds_units = (flags & HRT_FLAG_NO_LDS_TREE) ? 0u : std::min<uint32_t>(s->lds_units, 4096u);
-#else
-    Q.lds_units = 0u;
-#endif
-    Q.bound = s->bound;
     const bool exact = (flags & HRT_FLAG_EXACT_ONLY) != 0u;
     const bool lights = s->d.n_lights != 0u;
     void (*const k)(const DRadiance) = exact ? (lights ? hrt_radiance_kernel_lights_exact : hrt_radiance_kernel_exact)
                                              : (lights ? hrt_radiance_kernel_lights : hrt_radiance_kernel);
-    const size_t lds_bytes = (size_t)Q.lds_units * 16u;
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k, (int)HRT_RADIANCE_WG, lds_bytes));
-    const uint64_t resident = (uint64_t)std::max(per_cu, 1) * (uint64_t)std::max(g_rt.cus, 1);
-    const uint64_t needed = ((uint64_t)n + HRT_RADIANCE_WG - 1u) / HRT_RADIANCE_WG;
-    const uint32_t grid = (uint32_t)std::min(resident, needed);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(HRT_RADIANCE_WG), lds_bytes, (hipStream_t)stream, Q);
-    HIP_TRY(hipGetLastError());
-    return HRT_OK;
+    // The tree prefix is NOT staged by default: measured on MI355X (DESIGN.md section 5 "Radiance queries"), its 36 KiB per workgroup
+    // cost a fifth of the resident waves at 5 waves per SIMD and -12..-16 % on the mesh scenes.  HRT_RADIANCE_STAGE_TREE builds keep
+    // the staged form for A/B runs (HRT_FLAG_NO_LDS_TREE turns it off there).
+    return query_launch(k, Q, s, HRT_RADIANCE_STAGE_TREE, HRT_RADIANCE_WG, stream);
 }
 
 int hrt_camera_rays(const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t sample, uint64_t seed, float *d_rays, void *stream) {
@@ -276,8 +217,7 @@ int hrt_camera_rays(const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t samp
     if (!cam) return fail(HRT_ERR_INVALID, who + ": cam is NULL");
     DCamera C;
     { const int crc = make_camera(cam, C); if (crc != HRT_OK) return crc; }  // refused as hrt_render refuses it
-    if (!w || !h) return fail(HRT_ERR_INVALID, who + ": w and h must be positive");
-    if ((uint64_t)w * h > 0x7fffffffull) return fail(HRT_ERR_INVALID, who + ": w * h must be at most 2^31 - 1");
+    { const int frc = check_frame(who, w, h, k_max_pixels); if (frc != HRT_OK) return frc; }
     if (!d_rays) return fail(HRT_ERR_INVALID, who + ": d_rays is NULL");
     if ((uintptr_t)d_rays % 16u) return fail(HRT_ERR_INVALID, who + ": d_rays is not 16-byte aligned");
     if (!g_rt.ready) return fail(HRT_ERR_STATE, who + ": call hrt_init first");

@@ -1,5 +1,8 @@
 // Ray queries on caller rays (include/hrt.h hrt_trace_rays): closest hit, closest hit + shading, occlusion.
-// Included by hrt_api.hip inside its extern "C" block, after everything it builds on.
+// Included by hrt_api.hip inside its extern "C" block, after everything it builds on.  What a query on caller rays needs whatever
+// it computes -- the ray record (query_ray), its margin and far-origin rule (query_margin), the context with the staged tree
+// (query_context), and on the host the argument checks and the launch (query_check, query_launch) -- is here once, for this file
+// and for the radiance queries of hrt_radiance.hip.
 //
 // One lane per ray, in a grid-stride loop over the batch: the grid is sized to the workgroups that can be resident at once, so a
 // build with HRT_RAYS_STAGE_TREE can stage the top of the KD-trees (hrt_scene::lds_units nodelets, as trace_body does) into LDS
@@ -14,7 +17,10 @@
 
 #define HRT_RAYS_WG 256u
 #ifndef HRT_RAYS_FAR
-#define HRT_RAYS_FAR 16.f  // an origin farther than this many (scene bound + 1) from the world origin counts as far (see rays_body)
+#define HRT_RAYS_FAR 16.f  // an origin farther than this many (scene bound + 1) from the world origin counts as far (see query_margin)
+#endif
+#ifndef HRT_RAYS_STAGE_TREE
+#define HRT_RAYS_STAGE_TREE 0  // -DHRT_RAYS_STAGE_TREE: the A/B build that stages the tree prefix (see hrt_trace_rays)
 #endif
 
 struct DRays {
@@ -31,6 +37,55 @@ extern "C++" {
 namespace hrtk {
 
 __device__ __forceinline__ bool rays_finite(float v) { return __builtin_isfinite(v); }
+
+// Record i, {o, time} {d, tmax}, of the batch of launch record Q (DRays or DRadiance: its rays and flags) as a Ray and its tmax;
+// false if it is degenerate: a component that is not finite or a zero direction (include/hrt.h hrt_trace_rays).
+// HRT_RAYS_NORMALIZE: the direction goes through the Ray constructor (Line.h:13-16), and a length that under- or overflows is
+// degenerate too.  Q is taken whole, by reference, as the kernels' other helpers take it: handing its fields over by value cost
+// hrt_radiance_kernel 20 more spilled VGPRs.
+template <class QT>
+__device__ __forceinline__ bool query_ray(const QT &Q, uint32_t i, Ray &ray, float &tmax) {
+    const gf4 rays = (gf4)Q.rays;
+    const float4 a = ld(rays, 2u * i), b = ld(rays, 2u * i + 1u);
+    ray.o = mk(a.x, a.y, a.z);
+    ray.time = a.w;
+    ray.d = mk(b.x, b.y, b.z);
+    tmax = b.w;
+    bool ok = rays_finite(a.x) && rays_finite(a.y) && rays_finite(a.z) && rays_finite(a.w) && rays_finite(b.x) &&
+              rays_finite(b.y) && rays_finite(b.z) && !(b.x == 0.f && b.y == 0.f && b.z == 0.f);
+    if (ok && (Q.flags & HRT_RAYS_NORMALIZE)) {
+        ray.d = normalize(ray.d);
+        ok = rays_finite(ray.d.x) && rays_finite(ray.d.y) && rays_finite(ray.d.z) && !(ray.d.x == 0.f && ray.d.y == 0.f && ray.d.z == 0.f);
+    }
+    return ok;
+}
+
+// For a segment that starts at the caller's origin: the filters' margin scale (CtxT::err_abs), and the launch flags with
+// HRT_FLAG_MESH_BRUTE added for an origin farther than `far` from the world origin (every triangle of a gated mesh is tested, no
+// walk).  far = query_far(bound), which a kernel works out once.
+__device__ __forceinline__ float query_far(float bound) { return HRT_RAYS_FAR * (bound + 1.f); }
+__device__ __forceinline__ void query_margin(const Ray &ray, float bound, float far, uint32_t flags, float &err_abs, uint32_t &ray_flags) {
+    const float olen = length(ray.o);
+    err_abs = fabsf(dot(ray.d, ray.d) - 1.f) <= 1e-5f ? margin_scale(bound, olen) : __builtin_inff();
+    ray_flags = olen > far ? (flags | HRT_FLAG_MESH_BRUTE) : flags;
+}
+
+// The context of a query kernel: tables from global memory, the leading lds_units nodelets staged into LDS by the whole workgroup
+// (so every lane of it must call this), MESH_BRUTE honoured per ray.  `stamps`: 17 words of the caller's.
+template <class CX>
+__device__ __forceinline__ void query_context(CX &cx, const DScene *scene, uint32_t lds_units, uint32_t flags, unsigned long long *stamps) {
+    extern __shared__ uint4 s_units[];
+    cx.S = (cscene)scene;
+    cx.set_tables((gf4)cx.S->tabs, (gf1)c_u8_lut, cx.S);
+    cx.lds = (lu4)s_units;
+    cx.lds_n = lds_units;
+    cx.flags = flags;
+    cx.err_abs = 0.f;
+    cx.st = stamps;
+    gu4 g_units = (gu4)cx.S->kd_units;
+    for (uint32_t i = threadIdx.x; i < cx.lds_n; i += blockDim.x) s_units[i] = ld(g_units, i);
+    __syncthreads();
+}
 
 // Scene::computeShadow (Scene.h:235-255) with every transparency 0: some object's own hit -- the value closest_hit compares for
 // it -- lies in [EPSILON, tmax).  Objects in closest_hit's order, first one in range ends the query.  A mesh's own hit is its
@@ -77,40 +132,16 @@ __device__ __forceinline__ bool rays_occluded(const CX &cx, const Ray &ray, floa
 // MODE: HRT_QUERY_CLOSEST, HRT_QUERY_SHADE or HRT_QUERY_OCCLUDED.  EXACT: the proof build (HRT_FLAG_EXACT_ONLY).
 template <uint32_t MODE, bool EXACT>
 __device__ __forceinline__ void rays_body(const DRays &Q) {
-    extern __shared__ uint4 s_units[];
     CtxT<EXACT, false, false, true> cx;
-    cx.S = (cscene)Q.scene;
-    cx.set_tables((gf4)cx.S->tabs, (gf1)c_u8_lut, cx.S);
-    cx.lds = (lu4)s_units;
-    cx.lds_n = Q.lds_units;
-    cx.flags = Q.flags;
     unsigned long long stamps_local[17] = {0};
-    cx.st = stamps_local;
-    {
-        gu4 g_units = (gu4)cx.S->kd_units;
-        for (uint32_t i = threadIdx.x; i < cx.lds_n; i += blockDim.x) s_units[i] = ld(g_units, i);
-    }
-    __syncthreads();
-    const gf4 rays = (gf4)Q.rays;
+    query_context(cx, Q.scene, Q.lds_units, Q.flags, stamps_local);
     const uint32_t stride = gridDim.x * blockDim.x;
+    const float far = query_far(Q.bound);
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < Q.n; i += stride) {
-        const float4 a = ld(rays, 2u * i), b = ld(rays, 2u * i + 1u);
         Ray ray;
-        ray.o = mk(a.x, a.y, a.z);
-        ray.time = a.w;
-        ray.d = mk(b.x, b.y, b.z);
-        const float tmax = b.w;
-        bool ok = rays_finite(a.x) && rays_finite(a.y) && rays_finite(a.z) && rays_finite(a.w) && rays_finite(b.x) &&
-                  rays_finite(b.y) && rays_finite(b.z) && !(b.x == 0.f && b.y == 0.f && b.z == 0.f) && tmax > 0.f;
-        if (ok && (Q.flags & HRT_RAYS_NORMALIZE)) {  // the Ray constructor (Line.h:13-16); a length that under- or overflows is degenerate
-            ray.d = normalize(ray.d);
-            ok = rays_finite(ray.d.x) && rays_finite(ray.d.y) && rays_finite(ray.d.z) && !(ray.d.x == 0.f && ray.d.y == 0.f && ray.d.z == 0.f);
-        }
-        const float a2 = dot(ray.d, ray.d);
-        const float olen = length(ray.o);
-        cx.err_abs = fabsf(a2 - 1.f) <= 1e-5f ? 2e-6f * (Q.bound + olen + 1.f) : __builtin_inff();
-        // an origin far outside the scene: every triangle of a gated mesh is tested (mesh_brute), no walk
-        cx.flags = (olen > HRT_RAYS_FAR * (Q.bound + 1.f)) ? (Q.flags | HRT_FLAG_MESH_BRUTE) : Q.flags;
+        float tmax;
+        const bool ok = query_ray(Q, i, ray, tmax) && tmax > 0.f;  // a tmax that is NaN or <= 0 is degenerate here
+        query_margin(ray, Q.bound, far, Q.flags, cx.err_abs, cx.flags);
         if (MODE == HRT_QUERY_OCCLUDED) {
             const bool occ = ok && rays_occluded(cx, ray, fminf(tmax, HRT_FLT_MAX));
             ((uint32_t *)Q.out)[i] = occ ? 1u : 0u;
@@ -153,50 +184,59 @@ extern "C" __global__ void __launch_bounds__(HRT_RAYS_WG) hrt_rays_closest_exact
 extern "C" __global__ void __launch_bounds__(HRT_RAYS_WG) hrt_rays_shade_exact_kernel(const DRays Q) { rays_body<HRT_QUERY_SHADE, true>(Q); }
 extern "C" __global__ void __launch_bounds__(HRT_RAYS_WG) hrt_rays_occluded_exact_kernel(const DRays Q) { rays_body<HRT_QUERY_OCCLUDED, true>(Q); }
 
-int hrt_trace_rays(hrt_scene *s, const float *d_rays, uint32_t n, uint32_t mode, uint32_t flags, void *d_out, void *stream) {
-    const std::string who = "hrt_trace_rays";
-    if (mode > HRT_QUERY_OCCLUDED) return fail(HRT_ERR_INVALID, who + ": mode must be HRT_QUERY_CLOSEST, _SHADE or _OCCLUDED (got " + std::to_string(mode) + ")");
-    const uint32_t known = HRT_FLAG_EXACT_ONLY | HRT_FLAG_MESH_BRUTE | HRT_FLAG_NO_LDS_TREE | HRT_RAYS_NORMALIZE;
+// The checks hrt_trace_rays and hrt_trace_radiance share, in their order: the flags (the common ones and the entry point's
+// `extra` bits), the pointers when there is a ray to read (d_keys may be NULL; d_out aligned to out_align bytes), the batch size.
+static int query_check(const std::string &who, uint32_t flags, uint32_t extra, const void *d_rays, const void *d_keys, const void *d_out,
+                       uintptr_t out_align, uint32_t n) {
+    const uint32_t known = HRT_FLAG_EXACT_ONLY | HRT_FLAG_MESH_BRUTE | HRT_FLAG_NO_LDS_TREE | HRT_RAYS_NORMALIZE | extra;
     if (flags & ~known) return fail(HRT_ERR_INVALID, who + ": unknown flags bits " + std::to_string(flags & ~known));
-    if ((flags & HRT_FLAG_MESH_BRUTE) && !(flags & HRT_FLAG_EXACT_ONLY)) return fail(HRT_ERR_INVALID, who + ": flags: HRT_FLAG_MESH_BRUTE needs HRT_FLAG_EXACT_ONLY");
+    { const int brc = check_mesh_brute(who, flags); if (brc != HRT_OK) return brc; }
     if (n > 0u) {
         if (!d_rays) return fail(HRT_ERR_INVALID, who + ": d_rays is NULL");
         if ((uintptr_t)d_rays % 16u) return fail(HRT_ERR_INVALID, who + ": d_rays is not 16-byte aligned");
+        if ((uintptr_t)d_keys % 4u) return fail(HRT_ERR_INVALID, who + ": d_keys is not 4-byte aligned");
         if (!d_out) return fail(HRT_ERR_INVALID, who + ": d_out is NULL");
-        const uintptr_t align = mode == HRT_QUERY_OCCLUDED ? 4u : 16u;
-        if ((uintptr_t)d_out % align) return fail(HRT_ERR_INVALID, who + ": d_out is not " + std::to_string(align) + "-byte aligned");
+        if ((uintptr_t)d_out % out_align) return fail(HRT_ERR_INVALID, who + ": d_out is not " + std::to_string(out_align) + "-byte aligned");
     }
     if (n > 0x7fffffffu) return fail(HRT_ERR_INVALID, who + ": n must be at most 2^31 - 1 (got " + std::to_string(n) + ")");
-    if (!s) return fail(HRT_ERR_INVALID, who + ": scene is NULL");
-    if (!g_rt.ready) return fail(HRT_ERR_STATE, who + ": call hrt_init first");
-    if (n == 0u) return HRT_OK;
-    { const int drc = use_device(s->device); if (drc != HRT_OK) return drc; }
-    DRays Q;
+    return HRT_OK;
+}
+
+// Launches query kernel k over the Q.n rays of Q (DRays or DRadiance; the scene entered), one lane per ray in a grid-stride loop.
+// stage_tree: the workgroups stage the top of the KD-trees into LDS (unless HRT_FLAG_NO_LDS_TREE) -- at most 64 KiB, so there is
+// no attribute to raise.  The grid is the workgroups that can be resident at once, or as many as the batch fills.
+extern "C++" {
+template <class QT>
+static int query_launch(void (*k)(const QT), QT &Q, const hrt_scene *s, bool stage_tree, uint32_t wg, void *stream) {
     Q.scene = s->d_scene;
+    Q.bound = s->bound;
+    Q.lds_units = (stage_tree && !(Q.flags & HRT_FLAG_NO_LDS_TREE)) ? std::min<uint32_t>(s->lds_units, 4096u) : 0u;
+    const size_t lds_bytes = (size_t)Q.lds_units * 16u;
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k, (int)wg, lds_bytes));
+    const uint64_t resident = (uint64_t)std::max(per_cu, 1) * (uint64_t)std::max(g_rt.cus, 1);
+    const uint64_t needed = ((uint64_t)Q.n + wg - 1u) / wg;
+    hipLaunchKernelGGL(k, dim3((uint32_t)std::min(resident, needed)), dim3(wg), lds_bytes, (hipStream_t)stream, Q);
+    HIP_TRY(hipGetLastError());
+    return HRT_OK;
+}
+}  // extern "C++"
+
+int hrt_trace_rays(hrt_scene *s, const float *d_rays, uint32_t n, uint32_t mode, uint32_t flags, void *d_out, void *stream) {
+    const std::string who = "hrt_trace_rays";
+    if (mode > HRT_QUERY_OCCLUDED) return fail(HRT_ERR_INVALID, who + ": mode must be HRT_QUERY_CLOSEST, _SHADE or _OCCLUDED (got " + std::to_string(mode) + ")");
+    int rc = query_check(who, flags, 0u, d_rays, nullptr, d_out, mode == HRT_QUERY_OCCLUDED ? 4u : 16u, n);
+    if (rc == HRT_OK) rc = enter_scene(who, s, n != 0u);  // also checked for an empty batch, which leaves the current device alone
+    if (rc != HRT_OK || n == 0u) return rc;
+    DRays Q;
     Q.rays = (const float4 *)d_rays;
     Q.out = d_out;
     Q.n = n;
     Q.flags = flags;
-    // The tree prefix is NOT staged by default: measured on MI355X (DESIGN.md section 5 "Ray queries"), staging it costs more than it
-    // saves for CLOSEST and OCCLUDED (-10..-15 %) and is even for SHADE.  HRT_RAYS_STAGE_TREE builds keep the staged form for A/B runs.
-#ifdef HRT_RAYS_STAGE_TREE
-    Q.lds_units = (flags & HRT_FLAG_NO_LDS_TREE) ? 0u : std::min<uint32_t>(s->lds_units, 4096u);  // <= 64 KiB: no attribute to raise
-#else
-    Q.lds_units = 0u;
-#endif
-    Q.bound = s->bound;
-    const bool exact = (flags & HRT_FLAG_EXACT_ONLY) != 0u;
     void (*const kernels[2][3])(const DRays) = {
         {hrt_rays_closest_kernel, hrt_rays_shade_kernel, hrt_rays_occluded_kernel},
         {hrt_rays_closest_exact_kernel, hrt_rays_shade_exact_kernel, hrt_rays_occluded_exact_kernel}};
-    void (*const k)(const DRays) = kernels[exact ? 1 : 0][mode];
-    const size_t lds_bytes = (size_t)Q.lds_units * 16u;
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k, (int)HRT_RAYS_WG, lds_bytes));
-    const uint64_t resident = (uint64_t)std::max(per_cu, 1) * (uint64_t)std::max(g_rt.cus, 1);
-    const uint64_t needed = ((uint64_t)n + HRT_RAYS_WG - 1u) / HRT_RAYS_WG;
-    const uint32_t grid = (uint32_t)std::min(resident, needed);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(HRT_RAYS_WG), lds_bytes, (hipStream_t)stream, Q);
-    HIP_TRY(hipGetLastError());
-    return HRT_OK;
+    // The tree prefix is NOT staged by default: measured on MI355X (DESIGN.md section 5 "Ray queries"), staging it costs more than it
+    // saves for CLOSEST and OCCLUDED (-10..-15 %) and is even for SHADE.  HRT_RAYS_STAGE_TREE builds keep the staged form for A/B runs.
+    return query_launch(kernels[(flags & HRT_FLAG_EXACT_ONLY) ? 1 : 0][mode], Q, s, HRT_RAYS_STAGE_TREE, HRT_RAYS_WG, stream);
 }

@@ -1,7 +1,7 @@
 """NumPy statement of the variance-guided denoiser of include/hrt.h (hrt_denoise_var): demodulate both frames, variance of the
 mean, prefilter, a-trous iterations that carry the variance, remodulate.
 
-Every step is fp32 in the order the header writes it down (and csrc/hrt_denoise_var.hip evaluates it), so the device result agrees
+Every step is fp32 in the order the header writes it down (and csrc/hrt_denoise.hip evaluates it), so the device result agrees
 with this one to the rounding of expf / pow alone.  Arrays: colour and half colour (h, w, 3), features (h, w, 12) float32."""
 import numpy as np
 

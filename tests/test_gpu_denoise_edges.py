@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 F32 = np.float32
 INF = np.inf
 FMAX = np.finfo(F32).max
-LIMIT = 0x7FFFFFFF // 16  # the largest pixel count dn_check_size admits
+LIMIT = 0x7FFFFFFF // 16  # the largest pixel count the denoiser's frame-size check admits
 
 
 def dev_denoise(gpu, c, f, iterations, flags=0, stream=None, **params):
