@@ -140,6 +140,16 @@ class DenoiseVarParams(C.Structure):
         super().__init__(iterations, prefilter, sigma_variance, sigma_normal, sigma_albedo, sigma_depth, variance_floor)
 
 
+class TemporalParams(C.Structure):
+    """``hrt_temporal_params``: the floor of the current frame's blend weight, the history length at which accumulation saturates,
+    and what a reprojected tap may differ by in relative depth, |normal difference|^2 and |albedo difference|^2 (include/hrt.h)."""
+    _fields_ = [("alpha_min", C.c_float), ("max_history", C.c_float), ("depth_tol", C.c_float), ("normal_tol", C.c_float),
+                ("albedo_tol", C.c_float)]
+
+    def __init__(self, alpha_min=0.02, max_history=64.0, depth_tol=0.05, normal_tol=0.1, albedo_tol=0.05):
+        super().__init__(alpha_min, max_history, depth_tol, normal_tol, albedo_tol)
+
+
 def _load(name: str) -> C.CDLL:
     path = os.path.join(_HERE, name)
     if not os.path.exists(path):
@@ -240,6 +250,16 @@ def device_lib() -> C.CDLL:
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.hrt_render_denoised_var.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                                 C.c_uint32, C.POINTER(DenoiseVarParams), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_temporal_accumulate.argtypes = [C.POINTER(Camera), C.POINTER(Camera), C.c_uint32, C.c_uint32] + [C.c_void_p] * 7 + \
+                                              [C.POINTER(TemporalParams)] + [C.c_void_p] * 4
+        lib.hrt_history_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        lib.hrt_history_reset.argtypes = [C.c_void_p]
+        lib.hrt_history_reset.restype = None
+        lib.hrt_history_destroy.argtypes = [C.c_void_p]
+        lib.hrt_history_destroy.restype = None
+        lib.hrt_render_temporal.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            C.c_uint64, C.c_uint32, C.POINTER(TemporalParams), C.POINTER(DenoiseVarParams), C.c_void_p,
+                                            C.c_void_p, C.POINTER(Stats)]
         lib.hrt_debug_kat.argtypes = [C.c_uint32, C.POINTER(Camera), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.hrt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.hrt_trace_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
@@ -482,6 +502,21 @@ class DeviceScene:
                                                       None if stats is None else C.byref(stats)))
         return (out, var) if variance else out
 
+    def render_temporal(self, history: "History", cam: Camera, w: int, h: int, spp: int, feature_spp: int, seed: int = 1, flags: int = 0,
+                        tparams: Optional[TemporalParams] = None, dparams: Optional[DenoiseVarParams] = None,
+                        stats: Optional[Stats] = None):
+        """hrt_render_temporal: one frame of the frame loop -> (frame (h, w, 3) float32, history lengths (h, w) float32).  The frame
+        of ``spp`` samples (even) is accumulated onto what ``history`` holds, reprojected from its camera, and the history is
+        updated; with ``dparams`` the accumulated pair goes through the variance-guided filter, without it the accumulated frame
+        is returned.  Pass a different ``seed`` every frame.  ``tparams`` None: the default TemporalParams."""
+        out = np.empty((h, w, 3), dtype=np.float32)
+        hist = np.empty((h, w), dtype=np.float32)
+        tp = TemporalParams() if tparams is None else tparams
+        self._check(self._lib.hrt_render_temporal(self._h, history._h, C.byref(cam), w, h, spp, feature_spp, seed, flags, C.byref(tp),
+                                                  None if dparams is None else C.byref(dparams), out.ctypes.data, hist.ctypes.data,
+                                                  None if stats is None else C.byref(stats)))
+        return out, hist
+
     def trace_rays(self, rays, mode: str = "closest", flags: int = 0, normalize: bool = False):
         """hrt_trace_rays: the scene traced with caller rays, (n, RAY_FLOATS) float32 rows {o, time, d, tmax}.
 
@@ -595,6 +630,31 @@ class DeviceScene:
         ms = C.c_double()
         self._check(self._lib.hrt_last_kernel_ms(self._h, C.byref(ms)))
         return ms.value
+
+
+class History:
+    """``hrt_history``: what one frame of DeviceScene.render_temporal hands to the next, on the scene's device."""
+
+    def __init__(self, scene: DeviceScene):
+        self._lib = scene._lib
+        self._scene = scene  # the history must not outlive its scene
+        self._h = C.c_void_p()
+        scene._check(self._lib.hrt_history_create(scene._h, C.byref(self._h)))
+
+    def reset(self):
+        """The next frame restarts everywhere."""
+        self._lib.hrt_history_reset(self._h)
+
+    def close(self):
+        if self._h:
+            self._lib.hrt_history_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 KAT_CAMERA, KAT_TRIANGLE, KAT_AABB, KAT_SPHERE, KAT_QUAD, KAT_OPTICS, KAT_NORMALIZE = range(7)
@@ -755,6 +815,23 @@ def denoise_var(d_color_ptr: int, d_color_half_ptr: int, d_features_ptr: int, w:
                              C.c_void_p(d_scratch_ptr), C.c_void_p(d_out_ptr), C.c_void_p(d_variance_out_ptr), C.c_void_p(stream_ptr))
     if rc < 0:
         raise HrtError(f"hrt_denoise_var failed ({rc}): {lib.hrt_last_error().decode()}")
+
+
+def temporal_accumulate(cam: Camera, prev_cam: Optional[Camera], w: int, h: int, d_color_ptr: int, d_color_half_ptr: int, d_features_ptr: int,
+                        d_prev_color_ptr: int, d_prev_color_half_ptr: int, d_prev_features_ptr: int, d_prev_history_ptr: int,
+                        params: Optional[TemporalParams], d_out_ptr: int, d_out_half_ptr: int, d_history_out_ptr: int, stream_ptr: int = 0):
+    """hrt_temporal_accumulate on device pointers (asynchronous on the stream): the current frame's linear means, first-half means
+    (0: none) and features, the previous call's outputs with the features and camera of that frame (``prev_cam`` None and 0s: the
+    first frame) -> accumulated colour, half colour and history lengths.  ``params`` None: the default TemporalParams."""
+    lib = device_lib()
+    p = TemporalParams() if params is None else params
+    ptr = lambda v: C.c_void_p(v) if v else None
+    rc = lib.hrt_temporal_accumulate(C.byref(cam), None if prev_cam is None else C.byref(prev_cam), w, h, ptr(d_color_ptr),
+                                     ptr(d_color_half_ptr), ptr(d_features_ptr), ptr(d_prev_color_ptr), ptr(d_prev_color_half_ptr),
+                                     ptr(d_prev_features_ptr), ptr(d_prev_history_ptr), C.byref(p), ptr(d_out_ptr), ptr(d_out_half_ptr),
+                                     ptr(d_history_out_ptr), C.c_void_p(stream_ptr))
+    if rc < 0:
+        raise HrtError(f"hrt_temporal_accumulate failed ({rc}): {lib.hrt_last_error().decode()}")
 
 
 def encode_ppm(d_frame_ptr: int, w: int, h: int, fmt: int, d_out_ptr: int, capacity: int, stream_ptr: int = 0) -> int:

@@ -19,6 +19,7 @@
 #include <cstddef>
 #include <cstring>
 #include <functional>
+#include <new>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -1484,6 +1485,7 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 #include "hrt_multi.hip"
 #include "hrt_adaptive.hip"
 #include "hrt_denoise.hip"
+#include "hrt_temporal.hip"
 #include "hrt_rays.hip"
 #include "hrt_radiance.hip"
 

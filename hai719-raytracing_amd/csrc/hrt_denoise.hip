@@ -85,6 +85,12 @@ __device__ __forceinline__ bool dn_finite(float v) { return __builtin_isfinite(v
 __device__ __forceinline__ float dn_div(float a, float d) { return d > 0.f ? a / d : a; }  // demodulation divisor: albedo if > 0, else 1
 // One term of the exponent: 0 when the difference is 0 or the term is switched off (den = +inf), else num / den.
 __device__ __forceinline__ float dn_term(float num, float den) { return (num == 0.f || den == __builtin_inff()) ? 0.f : num / den; }
+// Steps 1 and 3 of THE FILTER for one channel (albedo a, e6 = emission / 6), shared with hrt_temporal.hip: x = (c - e/6) / d and back.
+__device__ __forceinline__ float dn_demodulate(float c, float e6, float a) { return dn_div(c - e6, a); }
+__device__ __forceinline__ float dn_remodulate(float y, float e, float a) {
+    const float d = a > 0.f ? a : 1.f;
+    return d * y + e / 6.f;
+}
 
 // The arguments of one pass of the filter over the colour records xin, the same list for every pass kernel.  cw: the colour term's
 // denominator sigma_c^2, or variance-guided sigma_v^2, which the pair's variances and vfloor then scale.  A pass that is not the
@@ -107,12 +113,12 @@ __device__ __forceinline__ void dn_prep(const float *__restrict__ color, const f
     const float *c = color + (size_t)i * 3u;
     const float a0 = f[0], a1 = f[1], a2 = f[2];
     const float e0 = f[6] / 6.f, e1 = f[7] / 6.f, e2 = f[8] / 6.f;
-    float x0 = dn_div(c[0] - e0, a0), x1 = dn_div(c[1] - e1, a1), x2 = dn_div(c[2] - e2, a2);
+    float x0 = dn_demodulate(c[0], e0, a0), x1 = dn_demodulate(c[1], e1, a1), x2 = dn_demodulate(c[2], e2, a2);
     bool ok = dn_finite(x0) && dn_finite(x1) && dn_finite(x2);
     float v = 0.f;
     if (VAR) {
         const float *ch = half + (size_t)i * 3u;
-        const float h0 = dn_div(ch[0] - e0, a0), h1 = dn_div(ch[1] - e1, a1), h2 = dn_div(ch[2] - e2, a2);
+        const float h0 = dn_demodulate(ch[0], e0, a0), h1 = dn_demodulate(ch[1], e1, a1), h2 = dn_demodulate(ch[2], e2, a2);
         ok = ok && dn_finite(h0) && dn_finite(h1) && dn_finite(h2);
         const float d0 = x0 - h0, d1 = x1 - h1, d2 = x2 - h2;
         v = (d0 * d0 + d1 * d1) + d2 * d2;
@@ -198,8 +204,7 @@ __device__ __forceinline__ void dn_pass(HRT_DN_PASS_PARAMS) {
     float r[3] = {y.x, y.y, y.z};
     bool fin = true;
     for (int k = 0; k < 3; ++k) {
-        const float d = f[k] > 0.f ? f[k] : 1.f;
-        r[k] = d * r[k] + f[6 + k] / 6.f;
+        r[k] = dn_remodulate(r[k], f[6 + k], f[k]);
         fin = fin && dn_finite(r[k]);
     }
     for (int k = 0; k < 3; ++k) {
@@ -346,9 +351,33 @@ int hrt_render_features(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
     return features_launch(s, cam, w, h, first_sample, n_samples, seed, d_features, (hipStream_t)stream);
 }
 
+// The linear frame of hrt_render at spp samples (even) and the frame of its first half, row-major on the device: sums of samples
+// [0, spp/2), a copy of them, then [spp/2, spp) on top -- the full sums are hrt_render's, bit for bit -- both finalised without
+// gamma, every launch checked.  The scene's tile buffers are the scratch (grown here); ms_half: the first launch's kernel time.
+static int dn_render_pair(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed, uint32_t lin,
+                          float *d_frame, float *d_frame_half, double *ms_half) {
+    const uint32_t tiles = hrt_tiles_total(w, h), half = spp / 2u;
+    const size_t tile_bytes = (size_t)tiles * 64 * 3 * sizeof(float);
+    int rc = s->tiles.grow(tile_bytes);
+    if (rc == HRT_OK) rc = s->dnv_half_tiles.grow(tile_bytes);
+    if (rc != HRT_OK) return rc;
+    float *const d_tiles = s->tiles.as<float>(), *const d_half = s->dnv_half_tiles.as<float>();
+    HIP_TRY(hipMemsetAsync(d_tiles, 0, tile_bytes, nullptr));
+    rc = hrt_render_accumulate(s, cam, w, h, 0, half, seed, lin, 0, 1, d_tiles, nullptr);
+    if (rc == HRT_OK) rc = hrt_last_kernel_ms(s, ms_half);  // waits for the launch and checks it (hrt_check_last_launch)
+    if (rc != HRT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(d_half, d_tiles, tile_bytes, hipMemcpyDeviceToDevice, nullptr));
+    rc = hrt_render_accumulate(s, cam, w, h, half, spp - half, seed, lin, 0, 1, d_tiles, nullptr);
+    if (rc == HRT_OK) rc = hrt_check_last_launch(s);  // never denoise a frame the kernel did not finish
+    if (rc == HRT_OK) rc = hrt_finalize_tiles(d_half, tiles, half, 0, d_half, nullptr);
+    if (rc == HRT_OK) rc = hrt_finalize_tiles(d_tiles, tiles, spp, 0, d_tiles, nullptr);
+    if (rc == HRT_OK) rc = hrt_assemble_frame(d_half, tiles, w, h, 1, d_frame_half, nullptr);
+    if (rc == HRT_OK) rc = hrt_assemble_frame(d_tiles, tiles, w, h, 1, d_frame, nullptr);
+    return rc;
+}
+
 // hrt_render_denoised and hrt_render_denoised_var after their checks of the parameters, the frame size and spp.  The frame is
-// hrt_render's at spp samples, linear.  F.var: it is rendered as sums of samples [0, spp/2), a copy of them, then [spp/2, spp) on
-// top -- the full sums are hrt_render's, bit for bit -- and the copy becomes the first half's frame.
+// hrt_render's at spp samples, linear; F.var: with the first half's frame beside it (dn_render_pair).
 static int dn_render(const std::string &who, hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp,
                      uint64_t seed, uint32_t flags, const DnFilter &F, float *out_rgb, float *out_variance, hrt_stats *stats) {
     if (feature_spp > spp) return fail(HRT_ERR_INVALID, who + ": feature_spp must be at most spp (got " + std::to_string(feature_spp) + " > " + std::to_string(spp) + ")");
@@ -360,28 +389,16 @@ static int dn_render(const std::string &who, hrt_scene *s, const hrt_camera *cam
     const uint32_t tiles = hrt_tiles_total(w, h), lin = flags & ~(uint32_t)HRT_FLAG_GAMMA;
     const size_t npix = (size_t)w * h, tile_bytes = (size_t)tiles * 64 * 3 * sizeof(float);
     if ((rc = s->tiles.grow(tile_bytes)) != HRT_OK) return rc;
-    if (F.var && (rc = s->dnv_half_tiles.grow(tile_bytes)) != HRT_OK) return rc;
     if ((rc = s->dn_frame.grow(npix * 3 * sizeof(float))) != HRT_OK) return rc;
     if (F.var && (rc = s->dnv_frame_half.grow(npix * 3 * sizeof(float))) != HRT_OK) return rc;
     if ((rc = s->dn_feat.grow(npix * HRT_FEATURE_FLOATS * sizeof(float))) != HRT_OK) return rc;
     if ((rc = s->dn_scratch.grow(hrt_denoise_scratch_bytes(w, h))) != HRT_OK) return rc;
     if ((rc = s->dn_out.grow(npix * 3 * sizeof(float))) != HRT_OK) return rc;
     if (out_variance && (rc = s->dnv_var.grow(npix * sizeof(float))) != HRT_OK) return rc;
-    float *const d_tiles = s->tiles.as<float>(), *const d_half = s->dnv_half_tiles.as<float>();
+    float *const d_tiles = s->tiles.as<float>();
     double ms_half = 0.0;
     if (F.var) {
-        const uint32_t half = spp / 2u;
-        HIP_TRY(hipMemsetAsync(d_tiles, 0, tile_bytes, nullptr));
-        rc = hrt_render_accumulate(s, cam, w, h, 0, half, seed, lin, 0, 1, d_tiles, nullptr);
-        if (rc == HRT_OK) rc = hrt_last_kernel_ms(s, &ms_half);  // waits for the launch and checks it (hrt_check_last_launch)
-        if (rc != HRT_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(d_half, d_tiles, tile_bytes, hipMemcpyDeviceToDevice, nullptr));
-        rc = hrt_render_accumulate(s, cam, w, h, half, spp - half, seed, lin, 0, 1, d_tiles, nullptr);
-        if (rc == HRT_OK) rc = hrt_check_last_launch(s);  // never denoise a frame the kernel did not finish
-        if (rc == HRT_OK) rc = hrt_finalize_tiles(d_half, tiles, half, 0, d_half, nullptr);
-        if (rc == HRT_OK) rc = hrt_finalize_tiles(d_tiles, tiles, spp, 0, d_tiles, nullptr);
-        if (rc == HRT_OK) rc = hrt_assemble_frame(d_half, tiles, w, h, 1, s->dnv_frame_half.as<float>(), nullptr);
-        if (rc == HRT_OK) rc = hrt_assemble_frame(d_tiles, tiles, w, h, 1, s->dn_frame.as<float>(), nullptr);
+        rc = dn_render_pair(s, cam, w, h, spp, seed, lin, s->dn_frame.as<float>(), s->dnv_frame_half.as<float>(), &ms_half);
     } else {
         rc = hrt_render_tiles(s, cam, w, h, spp, seed, lin, 0, 1, d_tiles, nullptr);
         if (rc == HRT_OK) rc = hrt_assemble_frame(d_tiles, tiles, w, h, 1, s->dn_frame.as<float>(), nullptr);

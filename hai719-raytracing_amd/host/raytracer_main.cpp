@@ -14,7 +14,13 @@
 //                                                  parameters and N iterations (one GPU)
 //             [--denoise-var FEATURE_SPP [--denoise-iters N]] variance-guided denoised frame (hrt_render_denoised_var): --spp samples
 //                                                  (even), the colour width of every pair of pixels set by the noise of their own means (one GPU)
+//             [--temporal FRAMES [--orbit DEGREES] [--denoise-var FEATURE_SPP]] FRAMES frames of --spp samples (even) with seeds seed,
+//                                                  seed + 1, ..., each accumulated onto the reprojected last one (hrt_render_temporal); the
+//                                                  camera turns about the scene's up axis by DEGREES / FRAMES per frame; with --denoise-var
+//                                                  every frame's accumulated pair goes through the variance-guided filter; the last
+//                                                  frame is written (one GPU)
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -40,10 +46,59 @@ static uint32_t feature_spp = 0;
 static hrt_denoise_params denoise_params = {4u, 8.0f, 0.05f, 0.4f, 0.05f};
 static bool denoise_var = false;  // --denoise-var: hrt_render_denoised_var with the default parameters (the Python DenoiseVarParams())
 static hrt_denoise_var_params denoise_var_params = {4u, 2u, 8.0f, 0.05f, 0.4f, 0.05f, 1e-8f};
+static uint32_t temporal_frames = 0;  // --temporal: hrt_render_temporal over that many frames, the default hrt_temporal_params
+static double orbit_degrees = 0.0;    // --orbit: the camera's turn about the up axis over the whole run
+static hrt_temporal_params temporal_params = {0.02f, 64.f, 0.05f, 0.1f, 0.05f};  // the Python TemporalParams()
 
 // Drop-in for ray_trace_from_camera(): same inputs (current scene, nsamples, window size, camera),
 // same output file and quantisation; returns non-zero instead of printing-and-returning on failure.
 static hrt_multi *multi = nullptr;  // --gpus / --devices: the same frame, tiles across several GPUs
+
+// cam turned by `degrees` about the world's up axis (y) through the origin
+static hrt_camera orbited(const hrt_camera &cam, double degrees) {
+    const double a = degrees * M_PI / 180.0, c = std::cos(a), s = std::sin(a);
+    hrt_camera out = cam;
+    const float *from[4] = {cam.eye, cam.right, cam.up, cam.forward};
+    float *to[4] = {out.eye, out.right, out.up, out.forward};
+    for (int k = 0; k < 4; ++k) {
+        to[k][0] = (float)(c * from[k][0] + s * from[k][2]);
+        to[k][2] = (float)(-s * from[k][0] + c * from[k][2]);
+    }
+    return out;
+}
+
+// --temporal: the frame loop.  Frame k has seed + k and the camera turned by k * orbit / frames; the last frame is written.
+static int ray_trace_frames() {
+    const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
+    std::vector<float> image((size_t)w * h * 3, 0.f), lengths((size_t)w * h, 0.f);
+    const hrt_camera cam0 = default_camera((float)w / (float)h);
+    std::cout << "Ray tracing " << temporal_frames << " frames of a " << w << " x " << h << " image on the GPU using " << nsamples
+              << " samples per pixel each, accumulated over time (orbit " << orbit_degrees << " degrees)"
+              << (denoise_var ? ", denoised by variance (features of " + std::to_string(feature_spp) + " samples, " + std::to_string(denoise_var_params.iterations) + " iterations)" : std::string())
+              << std::endl;
+    hrt_history *history = nullptr;
+    int rc = hrt_history_create(device_scene, &history);
+    double kernel_ms = 0.0, total_ms = 0.0;
+    for (uint32_t k = 0; rc == HRT_OK && k < temporal_frames; ++k) {
+        const hrt_camera cam = orbited(cam0, orbit_degrees * (double)k / (double)temporal_frames);
+        hrt_stats st;
+        rc = hrt_render_temporal(device_scene, history, &cam, w, h, nsamples, denoise_var ? feature_spp : 0u, seed + k, HRT_FLAG_GAMMA, &temporal_params,
+                                 denoise_var ? &denoise_var_params : nullptr, image.data(), lengths.data(), &st);
+        if (rc == HRT_OK) { kernel_ms += st.kernel_ms; total_ms += st.total_ms; }
+    }
+    hrt_history_destroy(history);
+    if (rc != HRT_OK) {
+        std::cout << "hrt_render_temporal failed: " << hrt_last_error() << std::endl;
+        return rc;
+    }
+    double mean = 0.0;
+    for (float v : lengths) mean += v;
+    std::cout << "  Done in " << total_ms / 1000.0 << " seconds (kernels " << kernel_ms << " ms, mean history of the last frame "
+              << mean / (double)lengths.size() << " frames)" << std::endl;
+    rc = hrt_write_ppm(out_path.c_str(), image.data(), w, h);
+    if (rc != HRT_OK) std::cout << hrt_last_error() << std::endl;
+    return rc;
+}
 
 static int ray_trace_from_camera() {
     const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
@@ -98,6 +153,8 @@ int main(int argc, char **argv) {
         else if (k == "--denoise") { denoise = true; feature_spp = (uint32_t)strtoul(v.c_str(), nullptr, 10); }
         else if (k == "--denoise-var") { denoise_var = true; feature_spp = (uint32_t)strtoul(v.c_str(), nullptr, 10); }
         else if (k == "--denoise-iters") denoise_params.iterations = denoise_var_params.iterations = (uint32_t)strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--temporal") temporal_frames = (uint32_t)strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--orbit") orbit_degrees = strtod(v.c_str(), nullptr);
         else if (k == "--gpus") { devices.clear(); for (int d = 0; d < atoi(v.c_str()); ++d) devices.push_back(d); }
         else if (k == "--devices") {
             devices.clear();
@@ -133,6 +190,19 @@ int main(int argc, char **argv) {
         std::cerr << "--denoise-var compares the two halves of the samples: --spp must be even and at least 2" << std::endl;
         return 2;
     }
+    const bool temporal = temporal_frames != 0u;
+    if (temporal && (adaptive || denoise || !devices.empty())) {
+        std::cerr << "--temporal accumulates uniform renders on one GPU: it cannot be combined with --adaptive, --denoise or --gpus / --devices (--denoise-var is its filter)" << std::endl;
+        return 2;
+    }
+    if (temporal && (nsamples < 2u || (nsamples & 1u))) {
+        std::cerr << "--temporal keeps the two halves of every frame's samples: --spp must be even and at least 2" << std::endl;
+        return 2;
+    }
+    if (!temporal && orbit_degrees != 0.0) {
+        std::cerr << "--orbit turns the camera over the frames of --temporal: give --temporal FRAMES" << std::endl;
+        return 2;
+    }
     scene.asset_root = assets;
     if (!scene.setup_by_name(name, (float)SCREENWIDTH / (float)SCREENHEIGHT, seed)) {
         std::cerr << scene.error << std::endl;
@@ -154,7 +224,7 @@ int main(int argc, char **argv) {
         std::cout << "Image tiles across " << devices.size() << " GPU slot(s), gather: " << hrt_multi_gather(multi)
                   << (note.empty() ? "" : " (" + note + ")") << std::endl;
     }
-    int rc = ray_trace_from_camera();  // the 'r' key
+    int rc = temporal ? ray_trace_frames() : ray_trace_from_camera();  // the 'r' key, once or frame after frame
     hrt_scene_destroy(device_scene);
     hrt_multi_destroy(multi);
     hrt_shutdown();

@@ -499,6 +499,77 @@ HRT_API int hrt_denoise_var(const float *d_color, const float *d_color_half, con
  * kernel_ms = the two trace launches' time. */
 HRT_API int hrt_render_denoised_var(hrt_scene *scene, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp, uint64_t seed, uint32_t flags, const hrt_denoise_var_params *p, float *out_rgb, float *out_variance, hrt_stats *stats);
 
+/* ---- temporal accumulation: the previous accumulated frame reprojected under a moved camera and blended with the current one
+ * (the temporal half of SVGF, Schied et al., HPG 2017).  The frame c and its first-half frame c_half are accumulated with the same
+ * taps and the same weights, so x - x_half of the accumulated pair is the weighted sum of the frames' own differences, and its
+ * square estimates the variance of the accumulated mean: the accumulated pair can be handed to the unchanged hrt_denoise_var, whose
+ * colour width then narrows by itself as history grows.  No existing entry point changes.
+ * Input: c (and c_half) = linear means of the current frame, its features (a, n, e, z, cov as hrt_render_features writes them) and
+ * camera; the previous call's outputs (colour, half colour, history), the features they were accumulated with and that frame's
+ * camera.  All arithmetic is fp32 without fused multiply-add, in the order written; tests/temporal_ref.py states the same rule in
+ * numpy.  d, |v|^2 and "finite" are those of THE FILTER above.  For pixel p = (x, y):
+ * 1. Demodulate c (and c_half) with step 1 of THE FILTER: x_p (and xh_p).  p is a RESTART pixel if it is invalid under that rule
+ *    (for either frame), if cov == 0 (no sample hit anything), if no previous frame was given, or if a later step finds no usable
+ *    history.  A restart pixel writes out = c, out_half = c_half, history_out = 1.
+ * 2. World point: zbar = z / cov;  r = camera_ray(cam, (x + 0.5) / w, (y + 0.5) / h, 0), the device function of the trace kernels
+ *    (what hrt_debug_kat(HRT_KAT_CAMERA) returns for that u, v);  P_k = r.o_k + zbar * r.d_k.
+ * 3. Project into the previous camera: s = P - prev_cam->eye;  xc = (s0 R0 + s1 R1) + s2 R2 with R = prev_cam->right, yc and zc the
+ *    same with up and forward.  !(zc > 0): restart.  With cot = cos(rad) / sin(rad), rad = fovy_deg / 2 * pi / 180 in fp64 on the host
+ *    (the projection hrt_render builds), kx = (float)(cot / aspect), ky = (float)cot of prev_cam:
+ *        px = (((kx * xc) / zc + 1) * 0.5f) * (float)w - 0.5f,   py = ((1 - (ky * yc) / zc) * 0.5f) * (float)h - 0.5f,
+ *        zexp = sqrtf((s0 s0 + s1 s1) + s2 s2)            (the depth the previous frame would have recorded for P).
+ *    STATIC CAMERA: when memcmp(cam, prev_cam, sizeof(hrt_camera)) == 0, px = x, py = y, zexp = zbar instead: a still camera
+ *    accumulates pixel onto pixel, without resampling blur.
+ * 4. Taps: ix = floorf(px), iy = floorf(py), fx = px - ix, fy = py - iy; the taps q are (ix, iy), (ix+1, iy), (ix, iy+1),
+ *    (ix+1, iy+1) in that order with weights (1-fx)(1-fy), fx(1-fy), (1-fx)fy, fx fy.  A tap is USED only if it lies inside the
+ *    image, history_prev[q] >= 1, q's previous features 0..10 are finite with cov_q > 0, q's previous colour(s) demodulated with
+ *    q's previous features are finite, and
+ *        |zexp - z_q / cov_q| <= depth_tol * fmaxf(zexp, 1e-3f),   |n_p - n_q|^2 <= normal_tol,   |a_p - a_q|^2 <= albedo_tol
+ *    (a tolerance of +inf passes its test always).  Sums in tap order over the used taps: sw += w, sx += w * x_q per channel,
+ *    sxh += w * xh_q, sn += w * history_prev[q].  !(sw > 0): restart.
+ * 5. Blend: n_new = fminf(sn / sw + 1, max_history), alpha = fmaxf(1 / n_new, alpha_min), xhist = sx / sw,
+ *    y = xhist + alpha * (x_p - xhist), and the same for the half frame with the same alpha.  Remodulate with the CURRENT features as
+ *    step 3 of THE FILTER: r_k = d_k * y_k + e_k / 6.  A non-finite component of r (of either frame) writes the input pixel and
+ *    history_out = 1; otherwise out = r, out_half = r_half, history_out = n_new.
+ * Colours are h*w*3, features h*w*HRT_FEATURE_FLOATS, history h*w floats, all device pointers; asynchronous on `stream`, no scene:
+ * the call runs on the calling thread's current device, like hrt_camera_rays.  prev_cam and the four d_prev_* pointers are all given
+ * or all NULL (NULL: the first frame, every pixel restarts); d_prev_color_half is given iff d_color_half is, d_out_half iff
+ * d_color_half is.  Outputs must not alias any input.
+ * Checked before any device call, HRT_ERR_INVALID with hrt_last_error() naming hrt_temporal_accumulate and the culprit: NULL or
+ * inconsistent pointers, w or h zero or w*h over the denoisers' frame limit, alpha_min outside (0, 1] or NaN, max_history < 1, NaN or
+ * infinite, a tolerance <= 0 or NaN, a camera hrt_render refuses. */
+typedef struct hrt_temporal_params {
+    float alpha_min;      /* (0, 1]: floor of the blend weight of the current frame; 1 = no history is used        */
+    float max_history;    /* >= 1, finite: history length saturates here                                            */
+    float depth_tol;      /* > 0, +inf switches the test off: relative depth disagreement a tap may have            */
+    float normal_tol;     /* > 0, +inf off: |n_p - n_q|^2 a tap may have                                            */
+    float albedo_tol;     /* > 0, +inf off: |a_p - a_q|^2 a tap may have                                            */
+} hrt_temporal_params;
+HRT_API int hrt_temporal_accumulate(const hrt_camera *cam, const hrt_camera *prev_cam, uint32_t w, uint32_t h,
+    const float *d_color, const float *d_color_half /* may be NULL */, const float *d_features,
+    const float *d_prev_color, const float *d_prev_color_half, const float *d_prev_features, const float *d_prev_history,
+    const hrt_temporal_params *p,
+    float *d_out, float *d_out_half /* NULL iff d_color_half is */, float *d_history_out, void *stream);
+/* THE FRAME LOOP.  An hrt_history holds, on the scene's device, what one frame hands to the next: the accumulated pair, the
+ * features it was accumulated with, the history lengths, the camera and the frame size.  hrt_render_temporal renders one frame into
+ * the HOST buffer out_rgb[h*w*3]: the two half renders and the features exactly as hrt_render_denoised_var makes them (spp even and
+ * >= 2, feature_spp <= spp, every launch checked), hrt_temporal_accumulate against the stored state (none after create or reset, or
+ * when w or h differ from the stored frame's: then every pixel restarts), the outputs stored as the new state (two buffer sets swap
+ * roles, nothing is copied); then with dp hrt_denoise_var on the accumulated pair and the current features, HRT_FLAG_GAMMA as given in
+ * flags, or without dp the accumulated frame itself with hrt_finalize_tiles' gamma.  The filtered frame is never fed back: only the
+ * accumulated pair is history.  out_history (host, h*w, may be NULL) receives the history lengths.
+ * CONTRACT: the result is bit-identical to composing hrt_render(spp), hrt_render(spp / 2), hrt_render_features(0, feature_spp),
+ * hrt_temporal_accumulate and hrt_denoise_var by hand.  The caller passes a DIFFERENT seed for every frame: with the same seed a
+ * still camera renders the same samples again and gains nothing.  A history belongs to the scene it was created for. */
+typedef struct hrt_history hrt_history;
+HRT_API int hrt_history_create(hrt_scene *scene, hrt_history **out);
+HRT_API void hrt_history_reset(hrt_history *hist);      /* the next frame restarts everywhere */
+HRT_API void hrt_history_destroy(hrt_history *hist);
+HRT_API int hrt_render_temporal(hrt_scene *scene, hrt_history *hist, const hrt_camera *cam, uint32_t w, uint32_t h,
+                                uint32_t spp, uint32_t feature_spp, uint64_t seed, uint32_t flags,
+                                const hrt_temporal_params *tp, const hrt_denoise_var_params *dp /* NULL: no spatial filter */,
+                                float *out_rgb, float *out_history /* host h*w, may be NULL */, hrt_stats *stats);
+
 /* ---- ray queries: the scene traced with the caller's own rays (picking, visibility, baking, hit buffers for other code)
  * RAYS: n records of 8 floats (32 bytes, the array 16-byte aligned) {o.x, o.y, o.z, time, d.x, d.y, d.z, tmax}, device memory.
  * CLOSEST: Scene::computeIntersection (Scene.h:202-230) on the ray exactly as given -- no normalisation unless HRT_RAYS_NORMALIZE,
