@@ -84,6 +84,11 @@ class Camera(C.Structure):
     ]
 
 
+class View(C.Structure):
+    """``hrt_view``: one camera of a batched render with the seed of its frame (include/hrt.h)."""
+    _fields_ = [("cam", Camera), ("seed", C.c_uint64)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("kernel_ms", C.c_double), ("total_ms", C.c_double), ("samples", C.c_uint64),
@@ -265,6 +270,10 @@ def device_lib() -> C.CDLL:
         lib.hrt_trace_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                            C.c_uint32, C.c_void_p, C.c_void_p]
         lib.hrt_camera_rays.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
+        lib.hrt_render_views_device.argtypes = [C.c_void_p, C.POINTER(View), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                C.c_void_p, C.c_void_p]
+        lib.hrt_render_views.argtypes = [C.c_void_p, C.POINTER(View), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.c_void_p, C.POINTER(Stats)]
         _dev = lib
     return _dev
 
@@ -621,6 +630,35 @@ class DeviceScene:
             out[...] = r
             return out
         return r
+
+    def render_views(self, cams, w: int, h: int, spp: int, seeds=None, flags: int = 0, out=None, stats: Optional[Stats] = None):
+        """hrt_render_views: every camera of ``cams`` as a w x h frame of ``spp`` samples, in one launch -> (n, h, w, 3) float32;
+        frame v has the bits of ``render(cams[v], w, h, spp, seeds[v], flags)``.  ``seeds``: one per view (default 1 for each, as
+        ``render``).  With ``out`` a contiguous (n, h, w, 3) float32 torch tensor on the GPU the call runs on the current torch
+        stream of its device without synchronising and returns ``out`` (hrt_render_views_device; ``check_last_launch`` before the
+        frames are trusted).  Without it the frames come back as a NumPy array; ``stats``: a Stats to fill, if wanted."""
+        cams = list(cams)
+        n = len(cams)
+        seeds = [1] * n if seeds is None else [int(x) for x in seeds]
+        if len(seeds) != n:
+            raise ValueError(f"render_views: {n} cameras but {len(seeds)} seeds")
+        views = (View * max(n, 1))()
+        for v, (cam, seed) in enumerate(zip(cams, seeds)):
+            views[v].cam = cam
+            views[v].seed = seed
+        if out is not None:
+            import torch
+            if (not isinstance(out, torch.Tensor) or out.device.type != "cuda" or out.dtype != torch.float32
+                    or tuple(out.shape) != (n, h, w, 3) or not out.is_contiguous()):
+                raise ValueError(f"render_views: out must be a contiguous ({n}, {h}, {w}, 3) float32 tensor on the GPU")
+            s = torch.cuda.current_stream(out.device)
+            self._check(self._lib.hrt_render_views_device(self._h, views, n, w, h, spp, flags, C.c_void_p(out.data_ptr()),
+                                                          C.c_void_p(s.cuda_stream)))
+            return out
+        frames = np.empty((n, h, w, 3), dtype=np.float32)
+        self._check(self._lib.hrt_render_views(self._h, views, n, w, h, spp, flags, frames.ctypes.data,
+                                               None if stats is None else C.byref(stats)))
+        return frames
 
     def check_last_launch(self):
         """hrt_check_last_launch: waits for the last launch; raises if the trace kernel gave up (incomplete tiles)."""

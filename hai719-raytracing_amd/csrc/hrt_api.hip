@@ -302,6 +302,15 @@ struct hrt_scene {
     hipEvent_t ev_feat = nullptr;
     bool feat_used = false;
     hipStream_t feat_stream = nullptr;
+    // Batched views (hrt_views.hip): the per-view blocks of the launch in hand on the device, their pinned host staging copy (the
+    // caller's views are free when the call returns) with the event that says the upload has read it, the item-major tile sums of
+    // all views with the event and stream of the assemble launch that read them last, and the host form's frames.
+    Scratch vw_blocks, vw_tiles, vw_frames;
+    DView *h_views = nullptr;
+    size_t h_views_cap = 0;  // in views
+    hipEvent_t ev_views = nullptr, ev_views_done = nullptr;
+    bool views_uploading = false, views_used = false;
+    hipStream_t views_stream = nullptr;
 };
 
 namespace {
@@ -375,6 +384,8 @@ int hrt_init(int device_ordinal) {
         HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_lights_exact, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)g_rt.lds_budget));
         HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_lights_exact_list, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_rt.lds_budget));
+        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_views, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_rt.lds_budget));
+        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_lights_views, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_rt.lds_budget));
     }
     if (HRT_WG > 256) {  // one big workgroup per CU: backed-up streams + nodelets go past the 64 KiB default
         HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -396,7 +407,9 @@ int hrt_init(int device_ordinal) {
         HIP_TRY(hipFuncSetAttribute((const void *)hrt_wgstream_kernel_sph, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
         HIP_TRY(hipFuncSetAttribute((const void *)hrt_wgstream_kernel_lights_sph, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
         for (const void *k : {(const void *)hrt_wgstream_kernel_list, (const void *)hrt_wgstream_kernel_lights_list, (const void *)hrt_wgstream_kernel_exact_list,
-                              (const void *)hrt_wgstream_kernel_lights_exact_list, (const void *)hrt_wgstream_kernel_sph_list, (const void *)hrt_wgstream_kernel_lights_sph_list})
+                              (const void *)hrt_wgstream_kernel_lights_exact_list, (const void *)hrt_wgstream_kernel_sph_list, (const void *)hrt_wgstream_kernel_lights_sph_list,
+                              (const void *)hrt_wgstream_kernel_views, (const void *)hrt_wgstream_kernel_lights_views, (const void *)hrt_wgstream_kernel_sph_views,
+                              (const void *)hrt_wgstream_kernel_lights_sph_views})
             HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
         const char *k = std::getenv("HRT_KERNEL");
         const std::string ks = k ? k : "";
@@ -422,6 +435,10 @@ void hrt_scene_destroy(hrt_scene *s) {
     for (Scratch *b : s->scratch()) b->release();
     if (s->d_cam_feat) (void)hipFree(s->d_cam_feat);
     if (s->ev_feat) (void)hipEventDestroy(s->ev_feat);
+    for (Scratch *b : {&s->vw_blocks, &s->vw_tiles, &s->vw_frames}) b->release();
+    if (s->h_views) (void)hipHostFree(s->h_views);
+    if (s->ev_views) (void)hipEventDestroy(s->ev_views);
+    if (s->ev_views_done) (void)hipEventDestroy(s->ev_views_done);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     delete s;
@@ -1039,16 +1056,19 @@ static int fill_render(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t
 }
 
 // The kernel of that name, or its build over a tile list (DRender::tile_list) when the launch has one.
-#define HRT_PICK(k) (R.tile_list ? k##_list : k)
+#define HRT_PICK(k) (list ? k##_list : k)
 
 // One launch of the trace kernel over this rank's tiles: samples [s0, s0 + spp) of every pixel.
 // accumulate = false: d_tiles receives the pixel means (s0 must be 0).
 // accumulate = true : d_tiles holds the running sums of samples [0, s0) and receives the sums of [0, s0 + spp).
 // list (device, list_n rank slots; adaptive sampling): only those tiles, into a COMPACT d_tiles (entry j of the list at slot j).
 // The kernel-form and grid choices below then see list_n tiles.
+// n_views != 0 (batched views, hrt_views.hip; rank 0 of world 1, no list, no accumulation): the n_views blocks staged in s->h_views
+// are uploaded to s->vw_blocks in place of the camera block, and the queue is n_views x the frame's tiles, view-major; cam is view
+// 0's, seed is not used.  The kernel-form and grid choices see all views' tiles; the two-stream and proof forms have no such build.
 static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t s0, uint32_t spp, uint64_t seed,
                         uint32_t flags, uint32_t rank, uint32_t world, float *d_tiles, void *stream_, bool accumulate,
-                        const uint32_t *list = nullptr, uint32_t list_n = 0) {
+                        const uint32_t *list = nullptr, uint32_t list_n = 0, uint32_t n_views = 0) {
     DRender R;
     DCamera C;
     int rc = fill_render(s, cam, w, h, spp, seed, flags, rank, world, R, C);
@@ -1057,6 +1077,10 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
         if (list_n > R.tiles_owned) return fail(HRT_ERR_INVALID, "render: tile list longer than the rank's tiles");
         R.tile_list = list;
         R.tiles_owned = list_n;
+    }
+    if (n_views) {
+        R.views = s->vw_blocks.as<DView>();
+        R.tiles_owned = n_views * R.tiles_total;
     }
     R.cam = s->d_cam;
     if (!d_tiles) return fail(HRT_ERR_INVALID, "render: NULL tile buffer");
@@ -1085,11 +1109,19 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
     const bool exact = (flags & HRT_FLAG_EXACT_ONLY) != 0u;  // proof builds exist for the lane-per-pixel and streaming forms
     if ((rc = check_mesh_brute("render", flags)) != HRT_OK) return rc;
     if (exact && (flags & HRT_FLAG_DUAL_KERNEL)) return fail(HRT_ERR_INVALID, "render: no exact-only build of the two-stream kernel");
-    const bool dual_kernel = !exact && !stream_kernel && (g_rt.use_dual || (flags & HRT_FLAG_DUAL_KERNEL)) && s->d.n_meshes > 0u &&
+    const bool dual_kernel = !exact && !stream_kernel && !n_views && (g_rt.use_dual || (flags & HRT_FLAG_DUAL_KERNEL)) && s->d.n_meshes > 0u &&
                              !(flags & HRT_FLAG_WAVE_KERNEL);
+    const bool sph_build = s->d.n_spheres >= HRT_SPHERE_FILTER_MIN && s->d.n_spheres <= 128u;  // a crowd of spheres: the streaming builds with the pair filter
+    // the kernel of a batched launch, picked once: the occupancy query and the launch below use this one
+    void (*const views_kernel)(const DRender) =
+        !n_views ? nullptr
+        : !stream_kernel ? (s->d.n_lights ? hrt_trace_kernel_lights_views : hrt_trace_kernel_views)
+        : sph_build ? (s->d.n_lights ? hrt_wgstream_kernel_lights_sph_views : hrt_wgstream_kernel_sph_views)
+                    : (s->d.n_lights ? hrt_wgstream_kernel_lights_views : hrt_wgstream_kernel_views);
     uint32_t grid, lds_bytes;
     if (stream_kernel) {
         const uint32_t fixed = (uint32_t)((HRT_SP_GLOBAL ? 0 : SP_FIELDS * HRT_SP_POOL * 4) + HRT_SP_NQ * HRT_SP_POOL * 2 + HRT_SP_STREAMS * sizeof(SpCtl) + sizeof(SpShared) + HRT_SP_UNITS * sizeof(SpUnit) + HRT_SP_UNITS * HRT_SP_MAXG * 4) +
+                               (n_views ? HRT_SP_UNITS * HRT_SP_MAXG * 16u : 0u) +  // the VIEWS builds' table of view rows
                                2048u + s->d.tab_rows * 16u  // + the scene's per-object tables (stream_tables_fit)
 #ifdef HRT_WALK_SEG
                                + 2048u  // diagnostic build: 16 accumulators per wave
@@ -1119,7 +1151,8 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
         R.sp_scratch = s->sp_scratch.as<float>();
         R.sp_pool = s->sp_pool.as<uint32_t>();
     } else {
-        const void *kfn = exact ? (s->d.n_lights ? (const void *)HRT_PICK(hrt_trace_kernel_lights_exact) : (const void *)HRT_PICK(hrt_trace_kernel_exact))
+        const void *kfn = n_views ? (const void *)views_kernel
+                          : exact ? (s->d.n_lights ? (const void *)HRT_PICK(hrt_trace_kernel_lights_exact) : (const void *)HRT_PICK(hrt_trace_kernel_exact))
                                 : (s->d.n_lights ? (const void *)HRT_PICK(hrt_trace_kernel_lights) : (const void *)HRT_PICK(hrt_trace_kernel));
         lds_bytes = R.lds_units * 16u;
         if (dual_kernel) {
@@ -1149,7 +1182,11 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
     // its own is enqueued, the copy of a new camera block included (the previous launch may still be reading the old one).
     if (s->timed && s->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->ev1, 0));
     s->last_stream = stream;
-    if (!s->cam_valid || std::memcmp(&C, &s->h_cam, sizeof(C)) != 0) {
+    if (n_views) {
+        HIP_TRY(hipMemcpyAsync(s->vw_blocks.p, s->h_views, (size_t)n_views * sizeof(DView), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(s->ev_views, stream));
+        s->views_uploading = true;
+    } else if (!s->cam_valid || std::memcmp(&C, &s->h_cam, sizeof(C)) != 0) {
         s->h_cam = C;
         HIP_TRY(hipMemcpyAsync(s->d_cam, &s->h_cam, sizeof(C), hipMemcpyHostToDevice, stream));
         s->cam_valid = true;
@@ -1157,10 +1194,12 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
     HIP_TRY(hipMemsetAsync(s->tile_counter, 0, sizeof(uint32_t), stream));
     HIP_TRY(hipMemsetAsync(s->stamps, 0, 16 * sizeof(unsigned long long), stream));  // [15] = give-up code of the streaming kernel
     HIP_TRY(hipEventRecord(s->ev0, stream));
-    if (stream_kernel && exact) {
+    if (n_views) {
+        hipLaunchKernelGGL(views_kernel, dim3(grid), dim3(stream_kernel ? HRT_SP_WG : HRT_WG), lds_bytes, stream, R);
+    } else if (stream_kernel && exact) {
         if (s->d.n_lights) hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel_lights_exact), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
         else hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel_exact), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
-    } else if (stream_kernel && s->d.n_spheres >= HRT_SPHERE_FILTER_MIN && s->d.n_spheres <= 128u) {  // a crowd of spheres: the builds with the pair filter
+    } else if (stream_kernel && sph_build) {
         if (s->d.n_lights) hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel_lights_sph), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
         else hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel_sph), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
     } else if (stream_kernel) {
@@ -1488,6 +1527,7 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 #include "hrt_temporal.hip"
 #include "hrt_rays.hip"
 #include "hrt_radiance.hip"
+#include "hrt_views.hip"
 
 int hrt_kd_build_gpu(const hrt_kd_build_input *in, hrt_kd_build_output *out, void *user) {
     (void)user;

@@ -110,6 +110,15 @@ struct DCamera {
     float pad;
 };
 
+// One view of a batched launch (hrt_render_views, hrt_views.hip): what a one-camera launch keeps in DRender::cam, seed_lo / seed_hi
+// and err_abs.  160 bytes; the VIEWS kernels read it with scalar loads where the view is wave-uniform.
+struct DView {
+    DCamera cam;
+    uint32_t seed_lo, seed_hi;
+    float err_abs;                 // margin_scale of this view's eye
+    uint32_t pad;
+};
+
 // Kernel argument block: small on purpose.  The scene and the camera live in device memory and
 // are read through constant-address-space pointers (scalar loads at the point of use), which keeps
 // the SGPR file for exec masks and primitive rows instead of pinning 60+ SGPRs of arguments.
@@ -133,9 +142,13 @@ struct DRender {
     uint32_t sp_band_log2;       // streaming kernel: a work unit is one ROW BAND of a tile, 8 x (8 >> this) pixels (then one tile per unit): finer
                                  // items on the tile queue when tiles are few and heavy (many samples per pixel)
     uint32_t *sp_pool;           // streaming kernel built with HRT_SP_GLOBAL: per-workgroup path records
-    const uint32_t *tile_list;   // the *_list kernels (adaptive sampling, hrt_adaptive.hip): work-queue item j is rank slot tile_list[j],
-                                 // tiles_owned is the list's length and out_tiles a COMPACT buffer (slot j of the list at j).  Read only by
-                                 // the LIST instantiations: the other kernels compile as if the field did not exist
+    union {                      // one slot of the argument block, read by no kernel but those named (the others compile as if it did not exist):
+        const uint32_t *tile_list;   // the *_list kernels (adaptive sampling, hrt_adaptive.hip): work-queue item j is rank slot tile_list[j],
+                                     // tiles_owned is the list's length and out_tiles a COMPACT buffer (slot j of the list at j)
+        const DView *views;          // the *_views kernels (batched views, hrt_views.hip): work-queue item j is tile j % tiles_total of view
+                                     // j / tiles_total (rank 0 of world 1), tiles_owned = views x tiles_total, out_tiles item-major; the view's
+                                     // block stands in for cam, seed_lo / seed_hi and err_abs above
+    };
 };
 
 // Rank slot of work-queue item j: the item itself, or -- in the LIST builds -- the item-th entry of R.tile_list.

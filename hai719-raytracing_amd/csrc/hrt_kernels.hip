@@ -89,6 +89,7 @@ typedef const v4u __attribute__((address_space(3))) *lu4;
 typedef const DMesh __attribute__((address_space(4))) *cmesh;
 typedef const DScene __attribute__((address_space(4))) *cscene;
 typedef const DCamera __attribute__((address_space(4))) *ccam;
+typedef const DView __attribute__((address_space(4))) *cview;
 typedef const DImage __attribute__((address_space(1))) *gimg;
 typedef const v4f __attribute__((address_space(3))) *lf4;         // scene tables staged in LDS (streaming kernel)
 typedef const DMesh __attribute__((address_space(1))) *gmesh;     // per-lane mesh records, global
@@ -1296,7 +1297,9 @@ __device__ __forceinline__ Ray camera_ray(CP C, float u, float v, float time) {
 // The megakernel body.  LIGHTS = the scene has point lights (soft-shadow fan-out, Scene.h:305-334,
 // compiled in); scenes without lights run the variant that carries none of that code or its registers.
 // ---------------------------------------------------------------------------
-template <bool LIGHTS, bool EXACT = false, bool LIST = false>
+// VIEWS = a batched launch (DRender::views): a wave holds one tile, so its view is wave-uniform and the view's block is read where
+// R.cam, R.seed_lo / seed_hi and R.err_abs are otherwise -- scalar loads at the point of use.
+template <bool LIGHTS, bool EXACT = false, bool LIST = false, bool VIEWS = false>
 __device__ __forceinline__ void trace_body(const DRender &R) {
     extern __shared__ uint4 s_units[];
     CtxT<EXACT> cx;
@@ -1329,7 +1332,9 @@ __device__ __forceinline__ void trace_body(const DRender &R) {
         if (lane == 0) j = atomicAdd(R.tile_counter, 1u);
         j = __builtin_amdgcn_readfirstlane(j);
         if (j >= R.tiles_owned) break;  // the queue is finite: every wave gets here
-        const uint32_t tile = R.rank + rank_slot<LIST>(R, j) * R.world;
+        const uint32_t tile = VIEWS ? j % R.tiles_total : R.rank + rank_slot<LIST>(R, j) * R.world;
+        const cview V = (cview)R.views + (VIEWS ? j / R.tiles_total : 0u);  // (VIEWS only)
+        if (VIEWS) { cam = (ccam)&V->cam; cx.err_abs = V->err_abs; }
         const uint32_t px = (tile % R.tiles_x) * 8u + (lane & 7u);
         const uint32_t py = (tile / R.tiles_x) * 8u + (lane >> 3);
         const bool inside = px < R.w && py < R.h;
@@ -1357,7 +1362,7 @@ __device__ __forceinline__ void trace_body(const DRender &R) {
             // ---- stage A: (re)generate, spheres + squares, mesh gates
             if (live && stage == 0u) {
                 if (remaining == 0) {  // next camera sample of this pixel (main.cpp:188-192)
-                    rng.start(R.seed_lo, R.seed_hi, pixel, R.s0 + s);
+                    rng.start(VIEWS ? V->seed_lo : R.seed_lo, VIEWS ? V->seed_hi : R.seed_hi, pixel, R.s0 + s);
                     const float u = ((float)px + rng.next()) / (float)R.w;
                     const float v = ((float)py + rng.next()) / (float)R.h;
                     const float tm = rng.next();
@@ -1460,6 +1465,9 @@ extern "C" __global__ void __launch_bounds__(HRT_WG, HRT_MIN_WAVES_SINGLE) hrt_t
 extern "C" __global__ void __launch_bounds__(HRT_WG, HRT_MIN_WAVES_SINGLE_LIGHTS) hrt_trace_kernel_lights_list(const DRender R) { trace_body<true, false, true>(R); }
 extern "C" __global__ void __launch_bounds__(HRT_WG, 2) hrt_trace_kernel_exact_list(const DRender R) { trace_body<false, true, true>(R); }
 extern "C" __global__ void __launch_bounds__(HRT_WG, 2) hrt_trace_kernel_lights_exact_list(const DRender R) { trace_body<true, true, true>(R); }
+// The tuned two over a batch of views (DRender::views; hrt_views.hip)
+extern "C" __global__ void __launch_bounds__(HRT_WG, HRT_MIN_WAVES_SINGLE) hrt_trace_kernel_views(const DRender R) { trace_body<false, false, false, true>(R); }
+extern "C" __global__ void __launch_bounds__(HRT_WG, HRT_MIN_WAVES_SINGLE_LIGHTS) hrt_trace_kernel_lights_views(const DRender R) { trace_body<true, false, false, true>(R); }
 
 // gamma_correct (Functions.cpp:56-60): pow(c, 1/2.2) in double, over this rank's tile buffer.  Kept out of
 // the megakernel: fp64 pow is register-hungry and runs once per pixel.

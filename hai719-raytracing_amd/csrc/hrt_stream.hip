@@ -281,7 +281,11 @@ __device__ __forceinline__ void sp_push_all(const SpLds &L, SpCtl &C, uint32_t o
     }
 }
 
-template <bool LIGHTS, bool EXACT = false, bool SPHF = false, bool LIST = false>
+// VIEWS = a batched launch (DRender::views).  A unit groups tiles of the ONE queue of views x tiles items, so a unit, and with it a
+// chunk of hit visits, can mix views: the view travels with the unit's tile, as a row {view, seed_lo, seed_hi, err_abs} of an LDS
+// table beside the packed tile origins (tile_vw, written with them by the serial section).  Seeds and the filters' margin are then
+// per lane, from that row; the camera block stays on the scalar path (see the G chunk).
+template <bool LIGHTS, bool EXACT = false, bool SPHF = false, bool LIST = false, bool VIEWS = false>
 __device__ __forceinline__ void stream_body(const DRender &R) {
     extern __shared__ uint4 s_raw[];
     SpLds L;
@@ -296,7 +300,9 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
     SpShared &SH = *reinterpret_cast<SpShared *>(L.ctl + HRT_SP_STREAMS);
     SpUnit *const U = reinterpret_cast<SpUnit *>(&SH + 1);                // the two work units in flight
     uint32_t *tile_xy = reinterpret_cast<uint32_t *>(U + HRT_SP_UNITS);              // [unit slot][tile]: x0 | y0 << 16, ~0: no such tile
-    float *s_lut = reinterpret_cast<float *>(tile_xy + HRT_SP_UNITS * HRT_SP_MAXG);  // the u8 -> float tables (512 floats)
+    uint4 *tile_vw = reinterpret_cast<uint4 *>(tile_xy + HRT_SP_UNITS * HRT_SP_MAXG);  // VIEWS only: [unit slot][tile] {view, seed_lo, seed_hi, err_abs}
+    float *s_lut = VIEWS ? reinterpret_cast<float *>(tile_vw + HRT_SP_UNITS * HRT_SP_MAXG)
+                         : reinterpret_cast<float *>(tile_xy + HRT_SP_UNITS * HRT_SP_MAXG);  // the u8 -> float tables (512 floats)
     float4 *s_tabs = reinterpret_cast<float4 *>(s_lut + 512);            // 16-byte aligned: every size above is a multiple of 16
     CtxT<EXACT, true, SPHF> cx;
     cx.S = (cscene)R.scene;
@@ -352,6 +358,8 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
     const uint32_t glog = R.sp_group_log2, G = 1u << glog, blog = R.sp_band_log2;  // tiles per unit; or ONE row band of a tile, 8 x (8 >> blog) pixels
     const uint32_t upix = (64u << glog) >> blog, upix_log2 = 6u + glog - blog;     // pixels per unit
     const uint32_t items = R.tiles_owned << blog;                                  // what the tile queue hands out: tiles, or bands of tiles
+    // VIEWS: the view row of the tile a path belongs to, from the path's number (unit slot on top, sample-major path-in-unit below)
+    auto view_row = [&](uint32_t pnum) { return tile_vw[(pnum >> 30) * HRT_SP_MAXG + (((pnum & 0x3FFFFFFFu) & (upix - 1u)) >> 6)]; };
 #define SP_UNI(x) __builtin_amdgcn_readfirstlane(x)
 
 #ifndef HRT_SP_SEG_KIND
@@ -446,10 +454,15 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                                 for (uint32_t t = 0; t < G; ++t) {
                                     uint32_t xy = 0xFFFFFFFFu;
                                     if (j + t < items) {
-                                        const uint32_t tile = R.rank + rank_slot<LIST>(R, (j + t) >> blog) * R.world, band = (j + t) & ((1u << blog) - 1u);
+                                        const uint32_t tile = VIEWS ? ((j + t) >> blog) % R.tiles_total : R.rank + rank_slot<LIST>(R, (j + t) >> blog) * R.world, band = (j + t) & ((1u << blog) - 1u);
                                         xy = ((tile % R.tiles_x) * 8u) | (((tile / R.tiles_x) * 8u + band * (8u >> blog)) << 16);  // the band's first row
                                     }
                                     tile_xy[k * HRT_SP_MAXG + t] = xy;
+                                    if (VIEWS) {  // the tile's view row (of view 0 where there is no tile: never used, but a valid block)
+                                        const uint32_t view = j + t < items ? ((j + t) >> blog) / R.tiles_total : 0u;
+                                        const DView *V = R.views + view;
+                                        tile_vw[k * HRT_SP_MAXG + t] = make_uint4(view, V->seed_lo, V->seed_hi, __float_as_uint(V->err_abs));
+                                    }
                                 }
                                 cur = k;
                             }
@@ -766,12 +779,27 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                     const uint32_t p = q & 63u, txy = tile_xy[gs * HRT_SP_MAXG + (q >> 6)];
                     const uint32_t px = (txy & 0xFFFFu) + (p & 7u), py = (txy >> 16) + (p >> 3);
                     if (txy != 0xFFFFFFFFu && px < R.w && py < R.h) {
+                        uint4 vw = make_uint4(0u, R.seed_lo, R.seed_hi, 0u);
+                        if (VIEWS) { vw = view_row(n | (gs << 30)); cx.err_abs = __uint_as_float(vw.w); }
                         Rng rng;
-                        rng.start(R.seed_lo, R.seed_hi, py * R.w + px, R.s0 + s);
+                        rng.start(vw.y, vw.z, py * R.w + px, R.s0 + s);
                         const float u = ((float)px + rng.next()) / (float)R.w;
                         const float v = ((float)py + rng.next()) / (float)R.h;
                         const float tm = rng.next();
-                        ray = camera_ray<EXACT>(cam, u, v, tm);
+                        if (VIEWS) {
+                            // The camera block by SCALAR loads, as in the one-camera builds: one pass per distinct view among the chunk's
+                            // lanes.  A chunk is 64 consecutive paths of a unit and starts at a multiple of 64 (whole chunks are handed
+                            // out, HRT_SP_DEFER), so it lies in one tile or one band and the loop runs once; loading the block per lane
+                            // instead would put 36 more VGPRs of camera constants into a kernel that already spills.
+                            for (uint64_t todo = __ballot(1); todo != 0ull;) {  // (a uniform loop: every lane stays until all are served)
+                                const uint32_t view = __builtin_amdgcn_readlane(vw.x, __builtin_ctzll(todo));
+                                const bool mine = vw.x == view;
+                                if (mine) ray = camera_ray<EXACT>((ccam)&((cview)R.views + view)->cam, u, v, tm);
+                                todo &= ~__ballot(mine);
+                            }
+                        } else {
+                            ray = camera_ray<EXACT>(cam, u, v, tm);
+                        }
                         pnum = n | (gs << 30);
 #if !HRT_SP_NOG5
                         sp_st4(L, 5, slot, make_uint4(__float_as_uint(tm), rng.k0, rng.k1, pnum));
@@ -801,7 +829,9 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                         const uint32_t kq = kn & (upix - 1u), ks = U[ku].s0 + (kn >> upix_log2);
                         const uint32_t kxy = tile_xy[ku * HRT_SP_MAXG + (kq >> 6)];
                         const uint32_t kx = (kxy & 0xFFFFu) + (kq & 7u), ky = (kxy >> 16) + ((kq & 63u) >> 3);
-                        key.start(R.seed_lo, R.seed_hi, ky * R.w + kx, R.s0 + ks);
+                        uint4 vw = make_uint4(0u, R.seed_lo, R.seed_hi, 0u);
+                        if (VIEWS) { vw = view_row(pnum); cx.err_abs = __uint_as_float(vw.w); }
+                        key.start(vw.y, vw.z, ky * R.w + kx, R.s0 + ks);
                         key.i = 2u;
                     }
                     Hit h;
@@ -819,6 +849,7 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                     sp_unpack_ray_hit(g0, g1, g2, ray, h, pm_unused);
                     ray.time = __uint_as_float(g5.x);
                     pnum = g5.w;
+                    if (VIEWS) cx.err_abs = __uint_as_float(view_row(pnum).w);
 #endif
                     f3 thr = mk(__uint_as_float(g6.x), __uint_as_float(g6.y), __uint_as_float(g6.z));
                     rad = mk(__uint_as_float(g6.w), __uint_as_float(g7.x), __uint_as_float(g7.y));
@@ -997,3 +1028,9 @@ extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstrea
 extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstream_kernel_lights_sph_list(const DRender R) { hrtk::stream_body<true, false, true, true>(R); }
 extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstream_kernel_exact_list(const DRender R) { hrtk::stream_body<false, true, false, true>(R); }
 extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstream_kernel_lights_exact_list(const DRender R) { hrtk::stream_body<true, true, false, true>(R); }
+// The tuned four over a batch of views (DRender::views; hrt_views.hip).  Outputs are item-major (view-major, each view tile-major),
+// so the reductions' out_tiles indexing is again the same.
+extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstream_kernel_views(const DRender R) { hrtk::stream_body<false, false, false, false, true>(R); }
+extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstream_kernel_lights_views(const DRender R) { hrtk::stream_body<true, false, false, false, true>(R); }
+extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstream_kernel_sph_views(const DRender R) { hrtk::stream_body<false, false, true, false, true>(R); }
+extern "C" __global__ void __launch_bounds__(HRT_SP_WG, HRT_SP_MINW) hrt_wgstream_kernel_lights_sph_views(const DRender R) { hrtk::stream_body<true, false, true, false, true>(R); }

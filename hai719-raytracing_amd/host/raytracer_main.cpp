@@ -19,6 +19,9 @@
 //                                                  camera turns about the scene's up axis by DEGREES / FRAMES per frame; with --denoise-var
 //                                                  every frame's accumulated pair goes through the variance-guided filter; the last
 //                                                  frame is written (one GPU)
+//             [--views N [--orbit DEGREES]]        N cameras, each turned DEGREES further about the scene's up axis than the one before,
+//                                                  rendered in ONE launch (hrt_render_views) with seeds seed, seed + 1, ...; written as
+//                                                  NAME_000.ppm, NAME_001.ppm, ... for --out NAME.ppm (one GPU)
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -48,6 +51,7 @@ static bool denoise_var = false;  // --denoise-var: hrt_render_denoised_var with
 static hrt_denoise_var_params denoise_var_params = {4u, 2u, 8.0f, 0.05f, 0.4f, 0.05f, 1e-8f};
 static uint32_t temporal_frames = 0;  // --temporal: hrt_render_temporal over that many frames, the default hrt_temporal_params
 static double orbit_degrees = 0.0;    // --orbit: the camera's turn about the up axis over the whole run
+static uint32_t n_views = 0;          // --views: hrt_render_views over that many cameras, --orbit degrees apart
 static hrt_temporal_params temporal_params = {0.02f, 64.f, 0.05f, 0.1f, 0.05f};  // the Python TemporalParams()
 
 // Drop-in for ray_trace_from_camera(): same inputs (current scene, nsamples, window size, camera),
@@ -96,6 +100,36 @@ static int ray_trace_frames() {
     std::cout << "  Done in " << total_ms / 1000.0 << " seconds (kernels " << kernel_ms << " ms, mean history of the last frame "
               << mean / (double)lengths.size() << " frames)" << std::endl;
     rc = hrt_write_ppm(out_path.c_str(), image.data(), w, h);
+    if (rc != HRT_OK) std::cout << hrt_last_error() << std::endl;
+    return rc;
+}
+
+// --views: N cameras in one launch.  View k has seed + k and the camera turned by k * orbit; frame k goes to NAME_kkk.ppm.
+static int ray_trace_views() {
+    const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
+    const size_t frame = (size_t)w * h * 3;
+    std::vector<float> images(frame * n_views, 0.f);
+    const hrt_camera cam0 = default_camera((float)w / (float)h);
+    std::vector<hrt_view> views(n_views);
+    for (uint32_t k = 0; k < n_views; ++k) { views[k].cam = orbited(cam0, orbit_degrees * (double)k); views[k].seed = seed + k; }
+    std::cout << "Ray tracing " << n_views << " views of " << w << " x " << h << " pixels, " << orbit_degrees << " degrees apart, on the GPU in one launch using "
+              << nsamples << " samples per pixel" << std::endl;
+    hrt_stats st;
+    int rc = hrt_render_views(device_scene, views.data(), n_views, w, h, nsamples, HRT_FLAG_GAMMA, images.data(), &st);
+    if (rc != HRT_OK) {
+        std::cout << "hrt_render_views failed: " << hrt_last_error() << std::endl;
+        return rc;
+    }
+    std::cout << "  Done in " << st.total_ms / 1000.0 << " seconds (kernel " << st.kernel_ms << " ms, " << (double)st.samples / st.kernel_ms / 1e3
+              << " Msamples/s)" << std::endl;
+    const size_t dot = out_path.rfind('.'), slash = out_path.rfind('/');
+    const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+    const std::string stem = has_ext ? out_path.substr(0, dot) : out_path, ext = has_ext ? out_path.substr(dot) : std::string(".ppm");
+    for (uint32_t k = 0; rc == HRT_OK && k < n_views; ++k) {
+        char num[16];
+        std::snprintf(num, sizeof(num), "_%03u", k);
+        rc = hrt_write_ppm((stem + num + ext).c_str(), images.data() + frame * k, w, h);
+    }
     if (rc != HRT_OK) std::cout << hrt_last_error() << std::endl;
     return rc;
 }
@@ -154,6 +188,7 @@ int main(int argc, char **argv) {
         else if (k == "--denoise-var") { denoise_var = true; feature_spp = (uint32_t)strtoul(v.c_str(), nullptr, 10); }
         else if (k == "--denoise-iters") denoise_params.iterations = denoise_var_params.iterations = (uint32_t)strtoul(v.c_str(), nullptr, 10);
         else if (k == "--temporal") temporal_frames = (uint32_t)strtoul(v.c_str(), nullptr, 10);
+        else if (k == "--views") n_views = (uint32_t)strtoul(v.c_str(), nullptr, 10);
         else if (k == "--orbit") orbit_degrees = strtod(v.c_str(), nullptr);
         else if (k == "--gpus") { devices.clear(); for (int d = 0; d < atoi(v.c_str()); ++d) devices.push_back(d); }
         else if (k == "--devices") {
@@ -199,8 +234,12 @@ int main(int argc, char **argv) {
         std::cerr << "--temporal keeps the two halves of every frame's samples: --spp must be even and at least 2" << std::endl;
         return 2;
     }
-    if (!temporal && orbit_degrees != 0.0) {
-        std::cerr << "--orbit turns the camera over the frames of --temporal: give --temporal FRAMES" << std::endl;
+    if (n_views != 0u && (adaptive || denoise || denoise_var || temporal || !devices.empty())) {
+        std::cerr << "--views renders plain frames on one GPU: it cannot be combined with --adaptive, --denoise, --denoise-var, --temporal or --gpus / --devices" << std::endl;
+        return 2;
+    }
+    if (!temporal && n_views == 0u && orbit_degrees != 0.0) {
+        std::cerr << "--orbit turns the camera over the frames of --temporal or the cameras of --views: give --temporal FRAMES or --views N" << std::endl;
         return 2;
     }
     scene.asset_root = assets;
@@ -224,7 +263,7 @@ int main(int argc, char **argv) {
         std::cout << "Image tiles across " << devices.size() << " GPU slot(s), gather: " << hrt_multi_gather(multi)
                   << (note.empty() ? "" : " (" + note + ")") << std::endl;
     }
-    int rc = temporal ? ray_trace_frames() : ray_trace_from_camera();  // the 'r' key, once or frame after frame
+    int rc = n_views ? ray_trace_views() : temporal ? ray_trace_frames() : ray_trace_from_camera();  // the 'r' key, once or frame after frame
     hrt_scene_destroy(device_scene);
     hrt_multi_destroy(multi);
     hrt_shutdown();

@@ -306,7 +306,10 @@ HRT_API int hrt_assemble_frame(const float *d_gathered, uint32_t tiles_per_rank_
                        float *d_frame /* device, h*w*3 */, void *stream);
 /* One hrt_scene carries one launch at a time (it owns the work-queue head, the path pool and the camera block of the
  * launch).  Launches of the same scene on ONE stream are ordered by the stream; a launch on a different stream is made
- * to wait for the previous one.  Two scenes never interfere.
+ * to wait for the previous one.  Two scenes never interfere.  A batched launch (hrt_render_views*, below) uses the same work-queue
+ * head and path pool, with its per-view blocks in place of the camera block: it is ordered against the other launches of its
+ * scene exactly as an hrt_render_tiles on its stream is, and hrt_check_last_launch / hrt_last_kernel_ms speak of it when it was
+ * the last.
  *
  * hrt_check_last_launch: waits for the last launch of this scene and returns HRT_ERR_DEVICE when the trace kernel gave
  * up (its scheduler has a cycle bound so that a bug can never spin the GPU): the tiles of that launch are then
@@ -634,6 +637,37 @@ HRT_API int hrt_trace_radiance(hrt_scene *scene, const float *d_rays, const uint
  * on `stream`, and the camera block travels as a kernel argument.  Refused (HRT_ERR_INVALID): a NULL cam, a camera hrt_render
  * refuses, w or h zero, w*h > 2^31 - 1, d_rays NULL or misaligned (checked in that order, before the library state). */
 HRT_API int hrt_camera_rays(const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t sample, uint64_t seed, float *d_rays, void *stream);
+
+/* ---- Batched views: many cameras of one scene, every one a w x h frame of spp samples, in ONE trace launch.
+ * N views make one work queue of N x hrt_tiles_total(w, h) items (item j: tile j % tiles of view j / tiles), so the samples of
+ * all views are spread over all workgroups: small frames, which do not fill the device one at a time, do so together.
+ * CONTRACT: frame v is bit-identical to hrt_render(scene, &views[v].cam, w, h, spp, views[v].seed, flags), for every scene, every
+ * n_views and every permitted flag combination.  The random numbers of a sample depend only on (seed of its view, pixel y*w + x
+ * inside its view, sample).
+ * FLAGS: HRT_FLAG_GAMMA, HRT_FLAG_NO_LDS_TREE, HRT_FLAG_WAVE_KERNEL, HRT_FLAG_STREAM_KERNEL, HRT_FLAG_NO_SHADOW_CULL.  Refused by
+ * name: HRT_FLAG_DUAL_KERNEL, HRT_FLAG_EXACT_ONLY, HRT_FLAG_MESH_BRUTE (no batched builds of those kernel forms); any other bit is
+ * refused.  Without a forced form the kernel form is hrt_render_tiles' choice for the TOTAL tile count, which may differ from the
+ * form one view alone would get; all forms give the same pixels.
+ * hrt_render_views_device: d_frames (device) receives n_views * h * w * 3 floats, view-major, each view row-major as
+ * hrt_render's; asynchronous on `stream` (call hrt_check_last_launch before the frames are used).  `views` may be freed when the
+ * call returns.  The tile sums and the per-view blocks are scratch of the scene.
+ * hrt_render_views: the same into a HOST buffer, blocking, checked with hrt_check_last_launch; stats as hrt_render
+ * (samples = n_views * w * h * spp).
+ * LIMIT: n_views x hrt_tiles_total(w, h) <= HRT_VIEWS_MAX_TILES, so that a work-queue item (a tile, shifted left by up to 2 bits
+ * when tiles are split into row bands) and the float index of the tile sums (192 per tile) fit 32 bits.
+ * Checked in this order before the scene and the library state, HRT_ERR_INVALID with hrt_last_error() naming the entry point and
+ * the culprit: flags; (n_views == 0 returns HRT_OK here and launches nothing;) views NULL; w, h, spp as hrt_render checks them;
+ * every camera as hrt_render checks it, with the index of the offending view; the output pointer NULL or not 4-byte aligned;
+ * the limit above; then a NULL scene. */
+typedef struct hrt_view {
+    hrt_camera cam;
+    uint64_t seed;
+} hrt_view;
+#define HRT_VIEWS_MAX_TILES (1u << 24)
+HRT_API int hrt_render_views_device(hrt_scene *scene, const hrt_view *views, uint32_t n_views, uint32_t w, uint32_t h,
+                                    uint32_t spp, uint32_t flags, float *d_frames, void *stream);
+HRT_API int hrt_render_views(hrt_scene *scene, const hrt_view *views, uint32_t n_views, uint32_t w, uint32_t h,
+                             uint32_t spp, uint32_t flags, float *out_rgb, hrt_stats *stats /* may be NULL */);
 
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
