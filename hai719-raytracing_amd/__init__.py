@@ -89,6 +89,13 @@ class View(C.Structure):
     _fields_ = [("cam", Camera), ("seed", C.c_uint64)]
 
 
+class PickInput(C.Structure):
+    """hrt_pick_input (include/hrt.h): what the choice of a trace kernel build depends on."""
+    _fields_ = [("n_meshes", C.c_uint32), ("n_lights", C.c_uint32), ("n_spheres", C.c_uint32), ("tab_rows", C.c_uint32),
+                ("tiles", C.c_uint32), ("spp", C.c_uint32), ("flags", C.c_uint32), ("has_list", C.c_uint32), ("n_views", C.c_uint32),
+                ("hrt_kernel", C.c_char_p)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("kernel_ms", C.c_double), ("total_ms", C.c_double), ("samples", C.c_uint64),
@@ -274,6 +281,8 @@ def device_lib() -> C.CDLL:
                                                 C.c_void_p, C.c_void_p]
         lib.hrt_render_views.argtypes = [C.c_void_p, C.POINTER(View), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_debug_pick_kernel.argtypes = [C.POINTER(PickInput), C.c_char_p, C.c_size_t]
+        lib.hrt_debug_last_kernel.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         _dev = lib
     return _dev
 
@@ -446,6 +455,12 @@ class DeviceScene:
         st = Stats()
         self._check(self._lib.hrt_render(self._h, C.byref(cam), w, h, spp, seed, flags, out.ctypes.data, C.byref(st)))
         return out, st
+
+    def last_kernel(self) -> str:
+        """hrt_debug_last_kernel: the name of the build this scene's last trace launch ran ("" before any)."""
+        name = C.create_string_buffer(64)
+        self._check(self._lib.hrt_debug_last_kernel(self._h, name, len(name)))
+        return name.value.decode()
 
     def render_tiles(self, cam: Camera, w: int, h: int, spp: int, seed: int, flags: int, rank: int, world: int,
                      d_tiles_ptr: int, stream_ptr: int = 0):
@@ -698,6 +713,19 @@ class History:
 KAT_CAMERA, KAT_TRIANGLE, KAT_AABB, KAT_SPHERE, KAT_QUAD, KAT_OPTICS, KAT_NORMALIZE = range(7)
 _KAT_IN = {KAT_CAMERA: 2, KAT_TRIANGLE: 7, KAT_AABB: 7, KAT_SPHERE: 7, KAT_QUAD: 7, KAT_OPTICS: 8, KAT_NORMALIZE: 3}
 _KAT_OUT = {KAT_CAMERA: 12, KAT_TRIANGLE: 8, KAT_AABB: 2, KAT_SPHERE: 9, KAT_QUAD: 8, KAT_OPTICS: 8, KAT_NORMALIZE: 3}
+
+
+def pick_kernel(n_meshes: int, n_lights: int, n_spheres: int, tab_rows: int, tiles: int, spp: int, flags: int = 0, has_list: bool = False,
+                n_views: int = 0, kernel: str = "") -> str:
+    """hrt_debug_pick_kernel: the name of the trace kernel build a launch with these traits runs (``kernel``: the value of
+    HRT_KERNEL); raises HrtError where the launch would be refused.  Needs neither ``init`` nor a GPU."""
+    lib = device_lib()
+    name = C.create_string_buffer(64)
+    rc = lib.hrt_debug_pick_kernel(C.byref(PickInput(n_meshes, n_lights, n_spheres, tab_rows, tiles, spp, flags, int(has_list), n_views,
+                                                     kernel.encode())), name, len(name))
+    if rc < 0:
+        raise HrtError(f"hrt_debug_pick_kernel failed ({rc}): {lib.hrt_last_error().decode()}")
+    return name.value.decode()
 
 
 def debug_kat(which: int, inp, prim=None, cam: Optional[Camera] = None) -> np.ndarray:

@@ -149,7 +149,9 @@ static int adaptive_run(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
     const uint32_t half = p->min_spp / 2u;
 
     HIP_TRY(hipMemsetAsync(d_sums, 0, sum_bytes, stream));
-    rc = launch_trace(s, cam, w, h, 0u, half, seed, flags, rank, world, d_sums, stream, true);  // round 0
+    TraceJob job{w, h, 0u, half, seed, flags, d_sums, stream};  // round 0
+    job.rank = rank; job.world = world; job.accumulate = true;
+    rc = launch_trace(s, cam, job);
     if (rc == HRT_OK) rc = adaptive_trace_done(s, kernel_ms);
     if (rc != HRT_OK) return rc;
     uint32_t done = half, n = n_tiles, next = 0;
@@ -159,7 +161,8 @@ static int adaptive_run(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
         const dim3 grid((n + HRT_AD_WG / 64u - 1u) / (HRT_AD_WG / 64u));
         hipLaunchKernelGGL(hrt_ad_gather_kernel, grid, dim3(HRT_AD_WG), 0, stream, d_sums, active, n, compact);
         HIP_TRY(hipGetLastError());
-        rc = launch_trace(s, cam, w, h, done, add, seed, flags, rank, world, compact, stream, true, active, n);
+        job.s0 = done; job.spp = add; job.d_tiles = compact; job.list = active; job.list_n = n;
+        rc = launch_trace(s, cam, job);
         if (rc == HRT_OK) rc = adaptive_trace_done(s, kernel_ms);
         if (rc != HRT_OK) return rc;
         hipLaunchKernelGGL(hrt_ad_judge_kernel, grid, dim3(HRT_AD_WG), 0, stream, compact, d_sums, active, n, done, done + add,

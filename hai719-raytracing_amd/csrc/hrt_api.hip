@@ -39,14 +39,23 @@ int fail(int code, const std::string &msg) {
             return fail(HRT_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));        \
     } while (0)
 
+// The HRT_KERNEL environment variable: "single", "dual", "stream", or anything else for the default.
+struct KernelPref {
+    bool use_dual = true;  // two pixel streams per lane (hrt_dual.hip) for scenes with meshes; "single" turns it off
+    int use_stream = -1;   // workgroup-streaming kernel (hrt_stream.hip): -1 where it pays (default), 1 always ("stream"), 0 never
+};
+KernelPref parse_kernel_pref(const char *k) {
+    const std::string ks = k ? k : "";
+    return KernelPref{ks != "single", ks == "stream" ? 1 : ((ks == "single" || ks == "dual") ? 0 : -1)};
+}
+
 struct Runtime {
     bool ready = false;
     int device = -1;
     int cus = 0;
     int blocks_per_cu = 0;
     uint32_t lds_budget = 0;  // bytes of dynamic LDS per workgroup for nodelets
-    bool use_dual = true;     // two pixel streams per lane (hrt_dual.hip) for scenes with meshes; HRT_KERNEL=single turns it off
-    int use_stream = -1;      // workgroup-streaming kernel (hrt_stream.hip): -1 where it pays (default), 1 always (HRT_KERNEL=stream), 0 never
+    KernelPref pref;          // what HRT_KERNEL asks for
     hipFuncAttributes attr{};
     std::vector<int> dev_cus;  // per ordinal: CUs of the devices hrt_init has prepared (0 = not prepared); one process may drive several
 } g_rt;
@@ -269,6 +278,74 @@ int check_mesh_brute(const std::string &who, uint32_t flags) {
     return HRT_OK;
 }
 
+// ---- The builds of the trace kernels, stated once: hrt_init raises every row's dynamic-LDS limit,
+// pick_build chooses a row, launch_trace sizes and launches it.  tests/test_kernel_choice.py holds the table to the sources.
+enum KernelFamily { KF_LANE, KF_DUAL, KF_STREAM };  // lane-per-pixel (hrt_kernels.hip), two-stream (hrt_dual.hip), workgroup-streaming (hrt_stream.hip)
+enum : uint32_t { KB_LIGHTS = 1u, KB_EXACT = 2u, KB_SPH = 4u, KB_LIST = 8u, KB_VIEWS = 16u };  // lights, proof, sphere pair filter, tile list, batched views
+struct KernelBuild {
+    KernelFamily family; uint32_t bits; void (*fn)(const DRender); const char *name;
+    uint32_t wg() const { return family == KF_STREAM ? HRT_SP_WG : HRT_WG; }  // threads per workgroup
+};
+#define HRT_BUILD(k, family, bits) {family, bits, k, #k}
+const KernelBuild k_builds[] = {
+    HRT_BUILD(hrt_trace_kernel, KF_LANE, 0u),
+    HRT_BUILD(hrt_trace_kernel_lights, KF_LANE, KB_LIGHTS),
+    HRT_BUILD(hrt_trace_kernel_exact, KF_LANE, KB_EXACT),
+    HRT_BUILD(hrt_trace_kernel_lights_exact, KF_LANE, KB_LIGHTS | KB_EXACT),
+    HRT_BUILD(hrt_trace_kernel_list, KF_LANE, KB_LIST),
+    HRT_BUILD(hrt_trace_kernel_lights_list, KF_LANE, KB_LIGHTS | KB_LIST),
+    HRT_BUILD(hrt_trace_kernel_exact_list, KF_LANE, KB_EXACT | KB_LIST),
+    HRT_BUILD(hrt_trace_kernel_lights_exact_list, KF_LANE, KB_LIGHTS | KB_EXACT | KB_LIST),
+    HRT_BUILD(hrt_trace_kernel_views, KF_LANE, KB_VIEWS),
+    HRT_BUILD(hrt_trace_kernel_lights_views, KF_LANE, KB_LIGHTS | KB_VIEWS),
+    HRT_BUILD(hrt_trace2_kernel, KF_DUAL, 0u),
+    HRT_BUILD(hrt_trace2_kernel_lights, KF_DUAL, KB_LIGHTS),
+    HRT_BUILD(hrt_trace2_kernel_list, KF_DUAL, KB_LIST),
+    HRT_BUILD(hrt_trace2_kernel_lights_list, KF_DUAL, KB_LIGHTS | KB_LIST),
+    HRT_BUILD(hrt_wgstream_kernel, KF_STREAM, 0u),
+    HRT_BUILD(hrt_wgstream_kernel_lights, KF_STREAM, KB_LIGHTS),
+    HRT_BUILD(hrt_wgstream_kernel_sph, KF_STREAM, KB_SPH),
+    HRT_BUILD(hrt_wgstream_kernel_lights_sph, KF_STREAM, KB_LIGHTS | KB_SPH),
+    HRT_BUILD(hrt_wgstream_kernel_exact, KF_STREAM, KB_EXACT),
+    HRT_BUILD(hrt_wgstream_kernel_lights_exact, KF_STREAM, KB_LIGHTS | KB_EXACT),
+    HRT_BUILD(hrt_wgstream_kernel_list, KF_STREAM, KB_LIST),
+    HRT_BUILD(hrt_wgstream_kernel_lights_list, KF_STREAM, KB_LIGHTS | KB_LIST),
+    HRT_BUILD(hrt_wgstream_kernel_sph_list, KF_STREAM, KB_SPH | KB_LIST),
+    HRT_BUILD(hrt_wgstream_kernel_lights_sph_list, KF_STREAM, KB_LIGHTS | KB_SPH | KB_LIST),
+    HRT_BUILD(hrt_wgstream_kernel_exact_list, KF_STREAM, KB_EXACT | KB_LIST),
+    HRT_BUILD(hrt_wgstream_kernel_lights_exact_list, KF_STREAM, KB_LIGHTS | KB_EXACT | KB_LIST),
+    HRT_BUILD(hrt_wgstream_kernel_views, KF_STREAM, KB_VIEWS),
+    HRT_BUILD(hrt_wgstream_kernel_lights_views, KF_STREAM, KB_LIGHTS | KB_VIEWS),
+    HRT_BUILD(hrt_wgstream_kernel_sph_views, KF_STREAM, KB_SPH | KB_VIEWS),
+    HRT_BUILD(hrt_wgstream_kernel_lights_sph_views, KF_STREAM, KB_LIGHTS | KB_SPH | KB_VIEWS),
+};
+
+// Which build runs a launch: plain values in, a row of k_builds or an error out (in.hrt_kernel is not read: pref is its parsed
+// form).  All forms give identical pixels, so this is policy; the measurements behind its thresholds are in DESIGN.md section 5.
+int pick_build(const hrt_pick_input &in, KernelPref pref, const KernelBuild *&row) {
+    const uint32_t flags = in.flags;
+    // the streaming kernel stages the per-object tables (squares, materials, spheres, mesh records) in LDS beside its queues
+    const bool stream_fits = (size_t)in.tab_rows * 16u <= 48u * 1024u;
+    if ((flags & HRT_FLAG_STREAM_KERNEL) && !stream_fits)
+        return fail(HRT_ERR_INVALID, "render: the scene's object tables exceed the 48 KiB the streaming kernel keeps in LDS; use another kernel form");
+    const bool stream_pays = in.n_meshes > 0u || in.n_lights > 0u || (in.tiles <= 5120u && in.spp >= 8u);
+    const bool stream = stream_fits && !(flags & (HRT_FLAG_WAVE_KERNEL | HRT_FLAG_DUAL_KERNEL)) &&
+                        (pref.use_stream == 1 || (flags & HRT_FLAG_STREAM_KERNEL) || (pref.use_stream < 0 && stream_pays));
+    const bool exact = (flags & HRT_FLAG_EXACT_ONLY) != 0u;  // proof builds exist for the lane-per-pixel and streaming forms
+    if (const int rc = check_mesh_brute("render", flags)) return rc;
+    if (exact && (flags & HRT_FLAG_DUAL_KERNEL)) return fail(HRT_ERR_INVALID, "render: no exact-only build of the two-stream kernel");
+    const bool dual = !exact && !stream && !in.n_views && (pref.use_dual || (flags & HRT_FLAG_DUAL_KERNEL)) && in.n_meshes > 0u &&
+                      !(flags & HRT_FLAG_WAVE_KERNEL);
+    const KernelFamily family = stream ? KF_STREAM : (dual ? KF_DUAL : KF_LANE);
+    const bool sph = stream && !exact && in.n_spheres >= HRT_SPHERE_FILTER_MIN && in.n_spheres <= 128u;  // a crowd of spheres: the pair filter
+    const uint32_t bits = (in.n_lights ? KB_LIGHTS : 0u) | (exact ? KB_EXACT : 0u) | (sph ? KB_SPH : 0u) | (in.has_list ? KB_LIST : 0u) |
+                          (in.n_views ? KB_VIEWS : 0u);
+    for (const KernelBuild &b : k_builds)
+        if (b.family == family && b.bits == bits) { row = &b; return HRT_OK; }
+    return fail(HRT_ERR_INVALID, std::string("render: there is no build of the ") + (stream ? "streaming" : dual ? "two-stream" : "lane-per-pixel") + " kernel for" +
+                                 (in.n_views ? " batched views" : "") + (in.has_list ? " with a tile list" : "") + (exact ? " with HRT_FLAG_EXACT_ONLY" : ""));
+}
+
 }  // namespace
 
 struct hrt_scene {
@@ -294,6 +371,7 @@ struct hrt_scene {
     Scratch sp_scratch, sp_pool, tiles, frame, ad_compact, ad_words, dn_frame, dn_feat, dn_scratch, dn_out, dnv_half_tiles, dnv_frame_half, dnv_var;
     std::array<Scratch *, 13> scratch() { return {&sp_scratch, &sp_pool, &tiles, &frame, &ad_compact, &ad_words, &dn_frame, &dn_feat, &dn_scratch, &dn_out, &dnv_half_tiles, &dnv_frame_half, &dnv_var}; }
     uint32_t last_grid = 0, last_waves = 0, last_lds = 0;
+    const KernelBuild *last_build = nullptr;  // the row of k_builds the last trace launch ran (hrt_debug_last_kernel)
     hipStream_t last_stream = nullptr;  // stream of the previous launch on this scene
     int device = 0;                     // the device that holds this scene (current when it was created)
     // hrt_render_features' own camera block, with its host copy and the event that orders feature launches across streams
@@ -372,50 +450,17 @@ int hrt_init(int device_ordinal) {
     if (const char *e = std::getenv("HRT_LDS_KB")) kb = (uint32_t)std::max(0, atoi(e));
     if (kb > 160) kb = 160;
     g_rt.lds_budget = kb * 1024u;
-    if (g_rt.lds_budget > 64u * 1024u) {
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)g_rt.lds_budget));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_list, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_rt.lds_budget));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_lights, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)g_rt.lds_budget));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_lights_list, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_rt.lds_budget));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_rt.lds_budget));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_exact_list, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_rt.lds_budget));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_lights_exact, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)g_rt.lds_budget));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_lights_exact_list, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_rt.lds_budget));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_views, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_rt.lds_budget));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace_kernel_lights_views, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_rt.lds_budget));
-    }
-    if (HRT_WG > 256) {  // one big workgroup per CU: backed-up streams + nodelets go past the 64 KiB default
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace2_kernel_lights, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace2_kernel_list, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_trace2_kernel_lights_list, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
+    // Dynamic LDS past the 64 KiB default: the lane-per-pixel builds' nodelets when the budget asks for it, the two-stream builds'
+    // backed-up streams + nodelets when one big workgroup has the CU, the streaming builds' path pool (113 KiB + nodelets) always.
+    const uint32_t raise[] = {g_rt.lds_budget > 64u * 1024u ? g_rt.lds_budget : 0u, HRT_WG > 256 ? 160u * 1024u : 0u, 160u * 1024u};  // by KernelFamily; 0: leave
+    for (const KernelBuild &b : k_builds)
+        if (raise[b.family]) HIP_TRY(hipFuncSetAttribute((const void *)b.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)raise[b.family]));
     {   // u8 -> float tables in double, as the reference evaluates c/255. and c/127.5 - 1. (Material.cpp:87,124)
         float lut[512];
         for (int c = 0; c < 256; ++c) { lut[c] = (float)(c / 255.); lut[256 + c] = (float)(c / 127.5 - 1.); }
         HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_u8_lut), lut, sizeof(lut)));
     }
-    {   // the streaming kernel keeps its path pool in LDS: 113 KiB + nodelets, one 1024-thread workgroup per CU
-        const int max_lds = 160 * 1024;
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_wgstream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_wgstream_kernel_lights, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_wgstream_kernel_exact, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_wgstream_kernel_lights_exact, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_wgstream_kernel_sph, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        HIP_TRY(hipFuncSetAttribute((const void *)hrt_wgstream_kernel_lights_sph, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        for (const void *k : {(const void *)hrt_wgstream_kernel_list, (const void *)hrt_wgstream_kernel_lights_list, (const void *)hrt_wgstream_kernel_exact_list,
-                              (const void *)hrt_wgstream_kernel_lights_exact_list, (const void *)hrt_wgstream_kernel_sph_list, (const void *)hrt_wgstream_kernel_lights_sph_list,
-                              (const void *)hrt_wgstream_kernel_views, (const void *)hrt_wgstream_kernel_lights_views, (const void *)hrt_wgstream_kernel_sph_views,
-                              (const void *)hrt_wgstream_kernel_lights_sph_views})
-            HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        const char *k = std::getenv("HRT_KERNEL");
-        const std::string ks = k ? k : "";
-        g_rt.use_dual = ks != "single";
-        g_rt.use_stream = ks == "stream" ? 1 : ((ks == "single" || ks == "dual") ? 0 : -1);
-    }
+    g_rt.pref = parse_kernel_pref(std::getenv("HRT_KERNEL"));
     g_rt.dev_cus[device_ordinal] = prop.multiProcessorCount;
     g_rt.ready = true;
     return HRT_OK;
@@ -1055,135 +1100,123 @@ static int fill_render(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t
     return HRT_OK;
 }
 
-// The kernel of that name, or its build over a tile list (DRender::tile_list) when the launch has one.
-#define HRT_PICK(k) (list ? k##_list : k)
+// A streaming build's launch geometry: its LDS (queues, tables, as much of the tree as fits), grid, unit and band sizes, scratch.
+static int size_stream(hrt_scene *s, const KernelBuild &b, DRender &R, uint32_t &grid, uint32_t &lds_bytes) {
+    const uint32_t fixed = (uint32_t)((HRT_SP_GLOBAL ? 0 : SP_FIELDS * HRT_SP_POOL * 4) + HRT_SP_NQ * HRT_SP_POOL * 2 + HRT_SP_STREAMS * sizeof(SpCtl) + sizeof(SpShared) + HRT_SP_UNITS * sizeof(SpUnit) + HRT_SP_UNITS * HRT_SP_MAXG * 4) +
+                           ((b.bits & KB_VIEWS) ? HRT_SP_UNITS * HRT_SP_MAXG * 16u : 0u) +  // the VIEWS builds' table of view rows
+                           2048u + s->d.tab_rows * 16u  // + the scene's per-object tables (stream_tables_fit)
+#ifdef HRT_WALK_SEG
+                           + 2048u  // diagnostic build: 16 accumulators per wave
+#endif
+                           ;
+    uint32_t per_cu = (64u * 4u * HRT_SP_MINW) / HRT_SP_WG;  // workgroups resident per CU (HRT_SP_MINW waves per SIMD in all) ...
+    while (per_cu > 1u && 160u * 1024u / per_cu < fixed + 16u * 1024u) --per_cu;  // ... as far as the LDS pools allow
+    const uint32_t room = (160u * 1024u / per_cu - fixed) / 16u;
+    if (!(R.flags & HRT_FLAG_NO_LDS_TREE)) R.lds_units = std::min<uint32_t>(s->d.n_kd_units, room) & ~3u;  // whole 64-byte lines: no treelet or leaf straddles
+    lds_bytes = fixed + R.lds_units * 16u;
+    grid = std::min<uint32_t>((uint32_t)g_rt.cus * per_cu, R.tiles_owned);
+    {   // tiles per work unit: as many as keep one unit (tiles x 64 pixels x samples per fold) within HRT_SP_UNIT paths
+        const uint32_t per_tile = 64u * std::min<uint32_t>(R.spp, HRT_SP_SCHUNK);
+        uint32_t glog = 0;
+        while ((2u << glog) <= HRT_SP_MAXG && (per_tile << (glog + 1u)) <= HRT_SP_UNIT) ++glog;
+        R.sp_group_log2 = glog;
+        // Few, heavy tiles (a rank's share of a frame at thousands of samples per pixel): the launch ends when the last
+        // workgroup finishes its last item, and an item is a whole tile's samples -- in order, so a tile cannot be split
+        // across workgroups by samples.  Split it by ROWS instead: bands of 4, 2 rows until a workgroup has ~64 items.
+        uint32_t band = 0;
+        while (glog == 0u && band < 2u && ((uint64_t)R.tiles_owned << band) < 64ull * grid && (64u >> (band + 1u)) * (uint64_t)std::min<uint32_t>(R.spp, HRT_SP_SCHUNK) >= 4096u) ++band;
+        R.sp_band_log2 = band;
+    }
+    int rc = s->sp_scratch.grow((size_t)grid * HRT_SP_UNITS * HRT_SP_UNIT * 3u * sizeof(float));  // HRT_SP_UNITS units in flight per workgroup
+    if (rc == HRT_OK && HRT_SP_GLOBAL) rc = s->sp_pool.grow((size_t)grid * SP_FIELDS * HRT_SP_POOL * sizeof(uint32_t));
+    if (rc != HRT_OK) return rc;
+    R.sp_scratch = s->sp_scratch.as<float>();
+    R.sp_pool = s->sp_pool.as<uint32_t>();
+    return HRT_OK;
+}
+
+// A lane-per-pixel or two-stream build's: nodelets (and backed-up streams) in LDS, the workgroups the device keeps resident.
+static int size_lanes(const KernelBuild &b, DRender &R, uint32_t &grid, uint32_t &lds_bytes) {
+    const bool dual = b.family == KF_DUAL;
+    lds_bytes = R.lds_units * 16u;
+    if (dual) {
+        // 4 workgroups per CU: 160 KiB = 4 x (27 KiB of backed-up streams + 12 KiB of nodelets)
+        const uint32_t wgs = 1024u / HRT_WG, backup = HRT_DS_FIELDS * HRT_WG * 4u;
+        const uint32_t room = (156u * 1024u / wgs - backup) / 16u;
+        if (R.lds_units > room) R.lds_units = room & ~3u;
+        lds_bytes = R.lds_units * 16u + backup;
+    }
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)b.fn, HRT_WG, lds_bytes));
+    if (per_cu < 1) per_cu = 1;
+    grid = (uint32_t)(per_cu * g_rt.cus);
+    // 4 waves per workgroup, one tile (two in the dual-stream kernel) per wave at a time
+    const uint32_t per_wg = (HRT_WG / 64u) * (dual ? 2u : 1u);
+    const uint32_t need = (R.tiles_owned + per_wg - 1u) / per_wg;
+    if (grid > need) grid = need;
+    R.sp_scratch = nullptr;
+    R.sp_pool = nullptr;
+    return HRT_OK;
+}
 
 // One launch of the trace kernel over this rank's tiles: samples [s0, s0 + spp) of every pixel.
-// accumulate = false: d_tiles receives the pixel means (s0 must be 0).
-// accumulate = true : d_tiles holds the running sums of samples [0, s0) and receives the sums of [0, s0 + spp).
-// list (device, list_n rank slots; adaptive sampling): only those tiles, into a COMPACT d_tiles (entry j of the list at slot j).
-// The kernel-form and grid choices below then see list_n tiles.
-// n_views != 0 (batched views, hrt_views.hip; rank 0 of world 1, no list, no accumulation): the n_views blocks staged in s->h_views
-// are uploaded to s->vw_blocks in place of the camera block, and the queue is n_views x the frame's tiles, view-major; cam is view
-// 0's, seed is not used.  The kernel-form and grid choices see all views' tiles; the two-stream and proof forms have no such build.
-static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t s0, uint32_t spp, uint64_t seed,
-                        uint32_t flags, uint32_t rank, uint32_t world, float *d_tiles, void *stream_, bool accumulate,
-                        const uint32_t *list = nullptr, uint32_t list_n = 0, uint32_t n_views = 0) {
+struct TraceJob {
+    uint32_t w, h, s0, spp;
+    uint64_t seed;
+    uint32_t flags;
+    float *d_tiles;
+    void *stream;
+    uint32_t rank = 0, world = 1;
+    // false: d_tiles receives the pixel means (s0 must be 0).
+    // true : d_tiles holds the running sums of samples [0, s0) and receives the sums of [0, s0 + spp).
+    bool accumulate = false;
+    // (device, list_n rank slots; adaptive sampling): only those tiles, into a COMPACT d_tiles (entry j of the list at slot j).
+    const uint32_t *list = nullptr;
+    uint32_t list_n = 0;
+    // != 0 (batched views, hrt_views.hip; rank 0 of world 1, no list, no accumulation): the n_views blocks staged in s->h_views are
+    // uploaded to s->vw_blocks in place of the camera block, and the queue is n_views x the frame's tiles, view-major; cam is view
+    // 0's, seed is not used.  The kernel-form and grid choices see the list's tiles, or all views'.
+    uint32_t n_views = 0;
+};
+static int launch_trace(hrt_scene *s, const hrt_camera *cam, const TraceJob &J) {
     DRender R;
     DCamera C;
-    int rc = fill_render(s, cam, w, h, spp, seed, flags, rank, world, R, C);
+    int rc = fill_render(s, cam, J.w, J.h, J.spp, J.seed, J.flags, J.rank, J.world, R, C);
     if (rc != HRT_OK) return rc;
-    if (list) {
-        if (list_n > R.tiles_owned) return fail(HRT_ERR_INVALID, "render: tile list longer than the rank's tiles");
-        R.tile_list = list;
-        R.tiles_owned = list_n;
+    if (J.list) {
+        if (J.list_n > R.tiles_owned) return fail(HRT_ERR_INVALID, "render: tile list longer than the rank's tiles");
+        R.tile_list = J.list;
+        R.tiles_owned = J.list_n;
     }
-    if (n_views) {
+    if (J.n_views) {
         R.views = s->vw_blocks.as<DView>();
-        R.tiles_owned = n_views * R.tiles_total;
+        R.tiles_owned = J.n_views * R.tiles_total;
     }
     R.cam = s->d_cam;
-    if (!d_tiles) return fail(HRT_ERR_INVALID, "render: NULL tile buffer");
-    if ((uint64_t)s0 + spp > 0xffffffffull) return fail(HRT_ERR_INVALID, "render: sample index overflows 32 bits");
-    R.out_tiles = d_tiles;
-    R.s0 = s0;
-    R.accumulate = accumulate ? 1u : 0u;
-    if (accumulate) flags &= ~(uint32_t)HRT_FLAG_GAMMA;  // hrt_finalize_tiles applies the gamma
-    hipStream_t stream = (hipStream_t)stream_;
+    if (!J.d_tiles) return fail(HRT_ERR_INVALID, "render: NULL tile buffer");
+    if ((uint64_t)J.s0 + J.spp > 0xffffffffull) return fail(HRT_ERR_INVALID, "render: sample index overflows 32 bits");
+    R.out_tiles = J.d_tiles;
+    R.s0 = J.s0;
+    R.accumulate = J.accumulate ? 1u : 0u;
+    const bool gamma = (J.flags & HRT_FLAG_GAMMA) && !J.accumulate;  // of sums, hrt_finalize_tiles applies the gamma
+    hipStream_t stream = (hipStream_t)J.stream;
     if (R.tiles_owned == 0) { s->timed = false; return HRT_OK; }
-    // Which schedule of the same arithmetic (all give identical pixels).  Measured on MI355X at 1080p: the
-    // workgroup-streaming kernel wins where bounces diverge -- meshes (+3..10 %) and lit open scenes (random_spheres
-    // +30 %) -- and loses on a closed box of squares (-45 %), where the lane-per-pixel kernel keeps its lanes busy anyway.
-    // The streaming kernel pays where bounces diverge (meshes, lights) -- and on SMALL frames with many samples per pixel: the
-    // lane-per-pixel kernel gives a wave 64 pixels and walks their samples one after the other, so below ~5 k tiles (20 waves
-    // on each of 256 CUs) its time is spp x one sample's latency, while the streaming kernel spreads samples over the whole pool
-    // (Cornell box 256 x 256 on MI355X: 4 spp 0.22 vs 0.29 ms, 64 spp 3.22 vs 1.52 ms; 1080p @ 16: 8.6 vs 11.1 ms).
-    const bool small_and_deep = R.tiles_owned <= 5120u && spp >= 8u;
-    const bool stream_pays = s->d.n_meshes > 0u || s->d.n_lights > 0u || small_and_deep;
-    // the streaming kernel stages the per-object tables (squares, materials, spheres, mesh records) in LDS beside its queues
-    const bool stream_fits = (size_t)s->d.tab_rows * 16u <= 48u * 1024u;
-    if ((flags & HRT_FLAG_STREAM_KERNEL) && !stream_fits)
-        return fail(HRT_ERR_INVALID, "render: the scene's object tables exceed the 48 KiB the streaming kernel keeps in LDS; use another kernel form");
-    const bool stream_kernel = stream_fits && !(flags & (HRT_FLAG_WAVE_KERNEL | HRT_FLAG_DUAL_KERNEL)) &&
-                               (g_rt.use_stream == 1 || (flags & HRT_FLAG_STREAM_KERNEL) || (g_rt.use_stream < 0 && stream_pays));
-    const bool exact = (flags & HRT_FLAG_EXACT_ONLY) != 0u;  // proof builds exist for the lane-per-pixel and streaming forms
-    if ((rc = check_mesh_brute("render", flags)) != HRT_OK) return rc;
-    if (exact && (flags & HRT_FLAG_DUAL_KERNEL)) return fail(HRT_ERR_INVALID, "render: no exact-only build of the two-stream kernel");
-    const bool dual_kernel = !exact && !stream_kernel && !n_views && (g_rt.use_dual || (flags & HRT_FLAG_DUAL_KERNEL)) && s->d.n_meshes > 0u &&
-                             !(flags & HRT_FLAG_WAVE_KERNEL);
-    const bool sph_build = s->d.n_spheres >= HRT_SPHERE_FILTER_MIN && s->d.n_spheres <= 128u;  // a crowd of spheres: the streaming builds with the pair filter
-    // the kernel of a batched launch, picked once: the occupancy query and the launch below use this one
-    void (*const views_kernel)(const DRender) =
-        !n_views ? nullptr
-        : !stream_kernel ? (s->d.n_lights ? hrt_trace_kernel_lights_views : hrt_trace_kernel_views)
-        : sph_build ? (s->d.n_lights ? hrt_wgstream_kernel_lights_sph_views : hrt_wgstream_kernel_sph_views)
-                    : (s->d.n_lights ? hrt_wgstream_kernel_lights_views : hrt_wgstream_kernel_views);
+    const KernelBuild *build = nullptr;
+    const hrt_pick_input traits{s->d.n_meshes, s->d.n_lights, s->d.n_spheres, s->d.tab_rows, R.tiles_owned, J.spp, J.flags, J.list ? 1u : 0u, J.n_views, nullptr};
+    if ((rc = pick_build(traits, g_rt.pref, build)) != HRT_OK) return rc;
     uint32_t grid, lds_bytes;
-    if (stream_kernel) {
-        const uint32_t fixed = (uint32_t)((HRT_SP_GLOBAL ? 0 : SP_FIELDS * HRT_SP_POOL * 4) + HRT_SP_NQ * HRT_SP_POOL * 2 + HRT_SP_STREAMS * sizeof(SpCtl) + sizeof(SpShared) + HRT_SP_UNITS * sizeof(SpUnit) + HRT_SP_UNITS * HRT_SP_MAXG * 4) +
-                               (n_views ? HRT_SP_UNITS * HRT_SP_MAXG * 16u : 0u) +  // the VIEWS builds' table of view rows
-                               2048u + s->d.tab_rows * 16u  // + the scene's per-object tables (stream_tables_fit)
-#ifdef HRT_WALK_SEG
-                               + 2048u  // diagnostic build: 16 accumulators per wave
-#endif
-                               ;
-        uint32_t per_cu = (64u * 4u * HRT_SP_MINW) / HRT_SP_WG;  // workgroups resident per CU (HRT_SP_MINW waves per SIMD in all) ...
-        while (per_cu > 1u && 160u * 1024u / per_cu < fixed + 16u * 1024u) --per_cu;  // ... as far as the LDS pools allow
-        const uint32_t room = (160u * 1024u / per_cu - fixed) / 16u;
-        if (!(flags & HRT_FLAG_NO_LDS_TREE)) R.lds_units = std::min<uint32_t>(s->d.n_kd_units, room) & ~3u;  // whole 64-byte lines: no treelet or leaf straddles
-        lds_bytes = fixed + R.lds_units * 16u;
-        grid = std::min<uint32_t>((uint32_t)g_rt.cus * per_cu, R.tiles_owned);
-        {   // tiles per work unit: as many as keep one unit (tiles x 64 pixels x samples per fold) within HRT_SP_UNIT paths
-            const uint32_t per_tile = 64u * std::min<uint32_t>(spp, HRT_SP_SCHUNK);
-            uint32_t glog = 0;
-            while ((2u << glog) <= HRT_SP_MAXG && (per_tile << (glog + 1u)) <= HRT_SP_UNIT) ++glog;
-            R.sp_group_log2 = glog;
-            // Few, heavy tiles (a rank's share of a frame at thousands of samples per pixel): the launch ends when the last
-            // workgroup finishes its last item, and an item is a whole tile's samples -- in order, so a tile cannot be split
-            // across workgroups by samples.  Split it by ROWS instead: bands of 4, 2 rows until a workgroup has ~64 items.
-            uint32_t band = 0;
-            while (glog == 0u && band < 2u && ((uint64_t)R.tiles_owned << band) < 64ull * grid && (64u >> (band + 1u)) * (uint64_t)std::min<uint32_t>(spp, HRT_SP_SCHUNK) >= 4096u) ++band;
-            R.sp_band_log2 = band;
-        }
-        rc = s->sp_scratch.grow((size_t)grid * HRT_SP_UNITS * HRT_SP_UNIT * 3u * sizeof(float));  // HRT_SP_UNITS units in flight per workgroup
-        if (rc == HRT_OK && HRT_SP_GLOBAL) rc = s->sp_pool.grow((size_t)grid * SP_FIELDS * HRT_SP_POOL * sizeof(uint32_t));
-        if (rc != HRT_OK) return rc;
-        R.sp_scratch = s->sp_scratch.as<float>();
-        R.sp_pool = s->sp_pool.as<uint32_t>();
-    } else {
-        const void *kfn = n_views ? (const void *)views_kernel
-                          : exact ? (s->d.n_lights ? (const void *)HRT_PICK(hrt_trace_kernel_lights_exact) : (const void *)HRT_PICK(hrt_trace_kernel_exact))
-                                : (s->d.n_lights ? (const void *)HRT_PICK(hrt_trace_kernel_lights) : (const void *)HRT_PICK(hrt_trace_kernel));
-        lds_bytes = R.lds_units * 16u;
-        if (dual_kernel) {
-            // 4 workgroups per CU: 160 KiB = 4 x (27 KiB of backed-up streams + 12 KiB of nodelets)
-            const uint32_t wgs = 1024u / HRT_WG, backup = HRT_DS_FIELDS * HRT_WG * 4u;
-            const uint32_t room = (156u * 1024u / wgs - backup) / 16u;
-            if (R.lds_units > room) R.lds_units = room & ~3u;
-            lds_bytes = R.lds_units * 16u + backup;
-            kfn = s->d.n_lights ? (const void *)HRT_PICK(hrt_trace2_kernel_lights) : (const void *)HRT_PICK(hrt_trace2_kernel);
-        }
-        int per_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, HRT_WG, lds_bytes));
-        if (per_cu < 1) per_cu = 1;
-        grid = (uint32_t)(per_cu * g_rt.cus);
-        // 4 waves per workgroup, one tile (two in the dual-stream kernel) per wave at a time
-        const uint32_t per_wg = (HRT_WG / 64u) * (dual_kernel ? 2u : 1u);
-        const uint32_t need = (R.tiles_owned + per_wg - 1u) / per_wg;
-        if (grid > need) grid = need;
-        R.sp_scratch = nullptr;
-        R.sp_pool = nullptr;
-    }
+    rc = build->family == KF_STREAM ? size_stream(s, *build, R, grid, lds_bytes) : size_lanes(*build, R, grid, lds_bytes);
+    if (rc != HRT_OK) return rc;
     s->last_grid = grid;
     s->last_lds = lds_bytes;
-    s->last_waves = stream_kernel ? grid * (HRT_SP_WG / 64) : grid * (HRT_WG / 64u);
+    s->last_waves = grid * (build->wg() / 64u);
     // One hrt_scene carries ONE launch at a time (work-queue head, stamps, path pool, camera block).  Launches on one
     // stream are ordered by the stream; a launch on another stream first waits for the previous one -- before anything of
     // its own is enqueued, the copy of a new camera block included (the previous launch may still be reading the old one).
     if (s->timed && s->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->ev1, 0));
     s->last_stream = stream;
-    if (n_views) {
-        HIP_TRY(hipMemcpyAsync(s->vw_blocks.p, s->h_views, (size_t)n_views * sizeof(DView), hipMemcpyHostToDevice, stream));
+    if (J.n_views) {
+        HIP_TRY(hipMemcpyAsync(s->vw_blocks.p, s->h_views, (size_t)J.n_views * sizeof(DView), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipEventRecord(s->ev_views, stream));
         s->views_uploading = true;
     } else if (!s->cam_valid || std::memcmp(&C, &s->h_cam, sizeof(C)) != 0) {
@@ -1194,32 +1227,13 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
     HIP_TRY(hipMemsetAsync(s->tile_counter, 0, sizeof(uint32_t), stream));
     HIP_TRY(hipMemsetAsync(s->stamps, 0, 16 * sizeof(unsigned long long), stream));  // [15] = give-up code of the streaming kernel
     HIP_TRY(hipEventRecord(s->ev0, stream));
-    if (n_views) {
-        hipLaunchKernelGGL(views_kernel, dim3(grid), dim3(stream_kernel ? HRT_SP_WG : HRT_WG), lds_bytes, stream, R);
-    } else if (stream_kernel && exact) {
-        if (s->d.n_lights) hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel_lights_exact), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
-        else hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel_exact), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
-    } else if (stream_kernel && sph_build) {
-        if (s->d.n_lights) hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel_lights_sph), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
-        else hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel_sph), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
-    } else if (stream_kernel) {
-        if (s->d.n_lights) hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel_lights), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
-        else hipLaunchKernelGGL(HRT_PICK(hrt_wgstream_kernel), dim3(grid), dim3(HRT_SP_WG), lds_bytes, stream, R);
-    } else if (exact) {
-        if (s->d.n_lights) hipLaunchKernelGGL(HRT_PICK(hrt_trace_kernel_lights_exact), dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
-        else hipLaunchKernelGGL(HRT_PICK(hrt_trace_kernel_exact), dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
-    } else {
-        if (dual_kernel) {
-            if (s->d.n_lights) hipLaunchKernelGGL(HRT_PICK(hrt_trace2_kernel_lights), dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
-            else hipLaunchKernelGGL(HRT_PICK(hrt_trace2_kernel), dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
-        } else if (s->d.n_lights) hipLaunchKernelGGL(HRT_PICK(hrt_trace_kernel_lights), dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
-        else hipLaunchKernelGGL(HRT_PICK(hrt_trace_kernel), dim3(grid), dim3(HRT_WG), lds_bytes, stream, R);
-    }
+    hipLaunchKernelGGL(build->fn, dim3(grid), dim3(build->wg()), lds_bytes, stream, R);
+    s->last_build = build;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(s->ev1, stream));
-    if (flags & HRT_FLAG_GAMMA) {
+    if (gamma) {
         const uint32_t n = R.tiles_owned * 64u * 3u;
-        hipLaunchKernelGGL(hrt_gamma_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_tiles, n);
+        hipLaunchKernelGGL(hrt_gamma_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, J.d_tiles, n);
         HIP_TRY(hipGetLastError());
     }
     s->timed = true;
@@ -1230,14 +1244,18 @@ int hrt_render_tiles(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h
                      uint32_t flags, uint32_t rank, uint32_t world, float *d_tiles, void *stream) {
     const int rc = enter_render("hrt_render_tiles", s, cam);
     if (rc != HRT_OK) return rc;
-    return launch_trace(s, cam, w, h, 0u, spp, seed, flags, rank, world, d_tiles, stream, false);
+    TraceJob job{w, h, 0u, spp, seed, flags, d_tiles, stream};
+    job.rank = rank; job.world = world;
+    return launch_trace(s, cam, job);
 }
 
 int hrt_render_accumulate(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples,
                           uint64_t seed, uint32_t flags, uint32_t rank, uint32_t world, float *d_sum_tiles, void *stream) {
     const int rc = enter_render("hrt_render_accumulate", s, cam);
     if (rc != HRT_OK) return rc;
-    return launch_trace(s, cam, w, h, first_sample, n_samples, seed, flags, rank, world, d_sum_tiles, stream, true);
+    TraceJob job{w, h, first_sample, n_samples, seed, flags, d_sum_tiles, stream};
+    job.rank = rank; job.world = world; job.accumulate = true;
+    return launch_trace(s, cam, job);
 }
 
 int hrt_finalize_tiles(const float *d_sum_tiles, uint32_t n_tiles, uint32_t total_samples, uint32_t flags, float *d_tiles,
@@ -1350,6 +1368,20 @@ int hrt_debug_read_stamps(hrt_scene *s, uint64_t out[16]) {
     { const int drc = use_device(s->device); if (drc != HRT_OK) return drc; }
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, s->stamps, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return HRT_OK;
+}
+
+int hrt_debug_pick_kernel(const hrt_pick_input *in, char *name, size_t cap) {
+    if (!in || !name || !cap) return fail(HRT_ERR_INVALID, "hrt_debug_pick_kernel: bad argument");
+    const KernelBuild *build = nullptr;
+    const int rc = pick_build(*in, parse_kernel_pref(in->hrt_kernel), build);
+    std::snprintf(name, cap, "%s", build ? build->name : "");
+    return rc;
+}
+
+int hrt_debug_last_kernel(hrt_scene *s, char *name, size_t cap) {
+    if (!s || !name || !cap) return fail(HRT_ERR_INVALID, "hrt_debug_last_kernel: bad argument");
+    std::snprintf(name, cap, "%s", s->last_build ? s->last_build->name : "");
     return HRT_OK;
 }
 

@@ -73,7 +73,9 @@ static int views_launch(hrt_scene *s, const hrt_view *views, std::vector<DView> 
     // The tile sums are read by the assemble launch, behind the event launch_trace orders launches by: a batched launch on another
     // stream waits for the previous one's frames as well.
     if (s->views_used && s->views_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->ev_views_done, 0));
-    rc = launch_trace(s, &views[0].cam, w, h, 0u, spp, 0u, flags, 0u, 1u, s->vw_tiles.as<float>(), stream, false, nullptr, 0u, n_views);
+    TraceJob job{w, h, 0u, spp, 0u, flags, s->vw_tiles.as<float>(), stream};
+    job.n_views = n_views;
+    rc = launch_trace(s, &views[0].cam, job);
     if (rc != HRT_OK) return rc;
     const uint32_t n_pixels = n_views * w * h;
     hipLaunchKernelGGL(hrt_assemble_views_kernel, dim3((n_pixels + 255u) / 256u), dim3(256), 0, stream, s->vw_tiles.as<float>(), tiles, w, h,

@@ -352,6 +352,22 @@ HRT_API int hrt_debug_kat(uint32_t which, const hrt_camera *cam, const float *pr
  * -DHRT_STAMPS (diagnostic build, tools/variants.sh).  out: 16 values. */
 HRT_API int hrt_debug_read_stamps(hrt_scene *scene, uint64_t out[16]);
 
+/* Which build of the trace kernel a launch runs ("Builds and how one is chosen"): the library's own choice
+ * function on plain values, so that the policy can be tested without a GPU and without hrt_init.  The scene's traits (tab_rows:
+ * 16-byte rows of its per-object tables), the launch's tiles (after a tile list or batched views have set the count) and samples
+ * per pixel, its flags, whether it has a tile list, its views (0 = not batched), and the value of the HRT_KERNEL environment
+ * variable ("single", "dual", "stream"; NULL, "" or anything else = the default), which hrt_init parses with the same code.
+ * Writes the kernel's name to name[cap] and returns HRT_OK, or returns the error the launch would (name = ""). */
+typedef struct hrt_pick_input {
+    uint32_t n_meshes, n_lights, n_spheres, tab_rows;
+    uint32_t tiles, spp;
+    uint32_t flags, has_list, n_views;
+    const char *hrt_kernel;
+} hrt_pick_input;
+HRT_API int hrt_debug_pick_kernel(const hrt_pick_input *in, char *name, size_t cap);
+/* The name of the build the scene's last trace launch ran ("" before any). */
+HRT_API int hrt_debug_last_kernel(hrt_scene *scene, char *name, size_t cap);
+
 /* Output stage of main.cpp:252-262: P3 ASCII with (int)(255*min(1,c)). */
 /* The tree build's split search and partition on the GPU (a hrt_kd_builder_fn; `user` is ignored): level by level, every
  * candidate plane of every open node evaluated in parallel with the host builder's arithmetic and tie-breaking, so the
