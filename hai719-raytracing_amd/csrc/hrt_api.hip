@@ -510,6 +510,14 @@ static int scene_create_impl(const hrt_scene_desc *desc, hrt_scene *s) {
     if (D.skybox_image >= (int32_t)D.n_images) return fail(HRT_ERR_INVALID, "skybox image out of range");
     if (D.n_lights && !D.lights) return fail(HRT_ERR_INVALID, "lights missing");
     if (D.n_meshes > 32u) return fail(HRT_ERR_INVALID, "more than 32 meshes in one scene (the parked-mesh mask is 32 bits)");
+    {   // the soup of all meshes: a path record names a triangle by soup slot in 25 bits (hrt_stream.hip sp_hit_word).  By the counts alone,
+        // before any array is read: an irregular triangle takes one row, and there are at most min(n_exceptions, n_triangles) of them
+        uint64_t rows = 0;
+        for (uint32_t mi = 0; mi < D.n_meshes; ++mi) rows += (uint64_t)D.meshes[mi].n_leaf_tris + std::min(D.meshes[mi].n_exceptions, D.meshes[mi].n_triangles);
+        if (rows > (uint64_t)HRT_MAX_SOUP_SLOTS)
+            return fail(HRT_ERR_INVALID, "triangle soup of " + std::to_string(rows) + " rows (leaf triangles + irregular triangles of all meshes): more than HRT_MAX_SOUP_SLOTS = " +
+                                             std::to_string(HRT_MAX_SOUP_SLOTS) + " (a path record keeps 25 bits of soup slot)");
+    }
 
     // ---- scene extent: an upper bound on |point| for every point a ray can start from or hit
     {
@@ -1102,7 +1110,7 @@ static int fill_render(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t
 
 // A streaming build's launch geometry: its LDS (queues, tables, as much of the tree as fits), grid, unit and band sizes, scratch.
 static int size_stream(hrt_scene *s, const KernelBuild &b, DRender &R, uint32_t &grid, uint32_t &lds_bytes) {
-    const uint32_t fixed = (uint32_t)((HRT_SP_GLOBAL ? 0 : SP_FIELDS * HRT_SP_POOL * 4) + HRT_SP_NQ * HRT_SP_POOL * 2 + HRT_SP_STREAMS * sizeof(SpCtl) + sizeof(SpShared) + HRT_SP_UNITS * sizeof(SpUnit) + HRT_SP_UNITS * HRT_SP_MAXG * 4) +
+    const uint32_t fixed = (uint32_t)(HRT_SP_NQ * HRT_SP_POOL * 2 + HRT_SP_STREAMS * sizeof(SpCtl) + sizeof(SpShared) + HRT_SP_UNITS * sizeof(SpUnit) + HRT_SP_UNITS * HRT_SP_MAXG * 4) +
                            ((b.bits & KB_VIEWS) ? HRT_SP_UNITS * HRT_SP_MAXG * 16u : 0u) +  // the VIEWS builds' table of view rows
                            2048u + s->d.tab_rows * 16u  // + the scene's per-object tables (stream_tables_fit)
 #ifdef HRT_WALK_SEG
@@ -1128,7 +1136,7 @@ static int size_stream(hrt_scene *s, const KernelBuild &b, DRender &R, uint32_t 
         R.sp_band_log2 = band;
     }
     int rc = s->sp_scratch.grow((size_t)grid * HRT_SP_UNITS * HRT_SP_UNIT * 3u * sizeof(float));  // HRT_SP_UNITS units in flight per workgroup
-    if (rc == HRT_OK && HRT_SP_GLOBAL) rc = s->sp_pool.grow((size_t)grid * SP_FIELDS * HRT_SP_POOL * sizeof(uint32_t));
+    if (rc == HRT_OK) rc = s->sp_pool.grow((size_t)grid * SP_FIELDS * HRT_SP_POOL * sizeof(uint32_t));
     if (rc != HRT_OK) return rc;
     R.sp_scratch = s->sp_scratch.as<float>();
     R.sp_pool = s->sp_pool.as<uint32_t>();
@@ -1457,8 +1465,8 @@ int hrt_debug_path_stream(uint64_t seed, uint32_t pixel, uint32_t sample, uint32
 int hrt_debug_kat(uint32_t which, const hrt_camera *cam, const float *prim, const float *in, uint32_t n, float *out) {
     if (!g_rt.ready) return fail(HRT_ERR_STATE, "hrt_debug_kat: call hrt_init first");
     if (!in || !out || !n) return fail(HRT_ERR_INVALID, "hrt_debug_kat: bad argument");
-    static const uint32_t in_w[] = {2, 7, 7, 7, 7, 8, 3}, out_w[] = {12, 8, 2, 9, 8, 8, 3};
-    if (which > HRT_KAT_NORMALIZE) return fail(HRT_ERR_INVALID, "hrt_debug_kat: unknown instrument");
+    static const uint32_t in_w[] = {2, 7, 7, 7, 7, 8, 3, 3}, out_w[] = {12, 8, 2, 9, 8, 8, 3, 4};
+    if (which > HRT_KAT_HITWORD) return fail(HRT_ERR_INVALID, "hrt_debug_kat: unknown instrument");
     if ((which == HRT_KAT_CAMERA) != (cam != nullptr) || ((which >= HRT_KAT_TRIANGLE && which <= HRT_KAT_QUAD) != (prim != nullptr)))
         return fail(HRT_ERR_INVALID, "hrt_debug_kat: cam is for HRT_KAT_CAMERA, prim for the primitive instruments");
     std::vector<float4> rows, kat_qf;
@@ -1522,6 +1530,7 @@ int hrt_debug_kat(uint32_t which, const hrt_camera *cam, const float *prim, cons
                 if (e == hipSuccess) hipLaunchKernelGGL(hrt_kat_quad_kernel, grid, block, 0, 0, (const float4 *)d_prim, (const DScene *)d_scene, d_in, n, err_abs, d_out);
                 break;
             case HRT_KAT_OPTICS: hipLaunchKernelGGL(hrt_kat_optics_kernel, grid, block, 0, 0, d_in, n, d_out); break;
+            case HRT_KAT_HITWORD: hipLaunchKernelGGL(hrt_kat_hitword_kernel, grid, block, 0, 0, d_in, n, d_out); break;
             default: hipLaunchKernelGGL(hrt_kat_normalize_kernel, grid, block, 0, 0, d_in, n, d_out); break;
         }
         if (e == hipSuccess) e = hipGetLastError();

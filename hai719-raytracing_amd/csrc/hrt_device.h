@@ -141,7 +141,7 @@ struct DRender {
     uint32_t sp_group_log2;      // streaming kernel: log2 of the tiles per work unit
     uint32_t sp_band_log2;       // streaming kernel: a work unit is one ROW BAND of a tile, 8 x (8 >> this) pixels (then one tile per unit): finer
                                  // items on the tile queue when tiles are few and heavy (many samples per pixel)
-    uint32_t *sp_pool;           // streaming kernel built with HRT_SP_GLOBAL: per-workgroup path records
+    uint32_t *sp_pool;           // streaming kernel: per-workgroup path records (128 bytes per path)
     union {                      // one slot of the argument block, read by no kernel but those named (the others compile as if it did not exist):
         const uint32_t *tile_list;   // the *_list kernels (adaptive sampling, hrt_adaptive.hip): work-queue item j is rank slot tile_list[j],
                                      // tiles_owned is the list's length and out_tiles a COMPACT buffer (slot j of the list at j)

@@ -112,3 +112,17 @@ extern "C" __global__ void hrt_kat_normalize_kernel(const float *__restrict__ in
     const f3 v = normalize(mk(in[3 * i], in[3 * i + 1], in[3 * i + 2]));
     out[3 * i] = v.x; out[3 * i + 1] = v.y; out[3 * i + 2] = v.z;
 }
+
+// in n x 3 = kind, index, soup slot (bit patterns) -> out n x 4 = the hit word of a path record (hrt_stream.hip sp_hit_word), then the
+// kind, index and soup slot sp_hit_unword reads back from it (bit patterns)
+extern "C" __global__ void hrt_kat_hitword_kernel(const float *__restrict__ in, uint32_t n, float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Hit h;
+    h.kind = __float_as_uint(in[3 * i]); h.index = __float_as_uint(in[3 * i + 1]); h.tri = __float_as_uint(in[3 * i + 2]);
+    h.t = 0.f; h.a0 = 0.f; h.a1 = 0.f;
+    const uint32_t w = hrtk::sp_hit_word(h);
+    Hit g;
+    hrtk::sp_hit_unword(w, g);
+    out[4 * i] = __uint_as_float(w); out[4 * i + 1] = __uint_as_float(g.kind); out[4 * i + 2] = __uint_as_float(g.index); out[4 * i + 3] = __uint_as_float(g.tri);
+}

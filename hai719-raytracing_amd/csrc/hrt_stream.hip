@@ -5,8 +5,8 @@
 // (profiles/r01_pmc.json) shows 40 % VALU lane utilisation on Cornell+mesh because on any given bounce the 64
 // lanes of a wave want different things (new camera ray / mesh walk / shade a sphere, a square, a triangle).
 // Here the divergent rays are COMPACTED.  A 1024-thread workgroup (one per CU) keeps a pool of HRT_SP_POOL
-// paths as 128-byte records in global memory (sized to stay in the Infinity Cache) and queues of 16-bit slot
-// ids in LDS.  One cycle runs 64-entry chunks of
+// paths as 128-byte records in global memory (sized to stay in the Infinity Cache; a hit visit's state is one 64-byte half
+// of a record, see sp_ld4) and queues of 16-bit slot ids in LDS.  One cycle runs 64-entry chunks of
 //     G   free slot          -> camera ray (main.cpp:188-192), spheres + squares, mesh box gates
 //     T   ray + best hit     -> up to HRT_SP_TRIPS trips of the rope KD walk; an unfinished walk keeps its state
 //                               in the record and comes back next cycle, so T chunks stay full
@@ -41,9 +41,6 @@
                            // 2048 -> 306 / 354 / 775, 4096 -> 278 / 320 / 673 (unit 32768), 8192 -> 360 / 391 / 730: pool + scratch of all
                            // 256 workgroups should stay within the 256 MB Infinity Cache
 #endif
-#ifndef HRT_SP_GLOBAL
-#define HRT_SP_GLOBAL 1    // 1: the path pool lives in global memory (one 128-byte record per path, L2 / Infinity Cache
-#endif                     //    resident), which lets HRT_SP_POOL grow past what LDS holds; 0: SoA arrays in LDS
 #ifndef HRT_SP_WG
 #define HRT_SP_WG 1024     // threads per workgroup (16 waves = 4 per SIMD, one workgroup per CU)
 #endif
@@ -92,18 +89,9 @@
 #endif                     // that runs out of chunks in one stream's cycle does not idle at a barrier: it arrives (an LDS counter) and goes
                            // on with the other stream's cycle; the last wave to arrive prepares the stream's next cycle.  1 = one stream,
                            // the same code with nothing to overlap (equivalent to a barrier per cycle)
-#ifndef HRT_SP_NOG5
-#define HRT_SP_NOG5 1      // 1: hit visits do not load group 5 of the record (time, RNG keys, path number): recomputed from the number, kept in
-                           // g7.w.  1080p@64, Msamples/s Cornell+mesh / mesh_in_box / pool / random_spheres: 0 -> 3 294 / 2 831 / 1 824 / 4 419, 1 -> 3 380 / 2 951 / 1 843 / 4 541
-#endif
-#ifndef HRT_SP_PM4
-#define HRT_SP_PM4 1       // 1: the meshes still to walk and the walk ref travel in g4 and a T visit loads four groups (not g2); the sender's one store
-                           // of g4 replaces the invariant "walk ref NIL outside T" and its two dword stores.  1080p@64, Msamples/s Cornell+mesh /
-                           // mesh_in_box / pool: 0 -> 3 373 / 2 945 / 1 843, 1 -> 3 437 / 2 970 / 1 855
-#endif
 #ifndef HRT_SP_PMQ
-#define HRT_SP_PMQ 1       // 1 (needs HRT_SP_PM4): in scenes of <= 4 meshes the meshes to walk ride in the T-queue entry beside the slot id; the sender stores
-                           // no g4.  1080p@64, Msamples/s Cornell+mesh / mesh_in_box / pool: 0 -> 3 443 / 2 974 / 1 875, 1 -> 3 475 / 3 021 / 1 890
+#define HRT_SP_PMQ 1       // 1: in scenes of <= 4 meshes the meshes to walk ride in the T-queue entry beside the slot id; the sender stores
+                           // no walk group.  1080p@64, Msamples/s Cornell+mesh / mesh_in_box / pool: 0 -> 3 443 / 2 974 / 1 875, 1 -> 3 475 / 3 021 / 1 890
 #endif
 #ifndef HRT_SP_THALF
 #define HRT_SP_THALF 0     // experiment: T chunks of 32 paths (half the lanes idle) -- latency- or throughput-bound?
@@ -124,13 +112,15 @@
 
 namespace hrtk {
 
-// One path = one 128-byte record.  Dwords 0-19 are what a T visit touches (ray, best hit, meshes to walk, walk
-// state: five aligned 16-byte groups), 0-11 and 20-31 what a hit / new-path visit touches (it writes back 0-11 and 24-31).
-enum { SP_OX = 0, SP_OY, SP_OZ, SP_DX, SP_DY, SP_DZ, SP_HT, SP_HID, SP_HA0, SP_HA1, SP_HTRI, SP_PM,
-       SP_WREF, SP_WTE, SP_WKK, SP_WBT, SP_WTRI, SP_WBU, SP_WBV, SP_PAD,
-       SP_TM, SP_K0, SP_K1, SP_N,                            // written once, when the path starts
-       SP_TR, SP_TG, SP_TB, SP_RR, SP_RG, SP_RB, SP_RI, SP_REM,  // rewritten by every hit visit: two aligned 16-byte stores
-       SP_FIELDS };  // 32 dwords: one 128-byte record
+// One path = one 128-byte record.  Dwords 0-15, the first 64-byte half, are ALL a hit / new-path visit touches: it reads them
+// and rewrites every one of them (ray, closest hit, throughput, radiance, stream position, bounces | path number: four aligned
+// 16-byte groups, one whole 64-byte write).  Dwords 16-23, one 32-byte sector of the other half, are the state of a mesh walk
+// in progress, which only a T visit reads (with dwords 0-7).
+enum { SP_OX = 0, SP_OY, SP_OZ, SP_DX, SP_DY, SP_DZ, SP_HT, SP_HID,
+       SP_TR, SP_TG, SP_TB, SP_RR, SP_RG, SP_RB, SP_RI, SP_REM,
+       SP_WTRI, SP_WTE, SP_WKK, SP_WBT, SP_WREF, SP_WBU, SP_WBV, SP_PM,
+       SP_FREE = 24,  // dwords 24-31: unused
+       SP_FIELDS = 32 };  // 32 dwords: one 128-byte record
 
 struct SpCtl {           // control block of ONE stream in LDS (28 dwords)
     uint32_t cQ[6][2];       // queue fills, [queue][parity]: 0 = T, 1..4 = the closest-hit queues by hit kind (0 miss, 1 sphere, 2 square,
@@ -167,88 +157,91 @@ struct SpShared {        // what the streams of a workgroup share (8 dwords)
 static_assert(sizeof(SpCtl) % 16 == 0 && sizeof(SpShared) % 16 == 0 && sizeof(SpUnit) % 16 == 0, "the LDS regions behind the control blocks must stay 16-byte aligned");
 static_assert(HRT_SP_STREAMS == 1 || HRT_SP_STREAMS == 2, "one or two streams");
 static_assert(HRT_SP_UNITS >= 1 && HRT_SP_UNITS <= 4, "a path number carries its unit slot in its two top bits");
-static_assert(!HRT_SP_PMQ || (HRT_SP_PM4 && HRT_SP_POOL <= 4096), "a T-queue entry is 12 bits of slot id + 4 bits of meshes");
-static_assert(!HRT_SP_NOG5 || HRT_SP_UNIT <= 8192, "g7.w keeps 13 bits of the path's number in its unit beside the bounces left");
+static_assert(!HRT_SP_PMQ || HRT_SP_POOL <= 4096, "a T-queue entry is 12 bits of slot id + 4 bits of meshes");
+static_assert(HRT_SP_UNIT <= 8192, "g3.w keeps 13 bits of the path's number in its unit beside the bounces left");
 static_assert(HRT_SP_QCAP >= 512, "deferring partial chunks needs a queue that can hold a whole chunk whenever fewer than 64 slots are free (6 queues x 63 < QCAP - 64)");
 
 static_assert((HRT_SP_POOL & (HRT_SP_POOL - 1)) == 0 && HRT_SP_POOL <= 65536, "slot ids are 16-bit and masked with HRT_SP_POOL - 1");
-static_assert((HRT_SP_GLOBAL ? 0 : SP_FIELDS * HRT_SP_POOL * 4) + HRT_SP_NQ * HRT_SP_POOL * 2 + HRT_SP_MAXG * 8 + 512 <= 160 * 1024,
-              "pool + queues do not fit the CU's 160 KB of LDS (with HRT_SP_GLOBAL=0 use -DHRT_SP_POOL=1024)");
+static_assert(HRT_SP_NQ * HRT_SP_POOL * 2 + HRT_SP_MAXG * 8 + 512 <= 160 * 1024, "the queues do not fit the CU's 160 KB of LDS");
 
 struct SpLds {
-    uint32_t *st;        // SP_FIELDS x POOL dwords
+    uint32_t *st;        // the workgroup's path records in global memory: HRT_SP_POOL x SP_FIELDS dwords
     uint16_t *q;         // HRT_SP_NQ queues x HRT_SP_QCAP entries of the stream in hand (streams follow each other)
     SpCtl *ctl;          // HRT_SP_STREAMS control blocks, then SpShared, the two SpUnit, 2 x HRT_SP_MAXG packed tile origins
 };
 
-#if HRT_SP_GLOBAL
 #define SP_AT(field, slot) ((slot) * (uint32_t)SP_FIELDS + (uint32_t)(field))
-#else
-#define SP_AT(field, slot) ((uint32_t)(field) * (uint32_t)HRT_SP_POOL + (slot))
-#endif
-#ifndef HRT_SP_NT
-#define HRT_SP_NT 0        // bit 0: path records are read, bit 1: written with the non-temporal hint (they stream through the CU: a record is
-#endif                     //    touched once per visit, 512 KB per workgroup per cycle against a 32 KB L1)
-template <class T>
-struct SpRef {             // one dword of a path record
-    T *p;
-    __device__ __forceinline__ operator T() const { return (HRT_SP_NT & 1) ? __builtin_nontemporal_load(p) : *p; }
-    __device__ __forceinline__ T operator=(T v) const {
-        if (HRT_SP_NT & 2) __builtin_nontemporal_store(v, p);
-        else *p = v;
-        return v;
-    }
-};
-__device__ __forceinline__ SpRef<float> spf(const SpLds &L, int field, uint32_t slot) { return SpRef<float>{reinterpret_cast<float *>(L.st) + SP_AT(field, slot)}; }
-__device__ __forceinline__ SpRef<uint32_t> spu(const SpLds &L, int field, uint32_t slot) { return SpRef<uint32_t>{L.st + SP_AT(field, slot)}; }
-// A path record is read and written in its eight aligned 16-byte GROUPS (one vector memory instruction each):
-//   g0 {o.xyz, d.x}  g1 {d.y, d.z, hit t, hit kind|index}  g2 {hit a0, a1, triangle, meshes still to walk}
-//   g3 {best triangle, t_entry, cursor, best t}  g4 {walk ref, bu, bv, meshes still to walk} (HRT_SP_PM4; else g3.x walk ref, g4.x triangle, g2.w meshes)
-//   g5 {time, RNG key k0, k1, path number} (unused with HRT_SP_NOG5)
-//   g6 {throughput.rgb, radiance.r}  g7 {radiance.g, .b, RNG position, bounces left | path number (sp_w7)}
+// A path record is read and written in aligned 16-byte GROUPS (one vector memory instruction each):
+//   g0 {o.xyz, d.x}  g1 {d.y, d.z, hit t, hit word (sp_hit_word)}
+//   g2 {throughput.rgb, radiance.r}  g3 {radiance.g, .b, RNG position, bounces left | path number (sp_w7)}
+//   g4 {best triangle, t_entry, cursor, best t}  g5 {walk ref, bu, bv, meshes still to walk}   (g6, g7: unused)
+// g0-g3 are one 64-byte half of the record and everything a hit visit carries: it loads the four and stores the four, so what
+// it writes leaves the L2 as ONE whole 64-byte request.  What the record does not hold is recomputed by the visit: the ray's time
+// and the keys of the path's random stream from the path's number, the hit's (u, v) / barycentrics from the stored ray, the
+// stored t and the one primitive that was hit (sp_hit_uv_square / sp_hit_uv_triangle).  A T visit loads g0, g1, g4, g5 and, when a mesh gives a closer hit, stores g1 alone;
+// g4 and g5 share one 32-byte sector.
 // (Left to the load / store vectoriser, the per-field accesses of a hit visit became 11 loads -- three of them issued late,
-// behind the first waits -- and 7 stores of mixed widths; by group they are 6 and 5.)
+// behind the first waits -- and 7 stores of mixed widths.)
 __device__ __forceinline__ uint4 sp_ld4(const SpLds &L, int g, uint32_t slot) {
-#if HRT_SP_GLOBAL
     // a NATIVE vector in the global address space; the caller pins the groups of a visit together (SP_PIN) once all are
     // requested: hipcc otherwise takes them apart, drops and sinks components and re-merges the rest across group boundaries
     const v4u v = ((gu4)(L.st + SP_AT(4 * g, slot)))[0];
     return make_uint4(v.x, v.y, v.z, v.w);
-#else
-    return make_uint4(L.st[SP_AT(4 * g, slot)], L.st[SP_AT(4 * g + 1, slot)], L.st[SP_AT(4 * g + 2, slot)], L.st[SP_AT(4 * g + 3, slot)]);
-#endif
 }
 __device__ __forceinline__ void sp_st4(const SpLds &L, int g, uint32_t slot, uint4 v) {
-#if HRT_SP_GLOBAL
     v4u w;
     w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
     *((v4u __attribute__((address_space(1))) *)(L.st + SP_AT(4 * g, slot))) = w;
-#else
-    L.st[SP_AT(4 * g, slot)] = v.x; L.st[SP_AT(4 * g + 1, slot)] = v.y; L.st[SP_AT(4 * g + 2, slot)] = v.z; L.st[SP_AT(4 * g + 3, slot)] = v.w;
-#endif
 }
 #define SP_PIN1(g) "+v"(g.x), "+v"(g.y), "+v"(g.z), "+v"(g.w)
-// g7.w: the bounces left (3 bits) and, with HRT_SP_NOG5, the path's number beside them (13 bits of path-in-unit, the unit slot on top)
-#if HRT_SP_NOG5
+// g3.w: the bounces left (3 bits) and the path's number beside them (13 bits of path-in-unit, the unit slot on top)
 __device__ __forceinline__ uint32_t sp_w7(uint32_t left, uint32_t pnum) { return left | ((pnum & 0x1FFFu) << 3) | (pnum & 0xC0000000u); }
 __device__ __forceinline__ uint32_t sp_w7_left(uint32_t w) { return w & 7u; }
 __device__ __forceinline__ uint32_t sp_w7_pnum(uint32_t w) { return ((w >> 3) & 0x1FFFu) | (w & 0xC0000000u); }
-#else
-__device__ __forceinline__ uint32_t sp_w7(uint32_t left, uint32_t) { return left; }
-__device__ __forceinline__ uint32_t sp_w7_left(uint32_t w) { return w; }
-#endif
+// g1.w, the whole closest hit beside its t: kind (2 bits) | index of the sphere / square (30 bits), or for a mesh hit
+// kind | mesh (5 bits: the first 32 meshes, mesh_gates) | soup slot of the triangle (25 bits: HRT_MAX_SOUP_SLOTS, hrt_scene_create)
+static_assert(HRT_MAX_SOUP_SLOTS == (1u << 25), "the hit word keeps 25 bits of soup slot");
+__device__ __forceinline__ uint32_t sp_hit_word(const Hit &h) {
+    return h.kind == 3u ? (3u << 30) | (h.index << 25) | h.tri : (h.kind << 30) | h.index;
+}
+__device__ __forceinline__ void sp_hit_unword(uint32_t w, Hit &h) {
+    h.kind = w >> 30;
+    const bool mesh = h.kind == 3u;
+    h.index = mesh ? (w >> 25) & 31u : w & 0x3FFFFFFFu;
+    h.tri = mesh ? w & 0x01FFFFFFu : 0u;
+}
 __device__ __forceinline__ uint4 sp_pack(float a, float b, float c, float d) { return make_uint4(__float_as_uint(a), __float_as_uint(b), __float_as_uint(c), __float_as_uint(d)); }
-__device__ __forceinline__ void sp_unpack_ray_hit(const uint4 g0, const uint4 g1, const uint4 g2, Ray &ray, Hit &h, uint32_t &pm) {
+// (h.a0, h.a1 are NOT in the record: 0 here, filled in front of shade() by the hit visit)
+__device__ __forceinline__ void sp_unpack_ray_hit(const uint4 g0, const uint4 g1, Ray &ray, Hit &h) {
     ray.o = mk(__uint_as_float(g0.x), __uint_as_float(g0.y), __uint_as_float(g0.z));
     ray.d = mk(__uint_as_float(g0.w), __uint_as_float(g1.x), __uint_as_float(g1.y));
-    h.t = __uint_as_float(g1.z); h.kind = g1.w >> 28; h.index = g1.w & 0x0FFFFFFFu;
-    h.a0 = __uint_as_float(g2.x); h.a1 = __uint_as_float(g2.y); h.tri = g2.z; pm = g2.w;
+    h.t = __uint_as_float(g1.z);
+    sp_hit_unword(g1.w, h);
+    h.a0 = 0.f; h.a1 = 0.f;
 }
-// g0, g1, g2 of a ray with its closest hit so far
-__device__ __forceinline__ void sp_store_ray_hit(const SpLds &L, uint32_t slot, const Ray &ray, const Hit &h, uint32_t pm) {
+__device__ __forceinline__ uint4 sp_g1(const Ray &ray, const Hit &h) {
+    return make_uint4(__float_as_uint(ray.d.y), __float_as_uint(ray.d.z), __float_as_uint(h.t), sp_hit_word(h));
+}
+// g0, g1 of a ray with its closest hit so far
+__device__ __forceinline__ void sp_store_ray_hit(const SpLds &L, uint32_t slot, const Ray &ray, const Hit &h) {
     sp_st4(L, 0, slot, sp_pack(ray.o.x, ray.o.y, ray.o.z, ray.d.x));
-    sp_st4(L, 1, slot, make_uint4(__float_as_uint(ray.d.y), __float_as_uint(ray.d.z), __float_as_uint(h.t), (h.kind << 28) | h.index));
-    sp_st4(L, 2, slot, make_uint4(__float_as_uint(h.a0), __float_as_uint(h.a1), h.tri, pm));
+    sp_st4(L, 1, slot, sp_g1(ray, h));
+}
+// What shade() reads of a square / mesh hit beyond the record: the arithmetic that found the hit, once more, on the one primitive.
+// Square: quad_t (the same t, the same u, v: it depends on the ray -- its time included -- and the square alone), rows per lane
+// from the staged tables.  Triangle: tri_inside on the triangle's rows with the stored t, which is the t the walk gave it
+// (tri_test_plane); the rows share a 64-byte line with the id row shade() fetches.
+template <class CX>
+__device__ __forceinline__ void sp_hit_uv_square(const CX &cx, const Ray &ray, Hit &h) {
+    float t, u = 0.f, v = 0.f;
+    if (quad_t(cx.tq + HRT_QUAD_ROWS * h.index, ray, HRT_FLT_MAX, t, u, v)) { h.a0 = u; h.a1 = v; }
+}
+template <class CX>
+__device__ __forceinline__ void sp_hit_uv_triangle(const CX &cx, const Ray &ray, Hit &h) {
+    const gf4 tr = (gf4)cx.S->tris + HRT_TRI_ROWS * h.tri;
+    float u1, u2;
+    (void)tri_inside(ld(tr, 0), ld(tr, 1), ld(tr, 2), ray, h.t, u1, u2);
+    h.a0 = u1; h.a1 = u2;
 }
 __device__ __forceinline__ uint16_t *spq(const SpLds &L, int which, uint32_t parity) { return L.q + (2 * which + parity) * HRT_SP_QCAP; }
 
@@ -289,13 +282,8 @@ template <bool LIGHTS, bool EXACT = false, bool SPHF = false, bool LIST = false,
 __device__ __forceinline__ void stream_body(const DRender &R) {
     extern __shared__ uint4 s_raw[];
     SpLds L;
-#if HRT_SP_GLOBAL
     L.st = R.sp_pool + (size_t)blockIdx.x * ((size_t)SP_FIELDS * HRT_SP_POOL);
     L.q = reinterpret_cast<uint16_t *>(s_raw);
-#else
-    L.st = reinterpret_cast<uint32_t *>(s_raw);
-    L.q = reinterpret_cast<uint16_t *>(L.st + SP_FIELDS * HRT_SP_POOL);
-#endif
     L.ctl = reinterpret_cast<SpCtl *>(L.q + HRT_SP_NQ * HRT_SP_POOL);
     SpShared &SH = *reinterpret_cast<SpShared *>(L.ctl + HRT_SP_STREAMS);
     SpUnit *const U = reinterpret_cast<SpUnit *>(&SH + 1);                // the two work units in flight
@@ -656,7 +644,7 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
 #endif
                 const uint32_t e = HRT_SP_THALF ? c * 32u + lane : c * 64u + lane;
                 const bool act = e < cTin && (!HRT_SP_THALF || lane < 32u);
-                uint32_t slot = 0, kind = 0, pm = 0, ref_in = HRT_KD_NIL, pm_before = 0;
+                uint32_t slot = 0, kind = 0, pm = 0, t_before = 0;
                 bool walked = false;
                 Ray ray;
                 ray.o = mk(0.f, 0.f, 0.f); ray.d = mk(0.f, 0.f, 1.f); ray.time = 0.f;
@@ -672,40 +660,22 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
 #else
                     slot = qTi[e] & (HRT_SP_POOL - 1u);
 #endif
-#if HRT_SP_PM4
-                    // Four groups: a T visit needs the ray, the distance and kind of the best hit so far, the state of its walk and the
-                    // meshes still to walk -- which the chunk that sent the path here wrote into the free dword of g4 -- but not the
-                    // hit's a0 / a1 / triangle (g2): those it only ever REPLACES, when a mesh gives a closer hit.
-                    uint4 g0 = sp_ld4(L, 0, slot), g1 = sp_ld4(L, 1, slot), g3 = sp_ld4(L, 3, slot), g4 = sp_ld4(L, 4, slot);
-                    asm volatile("" : SP_PIN1(g0), SP_PIN1(g1), SP_PIN1(g3), SP_PIN1(g4));
-                    {
-                        const uint4 z = make_uint4(0u, 0u, 0u, 0u);
-                        sp_unpack_ray_hit(g0, g1, z, ray, h, pm);
-                    }
-                    pm = g4.w;
-                    pm_before = __float_as_uint(h.t);  // (here: the best distance on entry)
-#else
-                    uint4 g0 = sp_ld4(L, 0, slot), g1 = sp_ld4(L, 1, slot), g2 = sp_ld4(L, 2, slot), g3 = sp_ld4(L, 3, slot),
-                          g4 = sp_ld4(L, 4, slot);
-#if HRT_SP_GLOBAL
-                    asm volatile("" : SP_PIN1(g0), SP_PIN1(g1), SP_PIN1(g2), SP_PIN1(g3), SP_PIN1(g4));
-#endif
-                    sp_unpack_ray_hit(g0, g1, g2, ray, h, pm);  // (the mesh walk does not read ray.time)
-                    pm_before = pm;
-#endif
-#if HRT_SP_PM4   // g3 {best triangle, t_entry, cursor, best t}  g4 {walk ref, bu, bv, meshes to walk}: the sender's ONE store of g4 also says "no walk in progress"
-                    w.ref = g4.x; w.t_entry = __uint_as_float(g3.y); w.kk = g3.z; w.best_t = __uint_as_float(g3.w);
-                    w.best_tri = g3.x; w.bu = __uint_as_float(g4.y); w.bv = __uint_as_float(g4.z);
-#else
-                    w.ref = g3.x; w.t_entry = __uint_as_float(g3.y); w.kk = g3.z; w.best_t = __uint_as_float(g3.w);
-                    w.best_tri = g4.x; w.bu = __uint_as_float(g4.y); w.bv = __uint_as_float(g4.z);
-#endif
+                    // Four groups, two from each half of the record: a T visit needs the ray, the distance of the best hit so far, the state
+                    // of its walk and the meshes still to walk -- which the chunk that sent the path here wrote into the free dword of g5
+                    // (or into the queue entry, below).  The hit itself it only ever REPLACES, when a mesh gives a closer one: g1 alone.
+                    uint4 g0 = sp_ld4(L, 0, slot), g1 = sp_ld4(L, 1, slot), g4 = sp_ld4(L, 4, slot), g5 = sp_ld4(L, 5, slot);
+                    asm volatile("" : SP_PIN1(g0), SP_PIN1(g1), SP_PIN1(g4), SP_PIN1(g5));
+                    sp_unpack_ray_hit(g0, g1, ray, h);  // (the mesh walk does not read ray.time)
+                    pm = g5.w;
+                    t_before = g1.z;  // the best distance on entry
+                    // g4 {best triangle, t_entry, cursor, best t}  g5 {walk ref, bu, bv, meshes to walk}: the sender's ONE store of g5 also says "no walk in progress"
+                    w.ref = g5.x; w.t_entry = __uint_as_float(g4.y); w.kk = g4.z; w.best_t = __uint_as_float(g4.w);
+                    w.best_tri = g4.x; w.bu = __uint_as_float(g5.y); w.bv = __uint_as_float(g5.z);
 #if HRT_SP_PMQ
-                    // A path that comes from a hit / new-path chunk carries its meshes in the queue entry (the sender then wrote nothing into g4):
-                    // no walk in progress.  One that comes back from a T visit has 0 there and its state in g3 / g4.
+                    // A path that comes from a hit / new-path chunk carries its meshes in the queue entry (the sender then wrote nothing into g5):
+                    // no walk in progress.  One that comes back from a T visit has 0 there and its state in g4 / g5.
                     if (pm_in_entry && (entry >> 12) != 0u) { w.ref = HRT_KD_NIL; pm = entry >> 12; }
 #endif
-                    ref_in = w.ref;
                 }
 #ifdef HRT_SP_SEG
                 asm volatile("" : "+v"(ray.o.x), "+v"(w.t_entry), "+v"(h.t));
@@ -720,36 +690,19 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                 }
                 SEG(1);  // T: walk
                 if (act) {
-                    const uint32_t pm_in = pm_before;
-#if HRT_SP_PM4
-                    if (__float_as_uint(h.t) != pm_in) {  // a mesh gave a closer hit (g1 also carries d.y, d.z: rewritten as read)
-#else
-                    if (pm != pm_in) {  // a mesh was finished: the best hit may have changed (g1 also carries d.y, d.z: rewritten as read)
-#endif
-                        sp_st4(L, 1, slot, make_uint4(__float_as_uint(ray.d.y), __float_as_uint(ray.d.z), __float_as_uint(h.t), (h.kind << 28) | h.index));
-                        sp_st4(L, 2, slot, make_uint4(__float_as_uint(h.a0), __float_as_uint(h.a1), h.tri, pm));
+                    // a mesh gave a closer hit: t and the hit word (g1 also carries d.y, d.z: rewritten as read)
+                    if (__float_as_uint(h.t) != t_before) sp_st4(L, 1, slot, sp_g1(ray, h));
+                    if (!walked) {  // the state of the walk in progress, and the meshes still to walk: one 32-byte sector
+                        sp_st4(L, 4, slot, make_uint4(w.best_tri, __float_as_uint(w.t_entry), w.kk, __float_as_uint(w.best_t)));
+                        sp_st4(L, 5, slot, make_uint4(w.ref, __float_as_uint(w.bu), __float_as_uint(w.bv), pm));
                     }
-#if HRT_SP_PM4
-                    if (!walked) {  // the state of the walk in progress, and the meshes still to walk
-                        sp_st4(L, 3, slot, make_uint4(w.best_tri, __float_as_uint(w.t_entry), w.kk, __float_as_uint(w.best_t)));
-                        sp_st4(L, 4, slot, make_uint4(w.ref, __float_as_uint(w.bu), __float_as_uint(w.bv), pm));
-                    }
-                    (void)ref_in;
-#else
-                    if (!walked) {  // the state of the walk in progress
-                        sp_st4(L, 3, slot, make_uint4(w.ref, __float_as_uint(w.t_entry), w.kk, __float_as_uint(w.best_t)));
-                        sp_st4(L, 4, slot, make_uint4(w.best_tri, __float_as_uint(w.bu), __float_as_uint(w.bv), 0u));
-                    } else if (ref_in != HRT_KD_NIL) {
-                        spu(L, SP_WREF, slot) = HRT_KD_NIL;  // invariant: SP_WREF is NIL whenever the path is not in a T queue
-                    }
-#endif
                     kind = h.kind;
                 }
 #if HRT_SP_TPRIO
                 __builtin_amdgcn_s_setprio(0);
 #endif
                 // unfinished: joins the next cycle's T chunks; finished: the closest-hit queue of its kind
-                sp_push_all(L, C, parity ^ 1u, !act ? SP_TO_NONE : (walked ? 1u + kind : 0u), slot);  // (back to T: a bare slot id, the state is in g3 / g4)
+                sp_push_all(L, C, parity ^ 1u, !act ? SP_TO_NONE : (walked ? 1u + kind : 0u), slot);  // (back to T: a bare slot id, the state is in g4 / g5)
                 SEG(2);  // T: stores + appends
 #ifdef HRT_SP_SEG
                 if (seg_on) { seg[7] += 1; seg[6] += (unsigned long long)__popcll(__ballot(act)); seg[5] += (unsigned long long)__popcll(__ballot(act && walked)); }
@@ -801,11 +754,8 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                             ray = camera_ray<EXACT>(cam, u, v, tm);
                         }
                         pnum = n | (gs << 30);
-#if !HRT_SP_NOG5
-                        sp_st4(L, 5, slot, make_uint4(__float_as_uint(tm), rng.k0, rng.k1, pnum));
-#endif
-                        sp_st4(L, 6, slot, sp_pack(1.f, 1.f, 1.f, 0.f));                                  // throughput 1, radiance 0
-                        sp_st4(L, 7, slot, make_uint4(0u, 0u, rng.i, sp_w7(6u, pnum)));                  // MAXBOUNCES
+                        sp_st4(L, 2, slot, sp_pack(1.f, 1.f, 1.f, 0.f));                                  // throughput 1, radiance 0
+                        sp_st4(L, 3, slot, make_uint4(0u, 0u, rng.i, sp_w7(6u, pnum)));                  // MAXBOUNCES
                         trace = true;
                     } else {  // pixel outside a ragged image: the sample is zero, the slot stays free
                         float *o = scratch + (size_t)gs * ((size_t)HRT_SP_UNIT * 3u) + (size_t)n * 3u;
@@ -815,14 +765,15 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                     }
                 } else if (act) {
                     slot = qHi[from_back ? (uint32_t)HRT_SP_QCAP - 1u - e : e] & (HRT_SP_POOL - 1u);
-#if HRT_SP_NOG5
-                    // Five groups, not six: what g5 held -- the ray's time, the keys of the path's random stream, the path's number -- never
-                    // changes after the path's first visit.  The number rides in g7.w beside the bounces left; the rest is recomputed
-                    // from it (the pixel from the unit's tile table in LDS, the sample from the unit's fold; Rng::start; the time is draw 2
-                    // of the stream, as in the G chunk): ~45 vector instructions for one vector memory instruction less per hit visit.
-                    uint4 g0 = sp_ld4(L, 0, slot), g1 = sp_ld4(L, 1, slot), g2 = sp_ld4(L, 2, slot), g6 = sp_ld4(L, 6, slot), g7 = sp_ld4(L, 7, slot);
-                    asm volatile("" : SP_PIN1(g0), SP_PIN1(g1), SP_PIN1(g2), SP_PIN1(g6), SP_PIN1(g7));
-                    pnum = sp_w7_pnum(g7.w);
+                    // Four groups, one 64-byte half of the record.  What else the visit needs never changes after the path's first visit or
+                    // follows from what is stored.  The path's number rides in g3.w beside the bounces left; the ray's time and the keys of
+                    // the path's random stream are recomputed from it (the pixel from the unit's tile table in LDS, the sample from the
+                    // unit's fold; Rng::start; the time is draw 2 of the stream, as in the G chunk): ~45 vector instructions for one vector
+                    // memory instruction less per hit visit.  The (u, v) of a square hit and the barycentrics of a triangle hit are
+                    // recomputed in front of shade(), below.
+                    uint4 g0 = sp_ld4(L, 0, slot), g1 = sp_ld4(L, 1, slot), g2 = sp_ld4(L, 2, slot), g3 = sp_ld4(L, 3, slot);
+                    asm volatile("" : SP_PIN1(g0), SP_PIN1(g1), SP_PIN1(g2), SP_PIN1(g3));
+                    pnum = sp_w7_pnum(g3.w);
                     Rng key;
                     {
                         const uint32_t kn = pnum & 0x3FFFFFFFu, ku = pnum >> 30;
@@ -835,25 +786,11 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                         key.i = 2u;
                     }
                     Hit h;
-                    uint32_t pm_unused;
-                    sp_unpack_ray_hit(g0, g1, g2, ray, h, pm_unused);
+                    sp_unpack_ray_hit(g0, g1, ray, h);
                     ray.time = moving ? key.next() : 0.f;  // (time x 0 == 0: without motion the time is never looked at)
-#else
-                    uint4 g0 = sp_ld4(L, 0, slot), g1 = sp_ld4(L, 1, slot), g2 = sp_ld4(L, 2, slot), g5 = sp_ld4(L, 5, slot),
-                          g6 = sp_ld4(L, 6, slot), g7 = sp_ld4(L, 7, slot);
-#if HRT_SP_GLOBAL
-                    asm volatile("" : SP_PIN1(g0), SP_PIN1(g1), SP_PIN1(g2), SP_PIN1(g5), SP_PIN1(g6), SP_PIN1(g7));
-#endif
-                    Hit h;
-                    uint32_t pm_unused;
-                    sp_unpack_ray_hit(g0, g1, g2, ray, h, pm_unused);
-                    ray.time = __uint_as_float(g5.x);
-                    pnum = g5.w;
-                    if (VIEWS) cx.err_abs = __uint_as_float(view_row(pnum).w);
-#endif
-                    f3 thr = mk(__uint_as_float(g6.x), __uint_as_float(g6.y), __uint_as_float(g6.z));
-                    rad = mk(__uint_as_float(g6.w), __uint_as_float(g7.x), __uint_as_float(g7.y));
-                    int remaining = (int)sp_w7_left(g7.w);
+                    f3 thr = mk(__uint_as_float(g2.x), __uint_as_float(g2.y), __uint_as_float(g2.z));
+                    rad = mk(__uint_as_float(g2.w), __uint_as_float(g3.x), __uint_as_float(g3.y));
+                    int remaining = (int)sp_w7_left(g3.w);
 #ifdef HRT_SP_SEG
                     asm volatile("" : "+v"(remaining), "+v"(ray.o.x), "+v"(thr.x), "+v"(rad.x));
 #endif
@@ -863,11 +800,10 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                         ended = true;
                     } else {
                         Rng rng;
-#if HRT_SP_NOG5
-                        rng.k0 = key.k0; rng.k1 = key.k1; rng.i = g7.z;
-#else
-                        rng.k0 = g5.y; rng.k1 = g5.z; rng.i = g7.z;
-#endif
+                        rng.k0 = key.k0; rng.k1 = key.k1; rng.i = g3.z;
+                        // (a chunk holds hits of ONE kind, so these are not divergent; unconditional: whether the material reads (u, v) is not asked)
+                        if (h.kind == 2u) sp_hit_uv_square(cx, ray, h);
+                        else if (h.kind == 3u) sp_hit_uv_triangle(cx, ray, h);
                         const Surface sf = shade(cx, ray, h);
                         SEG(1);  // shade: material rows, texel, normal map
                         f3 direct = mk(0.f, 0.f, 0.f);
@@ -881,8 +817,8 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                         ended = (remaining == 0);
                         if ((HRT_SP_PRUNE & 1) && prune && thr.x == 0.f && thr.y == 0.f && thr.z == 0.f) ended = true;  // nothing can reach the sample any more
                         if (!ended) {
-                            sp_st4(L, 6, slot, sp_pack(thr.x, thr.y, thr.z, rad.x));
-                            sp_st4(L, 7, slot, make_uint4(__float_as_uint(rad.y), __float_as_uint(rad.z), rng.i, sp_w7((uint32_t)remaining, pnum)));
+                            sp_st4(L, 2, slot, sp_pack(thr.x, thr.y, thr.z, rad.x));
+                            sp_st4(L, 3, slot, make_uint4(__float_as_uint(rad.y), __float_as_uint(rad.z), rng.i, sp_w7((uint32_t)remaining, pnum)));
                             trace = true;
                             last_seg = (HRT_SP_PRUNE & 2) && !LIGHTS && prune && remaining == 1;
                         }
@@ -907,10 +843,10 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                     f3 thr = mk(1.f, 1.f, 1.f);
                     int remaining = 6;
                     if (!is_gen) {
-                        const uint4 g6 = sp_ld4(L, 6, slot), g7 = sp_ld4(L, 7, slot);
-                        thr = mk(__uint_as_float(g6.x), __uint_as_float(g6.y), __uint_as_float(g6.z));
-                        rad = mk(__uint_as_float(g6.w), __uint_as_float(g7.x), __uint_as_float(g7.y));
-                        remaining = (int)sp_w7_left(g7.w);
+                        const uint4 g2 = sp_ld4(L, 2, slot), g3 = sp_ld4(L, 3, slot);
+                        thr = mk(__uint_as_float(g2.x), __uint_as_float(g2.y), __uint_as_float(g2.z));
+                        rad = mk(__uint_as_float(g2.w), __uint_as_float(g3.x), __uint_as_float(g3.y));
+                        remaining = (int)sp_w7_left(g3.w);
                     }
                     rad = rad + thr * sky(cx, ray.d, remaining);
                     trace = false; ended = true; last_seg = false;
@@ -934,15 +870,11 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                     freed = true;
                 }
                 if (trace) {
-                    sp_store_ray_hit(L, slot, ray, hn, pmn);
-#if HRT_SP_PM4
+                    sp_store_ray_hit(L, slot, ray, hn);  // with g2, g3 above: the whole 64-byte half
 #if HRT_SP_PMQ
                     if (!pm_in_entry)
 #endif
-                    if (pmn != 0u) sp_st4(L, 4, slot, make_uint4(HRT_KD_NIL, 0u, 0u, pmn));  // no walk in progress; the meshes to walk, where the T visit looks for them
-#else
-                    if (is_gen) spu(L, SP_WREF, slot) = HRT_KD_NIL;  // a fresh slot: no walk in progress (T keeps it so afterwards)
-#endif
+                    if (pmn != 0u) sp_st4(L, 5, slot, make_uint4(HRT_KD_NIL, 0u, 0u, pmn));  // no walk in progress; the meshes to walk, where the T visit looks for them
                     to_mesh = pmn != 0u;
                     kind = hn.kind;
                 }

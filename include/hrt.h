@@ -187,6 +187,12 @@ typedef struct hrt_mesh {
     const hrt_tri_exception *exceptions;
 } hrt_mesh;
 
+/* Limits hrt_scene_create enforces (HRT_ERR_INVALID, hrt_last_error() names the one that was passed): at most 32 meshes (the
+ * mask of the meshes a ray has still to walk is 32 bits), and at most HRT_MAX_SOUP_SLOTS rows in the triangle soup of all meshes
+ * together -- n_leaf_tris of every mesh plus one row per irregular triangle, which is counted by its bound min(n_exceptions,
+ * n_triangles) so that the limit is checked before any array is read.  A path record of the streaming kernel names the triangle of
+ * its closest hit by soup slot in 25 bits, beside the hit's kind and mesh in one word. */
+#define HRT_MAX_SOUP_SLOTS (1u << 25)
 typedef struct hrt_scene_desc {
     uint32_t n_materials;  const hrt_material *materials;
     uint32_t n_spheres;    const hrt_sphere *spheres;
@@ -343,9 +349,12 @@ HRT_API int hrt_debug_path_stream(uint64_t seed, uint32_t pixel, uint32_t sample
  *   HRT_KAT_SPHERE    prim = centre, radius, motion             ray 7    9: hit, t, theta, phi, normal, p.x, p.y (Sphere.h:91-132)
  *   HRT_KAT_QUAD      prim = v0, v1, v3, motion, glass          ray 7    8: hit, t, u, v, normal (Square.h:65-126), filter bit
  *   HRT_KAT_OPTICS    -                                         d, n, eta, cosine   8: reflect, refract, reflectance, gamma(|cosine|)
- *   HRT_KAT_NORMALIZE -                                         v        3: v / |v| (Vec3.h:46) */
+ *   HRT_KAT_NORMALIZE -                                         v        3: v / |v| (Vec3.h:46)
+ *   HRT_KAT_HITWORD   -                                         kind, index, soup slot (u32 bit patterns)   4: the hit word of a
+ *                     path record of the streaming kernel (kind | index, or kind | mesh | soup slot), then the kind, index and
+ *                     soup slot read back from it (u32 bit patterns) */
 enum { HRT_KAT_CAMERA = 0, HRT_KAT_TRIANGLE = 1, HRT_KAT_AABB = 2, HRT_KAT_SPHERE = 3, HRT_KAT_QUAD = 4, HRT_KAT_OPTICS = 5,
-       HRT_KAT_NORMALIZE = 6 };
+       HRT_KAT_NORMALIZE = 6, HRT_KAT_HITWORD = 7 };
 HRT_API int hrt_debug_kat(uint32_t which, const hrt_camera *cam, const float *prim, const float *in, uint32_t n, float *out);
 
 /* Cycle counters per kernel stage of the last launch; all zero unless libhrt.so was built with

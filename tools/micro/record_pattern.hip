@@ -1,7 +1,11 @@
 // Calibration of the L2 <-> fabric counters on the path pool's OWN access pattern (the guide:
 // "calibrate on a known byte count in your own access pattern before trusting an absolute").
 //
-// A hit visit of hrt_wgstream_kernel reads six aligned 16-byte groups of one 128-byte path record per lane
+// NOTE: this is the hit visit of the FORMER record layout, kept as measured: profiles/r03_traffic_calibration.json was taken
+// on it, and what it calibrates is the counters (bytes per request kind), not the kernel.  Today's hit visit loads four groups
+// (g0 g1 g2 g3, one 64-byte half of the record) and stores the same four (hrt_stream.hip sp_ld4).
+//
+// A hit visit of hrt_wgstream_kernel (then) reads six aligned 16-byte groups of one 128-byte path record per lane
 // (g0 g1 g2 g5 g6 g7: hrt_stream.hip sp_ld4, native global_load_dwordx4, pinned together) and writes five (g0 g1 g2 g6 g7:
 // sp_st4), every lane of a wave on a different record.  This program does exactly that -- the same instruction forms, 64
 // lanes on 64 pseudo-random records per visit -- over a pool of a chosen size, so that the bytes are KNOWN:
