@@ -89,6 +89,32 @@ class View(C.Structure):
     _fields_ = [("cam", Camera), ("seed", C.c_uint64)]
 
 
+LENS_PERSPECTIVE, LENS_ORTHOGRAPHIC, LENS_EQUIRECT, LENS_FISHEYE = 0, 1, 2, 3
+LENS_DRAW = 0x80000000  # HRT_LENS_DRAW: draw index of the first of the two lens draws
+_PROJECTIONS = {"perspective": LENS_PERSPECTIVE, "ortho": LENS_ORTHOGRAPHIC, "orthographic": LENS_ORTHOGRAPHIC,
+                "equirect": LENS_EQUIRECT, "fisheye": LENS_FISHEYE}
+
+
+class Lens(C.Structure):
+    """``hrt_lens``: a camera with a projection (include/hrt.h "Lens cameras").  ``projection``: "perspective", "ortho", "equirect",
+    "fisheye" or a LENS_* value; ``aperture`` and ``focus``: the thin lens' radius and the depth along forward of the plane in focus
+    (perspective only); ``extent``: the height of the view volume (ortho) or the field of view in degrees (fisheye)."""
+    _fields_ = [("cam", Camera), ("projection", C.c_uint32), ("aperture_radius", C.c_float), ("focus_distance", C.c_float),
+                ("extent", C.c_float)]
+
+    def __init__(self, cam: Camera, projection="perspective", aperture: float = 0.0, focus: float = 1.0, extent: float = 0.0):
+        super().__init__()
+        if isinstance(projection, str):
+            if projection not in _PROJECTIONS:
+                raise ValueError(f"Lens: projection must be one of {sorted(_PROJECTIONS)} (got {projection!r})")
+            projection = _PROJECTIONS[projection]
+        self.cam = cam
+        self.projection = int(projection)
+        self.aperture_radius = aperture
+        self.focus_distance = focus
+        self.extent = extent
+
+
 class PickInput(C.Structure):
     """hrt_pick_input (include/hrt.h): what the choice of a trace kernel build depends on."""
     _fields_ = [("n_meshes", C.c_uint32), ("n_lights", C.c_uint32), ("n_spheres", C.c_uint32), ("tab_rows", C.c_uint32),
@@ -281,6 +307,13 @@ def device_lib() -> C.CDLL:
                                                 C.c_void_p, C.c_void_p]
         lib.hrt_render_views.argtypes = [C.c_void_p, C.POINTER(View), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_lens_rays.argtypes = [C.POINTER(Lens), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
+        lib.hrt_render_lens_device.argtypes = [C.c_void_p, C.POINTER(Lens), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                               C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.hrt_render_lens.argtypes = [C.c_void_p, C.POINTER(Lens), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
+                                        C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_render_lens_features.argtypes = [C.c_void_p, C.POINTER(Lens), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                                 C.c_void_p, C.c_void_p]
         lib.hrt_debug_pick_kernel.argtypes = [C.POINTER(PickInput), C.c_char_p, C.c_size_t]
         lib.hrt_debug_last_kernel.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         _dev = lib
@@ -675,6 +708,55 @@ class DeviceScene:
                                                None if stats is None else C.byref(stats)))
         return frames
 
+    def render_lens(self, lens: Lens, w: int, h: int, spp: int, seed: int = 1, flags: int = 0, first_sample: int = 0, out=None,
+                    accumulate: bool = False, stats: Optional[Stats] = None):
+        """hrt_render_lens*: the frame of ``lens``, the mean over samples [first_sample, first_sample + spp) -> (h, w, 3) float32; with
+        ``accumulate`` the running sums (``out`` then holds the sums of the earlier samples and is updated in place).  With ``out`` a
+        contiguous (h, w, 3) float32 torch tensor on the GPU the call runs on the current torch stream of its device without
+        synchronising and returns ``out`` (hrt_render_lens_device).  Otherwise the frame comes back as NumPy and the call blocks;
+        ``stats``: a Stats to fill, if wanted (the blocking form of samples [0, spp) without ``out``: hrt_render_lens).
+        ``flags``: FLAG_EXACT_ONLY, FLAG_MESH_BRUTE, FLAG_NO_LDS_TREE, FLAG_GAMMA (not with ``accumulate``)."""
+        import torch
+        flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
+        if isinstance(out, torch.Tensor):
+            if out.device.type != "cuda" or out.dtype != torch.float32 or tuple(out.shape) != (h, w, 3) or not out.is_contiguous():
+                raise ValueError(f"render_lens: out must be a contiguous ({h}, {w}, 3) float32 tensor on the GPU")
+            s = torch.cuda.current_stream(out.device)
+            self._check(self._lib.hrt_render_lens_device(self._h, C.byref(lens), w, h, first_sample, spp, seed, flags,
+                                                         C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)))
+            return out
+        if out is not None:
+            o = np.asarray(out)
+            if o.shape != (h, w, 3) or o.dtype != np.float32:
+                raise ValueError(f"render_lens: out must be ({h}, {w}, 3) float32 (got {o.shape} {o.dtype})")
+        elif accumulate and first_sample != 0:
+            raise ValueError("render_lens: accumulate after sample 0 needs the running sums in `out`")
+        if out is None and not accumulate and first_sample == 0:
+            frame = np.empty((h, w, 3), dtype=np.float32)
+            self._check(self._lib.hrt_render_lens(self._h, C.byref(lens), w, h, spp, seed, flags, frame.ctypes.data,
+                                                  None if stats is None else C.byref(stats)))
+            return frame
+        d = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda") if out is None else torch.from_numpy(np.ascontiguousarray(o)).to("cuda")
+        s = torch.cuda.current_stream(d.device)
+        self._check(self._lib.hrt_render_lens_device(self._h, C.byref(lens), w, h, first_sample, spp, seed, flags, C.c_void_p(d.data_ptr()),
+                                                     C.c_void_p(s.cuda_stream)))
+        r = d.cpu().numpy()
+        if out is not None:
+            out[...] = r
+            return out
+        return r
+
+    def render_lens_features(self, lens: Lens, w: int, h: int, first_sample: int, n_samples: int, seed: int = 1) -> np.ndarray:
+        """hrt_render_lens_features: ``render_features`` through ``lens`` -> (h, w, FEATURE_FLOATS) float32.  The device buffer is a
+        torch tensor on the scene's device; the call waits for it."""
+        import torch
+        d = torch.empty((h, w, FEATURE_FLOATS), dtype=torch.float32, device="cuda")
+        s = torch.cuda.current_stream()
+        self._check(self._lib.hrt_render_lens_features(self._h, C.byref(lens), w, h, first_sample, n_samples, seed, C.c_void_p(d.data_ptr()),
+                                                       C.c_void_p(s.cuda_stream)))
+        s.synchronize()
+        return d.cpu().numpy()
+
     def check_last_launch(self):
         """hrt_check_last_launch: waits for the last launch; raises if the trace kernel gave up (incomplete tiles)."""
         self._check(self._lib.hrt_check_last_launch(self._h))
@@ -803,6 +885,20 @@ def camera_rays(cam: Camera, w: int, h: int, sample: int = 0, seed: int = 1):
                              C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc < 0:
         raise HrtError(f"hrt_camera_rays failed ({rc}): {lib.hrt_last_error().decode()}")
+    return out
+
+
+def lens_rays(lens: Lens, w: int, h: int, sample: int = 0, seed: int = 1):
+    """hrt_lens_rays: the rays of sample ``sample`` of a w x h frame of ``lens`` as a (w*h, RAY_FLOATS) float32 torch tensor on the
+    current device (pixel y*w + x), written on the current torch stream; a degenerate sample has direction 0.  Traced with
+    trace_radiance(first_sample=sample) they give the samples of ``DeviceScene.render_lens``."""
+    import torch
+    lib = device_lib()
+    out = torch.empty((w * h, RAY_FLOATS), dtype=torch.float32, device="cuda")
+    rc = lib.hrt_lens_rays(C.byref(lens), w, h, sample, seed, C.c_void_p(out.data_ptr()),
+                           C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if rc < 0:
+        raise HrtError(f"hrt_lens_rays failed ({rc}): {lib.hrt_last_error().decode()}")
     return out
 
 

@@ -1568,6 +1568,7 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 #include "hrt_temporal.hip"
 #include "hrt_rays.hip"
 #include "hrt_radiance.hip"
+#include "hrt_lens.hip"
 #include "hrt_views.hip"
 
 int hrt_kd_build_gpu(const hrt_kd_build_input *in, hrt_kd_build_output *out, void *user) {

@@ -38,12 +38,31 @@ __device__ __forceinline__ hrtk::Ray camera_sample(CP cam, uint32_t seed_lo, uin
 }
 }  // extern "C++"
 
+// Where features_body's rays come from: source(cx, R, n, idx, k, ray) makes the ray of pixel idx for the k-th sample of the launch
+// (n == 0: the pixel centre at time 0) and returns false for a sample that is not traced, which counts as a miss; a source may set
+// the context's margin for its ray.  FeatureCameraRays: the render's camera, the block R.cam points at.
+extern "C++" {
+struct FeatureCameraRays {
+    template <class CX>
+    __device__ __forceinline__ bool operator()(CX &, const DRender &R, uint32_t n, uint32_t idx, uint32_t k, hrtk::Ray &ray) const {
+        const ccam cam = (ccam)R.cam;
+        if (n == 0u) {
+            const uint32_t x = idx % R.w, y = idx / R.w;
+            ray = hrtk::camera_ray(cam, ((float)x + 0.5f) / (float)R.w, ((float)y + 0.5f) / (float)R.h, 0.f);
+        } else {
+            ray = camera_sample(cam, R.seed_lo, R.seed_hi, R.w, R.h, idx, R.s0 + k);
+        }
+        return true;
+    }
+};
+
 // Sums of the first-hit features over samples [s0, s0 + n) of every pixel (n == 0: the pixel centre at time 0, hrt_aov_kernel's ray).
-extern "C" __global__ void __launch_bounds__(256) hrt_features_kernel(const DRender R, uint32_t n, float *__restrict__ out) {
+template <class CX, class SRC>
+__device__ __forceinline__ void features_body(const DRender &R, uint32_t n, float *__restrict__ out, const SRC &source) {
+    using namespace hrtk;
     const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= R.w * R.h) return;
-    const uint32_t x = idx % R.w, y = idx / R.w;
-    Ctx cx;
+    CX cx;
     cx.S = (cscene)R.scene;
     cx.set_tables((gf4)cx.S->tabs, (gf1)c_u8_lut, cx.S);
     cx.lds = (lu4) nullptr;
@@ -52,18 +71,14 @@ extern "C" __global__ void __launch_bounds__(256) hrt_features_kernel(const DRen
     cx.flags = R.flags;
     unsigned long long stamps_local[17] = {0};
     cx.st = stamps_local;
-    const ccam cam = (ccam)R.cam;
     f3 alb = mk(0.f, 0.f, 0.f), nrm = mk(0.f, 0.f, 0.f), emi = mk(0.f, 0.f, 0.f);
     float depth = 0.f, hits = 0.f;
     const uint32_t count = n ? n : 1u;
     for (uint32_t k = 0; k < count; ++k) {
         Ray ray;
-        if (n == 0u) {
-            ray = camera_ray(cam, ((float)x + 0.5f) / (float)R.w, ((float)y + 0.5f) / (float)R.h, 0.f);
-        } else {
-            ray = camera_sample(cam, R.seed_lo, R.seed_hi, R.w, R.h, idx, R.s0 + k);
-        }
-        const Hit h = closest_hit(cx, ray);
+        Hit h;
+        h.kind = 0u;
+        if (source(cx, R, n, idx, k, ray)) h = closest_hit(cx, ray);
         if (h.kind) {
             const Surface sf = shade(cx, ray, h);
             alb = alb + sf.albedo;
@@ -79,6 +94,11 @@ extern "C" __global__ void __launch_bounds__(256) hrt_features_kernel(const DRen
     o[3] = nrm.x / c; o[4] = nrm.y / c; o[5] = nrm.z / c;
     o[6] = emi.x / c; o[7] = emi.y / c; o[8] = emi.z / c;
     o[9] = depth / c; o[10] = hits / c; o[11] = 0.f;
+}
+}  // extern "C++"
+
+extern "C" __global__ void __launch_bounds__(256) hrt_features_kernel(const DRender R, uint32_t n, float *__restrict__ out) {
+    features_body<Ctx>(R, n, out, FeatureCameraRays{});
 }
 
 __device__ __forceinline__ bool dn_finite(float v) { return __builtin_isfinite(v); }

@@ -38,8 +38,15 @@ struct DRadiance {
 extern "C++" {
 namespace hrtk {
 
-template <bool LIGHTS, bool EXACT>
-__device__ __forceinline__ void radiance_body(const DRadiance &Q) {
+// Where a lane's first segments come from (radiance_body's SRC).  RecordRays: record i of the caller's batch, one ray for all its
+// samples, keyed by Q.keys.  A source with per_sample (LensRays, hrt_lens.hip) makes the ray of every sample itself --
+// SRC::sample(Q, i, sample, ray), false for a sample that is not traced -- and lane i is pixel i with key i.
+struct RecordRays {
+    static constexpr bool per_sample = false;
+};
+
+template <bool LIGHTS, bool EXACT, class SRC = RecordRays, class QT = DRadiance>
+__device__ __forceinline__ void radiance_body(const QT &Q) {
     CtxT<EXACT, false, false, true> cx;
     unsigned long long stamps_local[17] = {0};
     query_context(cx, Q.scene, Q.lds_units, Q.flags, stamps_local);
@@ -65,23 +72,32 @@ __device__ __forceinline__ void radiance_body(const DRadiance &Q) {
     Hit h;
     h.kind = 0; h.index = 0; h.t = HRT_FLT_MAX; h.tri = 0; h.a0 = 0.f; h.a1 = 0.f;
     uint32_t parked = 0;     // meshes whose box this lane's ray enters and that are still to be walked
-    uint32_t stage = 0;      // 0: needs stage A   1: parked for stage B   2: ready for stage C   3: pruned
+    uint32_t stage = 0;      // 0: needs stage A   1: parked for stage B   2: ready for stage C   3: pruned   4: a sample that is not traced
     bool live = false;
 
     // The lane's next ray from i on that is not degenerate: its key, margin, flags and starting sum.  A degenerate ray adds
     // nothing: 0 in mean mode, its sums left as they are under HRT_RADIANCE_ACCUMULATE.
+    // A per-sample source has no ray yet: every pixel is live, and a sample that is not traced is skipped where it is made.
     auto next_ray = [&]() {
         live = false;
-        for (; i < Q.n; i += stride) {
-            if (query_ray(Q, i, ray, tmax)) {
-                live = true;
-                break;
+        if constexpr (SRC::per_sample) {
+            live = i < Q.n;
+        } else {
+            for (; i < Q.n; i += stride) {
+                if (query_ray(Q, i, ray, tmax)) {
+                    live = true;
+                    break;
+                }
+                if (!accumulate) { float *o_ = Q.out + (size_t)i * 3u; o_[0] = 0.f; o_[1] = 0.f; o_[2] = 0.f; }
             }
-            if (!accumulate) { float *o_ = Q.out + (size_t)i * 3u; o_[0] = 0.f; o_[1] = 0.f; o_[2] = 0.f; }
         }
         if (live) {
-            key = Q.keys ? Q.keys[i] : i;
-            query_margin(ray, Q.bound, far, Q.flags, cx.err_abs, first_flags);
+            if constexpr (SRC::per_sample) {
+                key = i;
+            } else {
+                key = Q.keys ? Q.keys[i] : i;
+                query_margin(ray, Q.bound, far, Q.flags, cx.err_abs, first_flags);
+            }
             sum = mk(0.f, 0.f, 0.f);
             if (accumulate) { const float *a_ = Q.out + (size_t)i * 3u; sum = mk(a_[0], a_[1], a_[2]); }
             s = 0;
@@ -92,8 +108,14 @@ __device__ __forceinline__ void radiance_body(const DRadiance &Q) {
     while (__ballot(live) != 0ull) {
         // ---- stage A: (re)start a path, spheres + squares, mesh gates
         if (live && stage == 0u) {
+            bool traced = true;    // a per-sample source may make a sample that is not traced: it ends at once, nothing is added
             if (remaining == 0) {  // sample first_sample + s of ray i: the caller's ray, RNG stream (seed, key, sample) from draw 3
-                (void)query_ray(Q, i, ray, tmax);
+                if constexpr (SRC::per_sample) {  // this sample's own ray, and the margin and far-origin flag of that ray
+                    traced = SRC::sample(Q, i, Q.first_sample + s, ray);
+                    if (traced) query_margin(ray, Q.bound, far, Q.flags, cx.err_abs, first_flags);
+                } else {
+                    (void)query_ray(Q, i, ray, tmax);
+                }
                 rng.start(Q.seed_lo, Q.seed_hi, key, Q.first_sample + s);
                 rng.i = 3u;  // draws 0..2 are the camera's u, v, time
                 cx.flags = first_flags;
@@ -101,9 +123,13 @@ __device__ __forceinline__ void radiance_body(const DRadiance &Q) {
                 rad = mk(0.f, 0.f, 0.f);
                 remaining = 6;  // MAXBOUNCES
             }
-            h = prims_hit(cx, ray);
-            parked = has_mesh ? mesh_gates(cx, ray) : 0u;
-            stage = parked ? 1u : 2u;
+            if (SRC::per_sample && !traced) {
+                h.kind = 0u; parked = 0u; stage = 4u;  // ends below
+            } else {
+                h = prims_hit(cx, ray);
+                parked = has_mesh ? mesh_gates(cx, ray) : 0u;
+                stage = parked ? 1u : 2u;
+            }
             if (!LIGHTS && prune && remaining == 1) {  // the path's last segment: only an emitting closest hit can still reach the sample
                 bool dead;
                 if (h.kind == 0u) {
@@ -130,8 +156,8 @@ __device__ __forceinline__ void radiance_body(const DRadiance &Q) {
         // ---- stage C: shade, scatter, end of path; end of ray
         if (live && stage >= 2u) {
             bool ended;
-            if (stage == 3u) {
-                ended = true;  // pruned on its last segment (stage A): nothing is added
+            if (stage == 3u || (SRC::per_sample && stage == 4u)) {
+                ended = true;  // pruned on its last segment (stage A), or not traced: nothing is added
             } else if (h.kind == 0u) {
                 rad = rad + thr * sky(cx, ray.d, remaining);
                 ended = true;
@@ -147,7 +173,7 @@ __device__ __forceinline__ void radiance_body(const DRadiance &Q) {
                 ended = (remaining == 0) || (prune && thr.x == 0.f && thr.y == 0.f && thr.z == 0.f);
             }
             if (ended) {
-                sum = sum + mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f);  // Scene.h:348
+                if (!(SRC::per_sample && stage == 4u)) sum = sum + mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f);  // Scene.h:348
                 remaining = 0;
                 if (++s == Q.n_samples) {  // the ray is done: its mean (or running sum), then the lane's next ray
                     const float ns = accumulate ? 1.f : (float)Q.n_samples;  // x / 1.f is exact

@@ -22,6 +22,10 @@
 //             [--views N [--orbit DEGREES]]        N cameras, each turned DEGREES further about the scene's up axis than the one before,
 //                                                  rendered in ONE launch (hrt_render_views) with seeds seed, seed + 1, ...; written as
 //                                                  NAME_000.ppm, NAME_001.ppm, ... for --out NAME.ppm (one GPU)
+//             [--lens perspective|ortho|equirect|fisheye [--aperture R --focus D] [--lens-extent X]] a lens camera (hrt_render_lens): the
+//                                                  thin lens of radius R focused at depth D (perspective), the view volume's height X
+//                                                  (ortho), a 360 x 180 degree panorama (equirect), X degrees of equidistant fisheye
+//                                                  (one GPU; plain frames only)
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -52,6 +56,8 @@ static hrt_denoise_var_params denoise_var_params = {4u, 2u, 8.0f, 0.05f, 0.4f, 0
 static uint32_t temporal_frames = 0;  // --temporal: hrt_render_temporal over that many frames, the default hrt_temporal_params
 static double orbit_degrees = 0.0;    // --orbit: the camera's turn about the up axis over the whole run
 static uint32_t n_views = 0;          // --views: hrt_render_views over that many cameras, --orbit degrees apart
+static bool use_lens = false;          // --lens: hrt_render_lens with the default camera behind the projection
+static hrt_lens lens_params = {{}, HRT_LENS_PERSPECTIVE, 0.f, 1.f, 0.f};
 static hrt_temporal_params temporal_params = {0.02f, 64.f, 0.05f, 0.1f, 0.05f};  // the Python TemporalParams()
 
 // Drop-in for ray_trace_from_camera(): same inputs (current scene, nsamples, window size, camera),
@@ -134,6 +140,28 @@ static int ray_trace_views() {
     return rc;
 }
 
+// --lens: one frame through a lens camera
+static int ray_trace_lens() {
+    const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
+    std::vector<float> image((size_t)w * h * 3, 0.f);
+    lens_params.cam = default_camera((float)w / (float)h);
+    static const char *const names[] = {"perspective", "orthographic", "equirectangular", "fisheye"};
+    std::cout << "Ray tracing a " << w << " x " << h << " image on the GPU using " << nsamples << " samples per pixel through a "
+              << names[lens_params.projection] << " lens (aperture " << lens_params.aperture_radius << ", focus " << lens_params.focus_distance
+              << ", extent " << lens_params.extent << ")" << std::endl;
+    hrt_stats st;
+    int rc = hrt_render_lens(device_scene, &lens_params, w, h, nsamples, seed, HRT_FLAG_GAMMA, image.data(), &st);
+    if (rc != HRT_OK) {
+        std::cout << "hrt_render_lens failed: " << hrt_last_error() << std::endl;
+        return rc;
+    }
+    std::cout << "  Done in " << st.total_ms / 1000.0 << " seconds (kernel " << st.kernel_ms << " ms, " << (double)st.samples / st.kernel_ms / 1e3
+              << " Msamples/s)" << std::endl;
+    rc = hrt_write_ppm(out_path.c_str(), image.data(), w, h);
+    if (rc != HRT_OK) std::cout << hrt_last_error() << std::endl;
+    return rc;
+}
+
 static int ray_trace_from_camera() {
     const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
     std::vector<float> image((size_t)w * h * 3, 0.f);
@@ -190,6 +218,17 @@ int main(int argc, char **argv) {
         else if (k == "--temporal") temporal_frames = (uint32_t)strtoul(v.c_str(), nullptr, 10);
         else if (k == "--views") n_views = (uint32_t)strtoul(v.c_str(), nullptr, 10);
         else if (k == "--orbit") orbit_degrees = strtod(v.c_str(), nullptr);
+        else if (k == "--lens") {
+            use_lens = true;
+            if (v == "perspective") lens_params.projection = HRT_LENS_PERSPECTIVE;
+            else if (v == "ortho") lens_params.projection = HRT_LENS_ORTHOGRAPHIC;
+            else if (v == "equirect") lens_params.projection = HRT_LENS_EQUIRECT;
+            else if (v == "fisheye") lens_params.projection = HRT_LENS_FISHEYE;
+            else { std::cerr << "--lens takes perspective, ortho, equirect or fisheye (got " << v << ")" << std::endl; return 2; }
+        }
+        else if (k == "--aperture") lens_params.aperture_radius = strtof(v.c_str(), nullptr);
+        else if (k == "--focus") lens_params.focus_distance = strtof(v.c_str(), nullptr);
+        else if (k == "--lens-extent") lens_params.extent = strtof(v.c_str(), nullptr);
         else if (k == "--gpus") { devices.clear(); for (int d = 0; d < atoi(v.c_str()); ++d) devices.push_back(d); }
         else if (k == "--devices") {
             devices.clear();
@@ -238,6 +277,14 @@ int main(int argc, char **argv) {
         std::cerr << "--views renders plain frames on one GPU: it cannot be combined with --adaptive, --denoise, --denoise-var, --temporal or --gpus / --devices" << std::endl;
         return 2;
     }
+    if (use_lens && (adaptive || denoise || denoise_var || temporal || n_views != 0u || !devices.empty())) {
+        std::cerr << "--lens renders plain frames on one GPU: it cannot be combined with --adaptive, --denoise, --denoise-var, --temporal, --views or --gpus / --devices" << std::endl;
+        return 2;
+    }
+    if (!use_lens && (lens_params.aperture_radius != 0.f || lens_params.focus_distance != 1.f || lens_params.extent != 0.f)) {
+        std::cerr << "--aperture, --focus and --lens-extent describe a lens: give --lens perspective|ortho|equirect|fisheye" << std::endl;
+        return 2;
+    }
     if (!temporal && n_views == 0u && orbit_degrees != 0.0) {
         std::cerr << "--orbit turns the camera over the frames of --temporal or the cameras of --views: give --temporal FRAMES or --views N" << std::endl;
         return 2;
@@ -263,7 +310,7 @@ int main(int argc, char **argv) {
         std::cout << "Image tiles across " << devices.size() << " GPU slot(s), gather: " << hrt_multi_gather(multi)
                   << (note.empty() ? "" : " (" + note + ")") << std::endl;
     }
-    int rc = n_views ? ray_trace_views() : temporal ? ray_trace_frames() : ray_trace_from_camera();  // the 'r' key, once or frame after frame
+    int rc = use_lens ? ray_trace_lens() : n_views ? ray_trace_views() : temporal ? ray_trace_frames() : ray_trace_from_camera();  // the 'r' key, once or frame after frame
     hrt_scene_destroy(device_scene);
     hrt_multi_destroy(multi);
     hrt_shutdown();

@@ -694,6 +694,70 @@ HRT_API int hrt_render_views_device(hrt_scene *scene, const hrt_view *views, uin
 HRT_API int hrt_render_views(hrt_scene *scene, const hrt_view *views, uint32_t n_views, uint32_t w, uint32_t h,
                              uint32_t spp, uint32_t flags, float *out_rgb, hrt_stats *stats /* may be NULL */);
 
+/* ---- Lens cameras: depth of field, orthographic, equirectangular and fisheye frames through the unchanged integrator.
+ * A lens is a camera hrt_render accepts plus a projection; hrt_camera itself and every entry point that takes one stay as they are.
+ * THE RULE (the ray of sample s of pixel p = y*w + x; tests/lens_ref.py states it again in NumPy):
+ *   Draws: g0, g1, g2 are draws 0, 1, 2 of stream (seed, p, s); u = (x + g0)/w, v = (y + g1)/h, time = g2, exactly as the render's
+ *   camera sample.  R, U, F, E are the camera's right, up, forward and eye as given.  All arithmetic is fp32 without fused
+ *   multiply-add, in the order written; sqrtf, sinf, cosf are the device's; normalize is the trace path's own (divide by the length).
+ *   PERSPECTIVE: r = the render's camera ray for (u, v, time).  aperture_radius == 0: the ray is r, untouched -- the record is
+ *     hrt_camera_rays' bit for bit.  Otherwise l0, l1 are draws HRT_LENS_DRAW and HRT_LENS_DRAW + 1 of the same stream (the
+ *     generator is counter-based; a path uses draws 3 onward and never comes near 2^31):
+ *       rad = aperture_radius * sqrtf(l0), phi = 6.2831855f * l1, a = rad * cosf(phi), b = rad * sinf(phi)
+ *       c = (d0 F0 + d1 F1) + d2 F2 with d = r.d; !(c > 0) makes a degenerate sample
+ *       tf = focus_distance / c, P = r.o + tf * r.d, O = r.o + (a * R + b * U); the ray is {O, normalize(P - O), time}
+ *     so every ray of a pixel sample passes through the point its pinhole ray has at depth focus_distance along forward.
+ *   ORTHOGRAPHIC: sx = (2u - 1) * ((0.5f * extent) * aspect), sy = (1 - 2v) * (0.5f * extent); O = E + (sx * R + sy * U),
+ *     d = normalize(F).
+ *   EQUIRECT (the frame spans 360 x 180 degrees, its centre looks along F): phi = (2u - 1) * 3.1415927f,
+ *     th = (0.5f - v) * 3.1415927f; d = normalize(((cosf(th) * sinf(phi)) * R + sinf(th) * U) + (cosf(th) * cosf(phi)) * F), O = E.
+ *   FISHEYE (equidistant, the image circle inscribed in the frame height): qx = (2u - 1) * aspect, qy = 1 - 2v,
+ *     rr = sqrtf(qx qx + qy qy); rr > 1 makes a degenerate sample; th = rr * (extent * 0.5f * (3.1415927f / 180.f)); rr == 0:
+ *     d = normalize(F), otherwise k = sinf(th) / rr, d = normalize(((k * qx) * R + (k * qy) * U) + cosf(th) * F); O = E.
+ *   A DEGENERATE sample is written by hrt_lens_rays as {E, time, 0, 0, 0, +inf}: d == 0 is the query layer's own rule for "not
+ *   traced".  It adds nothing to a pixel and still counts in the divisor.
+ * hrt_lens_rays: the sibling of hrt_camera_rays -- same record layout, no scene, the calling thread's current device, asynchronous on
+ * `stream`.  Checked in this order before the library state (HRT_ERR_INVALID, hrt_last_error() naming the entry point and the
+ * field): lens NULL; the camera, as hrt_render checks it; projection; aperture_radius; focus_distance; extent (each against the
+ * comments of hrt_lens); the frame, as hrt_camera_rays checks it; d_rays NULL or misaligned.
+ * hrt_render_lens_device: the frame without a ray buffer.  d_frame (device, h*w*3 floats, row-major) receives the mean over samples
+ * [first_sample, first_sample + n_samples); with HRT_RADIANCE_ACCUMULATE it holds running sums, exactly as hrt_trace_radiance's
+ * output does.  Asynchronous on `stream`; touches none of the scene's per-launch state, so it may overlap a render of the same
+ * scene.  Flags: HRT_FLAG_EXACT_ONLY, HRT_FLAG_MESH_BRUTE (with EXACT_ONLY), HRT_FLAG_NO_LDS_TREE, HRT_RADIANCE_ACCUMULATE,
+ * HRT_FLAG_GAMMA (hrt_finalize_tiles' arithmetic on the means; refused together with ACCUMULATE).  Any other bit is refused by name;
+ * that includes the kernel-form flags, since there is one form.  Checked in this order: flags; the lens checks above; the frame;
+ * n_samples == 0; first_sample + n_samples > 2^32; d_frame NULL or not 4-byte aligned; then a NULL scene.
+ * CONTRACT A: bit-identical to composing, for s in order, hrt_lens_rays(s) and hrt_trace_radiance(first_sample = s, n_samples = 1,
+ * d_keys = NULL), summed in fp32 and divided by (float)n_samples -- for every projection and flag set.
+ * CONTRACT B: PERSPECTIVE with aperture_radius == 0 is bit-identical to hrt_render(&lens->cam, ...) with the same gamma flag, under
+ * every kernel form of hrt_render.
+ * hrt_render_lens: the same into a HOST buffer, blocking, samples [0, spp); stats as hrt_render (kernel_ms from events, samples =
+ * w*h*spp).  HRT_RADIANCE_ACCUMULATE is refused (the sums live on the device).
+ * hrt_render_lens_features: hrt_render_features with the lens in place of the camera -- same layout and sums -- so that a
+ * depth-of-field or panorama frame can go into the unchanged hrt_denoise / hrt_denoise_var with guides that saw what the frame saw.
+ * n_samples == 0 is the pixel centre u = (x + .5)/w, v = (y + .5)/h at time 0 with l0 = l1 = 0.  A degenerate sample counts as a
+ * miss.  With PERSPECTIVE and aperture 0 it equals hrt_render_features bit for bit; with any other lens its hits are those of
+ * hrt_trace_rays(HRT_QUERY_SHADE) on the records of hrt_lens_rays.  Asynchronous on `stream`; the lens travels as a kernel argument,
+ * so unlike hrt_render_features the call takes no part in the ordering of the scene's feature launches.
+ * Not lens-aware (DESIGN.md section 5 "Lens cameras"): the streaming kernel, hrt_render_views, the adaptive sampler, temporal
+ * reprojection, the multi-GPU paths. */
+enum { HRT_LENS_PERSPECTIVE = 0, HRT_LENS_ORTHOGRAPHIC = 1, HRT_LENS_EQUIRECT = 2, HRT_LENS_FISHEYE = 3 };
+#define HRT_LENS_DRAW 0x80000000u   /* draw index of the first of the two lens draws */
+typedef struct hrt_lens {
+    hrt_camera cam;         /* eye + basis; must be a camera hrt_render accepts. fovy/znear/zfar are read by PERSPECTIVE only, aspect by all but EQUIRECT */
+    uint32_t projection;    /* HRT_LENS_* */
+    float aperture_radius;  /* >= 0, finite; 0 = pinhole. Must be 0 unless PERSPECTIVE */
+    float focus_distance;   /* > 0 and finite when aperture_radius > 0: depth ALONG FORWARD of the plane in focus; ignored (any value) otherwise */
+    float extent;           /* ORTHOGRAPHIC: height of the view volume in world units, > 0, finite. FISHEYE: full field of view in degrees, in (0, 360]. Otherwise must be 0 */
+} hrt_lens;
+HRT_API int hrt_lens_rays(const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t sample, uint64_t seed, float *d_rays, void *stream);
+HRT_API int hrt_render_lens_device(hrt_scene *scene, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples,
+                                   uint64_t seed, uint32_t flags, float *d_frame, void *stream);
+HRT_API int hrt_render_lens(hrt_scene *scene, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed, uint32_t flags,
+                            float *out_rgb, hrt_stats *stats /* may be NULL */);
+HRT_API int hrt_render_lens_features(hrt_scene *scene, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples,
+                                     uint64_t seed, float *d_features, void *stream);
+
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
  * format 6: the same integers as bytes (binary PPM; negative values, which P3 prints with a sign, clamp to 0).
