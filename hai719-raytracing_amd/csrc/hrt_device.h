@@ -1,23 +1,25 @@
 // Device-side scene layout of the MI355X trace path (gfx950 only).
 //
-// hrt_scene_create() repacks the hrt_scene_desc into the arrays below, all
+// hrt_scene_create() packs the hrt_scene_desc into the arrays below on the host
+// (hrt_pack.h pack_scene, which needs no device) and uploads them, all
 // resident in HBM for the life of the scene (they total a few MB, so after the
 // first touch they live in the per-XCD L2 / Infinity Cache; the top of every
 // KD-tree is additionally staged into LDS by each workgroup).
 //
 //   prim records  float4 rows, read with wave-uniform indices (scalar loads):
 //     sphere  2 rows: {c.xyz, r} {motion.xyz, material}
-//     quad    5 rows: {p0.xyz, D0} {n.xyz, flags} {R.xyz, |R|} {U.xyz, |U|} {motion.xyz, material}
-//             + 2 rows used only when shading: {T.xyz,0} {B.xyz,0}
+//     quad    7 rows: {p0.xyz, D0} {n.xyz, flags} {R.xyz, |R|} {U.xyz, |U|} {motion.xyz, material}
+//             and two used only when shading: {T.xyz,0} {B.xyz,0}
 //   quad filter   DScene::qfilter, wave-uniform rows of the no-division filter (hrt_kernels.hip quad_filter):
 //               static squares (nearly) in an axis plane, by normal axis K: {sgn D, centre_I, centre_J, half_I} {half_J, bits, par, cq}
 //               all others, (R, U) and (n.y, n.z) components side by side in aligned SGPR pairs:
 //               {p0.xyz, D0} {n.y, n.z, n.x, flags | index << 8} {R.x, U.x, R.y, U.y} {R.z, U.z, |R|, |U|}
 //   materials     8 float4 rows per material, read per lane at the closest hit (rows 6, 7: geometry of its texture / normal map)
 //   meshes        DMesh records (wave-uniform)
-//   kd units      uint4 nodelets (include/hrt.h), refs rebased to the global array
+//   kd units      uint4 units: the caller's nodelets (include/hrt.h) re-laid per mesh, breadth-first, as two-level treelets (2 units)
+//                 and leaves (4 units, on 64-byte lines), refs rebased to the global array (hrt_pack.h relay_kd)
 //   exceptions    irregular triangles (include/hrt.h hrt_tri_exception), one leaf entry each: {cull lo, soup slot} {cull hi, nb} followed by
-//                 its nb reference leaf boxes {lo, 0} {hi, 0} (its rows sit behind the mesh's leaf-ordered soup); bounding entry
+//                 its nb reference leaf boxes {lo, last} {hi, 0} (last = 1 on the final box of a reference leaf; its rows sit behind the mesh's leaf-ordered soup); bounding entry
 //                 {lo, HRT_EXC_INNER} {hi, skip}; threaded depth-first
 //   triangles     leaf-ordered soup in two arrays by slot: planes {n, D} (16 B: the planes of a leaf's triangles share a cache line) and
 //                 rows {c0, d11} {e1, d00} {e2, d01} {id, -, -, -} (one 64-byte line; three rows read when the plane is hit in front, the id at shading)
@@ -43,12 +45,12 @@ struct DMesh {
     float aabb_lo[3], aabb_hi[3];  // Mesh::computeAABB box (the reference's gate test)
     float kd_lo[3], kd_hi[3];      // root cell of the flattened tree
     uint32_t root;                 // rebased ref
-    uint32_t tri_base;             // first row-triple of this mesh in the soup (in triangles, not rows)
+    uint32_t tri_base;             // first soup slot of this mesh (in triangles, not rows)
     uint32_t material;
     int32_t color_type;
     uint32_t color_base;           // into colours (face) or into vert ids / vertex colours
     uint32_t vcolor_base;
-    uint32_t n_soup;               // rows-of-five in this mesh's leaf-ordered soup (straddlers repeated)
+    uint32_t n_soup;               // slots (HRT_TRI_ROWS rows and a plane each) of this mesh's leaf-ordered soup (straddlers repeated)
     uint32_t exc_base, n_exc;      // irregular triangles (hrt_tri_exception): entries [exc_base, exc_base + n_exc) of DScene::exceptions
     uint32_t pad1, pad2, pad3;     // 96 bytes
 };
@@ -75,7 +77,7 @@ struct DScene {
     const float4 *tabs;        // squares | materials | spheres | mesh records | sphere pair-filter rows (| short exception lists) in ONE array (what `quads`, `materials`, `spheres`, `meshes` above
                                // point into): the streaming kernel stages it in LDS for per-lane row fetches (hrt_kernels.hip CtxT)
     uint32_t tab_quads, tab_mats, tab_spheres, tab_meshes, tab_exc, tab_rows;  // row offsets of the tables, rows in all
-    uint32_t exc_in_tabs;      // 1: the meshes' exception lists are short (<= 512 rows) and sit in `tabs` at tab_exc; 0: in `exceptions`
+    uint32_t exc_in_tabs;      // 1: the meshes' exception lists are short (<= 1536 rows, 24 KB) and sit in `tabs` at tab_exc; 0: in `exceptions`
     const float4 *qfilter;     // rows of the squares' no-division filter: squares in an axis plane by normal axis x, y, z (2 rows each), then the rest (4 rows each)
     uint32_t qf_n[4];          // squares per section
     uint32_t tab_sfilter;      // row offset in `tabs` of the spheres' pair-filter rows (hrt_kernels.hip sphere_filter), 4 per PAIR of spheres
@@ -89,7 +91,7 @@ struct DScene {
     uint32_t n_kd_units;
     int32_t dark_sky, skybox_image;
     uint32_t any_motion;       // some material has a motion vector != 0: only then does a ray's time matter (hrt_stream.hip recomputes it per hit visit)
-    uint32_t prune_ok;         // no product a path can form overflows fp32 (hrt_scene_create bounds albedo-like colours ^ HRT_MAXBOUNCES x
+    uint32_t prune_ok;         // no product a path can form overflows fp32 (hrt_pack.h prune_bound bounds albedo-like colours ^ HRT_MAXBOUNCES x
                                // the largest emission / light / sky term in fp64): then every throughput is finite and throughput x value == 0
                                // whenever the throughput is 0, which the exact path pruning (hrt_stream.hip HRT_SP_PRUNE) relies on
 };

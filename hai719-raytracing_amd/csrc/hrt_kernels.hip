@@ -347,7 +347,7 @@ __device__ __forceinline__ void kd_fetch4(gu4 g, const CX &cx, uint32_t i, uint4
     if (i >= cx.lds_n) { a = ld(g, i); b = ld(g, i + 1u); c = ld(g, i + 2u); d = ld(g, i + 3u); }
 }
 
-// Inner nodes of the device's tree are TREELETS of two levels in 32 bytes (hrt_api.hip scene_create_impl builds them from the
+// Inner nodes of the device's tree are TREELETS of two levels in 32 bytes (hrt_pack.h relay_kd builds them from the
 // caller's 16-byte nodelets): {split, split of the left child, split of the right child, axes} {the four grandchildren's refs},
 // axes = 2 bits per node, 3 = "no such node: the child is a leaf, take the first exit of its pair".  One round trip (two
 // 16-byte loads of one half line) descends two levels; the per-node rule is KDTree.cpp's: left when the point lies below the
@@ -434,7 +434,7 @@ __device__ __forceinline__ bool mesh_exceptions_walk(cscene S, EP ex_all, MP M, 
     bool found = false;
     const EP ex = ex_all + 2u * M->exc_base;
     const Soup sp = soup_of(S);
-    // entries (hrt_api.hip scene_create_impl): {lo', HRT_EXC_INNER} {hi', skip} bounds of a subtree; {cull lo, soup slot} {cull hi, nb}
+    // entries (hrt_pack.h thread_exceptions): {lo', HRT_EXC_INNER} {hi', skip} bounds of a subtree; {cull lo, soup slot} {cull hi, nb}
     // one irregular triangle, followed by its nb reference leaf boxes {lo, 0} {hi, 0}
     for (uint32_t i = 0; i < n;) {
         const float4 lo = ld(ex, 2u * i), hi = ld(ex, 2u * i + 1u);
@@ -570,7 +570,7 @@ __device__ __forceinline__ float cget(f3 v) { return A == 0 ? v.x : (A == 1 ? v.
 // FILTER, squares that lie (nearly) in an axis plane -- every wall of the reference's scenes: setQuad builds them axis-
 // aligned and the set-up code's rotate_x / rotate_y by multiples of 90 degrees leave residues of a few 1e-8 in the other
 // components (cos(pi/2) in fp32).  The host recognises a static square whose folded normal is within eps_n of +-e_K and
-// whose edges run within the same tolerance along the other two axes (hrt_api.hip build_quad_filter) and stores
+// whose edges run within the same tolerance along the other two axes (hrt_pack.h build_quad_filter) and stores
 //   r0 {sgn * D, centre_I, centre_J, half_I}   r1 {half_J, bits, par, cq}     bits: 1 glass, 2 normal along -K, square index << 8
 // The reference's t = (D - o.n) / (d.n) then differs from ta = (sgn * D - o_K) / d_K by at most
 //   |t - ta| <= 1.15 (eps_n + 3e-7) (ext + |ta|) / |d_K|        (numerator and denominator each off by <= eps_n (ext | 1);

@@ -130,7 +130,7 @@ RefTreeAnalysis analyse_reference_tree(const float *positions, uint32_t nv, cons
     // Slivers: the barycentric solve of Triangle.h:62-75 has condition ~ 1 / sin^2(angle at c0); in fp32 it returns noise
     // once sin^2 <~ 1e-6.  Everything below 1e-4 (an angle under 0.6 degrees) is treated as irregular -- two orders of
     // margin; a well-shaped triangle accepts points at most ~1e-6 edge lengths outside itself.
-    // Both evaluated on the scaled vertices in fp32, like the constants the kernel folds (hrt_api.hip fold_triangle).
+    // Both evaluated on the scaled vertices in fp32, like the constants the kernel folds (csrc/hrt_pack.h fold_triangle).
     std::vector<uint8_t> dead(nt, 0);
     for (uint32_t t = 0; t < nt; ++t) {
         float c[3][3];

@@ -260,7 +260,8 @@ HRT_API void hrt_shutdown(void);
 HRT_API const char *hrt_last_error(void);
 HRT_API int hrt_device_count(void);
 
-/* Upload: repack the description into device SoA arrays.  The description
+/* Upload: repack the description into device SoA arrays (checked and packed on the host by
+ * csrc/hrt_pack.h pack_scene, which needs no device; then uploaded).  The description
  * (and everything it points to) may be freed after the call returns. */
 HRT_API int hrt_scene_create(const hrt_scene_desc *desc, hrt_scene **out);
 HRT_API void hrt_scene_destroy(hrt_scene *scene);
