@@ -115,6 +115,11 @@ class Lens(C.Structure):
         self.extent = extent
 
 
+class LensView(C.Structure):
+    """``hrt_lens_view``: one lens camera of a batched lens render with the seed of its frame (include/hrt.h)."""
+    _fields_ = [("lens", Lens), ("seed", C.c_uint64)]
+
+
 class PickInput(C.Structure):
     """hrt_pick_input (include/hrt.h): what the choice of a trace kernel build depends on."""
     _fields_ = [("n_meshes", C.c_uint32), ("n_lights", C.c_uint32), ("n_spheres", C.c_uint32), ("tab_rows", C.c_uint32),
@@ -314,6 +319,12 @@ def device_lib() -> C.CDLL:
                                         C.c_void_p, C.POINTER(Stats)]
         lib.hrt_render_lens_features.argtypes = [C.c_void_p, C.POINTER(Lens), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                                  C.c_void_p, C.c_void_p]
+        lib.hrt_render_lens_views_device.argtypes = [C.c_void_p, C.POINTER(LensView), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                     C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.hrt_render_lens_views.argtypes = [C.c_void_p, C.POINTER(LensView), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                              C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_render_lens_views_features.argtypes = [C.c_void_p, C.POINTER(LensView), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                       C.c_void_p, C.c_void_p]
         lib.hrt_debug_pick_kernel.argtypes = [C.POINTER(PickInput), C.c_char_p, C.c_size_t]
         lib.hrt_debug_last_kernel.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         _dev = lib
@@ -754,6 +765,71 @@ class DeviceScene:
         s = torch.cuda.current_stream()
         self._check(self._lib.hrt_render_lens_features(self._h, C.byref(lens), w, h, first_sample, n_samples, seed, C.c_void_p(d.data_ptr()),
                                                        C.c_void_p(s.cuda_stream)))
+        s.synchronize()
+        return d.cpu().numpy()
+
+    @staticmethod
+    def _lens_views(who: str, lenses, seeds):
+        lenses = list(lenses)
+        n = len(lenses)
+        seeds = [1] * n if seeds is None else [int(x) for x in seeds]
+        if len(seeds) != n:
+            raise ValueError(f"{who}: {n} lenses but {len(seeds)} seeds")
+        views = (LensView * max(n, 1))()
+        for v, (lens, seed) in enumerate(zip(lenses, seeds)):
+            C.memmove(C.byref(views[v].lens), C.byref(lens), C.sizeof(Lens))
+            views[v].seed = seed
+        return views, n
+
+    def render_lens_views(self, lenses, w: int, h: int, spp: int, seeds=None, flags: int = 0, first_sample: int = 0, out=None,
+                          accumulate: bool = False, stats: Optional[Stats] = None):
+        """hrt_render_lens_views*: every lens of ``lenses`` as a w x h frame, in one launch -> (n, h, w, 3) float32; frame v has the
+        bits of ``render_lens(lenses[v], w, h, spp, seeds[v], flags, first_sample)``.  ``seeds``: one per view (default 1 for each).
+        With ``accumulate`` the running sums (``out`` then holds the sums of the earlier samples and is updated in place).  With
+        ``out`` a contiguous (n, h, w, 3) float32 torch tensor on the GPU the call runs on the current torch stream of its device
+        without synchronising and returns ``out`` (hrt_render_lens_views_device).  Otherwise the frames come back as NumPy and the
+        call blocks; ``stats``: a Stats to fill, if wanted (the blocking form of samples [0, spp) without ``out``:
+        hrt_render_lens_views).  ``flags``: as ``render_lens``."""
+        import torch
+        views, n = DeviceScene._lens_views("render_lens_views", lenses, seeds)
+        flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
+        if isinstance(out, torch.Tensor):
+            if out.device.type != "cuda" or out.dtype != torch.float32 or tuple(out.shape) != (n, h, w, 3) or not out.is_contiguous():
+                raise ValueError(f"render_lens_views: out must be a contiguous ({n}, {h}, {w}, 3) float32 tensor on the GPU")
+            s = torch.cuda.current_stream(out.device)
+            self._check(self._lib.hrt_render_lens_views_device(self._h, views, n, w, h, first_sample, spp, flags, C.c_void_p(out.data_ptr()),
+                                                               C.c_void_p(s.cuda_stream)))
+            return out
+        if out is not None:
+            o = np.asarray(out)
+            if o.shape != (n, h, w, 3) or o.dtype != np.float32:
+                raise ValueError(f"render_lens_views: out must be ({n}, {h}, {w}, 3) float32 (got {o.shape} {o.dtype})")
+        elif accumulate and first_sample != 0:
+            raise ValueError("render_lens_views: accumulate after sample 0 needs the running sums in `out`")
+        if out is None and not accumulate and first_sample == 0:
+            frames = np.empty((n, h, w, 3), dtype=np.float32)
+            self._check(self._lib.hrt_render_lens_views(self._h, views, n, w, h, spp, flags, frames.ctypes.data,
+                                                        None if stats is None else C.byref(stats)))
+            return frames
+        d = torch.zeros((n, h, w, 3), dtype=torch.float32, device="cuda") if out is None else torch.from_numpy(np.ascontiguousarray(o)).to("cuda")
+        s = torch.cuda.current_stream(d.device)
+        self._check(self._lib.hrt_render_lens_views_device(self._h, views, n, w, h, first_sample, spp, flags, C.c_void_p(d.data_ptr()),
+                                                           C.c_void_p(s.cuda_stream)))
+        r = d.cpu().numpy()
+        if out is not None:
+            out[...] = r
+            return out
+        return r
+
+    def render_lens_views_features(self, lenses, w: int, h: int, first_sample: int, n_samples: int, seeds=None) -> np.ndarray:
+        """hrt_render_lens_views_features: ``render_lens_features`` of every lens of ``lenses`` with its seed, in one launch ->
+        (n, h, w, FEATURE_FLOATS) float32.  The device buffer is a torch tensor on the scene's device; the call waits for it."""
+        import torch
+        views, n = DeviceScene._lens_views("render_lens_views_features", lenses, seeds)
+        d = torch.empty((n, h, w, FEATURE_FLOATS), dtype=torch.float32, device="cuda")
+        s = torch.cuda.current_stream()
+        self._check(self._lib.hrt_render_lens_views_features(self._h, views, n, w, h, first_sample, n_samples, C.c_void_p(d.data_ptr()),
+                                                             C.c_void_p(s.cuda_stream)))
         s.synchronize()
         return d.cpu().numpy()
 

@@ -234,6 +234,8 @@ int pick_build(const hrt_pick_input &in, KernelPref pref, const KernelBuild *&ro
 
 }  // namespace
 
+struct DLensView;  // hrt_lens.hip
+
 struct hrt_scene {
     DScene d{};                  // host copy of the device scene header
     DScene *d_scene = nullptr;   // the header in HBM (read by the kernels through a constant-space pointer)
@@ -275,6 +277,14 @@ struct hrt_scene {
     hipEvent_t ev_views = nullptr, ev_views_done = nullptr;
     bool views_uploading = false, views_used = false;
     hipStream_t views_stream = nullptr;
+    // Batched lens views (hrt_lens.hip): the table of per-view blocks on the device, its pinned host staging copy with the event that
+    // says the upload has read it, and the event and stream of the launch that read the table last.  Nothing of the trace launches.
+    Scratch lv_blocks;
+    DLensView *h_lv = nullptr;
+    size_t h_lv_cap = 0;  // in views
+    hipEvent_t ev_lv = nullptr, ev_lv_done = nullptr;
+    bool lv_uploading = false, lv_used = false;
+    hipStream_t lv_stream = nullptr;
 };
 
 namespace {
@@ -380,6 +390,10 @@ void hrt_scene_destroy(hrt_scene *s) {
     if (s->h_views) (void)hipHostFree(s->h_views);
     if (s->ev_views) (void)hipEventDestroy(s->ev_views);
     if (s->ev_views_done) (void)hipEventDestroy(s->ev_views_done);
+    s->lv_blocks.release();
+    if (s->h_lv) (void)hipHostFree(s->h_lv);
+    if (s->ev_lv) (void)hipEventDestroy(s->ev_lv);
+    if (s->ev_lv_done) (void)hipEventDestroy(s->ev_lv_done);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     delete s;

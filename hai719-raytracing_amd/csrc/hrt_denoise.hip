@@ -43,6 +43,7 @@ __device__ __forceinline__ hrtk::Ray camera_sample(CP cam, uint32_t seed_lo, uin
 // the context's margin for its ray.  FeatureCameraRays: the render's camera, the block R.cam points at.
 extern "C++" {
 struct FeatureCameraRays {
+    __device__ __forceinline__ uint32_t items(const DRender &R) const { return R.w * R.h; }
     template <class CX>
     __device__ __forceinline__ bool operator()(CX &, const DRender &R, uint32_t n, uint32_t idx, uint32_t k, hrtk::Ray &ray) const {
         const ccam cam = (ccam)R.cam;
@@ -57,11 +58,13 @@ struct FeatureCameraRays {
 };
 
 // Sums of the first-hit features over samples [s0, s0 + n) of every pixel (n == 0: the pixel centre at time 0, hrt_aov_kernel's ray).
+// One lane per item, source.items(R) of them: the pixels of the frame, or for a source that maps an item to a pixel of one of
+// several frames (LensViewFeatureRays, hrt_lens.hip) the pixels of all of them; record idx of `out` is item idx's.
 template <class CX, class SRC>
 __device__ __forceinline__ void features_body(const DRender &R, uint32_t n, float *__restrict__ out, const SRC &source) {
     using namespace hrtk;
     const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= R.w * R.h) return;
+    if (idx >= source.items(R)) return;
     CX cx;
     cx.S = (cscene)R.scene;
     cx.set_tables((gf4)cx.S->tabs, (gf1)c_u8_lut, cx.S);

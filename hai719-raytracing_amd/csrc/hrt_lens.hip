@@ -9,6 +9,14 @@
 // hrt_lens_features_kernel is features_body with the lens in place of the camera.  The lens travels as a kernel argument: no call
 // here touches the per-launch state of a scene.
 //
+// Batched lens views (hrt_render_lens_views*): N lens frames of one scene as ONE dense index space of N * w * h items, item i being
+// pixel i % (w*h) of view i / (w*h).  The hrt_lens_views_kernel builds are radiance_body with the LensViewRays source, whose lane
+// takes the lens and the seed of its item's view from a table in device memory (DLensView) at the point of use -- per LANE: a wave
+// straddles views whenever w*h is no multiple of 64, and lanes take their next item by grid stride on their own, so the view is
+// never wave-uniform.  The item-major store is the view-major, row-major layout of the frames.  hrt_lens_views_features_kernel is
+// features_body over the same items.  The table is the scene's (a grow-only buffer with a pinned staging copy, as hrt_views.hip keeps
+// its view blocks); nothing of the trace launches' state is touched.
+//
 // All of it is fp32 without fused multiply-add (the library is built with -ffp-contract=off), in the order the header writes.
 
 // hrt_lens -> what lens_sample reads.  R, U, F, E are the camera's vectors as the caller gave them; `cam` is camera_ray's block.
@@ -26,6 +34,15 @@ struct DLens {
     uint32_t pad[3];
 };
 
+// One view of a batched lens launch: the lens, the seed of its frame and, for the features of a pinhole view, the render's margin
+// for its eye (what a one-lens launch keeps in DRender::err_abs).  240 bytes, read per lane with vector loads.
+struct DLensView {
+    DLens lens;
+    uint32_t seed_lo, seed_hi;
+    float err_abs;
+    uint32_t pad;
+};
+
 // The launch record of the hrt_lens_kernel builds: DRadiance with the lens and the frame in place of the ray and key arrays
 // (query_launch and radiance_body read the fields they share by name).
 struct DLensRadiance {
@@ -41,6 +58,19 @@ struct DLensRadiance {
     DLens lens;
 };
 
+// The launch record of the hrt_lens_views_kernel builds: the table of views in place of the one lens and the launch's seed.
+struct DLensViewsRadiance {
+    const DScene *scene;
+    float *out;            // 3 floats per item: view-major, each view row-major
+    uint32_t n;            // n_views * w * h
+    uint32_t flags;
+    uint32_t first_sample, n_samples;
+    uint32_t lds_units;
+    float bound;
+    uint32_t w, h, npix;   // npix = w * h
+    const DLensView *views;
+};
+
 extern "C++" {
 namespace hrtk {
 
@@ -51,7 +81,8 @@ __device__ __forceinline__ bool lens_traced(const Ray &r) {
 }
 
 // THE RULE for film position (u, v), time and lens draws (l0, l1); false for a degenerate sample, whose ray is {E, 0, time}.
-// The projection is the same for every lane: one branch on it, each arm straight-line code.
+// One branch on the projection, each arm straight-line code: the same arm for every lane of a one-lens launch; in a batch the
+// lanes of a wave may hold different views, and the arms their lenses name run one after the other.
 __device__ __forceinline__ bool lens_project(const DLens &L, float u, float v, float time, float l0, float l1, Ray &ray) {
     const f3 R = mk(L.right[0], L.right[1], L.right[2]), U = mk(L.up[0], L.up[1], L.up[2]), F = mk(L.forward[0], L.forward[1], L.forward[2]);
     const f3 E = mk(L.eye[0], L.eye[1], L.eye[2]);
@@ -126,8 +157,28 @@ __device__ __forceinline__ bool lens_sample(const DLens &L, uint32_t seed_lo, ui
 // radiance_body's source for a lens: the ray of (pixel, sample), traced if the rule makes one and the query layer accepts it.
 struct LensRays {
     static constexpr bool per_sample = true;
+    __device__ static __forceinline__ uint32_t key(const DLensRadiance &, uint32_t pixel) { return pixel; }
+    __device__ static __forceinline__ void seed(const DLensRadiance &Q, uint32_t, uint32_t &lo, uint32_t &hi) { lo = Q.seed_lo; hi = Q.seed_hi; }
     __device__ static __forceinline__ bool sample(const DLensRadiance &Q, uint32_t pixel, uint32_t sample, Ray &ray) {
         return lens_sample(Q.lens, Q.seed_lo, Q.seed_hi, Q.w, Q.h, pixel, sample, ray) && lens_traced(ray);
+    }
+};
+
+// radiance_body's source for a batch of lens views: item i is pixel i % npix of view i / npix, keyed by that pixel and its view's
+// seed.  The lens is NOT wave-uniform (see the head of this file): lens_sample reads the view's block through a reference into
+// the table, so every field is loaded by the lane that uses it where it uses it, and no lens is held in registers across the path.
+// i < Q.n = n_views * npix, so the view is inside the table.
+struct LensViewRays {
+    static constexpr bool per_sample = true;
+    __device__ static __forceinline__ uint32_t key(const DLensViewsRadiance &Q, uint32_t i) { return i % Q.npix; }
+    __device__ static __forceinline__ void seed(const DLensViewsRadiance &Q, uint32_t i, uint32_t &lo, uint32_t &hi) {
+        const DLensView &V = Q.views[i / Q.npix];
+        lo = V.seed_lo; hi = V.seed_hi;
+    }
+    __device__ static __forceinline__ bool sample(const DLensViewsRadiance &Q, uint32_t i, uint32_t sample, Ray &ray) {
+        const uint32_t view = i / Q.npix;
+        const DLensView &V = Q.views[view];
+        return lens_sample(V.lens, V.seed_lo, V.seed_hi, Q.w, Q.h, i - view * Q.npix, sample, ray) && lens_traced(ray);
     }
 };
 
@@ -137,6 +188,7 @@ struct LensRays {
 struct LensFeatureRays {
     const DLens &L;
     float bound;  // hrt_scene::bound
+    __device__ __forceinline__ uint32_t items(const DRender &R) const { return R.w * R.h; }
     template <class CX>
     __device__ __forceinline__ bool operator()(CX &cx, const DRender &R, uint32_t n, uint32_t idx, uint32_t k, Ray &ray) const {
         bool ok;
@@ -147,6 +199,36 @@ struct LensFeatureRays {
             ok = lens_sample(L, R.seed_lo, R.seed_hi, R.w, R.h, idx, R.s0 + k, ray);
         }
         if (!(L.projection == HRT_LENS_PERSPECTIVE && L.aperture == 0.f)) {
+            query_margin(ray, bound, query_far(bound), R.flags, cx.err_abs, cx.flags);
+        }
+        return ok && lens_traced(ray);
+    }
+};
+
+// features_body's source for a batch of lens views: item idx is pixel idx % (w*h) of view idx / (w*h), with that view's lens and
+// seed; R.w x R.h is one view's frame.  What LensFeatureRays does for its one lens, per lane: a pinhole view takes the render's
+// margin for its own eye from its block.
+struct LensViewFeatureRays {
+    const DLensView *views;
+    float bound;  // hrt_scene::bound
+    uint32_t n_items;
+    __device__ __forceinline__ uint32_t items(const DRender &) const { return n_items; }
+    template <class CX>
+    __device__ __forceinline__ bool operator()(CX &cx, const DRender &R, uint32_t n, uint32_t idx, uint32_t k, Ray &ray) const {
+        const uint32_t npix = R.w * R.h, view = idx / npix, pixel = idx - view * npix;
+        const DLensView &V = views[view];
+        const DLens &L = V.lens;
+        bool ok;
+        if (n == 0u) {
+            const uint32_t x = pixel % R.w, y = pixel / R.w;
+            ok = lens_project(L, ((float)x + 0.5f) / (float)R.w, ((float)y + 0.5f) / (float)R.h, 0.f, 0.f, 0.f, ray);
+        } else {
+            ok = lens_sample(L, V.seed_lo, V.seed_hi, R.w, R.h, pixel, R.s0 + k, ray);
+        }
+        if (L.projection == HRT_LENS_PERSPECTIVE && L.aperture == 0.f) {
+            cx.err_abs = V.err_abs;
+            cx.flags = R.flags;
+        } else {
             query_margin(ray, bound, query_far(bound), R.flags, cx.err_abs, cx.flags);
         }
         return ok && lens_traced(ray);
@@ -176,10 +258,22 @@ extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_W
 extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_lens_kernel_exact(const DLensRadiance Q) { radiance_body<false, true, LensRays>(Q); }
 extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_lens_kernel_lights_exact(const DLensRadiance Q) { radiance_body<true, true, LensRays>(Q); }
 
+// The fused frames of a batch: radiance_body over the items of all views.  Launch bounds and shape are hrt_lens_kernel's.
+extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_lens_views_kernel(const DLensViewsRadiance Q) { radiance_body<false, false, LensViewRays>(Q); }
+extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_lens_views_kernel_lights(const DLensViewsRadiance Q) { radiance_body<true, false, LensViewRays>(Q); }
+extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_lens_views_kernel_exact(const DLensViewsRadiance Q) { radiance_body<false, true, LensViewRays>(Q); }
+extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_lens_views_kernel_lights_exact(const DLensViewsRadiance Q) { radiance_body<true, true, LensViewRays>(Q); }
+
 // hrt_render_lens_features: hrt_features_kernel with the lens as a kernel argument in place of the scene's camera block.
 extern "C" __global__ void __launch_bounds__(256) hrt_lens_features_kernel(const DRender R, const DLens L, float bound, uint32_t n,
                                                                            float *__restrict__ out) {
     features_body<CtxT<false, false, false, true>>(R, n, out, LensFeatureRays{L, bound});
+}
+
+// hrt_render_lens_views_features: the same over the n_items = n_views * w * h items of a batch, the lenses from the table.
+extern "C" __global__ void __launch_bounds__(256) hrt_lens_views_features_kernel(const DRender R, const DLensView *__restrict__ views, float bound,
+                                                                                 uint32_t n_items, uint32_t n, float *__restrict__ out) {
+    features_body<CtxT<false, false, false, true>>(R, n, out, LensViewFeatureRays{views, bound, n_items});
 }
 
 // The lens checks, in the header's order; fills L.  `who` names the entry point in every message but the camera's own.
@@ -227,9 +321,8 @@ int hrt_lens_rays(const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t sample,
     return HRT_OK;
 }
 
-// The checks hrt_render_lens_device and hrt_render_lens share, in the header's order (all before the scene); fills L.
-static int lens_render_check(const std::string &who, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples,
-                             uint32_t flags, const float *out, const char *out_name, DLens &L) {
+// The flags of a fused lens launch, one frame or a batch.
+static int lens_flags_check(const std::string &who, uint32_t flags) {
     static const struct { uint32_t bit; const char *name; } no_form[] = {
         {HRT_FLAG_WAVE_KERNEL, "HRT_FLAG_WAVE_KERNEL"}, {HRT_FLAG_STREAM_KERNEL, "HRT_FLAG_STREAM_KERNEL"}, {HRT_FLAG_DUAL_KERNEL, "HRT_FLAG_DUAL_KERNEL"}};
     for (const auto &f : no_form)
@@ -241,8 +334,11 @@ static int lens_render_check(const std::string &who, const hrt_lens *lens, uint3
     { const int brc = check_mesh_brute(who, flags); if (brc != HRT_OK) return brc; }
     if ((flags & HRT_FLAG_GAMMA) && (flags & HRT_RADIANCE_ACCUMULATE))
         return fail(HRT_ERR_INVALID, who + ": flags: HRT_FLAG_GAMMA cannot be combined with HRT_RADIANCE_ACCUMULATE (running sums are linear)");
-    { const int lrc = lens_check(who, lens, L); if (lrc != HRT_OK) return lrc; }
-    { const int frc = check_frame(who, w, h, k_max_pixels); if (frc != HRT_OK) return frc; }
+    return HRT_OK;
+}
+
+// The samples and the output of a fused lens launch, one frame or a batch.
+static int lens_samples_check(const std::string &who, uint32_t first_sample, uint32_t n_samples, const float *out, const char *out_name) {
     if (n_samples == 0u) return fail(HRT_ERR_INVALID, who + ": n_samples must be positive");
     if ((uint64_t)first_sample + n_samples > 0x100000000ull)
         return fail(HRT_ERR_INVALID, who + ": first_sample + n_samples must be at most 2^32 (sample indices do not wrap)");
@@ -251,8 +347,28 @@ static int lens_render_check(const std::string &who, const hrt_lens *lens, uint3
     return HRT_OK;
 }
 
-// The fused launch into d_frame on `stream` (the scene entered), then the gamma: hrt_gamma_kernel, the in-place kernel of the
-// one-shot render (hrt_finalize_kernel's expression after its division), over the means, in pieces its 32-bit index can address.
+// The checks hrt_render_lens_device and hrt_render_lens share, in the header's order (all before the scene); fills L.
+static int lens_render_check(const std::string &who, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples,
+                             uint32_t flags, const float *out, const char *out_name, DLens &L) {
+    { const int frc = lens_flags_check(who, flags); if (frc != HRT_OK) return frc; }
+    { const int lrc = lens_check(who, lens, L); if (lrc != HRT_OK) return lrc; }
+    { const int frc = check_frame(who, w, h, k_max_pixels); if (frc != HRT_OK) return frc; }
+    return lens_samples_check(who, first_sample, n_samples, out, out_name);
+}
+
+// HRT_FLAG_GAMMA of a fused lens launch: hrt_gamma_kernel, the in-place kernel of the one-shot render (hrt_finalize_kernel's
+// expression after its division), over the `total` floats of the means, in pieces its 32-bit index can address.
+static int lens_gamma(float *d_frame, uint64_t total, hipStream_t stream) {
+    const uint64_t piece = 1ull << 30;
+    for (uint64_t at = 0; at < total; at += piece) {
+        const uint32_t n = (uint32_t)std::min(piece, total - at);
+        hipLaunchKernelGGL(hrt_gamma_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_frame + at, n);
+        HIP_TRY(hipGetLastError());
+    }
+    return HRT_OK;
+}
+
+// The fused launch into d_frame on `stream` (the scene entered), then the gamma.
 static int lens_launch(hrt_scene *s, const DLens &L, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples, uint64_t seed,
                        uint32_t flags, float *d_frame, hipStream_t stream) {
     DLensRadiance Q;
@@ -272,13 +388,7 @@ static int lens_launch(hrt_scene *s, const DLens &L, uint32_t w, uint32_t h, uin
                                                  : (lights ? hrt_lens_kernel_lights : hrt_lens_kernel);
     const int rc = query_launch(k, Q, s, HRT_RADIANCE_STAGE_TREE, HRT_RADIANCE_WG, stream);  // the tree from global memory, as hrt_trace_radiance
     if (rc != HRT_OK || !(flags & HRT_FLAG_GAMMA)) return rc;
-    const uint64_t total = (uint64_t)Q.n * 3u, piece = 1ull << 30;
-    for (uint64_t at = 0; at < total; at += piece) {
-        const uint32_t n = (uint32_t)std::min(piece, total - at);
-        hipLaunchKernelGGL(hrt_gamma_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_frame + at, n);
-        HIP_TRY(hipGetLastError());
-    }
-    return HRT_OK;
+    return lens_gamma(d_frame, (uint64_t)Q.n * 3u, stream);
 }
 
 int hrt_render_lens_device(hrt_scene *s, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples, uint64_t seed,
@@ -350,4 +460,180 @@ int hrt_render_lens_features(hrt_scene *s, const hrt_lens *lens, uint32_t w, uin
     hipLaunchKernelGGL(hrt_lens_features_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, R, L, s->bound, n_samples, d_features);
     HIP_TRY(hipGetLastError());
     return HRT_OK;
+}
+
+// ---- Batched lens views (include/hrt.h hrt_render_lens_views*)
+
+// Checks 2..4 of the header's order: an empty batch is the caller's to return on, `views` is there, every lens passes lens_check
+// (the message names the view).  Fills one block per view (all but err_abs, which needs the scene's extent).
+static int lens_views_blocks(const std::string &who, const hrt_lens_view *views, uint32_t n_views, std::vector<DLensView> &blocks) {
+    if (!views) return fail(HRT_ERR_INVALID, who + ": views is NULL");
+    for (uint32_t v = 0; v < n_views; ++v) {
+        const std::string where = who + ": views[" + std::to_string(v) + "].lens";
+        DLensView B;
+        const int lrc = lens_check(where, &views[v].lens, B.lens);
+        if (lrc != HRT_OK) return g_error.compare(0, where.size(), where) == 0 ? lrc : fail(lrc, where + ": " + g_error);  // the camera's own message names neither
+        B.seed_lo = (uint32_t)views[v].seed; B.seed_hi = (uint32_t)(views[v].seed >> 32);
+        B.err_abs = 0.f; B.pad = 0u;
+        blocks.push_back(B);
+    }
+    return HRT_OK;
+}
+
+// Check 9: the items of all views within what one frame may have.
+static int lens_views_limit(const std::string &who, uint32_t n_views, uint32_t w, uint32_t h, uint64_t max_items) {
+    const uint64_t items = (uint64_t)n_views * ((uint64_t)w * h);  // w * h <= max_items < 2^31: no overflow
+    if (items > max_items)
+        return fail(HRT_ERR_INVALID, who + ": n_views * w * h is " + std::to_string(items) + ", above the " + std::to_string(max_items) + " pixels one launch indexes");
+    return HRT_OK;
+}
+
+// The checks hrt_render_lens_views_device and hrt_render_lens_views share, in the header's order (all before the scene).
+static int lens_views_check(const std::string &who, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h, uint32_t first_sample,
+                            uint32_t n_samples, uint32_t flags, const float *out, const char *out_name, std::vector<DLensView> &blocks) {
+    { const int frc = lens_flags_check(who, flags); if (frc != HRT_OK) return frc; }
+    if (n_views == 0u) return HRT_OK;
+    { const int brc = lens_views_blocks(who, views, n_views, blocks); if (brc != HRT_OK) return brc; }
+    { const int frc = check_frame(who, w, h, k_max_pixels); if (frc != HRT_OK) return frc; }
+    { const int src = lens_samples_check(who, first_sample, n_samples, out, out_name); if (src != HRT_OK) return src; }
+    return lens_views_limit(who, n_views, w, h, k_max_pixels);
+}
+
+// Puts the blocks into the scene's table on `stream` (the scene entered) and returns it.  The pinned staging copy is reused by
+// every call: wait until the previous call's upload has read it (that upload sits in front of its kernel, so this does not wait
+// for the kernel).  The table is read by the previous batch's kernel: one on another stream is waited for on `stream`.
+static int lens_views_stage(hrt_scene *s, std::vector<DLensView> &blocks, hipStream_t stream, const DLensView **table) {
+    const size_t n_views = blocks.size(), bytes = n_views * sizeof(DLensView);
+    for (DLensView &B : blocks) {  // fill_render's margin, per view
+        const float *e = B.lens.eye;
+        B.err_abs = margin_scale(s->bound, std::sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]));
+    }
+    if (s->lv_uploading) { HIP_TRY(hipEventSynchronize(s->ev_lv)); s->lv_uploading = false; }
+    if (!s->ev_lv) HIP_TRY(hipEventCreateWithFlags(&s->ev_lv, hipEventDisableTiming));
+    if (!s->ev_lv_done) HIP_TRY(hipEventCreateWithFlags(&s->ev_lv_done, hipEventDisableTiming));
+    if (s->h_lv_cap < n_views) {
+        if (s->h_lv) (void)hipHostFree(s->h_lv);
+        s->h_lv = nullptr; s->h_lv_cap = 0;
+        HIP_TRY(hipHostMalloc((void **)&s->h_lv, bytes, hipHostMallocDefault));
+        s->h_lv_cap = n_views;
+    }
+    std::memcpy(s->h_lv, blocks.data(), bytes);
+    if (s->lv_blocks.cap < bytes && s->lv_used) HIP_TRY(hipEventSynchronize(s->ev_lv_done));  // the old table is freed: its last reader is done
+    { const int grc = s->lv_blocks.grow(bytes); if (grc != HRT_OK) return grc; }
+    if (s->lv_used && s->lv_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->ev_lv_done, 0));
+    HIP_TRY(hipMemcpyAsync(s->lv_blocks.p, s->h_lv, bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(s->ev_lv, stream));
+    s->lv_uploading = true;
+    *table = s->lv_blocks.as<DLensView>();
+    return HRT_OK;
+}
+// After the launch that reads the table.
+static int lens_views_staged(hrt_scene *s, hipStream_t stream) {
+    HIP_TRY(hipEventRecord(s->ev_lv_done, stream));
+    s->lv_used = true;
+    s->lv_stream = stream;
+    return HRT_OK;
+}
+
+// The fused launch over all views into d_frames on `stream` (the scene entered), then the gamma over all frames.
+static int lens_views_launch(hrt_scene *s, std::vector<DLensView> &blocks, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples,
+                             uint32_t flags, float *d_frames, hipStream_t stream) {
+    DLensViewsRadiance Q;
+    { const int src = lens_views_stage(s, blocks, stream, &Q.views); if (src != HRT_OK) return src; }
+    Q.out = d_frames;
+    Q.npix = w * h;
+    Q.n = (uint32_t)blocks.size() * Q.npix;
+    Q.flags = flags & ~(uint32_t)HRT_FLAG_GAMMA;
+    Q.first_sample = first_sample;
+    Q.n_samples = n_samples;
+    Q.w = w;
+    Q.h = h;
+    const bool exact = (flags & HRT_FLAG_EXACT_ONLY) != 0u;
+    const bool lights = s->d.n_lights != 0u;
+    void (*const k)(const DLensViewsRadiance) = exact ? (lights ? hrt_lens_views_kernel_lights_exact : hrt_lens_views_kernel_exact)
+                                                      : (lights ? hrt_lens_views_kernel_lights : hrt_lens_views_kernel);
+    int rc = query_launch(k, Q, s, HRT_RADIANCE_STAGE_TREE, HRT_RADIANCE_WG, stream);  // as lens_launch
+    if (rc == HRT_OK) rc = lens_views_staged(s, stream);
+    if (rc != HRT_OK || !(flags & HRT_FLAG_GAMMA)) return rc;
+    return lens_gamma(d_frames, (uint64_t)Q.n * 3u, stream);
+}
+
+int hrt_render_lens_views_device(hrt_scene *s, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h, uint32_t first_sample,
+                                 uint32_t n_samples, uint32_t flags, float *d_frames, void *stream) {
+    const std::string who = "hrt_render_lens_views_device";
+    std::vector<DLensView> blocks;
+    int rc = lens_views_check(who, views, n_views, w, h, first_sample, n_samples, flags, d_frames, "d_frames", blocks);
+    if (rc != HRT_OK || n_views == 0u) return rc;
+    if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
+    return lens_views_launch(s, blocks, w, h, first_sample, n_samples, flags, d_frames, (hipStream_t)stream);
+}
+
+// Blocking, into host memory.  The device frames and the two events are the call's own, as hrt_render_lens'.
+int hrt_render_lens_views(hrt_scene *s, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h, uint32_t spp, uint32_t flags,
+                          float *out_rgb, hrt_stats *stats) {
+    const std::string who = "hrt_render_lens_views";
+    std::vector<DLensView> blocks;
+    if (flags & HRT_RADIANCE_ACCUMULATE) return fail(HRT_ERR_INVALID, who + ": flags: HRT_RADIANCE_ACCUMULATE needs the running sums on the device (hrt_render_lens_views_device)");
+    int rc = lens_views_check(who, views, n_views, w, h, 0u, spp, flags, out_rgb, "out_rgb", blocks);
+    if (rc != HRT_OK) return rc;
+    if (n_views == 0u) {
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        return HRT_OK;
+    }
+    if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t bytes = (size_t)n_views * w * h * 3u * sizeof(float);
+    float *d_frames = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    float ms = 0.f;
+    auto run = [&]() -> int {
+        HIP_TRY(hipMalloc((void **)&d_frames, bytes));
+        HIP_TRY(hipEventCreate(&ev0));
+        HIP_TRY(hipEventCreate(&ev1));
+        HIP_TRY(hipEventRecord(ev0, nullptr));
+        const int lrc = lens_views_launch(s, blocks, w, h, 0u, spp, flags, d_frames, nullptr);
+        if (lrc != HRT_OK) return lrc;
+        HIP_TRY(hipEventRecord(ev1, nullptr));
+        HIP_TRY(hipMemcpy(out_rgb, d_frames, bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+        return HRT_OK;
+    };
+    rc = run();
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (d_frames) (void)hipFree(d_frames);
+    if (rc != HRT_OK) return rc;
+    if (stats) {
+        fill_stats(s, stats, t0, (double)ms, (uint64_t)n_views * w * h * spp);
+        stats->lds_bytes = 0u;  // the tree is read from global memory
+        stats->waves_launched = 0u;
+    }
+    return HRT_OK;
+}
+
+int hrt_render_lens_views_features(hrt_scene *s, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h, uint32_t first_sample,
+                                   uint32_t n_samples, float *d_features, void *stream) {
+    const std::string who = "hrt_render_lens_views_features";
+    std::vector<DLensView> blocks;
+    if (n_views == 0u) return HRT_OK;
+    int rc = lens_views_blocks(who, views, n_views, blocks);
+    if (rc == HRT_OK) rc = check_frame(who, w, h, k_max_records);
+    if (rc != HRT_OK) return rc;
+    if ((uint64_t)first_sample + n_samples > 0xffffffffull) return fail(HRT_ERR_INVALID, who + ": first_sample + n_samples overflows 32 bits");
+    if (!d_features) return fail(HRT_ERR_INVALID, who + ": d_features is NULL");
+    if ((uintptr_t)d_features % sizeof(float)) return fail(HRT_ERR_INVALID, who + ": d_features is not 4-byte aligned");
+    if ((rc = lens_views_limit(who, n_views, w, h, k_max_records)) != HRT_OK) return rc;
+    if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
+    DRender R;
+    DCamera C;
+    if ((rc = fill_render(s, &views[0].lens.cam, w, h, 1, 0, 0, 0, 1, R, C)) != HRT_OK) return rc;  // seed and margin are each view's own
+    R.cam = nullptr;  // the lenses are in the table
+    R.s0 = first_sample;
+    const DLensView *table = nullptr;
+    if ((rc = lens_views_stage(s, blocks, (hipStream_t)stream, &table)) != HRT_OK) return rc;
+    const uint32_t n_items = n_views * w * h;
+    hipLaunchKernelGGL(hrt_lens_views_features_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, R, table, s->bound, n_items,
+                       n_samples, d_features);
+    HIP_TRY(hipGetLastError());
+    return lens_views_staged(s, (hipStream_t)stream);
 }

@@ -39,8 +39,9 @@ extern "C++" {
 namespace hrtk {
 
 // Where a lane's first segments come from (radiance_body's SRC).  RecordRays: record i of the caller's batch, one ray for all its
-// samples, keyed by Q.keys.  A source with per_sample (LensRays, hrt_lens.hip) makes the ray of every sample itself --
-// SRC::sample(Q, i, sample, ray), false for a sample that is not traced -- and lane i is pixel i with key i.
+// samples, keyed by Q.keys.  A source with per_sample (LensRays, LensViewRays, hrt_lens.hip) makes the ray of every sample itself
+// -- SRC::sample(Q, i, sample, ray), false for a sample that is not traced -- and says how item i's samples are keyed: SRC::key(Q, i)
+// and SRC::seed(Q, i, lo, hi).  LensRays: lane i is pixel i with key i and the launch's seed.
 struct RecordRays {
     static constexpr bool per_sample = false;
 };
@@ -93,7 +94,7 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
         }
         if (live) {
             if constexpr (SRC::per_sample) {
-                key = i;
+                key = SRC::key(Q, i);
             } else {
                 key = Q.keys ? Q.keys[i] : i;
                 query_margin(ray, Q.bound, far, Q.flags, cx.err_abs, first_flags);
@@ -116,7 +117,13 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
                 } else {
                     (void)query_ray(Q, i, ray, tmax);
                 }
-                rng.start(Q.seed_lo, Q.seed_hi, key, Q.first_sample + s);
+                if constexpr (SRC::per_sample) {
+                    uint32_t seed_lo, seed_hi;
+                    SRC::seed(Q, i, seed_lo, seed_hi);
+                    rng.start(seed_lo, seed_hi, key, Q.first_sample + s);
+                } else {
+                    rng.start(Q.seed_lo, Q.seed_hi, key, Q.first_sample + s);
+                }
                 rng.i = 3u;  // draws 0..2 are the camera's u, v, time
                 cx.flags = first_flags;
                 thr = mk(1.f, 1.f, 1.f);

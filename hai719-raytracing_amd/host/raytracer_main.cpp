@@ -25,7 +25,8 @@
 //             [--lens perspective|ortho|equirect|fisheye [--aperture R --focus D] [--lens-extent X]] a lens camera (hrt_render_lens): the
 //                                                  thin lens of radius R focused at depth D (perspective), the view volume's height X
 //                                                  (ortho), a 360 x 180 degree panorama (equirect), X degrees of equidistant fisheye
-//                                                  (one GPU; plain frames only)
+//                                                  (one GPU; plain frames only).  With --views N [--orbit DEGREES]: N lens frames in
+//                                                  ONE launch (hrt_render_lens_views), cameras and seeds and files as --views has them
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -111,19 +112,31 @@ static int ray_trace_frames() {
 }
 
 // --views: N cameras in one launch.  View k has seed + k and the camera turned by k * orbit; frame k goes to NAME_kkk.ppm.
+// With --lens every view is that lens behind its camera (hrt_render_lens_views).
 static int ray_trace_views() {
     const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
     const size_t frame = (size_t)w * h * 3;
     std::vector<float> images(frame * n_views, 0.f);
     const hrt_camera cam0 = default_camera((float)w / (float)h);
-    std::vector<hrt_view> views(n_views);
-    for (uint32_t k = 0; k < n_views; ++k) { views[k].cam = orbited(cam0, orbit_degrees * (double)k); views[k].seed = seed + k; }
+    std::vector<hrt_view> views(use_lens ? 0u : n_views);
+    std::vector<hrt_lens_view> lens_views(use_lens ? n_views : 0u);
+    for (uint32_t k = 0; k < n_views; ++k) {
+        const hrt_camera cam = orbited(cam0, orbit_degrees * (double)k);
+        if (use_lens) { lens_views[k].lens = lens_params; lens_views[k].lens.cam = cam; lens_views[k].seed = seed + k; }
+        else { views[k].cam = cam; views[k].seed = seed + k; }
+    }
+    static const char *const names[] = {"perspective", "orthographic", "equirectangular", "fisheye"};
     std::cout << "Ray tracing " << n_views << " views of " << w << " x " << h << " pixels, " << orbit_degrees << " degrees apart, on the GPU in one launch using "
-              << nsamples << " samples per pixel" << std::endl;
+              << nsamples << " samples per pixel";
+    if (use_lens)
+        std::cout << " through a " << names[lens_params.projection] << " lens (aperture " << lens_params.aperture_radius << ", focus "
+                  << lens_params.focus_distance << ", extent " << lens_params.extent << ")";
+    std::cout << std::endl;
     hrt_stats st;
-    int rc = hrt_render_views(device_scene, views.data(), n_views, w, h, nsamples, HRT_FLAG_GAMMA, images.data(), &st);
+    int rc = use_lens ? hrt_render_lens_views(device_scene, lens_views.data(), n_views, w, h, nsamples, HRT_FLAG_GAMMA, images.data(), &st)
+                      : hrt_render_views(device_scene, views.data(), n_views, w, h, nsamples, HRT_FLAG_GAMMA, images.data(), &st);
     if (rc != HRT_OK) {
-        std::cout << "hrt_render_views failed: " << hrt_last_error() << std::endl;
+        std::cout << (use_lens ? "hrt_render_lens_views" : "hrt_render_views") << " failed: " << hrt_last_error() << std::endl;
         return rc;
     }
     std::cout << "  Done in " << st.total_ms / 1000.0 << " seconds (kernel " << st.kernel_ms << " ms, " << (double)st.samples / st.kernel_ms / 1e3
@@ -277,8 +290,8 @@ int main(int argc, char **argv) {
         std::cerr << "--views renders plain frames on one GPU: it cannot be combined with --adaptive, --denoise, --denoise-var, --temporal or --gpus / --devices" << std::endl;
         return 2;
     }
-    if (use_lens && (adaptive || denoise || denoise_var || temporal || n_views != 0u || !devices.empty())) {
-        std::cerr << "--lens renders plain frames on one GPU: it cannot be combined with --adaptive, --denoise, --denoise-var, --temporal, --views or --gpus / --devices" << std::endl;
+    if (use_lens && (adaptive || denoise || denoise_var || temporal || !devices.empty())) {
+        std::cerr << "--lens renders plain frames on one GPU: it cannot be combined with --adaptive, --denoise, --denoise-var, --temporal or --gpus / --devices" << std::endl;
         return 2;
     }
     if (!use_lens && (lens_params.aperture_radius != 0.f || lens_params.focus_distance != 1.f || lens_params.extent != 0.f)) {
@@ -310,7 +323,7 @@ int main(int argc, char **argv) {
         std::cout << "Image tiles across " << devices.size() << " GPU slot(s), gather: " << hrt_multi_gather(multi)
                   << (note.empty() ? "" : " (" + note + ")") << std::endl;
     }
-    int rc = use_lens ? ray_trace_lens() : n_views ? ray_trace_views() : temporal ? ray_trace_frames() : ray_trace_from_camera();  // the 'r' key, once or frame after frame
+    int rc = n_views ? ray_trace_views() : use_lens ? ray_trace_lens() : temporal ? ray_trace_frames() : ray_trace_from_camera();  // the 'r' key, once or frame after frame
     hrt_scene_destroy(device_scene);
     hrt_multi_destroy(multi);
     hrt_shutdown();

@@ -740,8 +740,9 @@ HRT_API int hrt_render_views(hrt_scene *scene, const hrt_view *views, uint32_t n
  * miss.  With PERSPECTIVE and aperture 0 it equals hrt_render_features bit for bit; with any other lens its hits are those of
  * hrt_trace_rays(HRT_QUERY_SHADE) on the records of hrt_lens_rays.  Asynchronous on `stream`; the lens travels as a kernel argument,
  * so unlike hrt_render_features the call takes no part in the ordering of the scene's feature launches.
- * Not lens-aware (DESIGN.md section 5 "Lens cameras"): the streaming kernel, hrt_render_views, the adaptive sampler, temporal
- * reprojection, the multi-GPU paths. */
+ * Not lens-aware (DESIGN.md section 5 "Lens cameras"): the streaming kernel, the adaptive sampler, temporal reprojection, the
+ * multi-GPU paths.  Many lens frames in one launch are hrt_render_lens_views below: a batch through the lens kernels, not through
+ * hrt_render_views, which stays a batch of pinhole cameras. */
 enum { HRT_LENS_PERSPECTIVE = 0, HRT_LENS_ORTHOGRAPHIC = 1, HRT_LENS_EQUIRECT = 2, HRT_LENS_FISHEYE = 3 };
 #define HRT_LENS_DRAW 0x80000000u   /* draw index of the first of the two lens draws */
 typedef struct hrt_lens {
@@ -758,6 +759,44 @@ HRT_API int hrt_render_lens(hrt_scene *scene, const hrt_lens *lens, uint32_t w, 
                             float *out_rgb, hrt_stats *stats /* may be NULL */);
 HRT_API int hrt_render_lens_features(hrt_scene *scene, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples,
                                      uint64_t seed, float *d_features, void *stream);
+
+/* ---- Batched lens views: many lens cameras of one scene, every one a w x h frame, in ONE launch of the fused lens kernel.
+ * The N views make one dense index space of n_views * w * h items; item i is pixel i % (w*h) of view i / (w*h), one lane per item
+ * in the grid-stride loop of hrt_render_lens_device, so small frames (light-probe grids, skybox faces, light fields), which do not
+ * fill the device one at a time, do so together.  A sample is keyed (seed of its view, pixel y*w + x inside its view, sample) --
+ * neither by the item nor by a launch-wide seed -- and every view may differ in everything: projection, aperture, camera, seed.
+ * CONTRACT: frame v is bit-identical to hrt_render_lens_device(scene, &views[v].lens, w, h, first_sample, n_samples, views[v].seed,
+ * flags), for every scene, every mix of projections in one batch, every n_views and every permitted flag set.  By the lens
+ * contracts it therefore equals hrt_lens_rays + hrt_trace_radiance per sample, and for pinhole views frame v of hrt_render_views.
+ * hrt_render_lens_views_device: d_frames (device) receives n_views * h * w * 3 floats, view-major, each view row-major as
+ * hrt_render_lens_device's: the means over samples [first_sample, first_sample + n_samples), or with HRT_RADIANCE_ACCUMULATE the
+ * running sums, exactly as there.  Asynchronous on `stream`.  FLAGS: those of hrt_render_lens_device, refused by the same names and
+ * texts; HRT_FLAG_GAMMA is applied in place over all frames and refused together with HRT_RADIANCE_ACCUMULATE.
+ * hrt_render_lens_views: the same into a HOST buffer, blocking, samples [0, spp); stats as hrt_render_lens (samples = n_views * w *
+ * h * spp; n_views == 0 zeroes them).  HRT_RADIANCE_ACCUMULATE is refused (the sums live on the device).
+ * hrt_render_lens_views_features: block v of d_features (n_views * h * w * HRT_FEATURE_FLOATS floats, view-major) is bit-identical
+ * to hrt_render_lens_features of views[v].lens with seed views[v].seed; n_samples == 0 is the pixel centres, as there.
+ * CONCURRENCY: the per-view table (n_views lens blocks do not fit a kernel argument) is scratch of the scene: a grow-only device
+ * buffer and a pinned staging copy, so `views` may be freed when a call returns.  A call waits on the host until the previous
+ * call's upload has read the staging copy (not for its kernel), and batched lens launches of one scene on different streams are
+ * ordered against each other, because they share the table.  Nothing of the trace launches' state (work-queue head, path pool,
+ * camera blocks) is touched: a batch may overlap a render of the same scene on another stream, as single lens frames do.
+ * LIMIT: n_views * w * h <= 2^31 - 1, the pixel limit of one lens frame (2^31 / 16 for the features, as hrt_render_lens_features).
+ * Checked in this order before the scene and the library state, HRT_ERR_INVALID with hrt_last_error() naming the entry point and
+ * the culprit: flags (the two frame forms); (n_views == 0 returns HRT_OK here and launches nothing;) views NULL; every lens as
+ * hrt_lens_rays checks it, the message prefixed "views[<index>].lens"; the frame; n_samples == 0 (the two frame forms);
+ * first_sample + n_samples > 2^32 (the features: > 2^32 - 1, as hrt_render_lens_features); the output pointer NULL or not 4-byte
+ * aligned; the limit above; then a NULL scene. */
+typedef struct hrt_lens_view {
+    hrt_lens lens;
+    uint64_t seed;
+} hrt_lens_view;
+HRT_API int hrt_render_lens_views_device(hrt_scene *scene, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h,
+                                         uint32_t first_sample, uint32_t n_samples, uint32_t flags, float *d_frames, void *stream);
+HRT_API int hrt_render_lens_views(hrt_scene *scene, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h,
+                                  uint32_t spp, uint32_t flags, float *out_rgb, hrt_stats *stats /* may be NULL */);
+HRT_API int hrt_render_lens_views_features(hrt_scene *scene, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h,
+                                           uint32_t first_sample, uint32_t n_samples, float *d_features, void *stream);
 
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
