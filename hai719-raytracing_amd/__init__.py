@@ -317,6 +317,10 @@ def device_lib() -> C.CDLL:
                                                C.c_uint32, C.c_void_p, C.c_void_p]
         lib.hrt_render_lens.argtypes = [C.c_void_p, C.POINTER(Lens), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
                                         C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_render_lens_adaptive_device.argtypes = [C.c_void_p, C.POINTER(Lens), C.c_uint32, C.c_uint32, C.POINTER(Adaptive), C.c_uint64,
+                                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.hrt_render_lens_adaptive.argtypes = [C.c_void_p, C.POINTER(Lens), C.c_uint32, C.c_uint32, C.POINTER(Adaptive), C.c_uint64,
+                                                 C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         lib.hrt_render_lens_features.argtypes = [C.c_void_p, C.POINTER(Lens), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                                  C.c_void_p, C.c_void_p]
         lib.hrt_render_lens_views_device.argtypes = [C.c_void_p, C.POINTER(LensView), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -756,6 +760,36 @@ class DeviceScene:
             out[...] = r
             return out
         return r
+
+    def render_lens_adaptive(self, lens: Lens, w: int, h: int, min_spp: int, max_spp: int, threshold: float, seed: int = 1,
+                             flags: int = 0, out=None, stats: Optional[Stats] = None):
+        """hrt_render_lens_adaptive*: ``render_adaptive`` through ``lens`` -> (frame (h, w, 3) float32, tile_spp (tiles_y, tiles_x)
+        uint32).  Every tile of the frame is bit-identical to the same tile of ``render_lens`` at that tile's count; with a pinhole
+        lens, frame and counts are ``render_adaptive``'s.  With ``out`` a contiguous (h, w, 3) float32 torch tensor on the GPU the
+        call runs on the current torch stream of its device (hrt_render_lens_adaptive_device; the stream is synchronised once per
+        round) and returns ``out`` and the counts as an int32 device tensor.  Otherwise both come back as NumPy and the call blocks;
+        ``stats``: a Stats to fill, if wanted (the blocking form only).  ``flags``: FLAG_EXACT_ONLY, FLAG_MESH_BRUTE, FLAG_NO_LDS_TREE,
+        FLAG_GAMMA."""
+        p = Adaptive(min_spp, max_spp, threshold)
+        ty, tx = (h + TILE - 1) // TILE, (w + TILE - 1) // TILE
+        if out is not None:
+            import torch
+            if (not isinstance(out, torch.Tensor) or out.device.type != "cuda" or out.dtype != torch.float32
+                    or tuple(out.shape) != (h, w, 3) or not out.is_contiguous()):
+                raise ValueError(f"render_lens_adaptive: out must be a contiguous ({h}, {w}, 3) float32 tensor on the GPU")
+            if stats is not None:
+                raise ValueError("render_lens_adaptive: stats are the blocking form's (no `out`)")
+            s = torch.cuda.current_stream(out.device)
+            counts = torch.empty((ty, tx), dtype=torch.int32, device=out.device)
+            self._check(self._lib.hrt_render_lens_adaptive_device(self._h, C.byref(lens), w, h, C.byref(p), seed, int(flags),
+                                                                  C.c_void_p(out.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                                                  C.c_void_p(s.cuda_stream)))
+            return out, counts
+        frame = np.empty((h, w, 3), dtype=np.float32)
+        spp = np.empty((ty, tx), dtype=np.uint32)
+        self._check(self._lib.hrt_render_lens_adaptive(self._h, C.byref(lens), w, h, C.byref(p), seed, int(flags), frame.ctypes.data,
+                                                       spp.ctypes.data, None if stats is None else C.byref(stats)))
+        return frame, spp
 
     def render_lens_features(self, lens: Lens, w: int, h: int, first_sample: int, n_samples: int, seed: int = 1) -> np.ndarray:
         """hrt_render_lens_features: ``render_features`` through ``lens`` -> (h, w, FEATURE_FLOATS) float32.  The device buffer is a

@@ -106,14 +106,19 @@ extern "C" __global__ void __launch_bounds__(HRT_AD_WG) hrt_ad_finalize_kernel(c
     }
 }
 
-// Checked BEFORE the scene and the library state, so that a machine without a GPU can test it.
-static int adaptive_check(const char *who, const hrt_adaptive *p, const hrt_camera *cam) {
-    const std::string w = who;
+// Checked BEFORE the scene and the library state, so that a machine without a GPU can test it.  The parameters alone (also
+// hrt_render_lens_adaptive*'s, hrt_lens_adaptive.hip), then with the camera.
+static int adaptive_params_check(const std::string &w, const hrt_adaptive *p) {
     if (!p) return fail(HRT_ERR_INVALID, w + ": params is NULL");
     if (p->min_spp < 2u || (p->min_spp & 1u)) return fail(HRT_ERR_INVALID, w + ": min_spp must be even and at least 2 (got " + std::to_string(p->min_spp) + ")");
     if (p->max_spp < p->min_spp) return fail(HRT_ERR_INVALID, w + ": max_spp must be at least min_spp (got " + std::to_string(p->max_spp) + " < " + std::to_string(p->min_spp) + ")");
     if (std::isnan(p->threshold) || p->threshold < 0.f) return fail(HRT_ERR_INVALID, w + ": threshold must be a non-negative number (+inf allowed)");
-    if (!cam) return fail(HRT_ERR_INVALID, w + ": camera is NULL");
+    return HRT_OK;
+}
+static int adaptive_check(const char *who, const hrt_adaptive *p, const hrt_camera *cam) {
+    const int rc = adaptive_params_check(who, p);
+    if (rc != HRT_OK) return rc;
+    if (!cam) return fail(HRT_ERR_INVALID, std::string(who) + ": camera is NULL");
     return HRT_OK;
 }
 

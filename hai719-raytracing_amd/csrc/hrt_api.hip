@@ -285,6 +285,13 @@ struct hrt_scene {
     hipEvent_t ev_lv = nullptr, ev_lv_done = nullptr;
     bool lv_uploading = false, lv_used = false;
     hipStream_t lv_stream = nullptr;
+    // Adaptive lens frames (hrt_lens_adaptive.hip): the tile-major sums of the whole frame, the host form's row-major frame, and the
+    // event and stream of the assemble launch that read the sums last.  The rounds' lists and keep words are ad_compact / ad_words,
+    // shared with hrt_render_adaptive.  Nothing of the trace launches.
+    Scratch la_tiles, la_frame;
+    hipEvent_t ev_la_done = nullptr;
+    bool la_used = false;
+    hipStream_t la_stream = nullptr;
 };
 
 namespace {
@@ -394,6 +401,8 @@ void hrt_scene_destroy(hrt_scene *s) {
     if (s->h_lv) (void)hipHostFree(s->h_lv);
     if (s->ev_lv) (void)hipEventDestroy(s->ev_lv);
     if (s->ev_lv_done) (void)hipEventDestroy(s->ev_lv_done);
+    for (Scratch *b : {&s->la_tiles, &s->la_frame}) b->release();
+    if (s->ev_la_done) (void)hipEventDestroy(s->ev_la_done);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     delete s;
@@ -1011,6 +1020,7 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 #include "hrt_rays.hip"
 #include "hrt_radiance.hip"
 #include "hrt_lens.hip"
+#include "hrt_lens_adaptive.hip"
 #include "hrt_views.hip"
 
 int hrt_kd_build_gpu(const hrt_kd_build_input *in, hrt_kd_build_output *out, void *user) {

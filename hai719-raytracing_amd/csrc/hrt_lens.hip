@@ -17,6 +17,11 @@
 // features_body over the same items.  The table is the scene's (a grow-only buffer with a pinned staging copy, as hrt_views.hip keeps
 // its view blocks); nothing of the trace launches' state is touched.
 //
+// Adaptive lens frames (hrt_render_lens_adaptive*, the rounds are in hrt_lens_adaptive.hip): the lens kernel over a LIST OF TILES.  The
+// hrt_lens_tiles_kernel builds are radiance_body with the LensTileRays source over n_active * 64 items, item i being lane i & 63 of
+// active tile i >> 6 -- the tile-major layout the adaptive rounds' judge reads, so the launch adds its samples straight onto the
+// compact sums buffer (HRT_RADIANCE_ACCUMULATE), with no scatter.  An item outside the image makes no traced sample.
+//
 // All of it is fp32 without fused multiply-add (the library is built with -ffp-contract=off), in the order the header writes.
 
 // hrt_lens -> what lens_sample reads.  R, U, F, E are the camera's vectors as the caller gave them; `cam` is camera_ray's block.
@@ -69,6 +74,22 @@ struct DLensViewsRadiance {
     float bound;
     uint32_t w, h, npix;   // npix = w * h
     const DLensView *views;
+};
+
+// The launch record of the hrt_lens_tiles_kernel builds: DLensRadiance over a list of 8 x 8 tiles.  out + 3 * i is the compact
+// tile-major sums buffer of the adaptive rounds (hrt_adaptive.hip): 64 items per active tile, item lane = (y & 7) * 8 + (x & 7).
+struct DLensTilesRadiance {
+    const DScene *scene;
+    float *out;            // 3 floats per item: 64 items per active tile, in list order
+    uint32_t n;            // n_active * 64
+    uint32_t flags;
+    uint32_t first_sample, n_samples;
+    uint32_t seed_lo, seed_hi;
+    uint32_t lds_units;
+    float bound;
+    uint32_t w, h, tiles_x;
+    const uint32_t *list;  // the active tiles, n_active of them (NULL: tile k is k, every tile of the frame)
+    DLens lens;
 };
 
 extern "C++" {
@@ -182,6 +203,36 @@ struct LensViewRays {
     }
 };
 
+// radiance_body's source for a list of tiles of one lens frame: item i is lane i & 63 of active tile k = i >> 6, whose tile is
+// list[k] (k itself without a list); the lane's pixel is x = (tile % tiles_x) * 8 + (lane & 7), y = (tile / tiles_x) * 8 + (lane >> 3)
+// -- hrt_ad_judge_kernel's layout for rank 0 of world 1 -- keyed y * w + x with the launch's seed, so a sample is LensRays' sample of
+// that pixel bit for bit.  An item outside the image makes no traced sample: under HRT_RADIANCE_ACCUMULATE, which every such
+// launch passes, its three floats are read and written back as they were.  i < Q.n = n_active * 64, so k is inside the list.
+// The workgroup is 256 lanes and the stride a multiple of 64, so the lanes of a wave walk the same tiles; but a lane takes its
+// next item the moment its own is done (radiance_body), so at any one time they may stand at different tiles: the slot is
+// loaded by the lane that needs it (4 bytes, shared by the tile's 64 lanes in the cache) and never broadcast.
+struct LensTileRays {
+    static constexpr bool per_sample = true;
+    // The pixel of item i; false outside the image.
+    __device__ static __forceinline__ bool pixel(const DLensTilesRadiance &Q, uint32_t i, uint32_t &p) {
+        const uint32_t k = i >> 6, lane = i & 63u;
+        const uint32_t tile = Q.list ? Q.list[k] : k;
+        const uint32_t x = (tile % Q.tiles_x) * 8u + (lane & 7u), y = (tile / Q.tiles_x) * 8u + (lane >> 3);
+        p = y * Q.w + x;
+        return x < Q.w && y < Q.h;
+    }
+    __device__ static __forceinline__ uint32_t key(const DLensTilesRadiance &Q, uint32_t i) {
+        uint32_t p;
+        (void)pixel(Q, i, p);
+        return p;
+    }
+    __device__ static __forceinline__ void seed(const DLensTilesRadiance &Q, uint32_t, uint32_t &lo, uint32_t &hi) { lo = Q.seed_lo; hi = Q.seed_hi; }
+    __device__ static __forceinline__ bool sample(const DLensTilesRadiance &Q, uint32_t i, uint32_t sample, Ray &ray) {
+        uint32_t p;
+        return pixel(Q, i, p) && lens_sample(Q.lens, Q.seed_lo, Q.seed_hi, Q.w, Q.h, p, sample, ray) && lens_traced(ray);
+    }
+};
+
 // features_body's source for a lens.  A pinhole keeps the render's margin (R.err_abs, R.flags), so that its features are
 // hrt_render_features' bit for bit; every other lens moves the origin or the direction per sample and takes the margin and the
 // far-origin rule of that sample's ray, as hrt_trace_rays does for the same record.
@@ -263,6 +314,12 @@ extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_W
 extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_lens_views_kernel_lights(const DLensViewsRadiance Q) { radiance_body<true, false, LensViewRays>(Q); }
 extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_lens_views_kernel_exact(const DLensViewsRadiance Q) { radiance_body<false, true, LensViewRays>(Q); }
 extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_lens_views_kernel_lights_exact(const DLensViewsRadiance Q) { radiance_body<true, true, LensViewRays>(Q); }
+
+// The fused frame over a list of tiles: radiance_body over the 64 items of every active tile.  Launch bounds and shape are hrt_lens_kernel's.
+extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_lens_tiles_kernel(const DLensTilesRadiance Q) { radiance_body<false, false, LensTileRays>(Q); }
+extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_lens_tiles_kernel_lights(const DLensTilesRadiance Q) { radiance_body<true, false, LensTileRays>(Q); }
+extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_lens_tiles_kernel_exact(const DLensTilesRadiance Q) { radiance_body<false, true, LensTileRays>(Q); }
+extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_lens_tiles_kernel_lights_exact(const DLensTilesRadiance Q) { radiance_body<true, true, LensTileRays>(Q); }
 
 // hrt_render_lens_features: hrt_features_kernel with the lens as a kernel argument in place of the scene's camera block.
 extern "C" __global__ void __launch_bounds__(256) hrt_lens_features_kernel(const DRender R, const DLens L, float bound, uint32_t n,

@@ -39,9 +39,10 @@ extern "C++" {
 namespace hrtk {
 
 // Where a lane's first segments come from (radiance_body's SRC).  RecordRays: record i of the caller's batch, one ray for all its
-// samples, keyed by Q.keys.  A source with per_sample (LensRays, LensViewRays, hrt_lens.hip) makes the ray of every sample itself
+// samples, keyed by Q.keys.  A source with per_sample (LensRays, LensViewRays, LensTileRays, hrt_lens.hip) makes the ray of every sample itself
 // -- SRC::sample(Q, i, sample, ray), false for a sample that is not traced -- and says how item i's samples are keyed: SRC::key(Q, i)
-// and SRC::seed(Q, i, lo, hi).  LensRays: lane i is pixel i with key i and the launch's seed.
+// and SRC::seed(Q, i, lo, hi).  LensRays: lane i is pixel i with key i and the launch's seed.  LensTileRays: item i is a lane of
+// a listed 8 x 8 tile, keyed by that lane's pixel.
 struct RecordRays {
     static constexpr bool per_sample = false;
 };

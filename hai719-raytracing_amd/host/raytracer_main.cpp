@@ -25,8 +25,10 @@
 //             [--lens perspective|ortho|equirect|fisheye [--aperture R --focus D] [--lens-extent X]] a lens camera (hrt_render_lens): the
 //                                                  thin lens of radius R focused at depth D (perspective), the view volume's height X
 //                                                  (ortho), a 360 x 180 degree panorama (equirect), X degrees of equidistant fisheye
-//                                                  (one GPU; plain frames only).  With --views N [--orbit DEGREES]: N lens frames in
-//                                                  ONE launch (hrt_render_lens_views), cameras and seeds and files as --views has them
+//                                                  (one GPU; no --denoise, --denoise-var, --temporal, --gpus).  With --adaptive
+//                                                  THRESHOLD [--spp-min N]: per-tile counts under the lens (hrt_render_lens_adaptive).
+//                                                  With --views N [--orbit DEGREES]: N lens frames in ONE launch
+//                                                  (hrt_render_lens_views), cameras and seeds and files as --views has them
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -153,7 +155,7 @@ static int ray_trace_views() {
     return rc;
 }
 
-// --lens: one frame through a lens camera
+// --lens: one frame through a lens camera; with --adaptive, per-tile sample counts from --spp-min up to --spp
 static int ray_trace_lens() {
     const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
     std::vector<float> image((size_t)w * h * 3, 0.f);
@@ -161,15 +163,21 @@ static int ray_trace_lens() {
     static const char *const names[] = {"perspective", "orthographic", "equirectangular", "fisheye"};
     std::cout << "Ray tracing a " << w << " x " << h << " image on the GPU using " << nsamples << " samples per pixel through a "
               << names[lens_params.projection] << " lens (aperture " << lens_params.aperture_radius << ", focus " << lens_params.focus_distance
-              << ", extent " << lens_params.extent << ")" << std::endl;
+              << ", extent " << lens_params.extent << ")";
+    if (adaptive) std::cout << " (adaptive from " << adaptive_params.min_spp << " samples per pixel, threshold " << adaptive_params.threshold << ")";
+    std::cout << std::endl;
     hrt_stats st;
-    int rc = hrt_render_lens(device_scene, &lens_params, w, h, nsamples, seed, HRT_FLAG_GAMMA, image.data(), &st);
+    adaptive_params.max_spp = nsamples;
+    int rc = adaptive ? hrt_render_lens_adaptive(device_scene, &lens_params, w, h, &adaptive_params, seed, HRT_FLAG_GAMMA, image.data(), nullptr, &st)
+                      : hrt_render_lens(device_scene, &lens_params, w, h, nsamples, seed, HRT_FLAG_GAMMA, image.data(), &st);
     if (rc != HRT_OK) {
-        std::cout << "hrt_render_lens failed: " << hrt_last_error() << std::endl;
+        std::cout << (adaptive ? "hrt_render_lens_adaptive" : "hrt_render_lens") << " failed: " << hrt_last_error() << std::endl;
         return rc;
     }
     std::cout << "  Done in " << st.total_ms / 1000.0 << " seconds (kernel " << st.kernel_ms << " ms, " << (double)st.samples / st.kernel_ms / 1e3
-              << " Msamples/s)" << std::endl;
+              << " Msamples/s";
+    if (adaptive) std::cout << ", mean " << (double)st.samples / ((double)w * h) << " spp";
+    std::cout << ")" << std::endl;
     rc = hrt_write_ppm(out_path.c_str(), image.data(), w, h);
     if (rc != HRT_OK) std::cout << hrt_last_error() << std::endl;
     return rc;
@@ -290,8 +298,8 @@ int main(int argc, char **argv) {
         std::cerr << "--views renders plain frames on one GPU: it cannot be combined with --adaptive, --denoise, --denoise-var, --temporal or --gpus / --devices" << std::endl;
         return 2;
     }
-    if (use_lens && (adaptive || denoise || denoise_var || temporal || !devices.empty())) {
-        std::cerr << "--lens renders plain frames on one GPU: it cannot be combined with --adaptive, --denoise, --denoise-var, --temporal or --gpus / --devices" << std::endl;
+    if (use_lens && (denoise || denoise_var || temporal || !devices.empty())) {
+        std::cerr << "--lens renders plain or adaptive frames on one GPU: it cannot be combined with --denoise, --denoise-var, --temporal or --gpus / --devices" << std::endl;
         return 2;
     }
     if (!use_lens && (lens_params.aperture_radius != 0.f || lens_params.focus_distance != 1.f || lens_params.extent != 0.f)) {

@@ -740,8 +740,8 @@ HRT_API int hrt_render_views(hrt_scene *scene, const hrt_view *views, uint32_t n
  * miss.  With PERSPECTIVE and aperture 0 it equals hrt_render_features bit for bit; with any other lens its hits are those of
  * hrt_trace_rays(HRT_QUERY_SHADE) on the records of hrt_lens_rays.  Asynchronous on `stream`; the lens travels as a kernel argument,
  * so unlike hrt_render_features the call takes no part in the ordering of the scene's feature launches.
- * Not lens-aware (DESIGN.md section 5 "Lens cameras"): the streaming kernel, the adaptive sampler, temporal reprojection, the
- * multi-GPU paths.  Many lens frames in one launch are hrt_render_lens_views below: a batch through the lens kernels, not through
+ * Not lens-aware (DESIGN.md section 5 "Lens cameras"): the streaming kernel, temporal reprojection, the multi-GPU paths.  Adaptive
+ * sampling under a lens is hrt_render_lens_adaptive further below.  Many lens frames in one launch are hrt_render_lens_views below: a batch through the lens kernels, not through
  * hrt_render_views, which stays a batch of pinhole cameras. */
 enum { HRT_LENS_PERSPECTIVE = 0, HRT_LENS_ORTHOGRAPHIC = 1, HRT_LENS_EQUIRECT = 2, HRT_LENS_FISHEYE = 3 };
 #define HRT_LENS_DRAW 0x80000000u   /* draw index of the first of the two lens draws */
@@ -797,6 +797,45 @@ HRT_API int hrt_render_lens_views(hrt_scene *scene, const hrt_lens_view *views, 
                                   uint32_t spp, uint32_t flags, float *out_rgb, hrt_stats *stats /* may be NULL */);
 HRT_API int hrt_render_lens_views_features(hrt_scene *scene, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h,
                                            uint32_t first_sample, uint32_t n_samples, float *d_features, void *stream);
+
+/* ---- Adaptive lens frames: the per-tile sample counts of hrt_render_adaptive under any lens.
+ * The rounds, the estimate and the counts are EXACTLY the rule stated at hrt_render_adaptive above, with the sums of
+ * hrt_render_lens in place of hrt_render's: round 0 adds samples [0, min_spp/2) to every HRT_TILE x HRT_TILE tile, round 1 adds
+ * [min_spp/2, min_spp) and judges every tile, every later round adds min(n, max_spp - n) samples to the tiles still active and judges
+ * them, until none is active.  Every round is one launch of the fused lens kernel over the list of active tiles (one lane per
+ * pixel of a listed tile, the lens a kernel argument), adding its samples in sample order onto the stored sums.  A DEGENERATE sample
+ * (see THE RULE above) adds nothing and counts in the divisor; a tile whose samples are all degenerate -- a tile of a fisheye frame
+ * wholly outside the image circle -- has tile_err 0, stops at min_spp and is all zeros.
+ * CONTRACT A: every tile of the result is bit-identical to the same tile of hrt_render_lens(lens, w, h, count of that tile, seed,
+ * flags), for every projection and every permitted flag set, HRT_FLAG_GAMMA included.
+ * CONTRACT B: with HRT_LENS_PERSPECTIVE and aperture_radius == 0, frame and counts equal those of hrt_render_adaptive(&lens->cam, ...)
+ * with the same parameters, seed and gamma flag, under every kernel form of that call.
+ * hrt_render_lens_adaptive_device: d_frame (device, h*w*3 floats, ROW-MAJOR) receives the means (gamma-corrected with
+ * HRT_FLAG_GAMMA), d_tile_spp (device, may be NULL) tiles_y * tiles_x uint32 counts, row-major.  Runs on `stream` (a hipStream_t,
+ * NULL = the default stream) and synchronises it once per round from round 1 on, as hrt_render_adaptive_tiles does: one 4-byte
+ * read-back (how many tiles are still active) sizes the next launch.  Every lens launch is checked for a HIP error when it is made;
+ * a fault while a round runs ends the call with HRT_ERR_DEVICE at that round's synchronisation.
+ * hrt_render_lens_adaptive: the same into HOST buffers out_rgb[h*w*3] and out_tile_spp (may be NULL), blocking.  stats (may be NULL):
+ * kernel_ms = the lens kernels' time summed over all rounds (HIP events), samples = sum over in-image pixels of their tile's count
+ * (degenerate samples count), as hrt_render_adaptive.
+ * FLAGS: HRT_FLAG_EXACT_ONLY, HRT_FLAG_MESH_BRUTE (with EXACT_ONLY), HRT_FLAG_NO_LDS_TREE, HRT_FLAG_GAMMA.  HRT_RADIANCE_ACCUMULATE
+ * (the rounds keep the running sums themselves) and every other bit are refused by name, with hrt_render_lens_device's texts.
+ * Checked in this order before the scene and the library state, HRT_ERR_INVALID with hrt_last_error() naming the entry point and
+ * the culprit: flags; params, as hrt_render_adaptive checks them; the lens, as hrt_lens_rays checks it; the frame; LIMIT:
+ * hrt_tiles_total(w, h) * 64 <= 2^31 - 1 (one launch indexes 64 items per tile); d_frame / out_rgb NULL or not 4-byte aligned,
+ * d_tile_spp / out_tile_spp not 4-byte aligned; then a NULL scene.
+ * CONCURRENCY: the tile-major sums of the frame are a grow-only buffer of the scene's own; the tile lists and keep words are the
+ * round scratch hrt_render_adaptive uses.  Nothing of the trace launches' state (work-queue head, path pool, camera blocks) is
+ * touched: the call may overlap a plain render or a query of the same scene on another stream.  It may NOT overlap another
+ * adaptive call of the same scene, lens or pinhole, because they share the round scratch.
+ * OUT OF SCOPE: batched views (hrt_render_lens_views stays uniform), rank / world partitions (one device renders the whole
+ * frame), the streaming kernel, and denoising of adaptive frames. */
+HRT_API int hrt_render_lens_adaptive_device(hrt_scene *scene, const hrt_lens *lens, uint32_t w, uint32_t h, const hrt_adaptive *params,
+                                            uint64_t seed, uint32_t flags, float *d_frame, uint32_t *d_tile_spp /* may be NULL */,
+                                            void *stream);
+HRT_API int hrt_render_lens_adaptive(hrt_scene *scene, const hrt_lens *lens, uint32_t w, uint32_t h, const hrt_adaptive *params,
+                                     uint64_t seed, uint32_t flags, float *out_rgb, uint32_t *out_tile_spp /* may be NULL */,
+                                     hrt_stats *stats /* may be NULL */);
 
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
