@@ -587,7 +587,8 @@ static int size_stream(hrt_scene *s, const KernelBuild &b, DRender &R, uint32_t 
         R.sp_band_log2 = band;
     }
     int rc = s->sp_scratch.grow((size_t)grid * HRT_SP_UNITS * HRT_SP_UNIT * 3u * sizeof(float));  // HRT_SP_UNITS units in flight per workgroup
-    if (rc == HRT_OK) rc = s->sp_pool.grow((size_t)grid * SP_FIELDS * HRT_SP_POOL * sizeof(uint32_t));
+    // per workgroup the slot records, then the hit records that mirror its hit queues (1 MB, of which only [0, fill) of a queue is ever touched)
+    if (rc == HRT_OK) rc = s->sp_pool.grow((size_t)grid * SP_WG_DWORDS * sizeof(uint32_t));
     if (rc != HRT_OK) return rc;
     R.sp_scratch = s->sp_scratch.as<float>();
     R.sp_pool = s->sp_pool.as<uint32_t>();

@@ -6,7 +6,9 @@
 // lanes of a wave want different things (new camera ray / mesh walk / shade a sphere, a square, a triangle).
 // Here the divergent rays are COMPACTED.  A 1024-thread workgroup (one per CU) keeps a pool of HRT_SP_POOL
 // paths as 128-byte records in global memory (sized to stay in the Infinity Cache; a hit visit's state is one 64-byte half
-// of a record, see sp_ld4) and queues of 16-bit slot ids in LDS.  One cycle runs 64-entry chunks of
+// of a record, see sp_ld4) and queues of 16-bit slot ids in LDS.  A path that goes from one hit visit to the next carries that
+// half with its QUEUE POSITION instead (the hit-record array, sp_hr_at), so a chunk's records are contiguous.  One cycle runs
+// 64-entry chunks of
 //     G   free slot          -> camera ray (main.cpp:188-192), spheres + squares, mesh box gates
 //     T   ray + best hit     -> up to HRT_SP_TRIPS trips of the rope KD walk; an unfinished walk keeps its state
 //                               in the record and comes back next cycle, so T chunks stay full
@@ -134,7 +136,9 @@ struct SpCtl {           // control block of ONE stream in LDS (28 dwords)
     uint32_t done, parity;
     uint32_t arrive;         // waves that have finished their part of a cycle of this stream, ever (monotonic)
     uint32_t ready;          // number of the cycle whose control values above are valid (monotonic; waves wait for it)
-    uint32_t pad[2];
+    uint32_t tails;          // deferred entries of the four hit queues (6 bits each, kind 0 lowest) whose travelling records this
+                             // cycle copies from the input arrays to the front of the output arrays (see the C chunks)
+    uint32_t pad;
 };
 struct SpUnit {          // a WORK UNIT in flight: G tiles x 64 pixels x the samples of one fold (8 dwords); a workgroup keeps two
     uint32_t state;          // SP_U_*
@@ -163,9 +167,12 @@ static_assert(HRT_SP_QCAP >= 512, "deferring partial chunks needs a queue that c
 
 static_assert((HRT_SP_POOL & (HRT_SP_POOL - 1)) == 0 && HRT_SP_POOL <= 65536, "slot ids are 16-bit and masked with HRT_SP_POOL - 1");
 static_assert(HRT_SP_NQ * HRT_SP_POOL * 2 + HRT_SP_MAXG * 8 + 512 <= 160 * 1024, "the queues do not fit the CU's 160 KB of LDS");
+static_assert(HRT_SP_POOL <= 32768, "a hit-queue entry keeps SP_POSITIONAL in bit 15, above the slot id");
+static_assert(HRT_SP_QCAP % 64 == 0, "a chunk's 64 queue positions are one block of the hit-record array, from either end");
 
 struct SpLds {
-    uint32_t *st;        // the workgroup's path records in global memory: HRT_SP_POOL x SP_FIELDS dwords
+    uint32_t *st;        // the workgroup's path records in global memory: HRT_SP_POOL x SP_FIELDS dwords, then its hit-record arrays
+    uint32_t hr;         // where the hit-record array of the stream in hand begins, in dwords from st (SP_HR_STREAM dwords, sp_hr_at)
     uint16_t *q;         // HRT_SP_NQ queues x HRT_SP_QCAP entries of the stream in hand (streams follow each other)
     SpCtl *ctl;          // HRT_SP_STREAMS control blocks, then SpShared, the two SpUnit, 2 x HRT_SP_MAXG packed tile origins
 };
@@ -194,6 +201,37 @@ __device__ __forceinline__ void sp_st4(const SpLds &L, int g, uint32_t slot, uin
     *((v4u __attribute__((address_space(1))) *)(L.st + SP_AT(4 * g, slot))) = w;
 }
 #define SP_PIN1(g) "+v"(g.x), "+v"(g.y), "+v"(g.z), "+v"(g.w)
+// TRAVELLING HIT RECORDS.  A path that a G chunk or a hit visit sends to a hit queue does not leave g0-g3 in its slot: they go
+// into the hit-record array at the position the path takes in that queue -- one entry per (stream, parity, hit buffer A or B,
+// position), the indices of the LDS entry itself, two-ended addressing included.  Entries lie in blocks of 64 positions, one
+// 1 KB run per group, so the g-th load or store of a chunk is 64 x 16 contiguous bytes (8 lines) where the slot records' is a
+// gather over 64 lines, and the next visit pulls 64 bytes per path across the fabric, not the 128-byte line of its slot.  The
+// queue entry says where the record is: SP_POSITIONAL beside the slot id, or nothing -- then it is in the slot, where a T visit
+// that finished a walk left it (T visits read and write slot records only; a path that goes to T gets g0-g3 there).
+#define SP_POSITIONAL 0x8000u
+#define SP_HR_STREAM (2u * 2u * (uint32_t)HRT_SP_QCAP * 16u)   // dwords of one stream: 2 parities x 2 buffers x positions x 64 bytes
+#define SP_HR_WG ((uint32_t)HRT_SP_STREAMS * SP_HR_STREAM)      // ... of one workgroup (1 MB), behind its slot records:
+#define SP_WG_DWORDS ((uint32_t)SP_FIELDS * HRT_SP_POOL + SP_HR_WG)  // one base address and 32-bit offsets reach both
+// buf: 1 = A, 2 = B (spq); idx: the index of the LDS entry in its buffer.  Dword offset of g0; g-th group 256 dwords further
+__device__ __forceinline__ uint32_t sp_hr_at(uint32_t buf, uint32_t parity, uint32_t idx) {
+    return ((parity * 2u + (buf - 1u)) * (uint32_t)HRT_SP_QCAP + (idx & ~63u)) * 16u + (idx & 63u) * 4u;
+}
+struct SpRec { uint32_t at, gs; };  // where g0-g3 of a path are: group g at dword at + g * gs of L.st
+__device__ __forceinline__ SpRec sp_rec(const SpLds &L, bool positional, uint32_t slot, uint32_t buf, uint32_t parity, uint32_t idx) {
+    SpRec r;
+    r.at = positional ? L.hr + sp_hr_at(buf, parity, idx) : SP_AT(0, slot);
+    r.gs = positional ? 256u : 4u;
+    return r;
+}
+__device__ __forceinline__ uint4 sp_ld4(const SpLds &L, const SpRec &r, uint32_t g) {
+    const v4u v = ((gu4)(L.st + (r.at + g * r.gs)))[0];
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void sp_st4(const SpLds &L, const SpRec &r, uint32_t g, uint4 v) {
+    v4u w;
+    w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
+    *((v4u __attribute__((address_space(1))) *)(L.st + (r.at + g * r.gs))) = w;
+}
 // g3.w: the bounces left (3 bits) and the path's number beside them (13 bits of path-in-unit, the unit slot on top)
 __device__ __forceinline__ uint32_t sp_w7(uint32_t left, uint32_t pnum) { return left | ((pnum & 0x1FFFu) << 3) | (pnum & 0xC0000000u); }
 __device__ __forceinline__ uint32_t sp_w7_left(uint32_t w) { return w & 7u; }
@@ -222,11 +260,6 @@ __device__ __forceinline__ void sp_unpack_ray_hit(const uint4 g0, const uint4 g1
 __device__ __forceinline__ uint4 sp_g1(const Ray &ray, const Hit &h) {
     return make_uint4(__float_as_uint(ray.d.y), __float_as_uint(ray.d.z), __float_as_uint(h.t), sp_hit_word(h));
 }
-// g0, g1 of a ray with its closest hit so far
-__device__ __forceinline__ void sp_store_ray_hit(const SpLds &L, uint32_t slot, const Ray &ray, const Hit &h) {
-    sp_st4(L, 0, slot, sp_pack(ray.o.x, ray.o.y, ray.o.z, ray.d.x));
-    sp_st4(L, 1, slot, sp_g1(ray, h));
-}
 // What shade() reads of a square / mesh hit beyond the record: the arithmetic that found the hit, once more, on the one primitive.
 // Square: quad_t (the same t, the same u, v: it depends on the ray -- its time included -- and the square alone), rows per lane
 // from the staged tables.  Triangle: tri_inside on the triangle's rows with the stored t, which is the t the walk gave it
@@ -248,9 +281,10 @@ __device__ __forceinline__ uint16_t *spq(const SpLds &L, int which, uint32_t par
 // All appends of a chunk at once.  Every lane names the queue its path goes to (`to`: 0 = T, 1..4 = closest hit of kind
 // to - 1, 5 = free list, SP_TO_NONE = nowhere); ONE LDS atomic, issued by the first lane of each queue on that queue's counter,
 // reserves the entries, one ds_bpermute hands the bases round, one write stores the slot ids.  (One sp_push per queue was a
-// chain of up to six atomic-with-return / shuffle pairs per chunk.)
+// chain of up to six atomic-with-return / shuffle pairs per chunk.)  Returns the index of the lane's entry in its buffer: where a
+// travelling hit record goes (sp_hr_at).
 #define SP_TO_NONE 6u
-__device__ __forceinline__ void sp_push_all(const SpLds &L, SpCtl &C, uint32_t out, uint32_t to, uint32_t slot) {
+__device__ __forceinline__ uint32_t sp_push_all(const SpLds &L, SpCtl &C, uint32_t out, uint32_t to, uint32_t slot) {
     uint32_t rank = 0, count = 0, leader = 0;
 #pragma unroll
     for (uint32_t q = 0; q < 6u; ++q) {
@@ -264,14 +298,17 @@ __device__ __forceinline__ void sp_push_all(const SpLds &L, SpCtl &C, uint32_t o
     uint32_t base = 0;
     if (to < SP_TO_NONE && rank == 0u) base = atomicAdd(&C.cQ[to][out], count);
     base = __shfl(base, (int)leader);
+    uint32_t idx = 0;
     if (to < SP_TO_NONE) {
         const uint32_t pos = base + rank;
         // buffers (spq): T -> 0 from the front; kinds 1 (sphere) and 2 (square) share 1, kinds 0 (miss) and 3 (mesh) share 2, the
         // first of each pair from the front, the second from the back; free slots -> 3
         const uint32_t buf = to == 0u ? 0u : (to == 5u ? 3u : ((to == 2u || to == 3u) ? 1u : 2u));
         const bool back = to == 3u || to == 4u;
-        spq(L, (int)buf, out)[back ? (uint32_t)HRT_SP_QCAP - 1u - pos : pos] = (uint16_t)slot;
+        idx = back ? (uint32_t)HRT_SP_QCAP - 1u - pos : pos;
+        spq(L, (int)buf, out)[idx] = (uint16_t)slot;
     }
+    return idx;
 }
 
 // VIEWS = a batched launch (DRender::views).  A unit groups tiles of the ONE queue of views x tiles items, so a unit, and with it a
@@ -282,7 +319,8 @@ template <bool LIGHTS, bool EXACT = false, bool SPHF = false, bool LIST = false,
 __device__ __forceinline__ void stream_body(const DRender &R) {
     extern __shared__ uint4 s_raw[];
     SpLds L;
-    L.st = R.sp_pool + (size_t)blockIdx.x * ((size_t)SP_FIELDS * HRT_SP_POOL);
+    L.st = R.sp_pool + (size_t)blockIdx.x * (size_t)SP_WG_DWORDS;
+    L.hr = (uint32_t)SP_FIELDS * HRT_SP_POOL;
     L.q = reinterpret_cast<uint16_t *>(s_raw);
     L.ctl = reinterpret_cast<SpCtl *>(L.q + HRT_SP_NQ * HRT_SP_POOL);
     SpShared &SH = *reinterpret_cast<SpShared *>(L.ctl + HRT_SP_STREAMS);
@@ -326,7 +364,7 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
         for (int k = 0; k < 4; ++k) C0.cQ[1 + k][0] = C0.cQ[1 + k][1] = 0;
         C0.cQ[5][0] = HRT_SP_QCAP; C0.cQ[5][1] = 0;
         C0.parity = 1; C0.done = 0; C0.arrive = 0; C0.ready = 0; C0.cursor = 0; C0.ngen = 0; C0.gen_n0 = 0; C0.gen_slot = 0; C0.gen_s0 = 0;
-        C0.red_slot = HRT_SP_UNITS; C0.red_j = 0; C0.red_s0 = 0; C0.red_ns = 0; C0.more = 1;
+        C0.red_slot = HRT_SP_UNITS; C0.red_j = 0; C0.red_s0 = 0; C0.red_ns = 0; C0.more = 1; C0.tails = 0;
         if (tid == 0) {
             SH.lock = 0; SH.cur = 0; SH.tiles_done = 0; SH.abort = 0; SH.stall = 0; SH.sections = 0;
             for (int k = 0; k < HRT_SP_UNITS; ++k) { U[k].state = SP_U_FREE; U[k].j = 0; U[k].s0 = 0; U[k].ns = 0; U[k].gen_next = 0; U[k].gen_total = 0; U[k].outstanding = 0; }
@@ -502,6 +540,8 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
         // waits for the next cycle (it moves to the front of the output queue, so the oldest entries go first): the paths are
         // independent and every fold is ordered, so when a path is advanced changes nothing -- and the chunks that do run have
         // all 64 lanes filled.  When every unit slot is draining, new paths wait for old ones to finish: then everything runs.
+        // (Only the LDS entries move here.  The records that travel with them are copied by the waves of the cycle that is
+        // being prepared, off the serial path: C.tails.)
         const bool defer = HRT_SP_DEFER && SP_UNI(C.more) != 0u;
         const uint32_t cT = SP_UNI(C.cQ[0][par]), rT = defer ? (cT & 63u) : 0u;
         if (lane < rT) qs[(2 * 0 + (par ^ 1u)) * HRT_SP_QCAP + lane] = qs[(2 * 0 + par) * HRT_SP_QCAP + cT - rT + lane];
@@ -523,6 +563,7 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
         if (lane == 0) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) { C.cQ[1 + k][par] = cKv[k] - rK[k]; C.cQ[1 + k][par ^ 1u] = rK[k]; }
+            C.tails = rK[0] | (rK[1] << 6) | (rK[2] << 12) | (rK[3] << 18);  // their travelling records follow in the cycle itself (C chunks)
             C.cQ[0][par] = cT - rT;
             C.cQ[0][par ^ 1u] = rT;
             C.cQ[5][par ^ 1u] = free_in - ngen;  // the unused free slots carry over, freed slots are appended after them
@@ -548,6 +589,7 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
         if (fin_mask & (1u << st)) continue;
         SpCtl &C = L.ctl[st];
         L.q = q_all + st * (HRT_SP_NQ * HRT_SP_QCAP);
+        L.hr = (uint32_t)SP_FIELDS * HRT_SP_POOL + st * SP_HR_STREAM;
         {   // wait for the control block of this stage (normally there already)
 #ifdef HRT_SP_DEBUG
             const unsigned long long dbg_q0 = __builtin_readcyclecounter();
@@ -579,6 +621,7 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
         const uint32_t parity = SP_UNI(C.parity);
         const uint32_t ngen = SP_UNI(C.ngen), n0 = SP_UNI(C.gen_n0), gs = SP_UNI(C.gen_slot), s0 = SP_UNI(C.gen_s0);
         const uint32_t red = SP_UNI(C.red_slot), nR = red < HRT_SP_UNITS ? (upix * 3u + 63u) >> 6 : 0u;  // reduction chunks: 64 columns each
+        const uint32_t nRC = nR + (SP_UNI(C.tails) != 0u ? 4u : 0u);  // ... and copy chunks: one per hit kind when any queue has a deferred tail
         const uint32_t cTin = SP_UNI(C.cQ[0][parity]);
         const uint32_t cK0 = SP_UNI(C.cQ[1][parity]), cK1 = SP_UNI(C.cQ[2][parity]), cK2 = SP_UNI(C.cQ[3][parity]),
                        cK3 = SP_UNI(C.cQ[4][parity]);
@@ -597,7 +640,7 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
             uint32_t c = 0;
             if (lane == 0) c = atomicAdd(&C.cursor, 1u);
             c = SP_UNI(c);
-            if (c >= nR + total) break;
+            if (c >= nRC + total) break;
             if (c < nR) {
                 // ---------------- R: 64 (pixel, channel) columns of a finished fold, its samples added in sample order (main.cpp:193)
                 // Plain loads: the scratch was written by waves of THIS workgroup (one CU), each of which waited for its stores
@@ -631,7 +674,29 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                 }
                 continue;
             }
-            c -= nR;
+            if (c < nRC) {
+                // ---------------- C: the travelling records of a hit queue's deferred tail.  The serial section moved the entries from
+                // behind the last whole chunk of the input queue (kind c: cK, a multiple of 64 now) to positions [0, r) of the output
+                // queue; their records follow here, from the input array (which nothing writes in this cycle) to the output array
+                // (whose positions below r no append of this cycle is given).  They are read in the NEXT cycle, behind this wave's
+                // arrival.  At most 63 records per kind and cycle; entries whose record is in the slot have nothing to copy.
+                const uint32_t k = c - nR, r = (SP_UNI(C.tails) >> (6u * k)) & 63u;
+                const uint32_t base = k == 0u ? cK0 : (k == 1u ? cK1 : (k == 2u ? cK2 : cK3));
+                const uint32_t buf = (k == 1u || k == 2u) ? 1u : 2u;  // the addressing of sp_push_all
+                const bool back = k >= 2u;
+                if (lane < r) {
+                    const uint32_t from = back ? (uint32_t)HRT_SP_QCAP - 1u - (base + lane) : base + lane;
+                    const uint32_t to = back ? (uint32_t)HRT_SP_QCAP - 1u - lane : lane;
+                    if (spq(L, (int)buf, parity ^ 1u)[to] & SP_POSITIONAL) {
+                        const SpRec ri = sp_rec(L, true, 0u, buf, parity, from), ro = sp_rec(L, true, 0u, buf, parity ^ 1u, to);
+                        uint4 g0 = sp_ld4(L, ri, 0), g1 = sp_ld4(L, ri, 1), g2 = sp_ld4(L, ri, 2), g3 = sp_ld4(L, ri, 3);
+                        asm volatile("" : SP_PIN1(g0), SP_PIN1(g1), SP_PIN1(g2), SP_PIN1(g3));
+                        sp_st4(L, ro, 0, g0); sp_st4(L, ro, 1, g1); sp_st4(L, ro, 2, g2); sp_st4(L, ro, 3, g3);
+                    }
+                }
+                continue;
+            }
+            c -= nRC;
 #ifdef HRT_SP_DEBUG
             ++dbg_chunks;
             const unsigned long long dbg_c0 = __builtin_readcyclecounter();
@@ -720,7 +785,9 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                 uint32_t slot = 0, kind = 0, fin_unit = 0, pnum = 0;
                 bool trace = false, freed = false;  // trace: the path has a new ray to intersect; freed: its path has ended (unit fin_unit)
                 bool ended = false, last_seg = false;  // ended: the sample's colour `rad` is final; last_seg: the new ray is the path's last segment
-                f3 rad = mk(0.f, 0.f, 0.f);
+                f3 rad = mk(0.f, 0.f, 0.f), thr = mk(1.f, 1.f, 1.f);  // a new path: radiance 0, throughput 1, MAXBOUNCES left
+                uint32_t rng_i = 0;
+                int remaining = 6;
                 SEG_START((HRT_SP_SEG_KIND == 1 && !is_gen && c >= e1 && c < e2) || (HRT_SP_SEG_KIND == 3 && !is_gen && c >= e3 && c < e1) ||
                           (HRT_SP_SEG_KIND == 4 && is_gen) || (HRT_SP_SEG_KIND == 5 && !is_gen && c < e3));  // the chunk class in hand
                 Ray ray;
@@ -754,8 +821,7 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                             ray = camera_ray<EXACT>(cam, u, v, tm);
                         }
                         pnum = n | (gs << 30);
-                        sp_st4(L, 2, slot, sp_pack(1.f, 1.f, 1.f, 0.f));                                  // throughput 1, radiance 0
-                        sp_st4(L, 3, slot, make_uint4(0u, 0u, rng.i, sp_w7(6u, pnum)));                  // MAXBOUNCES
+                        rng_i = rng.i;
                         trace = true;
                     } else {  // pixel outside a ragged image: the sample is zero, the slot stays free
                         float *o = scratch + (size_t)gs * ((size_t)HRT_SP_UNIT * 3u) + (size_t)n * 3u;
@@ -764,14 +830,17 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                         fin_unit = gs;
                     }
                 } else if (act) {
-                    slot = qHi[from_back ? (uint32_t)HRT_SP_QCAP - 1u - e : e] & (HRT_SP_POOL - 1u);
+                    const uint32_t qi = from_back ? (uint32_t)HRT_SP_QCAP - 1u - e : e, entry = qHi[qi];
+                    slot = entry & (HRT_SP_POOL - 1u);
+                    // the record: at this queue position (sent by a G chunk or a hit visit), or in the slot (sent by a T visit)
+                    const SpRec rec = sp_rec(L, (entry & SP_POSITIONAL) != 0u, slot, (c < e3 || c >= e2) ? 2u : 1u, parity, qi);
                     // Four groups, one 64-byte half of the record.  What else the visit needs never changes after the path's first visit or
                     // follows from what is stored.  The path's number rides in g3.w beside the bounces left; the ray's time and the keys of
                     // the path's random stream are recomputed from it (the pixel from the unit's tile table in LDS, the sample from the
                     // unit's fold; Rng::start; the time is draw 2 of the stream, as in the G chunk): ~45 vector instructions for one vector
                     // memory instruction less per hit visit.  The (u, v) of a square hit and the barycentrics of a triangle hit are
                     // recomputed in front of shade(), below.
-                    uint4 g0 = sp_ld4(L, 0, slot), g1 = sp_ld4(L, 1, slot), g2 = sp_ld4(L, 2, slot), g3 = sp_ld4(L, 3, slot);
+                    uint4 g0 = sp_ld4(L, rec, 0), g1 = sp_ld4(L, rec, 1), g2 = sp_ld4(L, rec, 2), g3 = sp_ld4(L, rec, 3);
                     asm volatile("" : SP_PIN1(g0), SP_PIN1(g1), SP_PIN1(g2), SP_PIN1(g3));
                     pnum = sp_w7_pnum(g3.w);
                     Rng key;
@@ -788,9 +857,9 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                     Hit h;
                     sp_unpack_ray_hit(g0, g1, ray, h);
                     ray.time = moving ? key.next() : 0.f;  // (time x 0 == 0: without motion the time is never looked at)
-                    f3 thr = mk(__uint_as_float(g2.x), __uint_as_float(g2.y), __uint_as_float(g2.z));
+                    thr = mk(__uint_as_float(g2.x), __uint_as_float(g2.y), __uint_as_float(g2.z));
                     rad = mk(__uint_as_float(g2.w), __uint_as_float(g3.x), __uint_as_float(g3.y));
-                    int remaining = (int)sp_w7_left(g3.w);
+                    remaining = (int)sp_w7_left(g3.w);
 #ifdef HRT_SP_SEG
                     asm volatile("" : "+v"(remaining), "+v"(ray.o.x), "+v"(thr.x), "+v"(rad.x));
 #endif
@@ -817,8 +886,7 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                         ended = (remaining == 0);
                         if ((HRT_SP_PRUNE & 1) && prune && thr.x == 0.f && thr.y == 0.f && thr.z == 0.f) ended = true;  // nothing can reach the sample any more
                         if (!ended) {
-                            sp_st4(L, 2, slot, sp_pack(thr.x, thr.y, thr.z, rad.x));
-                            sp_st4(L, 3, slot, make_uint4(__float_as_uint(rad.y), __float_as_uint(rad.z), rng.i, sp_w7((uint32_t)remaining, pnum)));
+                            rng_i = rng.i;
                             trace = true;
                             last_seg = (HRT_SP_PRUNE & 2) && !LIGHTS && prune && remaining == 1;
                         }
@@ -839,15 +907,7 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                 if (SPHF && trace && hn.kind == 0u && pmn == 0u) {
                     // The builds for open scenes (a crowd of spheres under a sky): a ray that meets nothing ends its path HERE instead of
                     // travelling to a miss chunk (Scene.h:302-303; one visit in four of random_spheres).  Throughput, radiance and the
-                    // bounces left were written to the record a moment ago by this lane (a new path: 1, 0, 6): read back, not kept live.
-                    f3 thr = mk(1.f, 1.f, 1.f);
-                    int remaining = 6;
-                    if (!is_gen) {
-                        const uint4 g2 = sp_ld4(L, 2, slot), g3 = sp_ld4(L, 3, slot);
-                        thr = mk(__uint_as_float(g2.x), __uint_as_float(g2.y), __uint_as_float(g2.z));
-                        rad = mk(__uint_as_float(g2.w), __uint_as_float(g3.x), __uint_as_float(g3.y));
-                        remaining = (int)sp_w7_left(g3.w);
-                    }
+                    // bounces left are still in registers: the record is written behind the queue append, below.
                     rad = rad + thr * sky(cx, ray.d, remaining);
                     trace = false; ended = true; last_seg = false;
                 }
@@ -870,19 +930,30 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                     freed = true;
                 }
                 if (trace) {
-                    sp_store_ray_hit(L, slot, ray, hn);  // with g2, g3 above: the whole 64-byte half
+                    to_mesh = pmn != 0u;
+                    kind = hn.kind;
+                }
+                // The queue first: which one is known only now, and the position in it is where the record goes.  To a hit queue: the
+                // entry says SP_POSITIONAL.  To T: a bare slot id (with the meshes to walk beside it where they fit), the record in the slot.
+                const uint32_t to = trace ? (to_mesh ? 0u : 1u + kind) : (freed ? 5u : SP_TO_NONE);
+                uint32_t entry = slot;
+                if (trace && !to_mesh) entry = slot | SP_POSITIONAL;
+#if HRT_SP_PMQ
+                if (trace && to_mesh && pm_in_entry) entry = slot | (pmn << 12);
+#endif
+                const uint32_t at = sp_push_all(L, C, parity ^ 1u, to, entry);
+                if (trace) {
+                    // g0-g3, the whole 64-byte half, in four stores issued together: at the path's position in its hit queue, or in its slot
+                    const SpRec rec = sp_rec(L, !to_mesh, slot, (to == 2u || to == 3u) ? 1u : 2u, parity ^ 1u, at);
+                    sp_st4(L, rec, 0, sp_pack(ray.o.x, ray.o.y, ray.o.z, ray.d.x));
+                    sp_st4(L, rec, 1, sp_g1(ray, hn));
+                    sp_st4(L, rec, 2, sp_pack(thr.x, thr.y, thr.z, rad.x));
+                    sp_st4(L, rec, 3, make_uint4(__float_as_uint(rad.y), __float_as_uint(rad.z), rng_i, sp_w7((uint32_t)remaining, pnum)));
 #if HRT_SP_PMQ
                     if (!pm_in_entry)
 #endif
                     if (pmn != 0u) sp_st4(L, 5, slot, make_uint4(HRT_KD_NIL, 0u, 0u, pmn));  // no walk in progress; the meshes to walk, where the T visit looks for them
-                    to_mesh = pmn != 0u;
-                    kind = hn.kind;
                 }
-#if HRT_SP_PMQ
-                sp_push_all(L, C, parity ^ 1u, trace ? (to_mesh ? 0u : 1u + kind) : (freed ? 5u : SP_TO_NONE), (trace && to_mesh && pm_in_entry) ? (slot | (pmn << 12)) : slot);
-#else
-                sp_push_all(L, C, parity ^ 1u, trace ? (to_mesh ? 0u : 1u + kind) : (freed ? 5u : SP_TO_NONE), slot);
-#endif
 #pragma unroll
                 for (uint32_t k = 0; k < HRT_SP_UNITS; ++k) fin[k] += (uint32_t)__popcll(__ballot(freed && fin_unit == k));
                 SEG(6);  // record stores + queue appends
