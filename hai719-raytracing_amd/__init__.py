@@ -120,6 +120,19 @@ class LensView(C.Structure):
     _fields_ = [("lens", Lens), ("seed", C.c_uint64)]
 
 
+class Quad(C.Structure):
+    """``hrt_quad``: a square of a flattened scene (include/hrt.h) -- corner v0, its neighbours v1 and v3, the normal-map frame."""
+    _fields_ = [("v0", C.c_float * 3), ("v1", C.c_float * 3), ("v3", C.c_float * 3), ("tangent", C.c_float * 3),
+                ("bitangent", C.c_float * 3), ("material", C.c_int32)]
+
+    @staticmethod
+    def make(v0, v1, v3, material: int = 0) -> "Quad":
+        q = Quad()
+        q.v0[:], q.v1[:], q.v3[:] = v0, v1, v3
+        q.material = material
+        return q
+
+
 class PickInput(C.Structure):
     """hrt_pick_input (include/hrt.h): what the choice of a trace kernel build depends on."""
     _fields_ = [("n_meshes", C.c_uint32), ("n_lights", C.c_uint32), ("n_spheres", C.c_uint32), ("tab_rows", C.c_uint32),
@@ -329,6 +342,13 @@ def device_lib() -> C.CDLL:
                                               C.c_void_p, C.POINTER(Stats)]
         lib.hrt_render_lens_views_features.argtypes = [C.c_void_p, C.POINTER(LensView), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                        C.c_void_p, C.c_void_p]
+        lib.hrt_bake_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
+        lib.hrt_bake_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
+                                        C.c_void_p, C.c_void_p]
+        lib.hrt_bake.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p,
+                                 C.POINTER(Stats)]
+        lib.hrt_bake_quad_points.argtypes = [C.POINTER(Quad), C.c_uint32, C.c_uint32, C.c_int32, C.c_float, C.c_float, C.c_void_p]
+        lib.hrt_bake_mesh_points.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_void_p]
         lib.hrt_debug_pick_kernel.argtypes = [C.POINTER(PickInput), C.c_char_p, C.c_size_t]
         lib.hrt_debug_last_kernel.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         _dev = lib
@@ -694,6 +714,76 @@ class DeviceScene:
             return out
         return r
 
+    def bake(self, points, spp: int = 1, first_sample: int = 0, seed: int = 1, keys=None, out=None, accumulate: bool = False,
+             flags: int = 0, stats: Optional[Stats] = None):
+        """hrt_bake*: the radiance arriving at surface points, (n, RAY_FLOATS) float32 rows {P, time, N, bias}, cosine-weighted about
+        N: samples [first_sample, first_sample + spp) of RNG stream (seed, key, sample); key i unless ``keys`` (n uint32 / int32).
+
+        Returns (n, 3) float32: the mean of the samples in the units of ``trace_radiance`` (irradiance = pi x the mean radiance; no
+        factor is applied), or with ``accumulate`` the running sums (``out`` then holds the sums of the earlier samples and is updated
+        in place).  A contiguous float32 torch tensor on the GPU runs on the current torch stream of its device and gives a torch
+        tensor there (``out``, if given, a device tensor), without synchronising (hrt_bake_device).  Anything else is taken as NumPy
+        and comes back as NumPy; samples [0, spp) without ``out`` go through the blocking hrt_bake, which fills ``stats`` if given.
+        ``flags``: FLAG_EXACT_ONLY, FLAG_MESH_BRUTE, FLAG_NO_LDS_TREE."""
+        import torch
+        flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
+        is_torch = isinstance(points, torch.Tensor)
+        if is_torch:
+            if (points.device.type != "cuda" or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != RAY_FLOATS
+                    or not points.is_contiguous()):
+                raise ValueError("bake: a torch tensor must be a contiguous (n, 8) float32 tensor on the GPU")
+        else:
+            a = np.ascontiguousarray(points, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != RAY_FLOATS:
+                raise ValueError(f"bake: points must have shape (n, {RAY_FLOATS}) (got {a.shape})")
+        n = points.shape[0] if is_torch else a.shape[0]
+        if n > 0x7FFFFFFF:
+            raise ValueError(f"bake: at most 2^31 - 1 points per call (got {n})")
+        k = None
+        if keys is not None:
+            if is_torch:
+                if (not isinstance(keys, torch.Tensor) or keys.device != points.device or keys.dtype not in (torch.int32, torch.uint32)
+                        or keys.shape != (n,) or not keys.is_contiguous()):
+                    raise ValueError("bake: keys must be a contiguous (n,) int32 tensor on the points' device")
+            else:
+                k = np.ascontiguousarray(keys)
+                if k.shape != (n,) or k.dtype not in (np.uint32, np.int32):
+                    raise ValueError(f"bake: keys must be (n,) uint32 (got {k.shape} {k.dtype})")
+        if out is None:
+            if accumulate and first_sample != 0:
+                raise ValueError("bake: accumulate after sample 0 needs the running sums in `out`")
+        elif is_torch:
+            if (not isinstance(out, torch.Tensor) or out.device != points.device or out.dtype != torch.float32 or out.shape != (n, 3)
+                    or not out.is_contiguous()):
+                raise ValueError("bake: out must be a contiguous (n, 3) float32 tensor on the points' device")
+        else:
+            o = np.asarray(out)
+            if o.shape != (n, 3) or o.dtype != np.float32:
+                raise ValueError(f"bake: out must be (n, 3) float32 (got {o.shape} {o.dtype})")
+        if not is_torch and out is None and not accumulate and first_sample == 0:
+            r = np.empty((n, 3), dtype=np.float32)
+            self._check(self._lib.hrt_bake(self._h, a.ctypes.data, None if k is None else k.ctypes.data, n, spp, seed, flags, r.ctypes.data,
+                                           None if stats is None else C.byref(stats)))
+            return r
+        if is_torch:
+            d_points, d_keys = points, keys
+            d_out = torch.zeros((n, 3), dtype=torch.float32, device=points.device) if out is None else out
+        else:
+            d_points = torch.from_numpy(a).to("cuda")
+            d_keys = None if k is None else torch.from_numpy(k.view(np.int32)).to(d_points.device)
+            d_out = (torch.zeros((n, 3), dtype=torch.float32, device=d_points.device) if out is None
+                     else torch.from_numpy(np.ascontiguousarray(o)).to(d_points.device))
+        s = torch.cuda.current_stream(d_points.device)
+        self._check(self._lib.hrt_bake_device(self._h, C.c_void_p(d_points.data_ptr()), None if d_keys is None else C.c_void_p(d_keys.data_ptr()),
+                                              n, first_sample, spp, seed, flags, C.c_void_p(d_out.data_ptr()), C.c_void_p(s.cuda_stream)))
+        if is_torch:
+            return d_out
+        r = d_out.cpu().numpy()
+        if out is not None:
+            out[...] = r
+            return out
+        return r
+
     def render_views(self, cams, w: int, h: int, spp: int, seeds=None, flags: int = 0, out=None, stats: Optional[Stats] = None):
         """hrt_render_views: every camera of ``cams`` as a w x h frame of ``spp`` samples, in one launch -> (n, h, w, 3) float32;
         frame v has the bits of ``render(cams[v], w, h, spp, seeds[v], flags)``.  ``seeds``: one per view (default 1 for each, as
@@ -1009,6 +1099,72 @@ def lens_rays(lens: Lens, w: int, h: int, sample: int = 0, seed: int = 1):
                            C.c_void_p(torch.cuda.current_stream().cuda_stream))
     if rc < 0:
         raise HrtError(f"hrt_lens_rays failed ({rc}): {lib.hrt_last_error().decode()}")
+    return out
+
+
+def bake_rays(points, sample: int = 0, seed: int = 1, keys=None):
+    """hrt_bake_rays: the rays of sample ``sample`` of bake points -- a contiguous (n, RAY_FLOATS) float32 torch tensor on the GPU,
+    rows {P, time, N, bias} -- as an (n, RAY_FLOATS) tensor on the same device, written on the current torch stream; a degenerate
+    sample has direction 0.  ``keys``: (n,) int32 on the same device.  Traced with trace_radiance(first_sample=sample, keys=keys)
+    they give the samples of ``DeviceScene.bake``."""
+    import torch
+    lib = device_lib()
+    if (not isinstance(points, torch.Tensor) or points.device.type != "cuda" or points.dtype != torch.float32 or points.dim() != 2
+            or points.shape[1] != RAY_FLOATS or not points.is_contiguous()):
+        raise ValueError("bake_rays: points must be a contiguous (n, 8) float32 tensor on the GPU")
+    n = points.shape[0]
+    if keys is not None and (not isinstance(keys, torch.Tensor) or keys.device != points.device or keys.dtype not in (torch.int32, torch.uint32)
+                             or keys.shape != (n,) or not keys.is_contiguous()):
+        raise ValueError("bake_rays: keys must be a contiguous (n,) int32 tensor on the points' device")
+    out = torch.empty((n, RAY_FLOATS), dtype=torch.float32, device=points.device)
+    with torch.cuda.device(points.device):
+        rc = lib.hrt_bake_rays(C.c_void_p(points.data_ptr()), None if keys is None else C.c_void_p(keys.data_ptr()), n, sample, seed,
+                               C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(points.device).cuda_stream))
+    if rc < 0:
+        raise HrtError(f"hrt_bake_rays failed ({rc}): {lib.hrt_last_error().decode()}")
+    return out
+
+
+class _SceneDescHead(C.Structure):
+    """The leading fields of ``hrt_scene_desc`` (include/hrt.h), up to the quads."""
+    _fields_ = [("n_materials", C.c_uint32), ("materials", C.c_void_p), ("n_spheres", C.c_uint32), ("spheres", C.c_void_p),
+                ("n_quads", C.c_uint32), ("quads", C.POINTER(Quad))]
+
+
+def scene_quads(desc) -> list:
+    """The quads of a flattened scene description (``HostScene.flatten()``) as copies, in the scene's order."""
+    head = C.cast(desc, C.POINTER(_SceneDescHead)).contents
+    return [Quad.from_buffer_copy(head.quads[i]) for i in range(head.n_quads)]
+
+
+def quad_points(quad: Quad, tw: int, th: int, side: int = 1, time: float = 0.0, bias: float = 1e-4) -> np.ndarray:
+    """hrt_bake_quad_points: the (tw * th, RAY_FLOATS) float32 bake points of a tw x th lightmap over ``quad``, row-major (texel
+    (i, j) at j * tw + i), at the texel centres with the quad's normal times ``side`` (+1: the side the trace path lights).  Host
+    only: needs no GPU."""
+    lib = device_lib()
+    n = int(tw) * int(th)
+    out = np.empty((n if 0 < n <= 0x7FFFFFFF else 1, RAY_FLOATS), dtype=np.float32)  # a frame the library refuses writes nothing
+    rc = lib.hrt_bake_quad_points(C.byref(quad), tw, th, side, time, bias, out.ctypes.data)
+    if rc < 0:
+        raise HrtError(f"hrt_bake_quad_points failed ({rc}): {lib.hrt_last_error().decode()}")
+    return out
+
+
+def mesh_points(positions, indices, time: float = 0.0, bias: float = 1e-4) -> np.ndarray:
+    """hrt_bake_mesh_points: one bake point per vertex of a triangle mesh -- ``positions`` (n_vertices, 3) float32, ``indices``
+    (n_triangles, 3) uint32 -- with the unnormalised sum of the cross products of its triangles as the normal (0 for a vertex no
+    triangle uses: a degenerate point).  Host only: needs no GPU."""
+    lib = device_lib()
+    p = np.ascontiguousarray(positions, dtype=np.float32)
+    ix = np.ascontiguousarray(indices, dtype=np.uint32)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError(f"mesh_points: positions must have shape (n_vertices, 3) (got {p.shape})")
+    if ix.size and (ix.ndim != 2 or ix.shape[1] != 3):
+        raise ValueError(f"mesh_points: indices must have shape (n_triangles, 3) (got {ix.shape})")
+    out = np.empty((p.shape[0], RAY_FLOATS), dtype=np.float32)
+    rc = lib.hrt_bake_mesh_points(p.ctypes.data, p.shape[0], ix.ctypes.data, ix.shape[0] if ix.size else 0, time, bias, out.ctypes.data)
+    if rc < 0:
+        raise HrtError(f"hrt_bake_mesh_points failed ({rc}): {lib.hrt_last_error().decode()}")
     return out
 
 

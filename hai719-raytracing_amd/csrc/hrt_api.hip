@@ -7,6 +7,7 @@
 #include "hrt_output.hip"
 #include "hrt_kat.hip"
 #include "hrt_pack.h"  // hrt_scene_desc -> host arrays (pack_scene): everything of scene creation that needs no device
+#include "hrt_bake_points.h"  // the host-only bake point generators (hrt_bake_quad_points, hrt_bake_mesh_points)
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types and prototypes only: librccl.so is opened with dlopen by hrt_multi_create (hrt_multi.hip)
@@ -1021,6 +1022,7 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 #include "hrt_rays.hip"
 #include "hrt_radiance.hip"
 #include "hrt_lens.hip"
+#include "hrt_bake.hip"
 #include "hrt_lens_adaptive.hip"
 #include "hrt_views.hip"
 

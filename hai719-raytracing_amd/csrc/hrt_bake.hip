@@ -1,0 +1,238 @@
+// Baking (include/hrt.h "Baking": hrt_bake_rays, hrt_bake_device, hrt_bake and the two host point generators): the radiance
+// arriving at caller-supplied surface points, cosine-weighted about their normals, through the unchanged integrator.  Included by
+// hrt_api.hip inside its extern "C" block, after hrt_lens.hip (radiance_body, the query helpers, lens_traced).
+//
+// bake_sample is the one implementation of THE RULE of include/hrt.h: the ray of sample `sample` of a point record.  Two kernels
+// call it: hrt_bake_rays_kernel writes the rays as records (the sibling of hrt_camera_rays_kernel and hrt_lens_rays_kernel); the
+// hrt_bake_kernel builds are radiance_body with the BakeRays source -- lane i is point i, and at the start of every sample the
+// point record is read again (two coalesced 16-byte loads, as RecordRays re-reads its ray) and the ray made in registers, so a bake
+// needs no n * 32-byte ray buffer and one launch instead of two per sample.  Nothing of the point lives past sample(): a bake
+// source holds no state of its own across a path.  No call here touches the per-launch state of a scene.
+//
+// All of it is fp32 without fused multiply-add (the library is built with -ffp-contract=off), in the order the header writes.
+
+// The launch record of the hrt_bake_kernel builds: DRadiance with the point records in place of the rays (query_launch and
+// radiance_body read the fields they share by name).
+struct DBake {
+    const DScene *scene;
+    const float4 *points;  // 2 float4 per point: {P, time} {N, bias}
+    const uint32_t *keys;  // RNG key of point i (NULL: i)
+    float *out;            // 3 floats per point
+    uint32_t n;
+    uint32_t flags;
+    uint32_t first_sample, n_samples;
+    uint32_t seed_lo, seed_hi;
+    uint32_t lds_units;
+    float bound;
+};
+
+extern "C++" {
+namespace hrtk {
+
+// THE RULE for the point record {a, b} = {P, time} {N, bias}, key and sample; false for a degenerate sample, whose ray is
+// {P, 0, time}.  Straight-line code but for the early return of a degenerate point, which draws nothing.
+__device__ __forceinline__ bool bake_sample(const float4 &a, const float4 &b, uint32_t seed_lo, uint32_t seed_hi, uint32_t key, uint32_t sample,
+                                            Ray &ray) {
+    const f3 P = mk(a.x, a.y, a.z), N = mk(b.x, b.y, b.z);
+    const float bias = b.w;
+    ray.o = P;
+    ray.d = mk(0.f, 0.f, 0.f);
+    ray.time = a.w;
+    if (!(rays_finite(a.x) && rays_finite(a.y) && rays_finite(a.z) && rays_finite(a.w) && rays_finite(b.x) && rays_finite(b.y) &&
+          rays_finite(b.z) && rays_finite(b.w)) || bias < 0.f || (N.x == 0.f && N.y == 0.f && N.z == 0.f))
+        return false;
+    const f3 Nn = normalize(N);
+    if (!(rays_finite(Nn.x) && rays_finite(Nn.y) && rays_finite(Nn.z)) || (Nn.x == 0.f && Nn.y == 0.f && Nn.z == 0.f)) return false;
+    Rng rng;
+    rng.start(seed_lo, seed_hi, key, sample);
+    const float b0 = rng.next(), b1 = rng.next();  // draws 0 and 1: the camera's u, v slots; a radiance path starts at draw 3
+    const float r = sqrtf(b0), phi = 6.2831855f * b1;
+    const float x = r * cosf(phi), y = r * sinf(phi), z = sqrtf(1.f - b0);  // cosine-weighted about +z
+    const float sg = copysignf(1.f, Nn.z), fa = -1.f / (sg + Nn.z), fb = (Nn.x * Nn.y) * fa;  // branch-free frame, no pole
+    const f3 T = mk(1.f + (sg * (Nn.x * Nn.x)) * fa, sg * fb, (-sg) * Nn.x);
+    const f3 B = mk(fb, sg + (Nn.y * Nn.y) * fa, -Nn.y);
+    const f3 d = normalize((x * T + y * B) + z * Nn);
+    const f3 O = P + bias * Nn;
+    if (!(rays_finite(O.x) && rays_finite(O.y) && rays_finite(O.z) && rays_finite(d.x) && rays_finite(d.y) && rays_finite(d.z)) ||
+        (d.x == 0.f && d.y == 0.f && d.z == 0.f))
+        return false;
+    ray.o = O;
+    ray.d = d;
+    return true;
+}
+
+// radiance_body's source for bake points: item i is point i, keyed by Q.keys with the launch's seed.  The record is read where it
+// is used, by the lane that uses it.
+struct BakeRays {
+    static constexpr bool per_sample = true;
+    __device__ static __forceinline__ uint32_t key(const DBake &Q, uint32_t i) { return Q.keys ? Q.keys[i] : i; }
+    __device__ static __forceinline__ void seed(const DBake &Q, uint32_t, uint32_t &lo, uint32_t &hi) { lo = Q.seed_lo; hi = Q.seed_hi; }
+    __device__ static __forceinline__ bool sample(const DBake &Q, uint32_t i, uint32_t sample, Ray &ray) {
+        const gf4 pts = (gf4)Q.points;
+        const float4 a = ld(pts, 2u * i), b = ld(pts, 2u * i + 1u);
+        return bake_sample(a, b, Q.seed_lo, Q.seed_hi, key(Q, i), sample, ray) && lens_traced(ray);
+    }
+};
+
+}  // namespace hrtk
+}  // extern "C++"
+
+// hrt_bake_rays: the ray of sample `sample` of every point as a {O, time} {d, +inf} record; a degenerate sample is {P, time} {0, +inf}.
+extern "C" __global__ void __launch_bounds__(256) hrt_bake_rays_kernel(const float4 *__restrict__ points, const uint32_t *__restrict__ keys,
+                                                                       uint32_t n, uint32_t sample, uint32_t seed_lo, uint32_t seed_hi,
+                                                                       float4 *__restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = points[2u * i], b = points[2u * i + 1u];
+    Ray r;
+    if (!bake_sample(a, b, seed_lo, seed_hi, keys ? keys[i] : i, sample, r)) {
+        r.o = mk(a.x, a.y, a.z);
+        r.d = mk(0.f, 0.f, 0.f);
+    }
+    out[2u * i] = make_float4(r.o.x, r.o.y, r.o.z, a.w);
+    out[2u * i + 1u] = make_float4(r.d.x, r.d.y, r.d.z, __builtin_inff());
+}
+
+// The fused bake: radiance_body over points.  Launch bounds and shape are hrt_lens_kernel's.
+extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_bake_kernel(const DBake Q) { radiance_body<false, false, BakeRays>(Q); }
+extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_bake_kernel_lights(const DBake Q) { radiance_body<true, false, BakeRays>(Q); }
+extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_bake_kernel_exact(const DBake Q) { radiance_body<false, true, BakeRays>(Q); }
+extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_bake_kernel_lights_exact(const DBake Q) { radiance_body<true, true, BakeRays>(Q); }
+
+// The flags of a bake.
+static int bake_flags_check(const std::string &who, uint32_t flags) {
+    static const struct { uint32_t bit; const char *name; const char *why; } refused[] = {
+        {HRT_FLAG_WAVE_KERNEL, "HRT_FLAG_WAVE_KERNEL", "a bake has one kernel form"},
+        {HRT_FLAG_STREAM_KERNEL, "HRT_FLAG_STREAM_KERNEL", "a bake has one kernel form"},
+        {HRT_FLAG_DUAL_KERNEL, "HRT_FLAG_DUAL_KERNEL", "a bake has one kernel form"},
+        {HRT_FLAG_NO_SHADOW_CULL, "HRT_FLAG_NO_SHADOW_CULL", "the query kernels have no such build"},
+        {HRT_RAYS_NORMALIZE, "HRT_RAYS_NORMALIZE", "the normal of a bake point is always normalised"},
+        {HRT_FLAG_GAMMA, "HRT_FLAG_GAMMA", "a bake is linear radiance, not a frame"}};
+    for (const auto &f : refused)
+        if (flags & f.bit) return fail(HRT_ERR_INVALID, who + ": flags: " + f.name + ": " + f.why);
+    const uint32_t known = HRT_FLAG_EXACT_ONLY | HRT_FLAG_MESH_BRUTE | HRT_FLAG_NO_LDS_TREE | HRT_RADIANCE_ACCUMULATE;
+    if (flags & ~known) return fail(HRT_ERR_INVALID, who + ": flags: unknown bits " + std::to_string(flags & ~known));
+    return check_mesh_brute(who, flags);
+}
+
+// Checks 3..5 of the header's order: the point records, the keys, the count.  `dev`: device pointers (d_ names, 16-byte records).
+static int bake_points_check(const std::string &who, const void *points, const void *keys, uint32_t n, bool dev) {
+    const std::string pn = dev ? "d_points" : "points", kn = dev ? "d_keys" : "keys";
+    const uintptr_t align = dev ? 16u : 4u;
+    if (!points) return fail(HRT_ERR_INVALID, who + ": " + pn + " is NULL");
+    if ((uintptr_t)points % align) return fail(HRT_ERR_INVALID, who + ": " + pn + " is not " + std::to_string(align) + "-byte aligned");
+    if ((uintptr_t)keys % 4u) return fail(HRT_ERR_INVALID, who + ": " + kn + " is not 4-byte aligned");
+    if (n > 0x7fffffffu) return fail(HRT_ERR_INVALID, who + ": n must be at most 2^31 - 1 (got " + std::to_string(n) + ")");
+    return HRT_OK;
+}
+
+int hrt_bake_rays(const float *d_points, const uint32_t *d_keys, uint32_t n, uint32_t sample, uint64_t seed, float *d_rays, void *stream) {
+    const std::string who = "hrt_bake_rays";
+    if (n == 0u) return HRT_OK;
+    { const int prc = bake_points_check(who, d_points, d_keys, n, true); if (prc != HRT_OK) return prc; }
+    if (!d_rays) return fail(HRT_ERR_INVALID, who + ": d_rays is NULL");
+    if ((uintptr_t)d_rays % 16u) return fail(HRT_ERR_INVALID, who + ": d_rays is not 16-byte aligned");
+    if (!g_rt.ready) return fail(HRT_ERR_STATE, who + ": call hrt_init first");
+    hipLaunchKernelGGL(hrt_bake_rays_kernel, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, (const float4 *)d_points, d_keys, n, sample,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), (float4 *)d_rays);
+    HIP_TRY(hipGetLastError());
+    return HRT_OK;
+}
+
+// The fused launch into d_out on `stream` (the scene entered).
+static int bake_launch(hrt_scene *s, const float *d_points, const uint32_t *d_keys, uint32_t n, uint32_t first_sample, uint32_t n_samples,
+                       uint64_t seed, uint32_t flags, float *d_out, hipStream_t stream) {
+    DBake Q;
+    Q.points = (const float4 *)d_points;
+    Q.keys = d_keys;
+    Q.out = d_out;
+    Q.n = n;
+    Q.flags = flags;
+    Q.first_sample = first_sample;
+    Q.n_samples = n_samples;
+    Q.seed_lo = (uint32_t)seed;
+    Q.seed_hi = (uint32_t)(seed >> 32);
+    const bool exact = (flags & HRT_FLAG_EXACT_ONLY) != 0u;
+    const bool lights = s->d.n_lights != 0u;
+    void (*const k)(const DBake) = exact ? (lights ? hrt_bake_kernel_lights_exact : hrt_bake_kernel_exact)
+                                         : (lights ? hrt_bake_kernel_lights : hrt_bake_kernel);
+    return query_launch(k, Q, s, HRT_RADIANCE_STAGE_TREE, HRT_RADIANCE_WG, stream);  // the tree from global memory, as hrt_trace_radiance
+}
+
+int hrt_bake_device(hrt_scene *s, const float *d_points, const uint32_t *d_keys, uint32_t n, uint32_t first_sample, uint32_t n_samples,
+                    uint64_t seed, uint32_t flags, float *d_out, void *stream) {
+    const std::string who = "hrt_bake_device";
+    int rc = bake_flags_check(who, flags);
+    if (rc != HRT_OK || n == 0u) return rc;
+    if ((rc = bake_points_check(who, d_points, d_keys, n, true)) != HRT_OK) return rc;
+    if ((rc = lens_samples_check(who, first_sample, n_samples, d_out, "d_out")) != HRT_OK) return rc;
+    if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
+    return bake_launch(s, d_points, d_keys, n, first_sample, n_samples, seed, flags, d_out, (hipStream_t)stream);
+}
+
+// Blocking, from and into host memory.  The device buffers and the two events are the call's own, so that this form, too, leaves
+// the scene's state alone.
+int hrt_bake(hrt_scene *s, const float *points, const uint32_t *keys, uint32_t n, uint32_t spp, uint64_t seed, uint32_t flags, float *out,
+             hrt_stats *stats) {
+    const std::string who = "hrt_bake";
+    if (flags & HRT_RADIANCE_ACCUMULATE) return fail(HRT_ERR_INVALID, who + ": flags: HRT_RADIANCE_ACCUMULATE needs the running sums on the device (hrt_bake_device)");
+    int rc = bake_flags_check(who, flags);
+    if (rc != HRT_OK) return rc;
+    if (n == 0u) {
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        return HRT_OK;
+    }
+    if ((rc = bake_points_check(who, points, keys, n, false)) != HRT_OK) return rc;
+    if ((rc = lens_samples_check(who, 0u, spp, out, "out")) != HRT_OK) return rc;
+    if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t pbytes = (size_t)n * HRT_RAY_FLOATS * sizeof(float), kbytes = (size_t)n * sizeof(uint32_t), obytes = (size_t)n * 3u * sizeof(float);
+    float *d_points = nullptr, *d_out = nullptr;
+    uint32_t *d_keys = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    float ms = 0.f;
+    auto run = [&]() -> int {
+        HIP_TRY(hipMalloc((void **)&d_points, pbytes));
+        HIP_TRY(hipMalloc((void **)&d_out, obytes));
+        HIP_TRY(hipMemcpy(d_points, points, pbytes, hipMemcpyHostToDevice));
+        if (keys) {
+            HIP_TRY(hipMalloc((void **)&d_keys, kbytes));
+            HIP_TRY(hipMemcpy(d_keys, keys, kbytes, hipMemcpyHostToDevice));
+        }
+        HIP_TRY(hipEventCreate(&ev0));
+        HIP_TRY(hipEventCreate(&ev1));
+        HIP_TRY(hipEventRecord(ev0, nullptr));
+        const int lrc = bake_launch(s, d_points, d_keys, n, 0u, spp, seed, flags, d_out, nullptr);
+        if (lrc != HRT_OK) return lrc;
+        HIP_TRY(hipEventRecord(ev1, nullptr));
+        HIP_TRY(hipMemcpy(out, d_out, obytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+        return HRT_OK;
+    };
+    rc = run();
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (d_points) (void)hipFree(d_points);
+    if (d_keys) (void)hipFree(d_keys);
+    if (d_out) (void)hipFree(d_out);
+    if (rc != HRT_OK) return rc;
+    if (stats) {
+        fill_stats(s, stats, t0, (double)ms, (uint64_t)n * spp);
+        stats->lds_bytes = 0u;  // the tree is read from global memory
+        stats->waves_launched = 0u;
+    }
+    return HRT_OK;
+}
+
+int hrt_bake_quad_points(const hrt_quad *quad, uint32_t tw, uint32_t th, int32_t side, float time, float bias, float *out_points) {
+    std::string error;
+    const int rc = bakepts::quad_points(quad, tw, th, side, time, bias, out_points, error);
+    return rc == HRT_OK ? rc : fail(rc, error);
+}
+
+int hrt_bake_mesh_points(const float *positions, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles, float time, float bias,
+                         float *out_points) {
+    std::string error;
+    const int rc = bakepts::mesh_points(positions, n_vertices, indices, n_triangles, time, bias, out_points, error);
+    return rc == HRT_OK ? rc : fail(rc, error);
+}

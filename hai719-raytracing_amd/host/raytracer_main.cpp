@@ -29,6 +29,11 @@
 //                                                  THRESHOLD [--spp-min N]: per-tile counts under the lens (hrt_render_lens_adaptive).
 //                                                  With --views N [--orbit DEGREES]: N lens frames in ONE launch
 //                                                  (hrt_render_lens_views), cameras and seeds and files as --views has them
+//             [--bake-quad INDEX [--bake-side 1|-1] [--bake-bias B]] a lightmap (hrt_bake): --w x --h texels over quad INDEX of the
+//                                                  flattened scene (hrt_bake_quad_points: texel centres, the quad's normal times
+//                                                  the side, +1 the lit one), --spp cosine-weighted samples per texel; written
+//                                                  row-major in the frame's linear units, radiance / 6, without gamma (one GPU,
+//                                                  no other mode)
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -61,6 +66,9 @@ static double orbit_degrees = 0.0;    // --orbit: the camera's turn about the up
 static uint32_t n_views = 0;          // --views: hrt_render_views over that many cameras, --orbit degrees apart
 static bool use_lens = false;          // --lens: hrt_render_lens with the default camera behind the projection
 static hrt_lens lens_params = {{}, HRT_LENS_PERSPECTIVE, 0.f, 1.f, 0.f};
+static long bake_quad = -1;             // --bake-quad: hrt_bake over the texels of that quad of the flattened scene
+static int32_t bake_side = 1;
+static float bake_bias = 1e-4f;
 static hrt_temporal_params temporal_params = {0.02f, 64.f, 0.05f, 0.1f, 0.05f};  // the Python TemporalParams()
 
 // Drop-in for ray_trace_from_camera(): same inputs (current scene, nsamples, window size, camera),
@@ -183,6 +191,30 @@ static int ray_trace_lens() {
     return rc;
 }
 
+// --bake-quad: a --w x --h lightmap of one quad of the flattened scene
+static int bake_lightmap(const hrt_scene_desc &desc) {
+    const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
+    std::vector<float> points((size_t)w * h * HRT_RAY_FLOATS), map((size_t)w * h * 3, 0.f);
+    int rc = hrt_bake_quad_points(&desc.quads[bake_quad], w, h, bake_side, 0.f, bake_bias, points.data());
+    if (rc != HRT_OK) {
+        std::cout << "hrt_bake_quad_points failed: " << hrt_last_error() << std::endl;
+        return rc;
+    }
+    std::cout << "Baking a " << w << " x " << h << " lightmap of quad " << bake_quad << " (side " << bake_side << ", bias " << bake_bias
+              << ") on the GPU using " << nsamples << " samples per texel" << std::endl;
+    hrt_stats st;
+    rc = hrt_bake(device_scene, points.data(), nullptr, w * h, nsamples, seed, 0u, map.data(), &st);
+    if (rc != HRT_OK) {
+        std::cout << "hrt_bake failed: " << hrt_last_error() << std::endl;
+        return rc;
+    }
+    std::cout << "  Done in " << st.total_ms / 1000.0 << " seconds (kernel " << st.kernel_ms << " ms, " << (double)st.samples / st.kernel_ms / 1e3
+              << " Msamples/s)" << std::endl;
+    rc = hrt_write_ppm(out_path.c_str(), map.data(), w, h);
+    if (rc != HRT_OK) std::cout << hrt_last_error() << std::endl;
+    return rc;
+}
+
 static int ray_trace_from_camera() {
     const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
     std::vector<float> image((size_t)w * h * 3, 0.f);
@@ -250,6 +282,9 @@ int main(int argc, char **argv) {
         else if (k == "--aperture") lens_params.aperture_radius = strtof(v.c_str(), nullptr);
         else if (k == "--focus") lens_params.focus_distance = strtof(v.c_str(), nullptr);
         else if (k == "--lens-extent") lens_params.extent = strtof(v.c_str(), nullptr);
+        else if (k == "--bake-quad") bake_quad = strtol(v.c_str(), nullptr, 10);
+        else if (k == "--bake-side") bake_side = (int32_t)strtol(v.c_str(), nullptr, 10);
+        else if (k == "--bake-bias") bake_bias = strtof(v.c_str(), nullptr);
         else if (k == "--gpus") { devices.clear(); for (int d = 0; d < atoi(v.c_str()); ++d) devices.push_back(d); }
         else if (k == "--devices") {
             devices.clear();
@@ -310,6 +345,15 @@ int main(int argc, char **argv) {
         std::cerr << "--orbit turns the camera over the frames of --temporal or the cameras of --views: give --temporal FRAMES or --views N" << std::endl;
         return 2;
     }
+    const bool bake = bake_quad != -1;
+    if (bake && (adaptive || denoise || denoise_var || temporal || n_views != 0u || use_lens || !devices.empty())) {
+        std::cerr << "--bake-quad bakes a lightmap on one GPU: it cannot be combined with a render mode or --gpus / --devices" << std::endl;
+        return 2;
+    }
+    if (!bake && (bake_side != 1 || bake_bias != 1e-4f)) {
+        std::cerr << "--bake-side and --bake-bias describe a lightmap: give --bake-quad INDEX" << std::endl;
+        return 2;
+    }
     scene.asset_root = assets;
     if (!scene.setup_by_name(name, (float)SCREENWIDTH / (float)SCREENHEIGHT, seed)) {
         std::cerr << scene.error << std::endl;
@@ -320,6 +364,10 @@ int main(int argc, char **argv) {
         scene.kd_params.builder = hrt_kd_build_gpu;
     }
     std::unique_ptr<FlatScene> flat = scene.flatten();
+    if (bake && (bake_quad < 0 || (unsigned long)bake_quad >= flat->desc.n_quads)) {  // before any device is touched
+        std::cerr << "--bake-quad " << bake_quad << ": the scene has " << flat->desc.n_quads << " quads" << std::endl;
+        return 2;
+    }
     const int up = devices.empty() ? (hrt_init(gpu) != HRT_OK ? HRT_ERR_DEVICE : hrt_scene_create(&flat->desc, &device_scene))
                                    : hrt_multi_create(&flat->desc, (uint32_t)devices.size(), devices.data(), &multi);
     if (up != HRT_OK) {
@@ -331,7 +379,7 @@ int main(int argc, char **argv) {
         std::cout << "Image tiles across " << devices.size() << " GPU slot(s), gather: " << hrt_multi_gather(multi)
                   << (note.empty() ? "" : " (" + note + ")") << std::endl;
     }
-    int rc = n_views ? ray_trace_views() : use_lens ? ray_trace_lens() : temporal ? ray_trace_frames() : ray_trace_from_camera();  // the 'r' key, once or frame after frame
+    int rc = bake ? bake_lightmap(flat->desc) : n_views ? ray_trace_views() : use_lens ? ray_trace_lens() : temporal ? ray_trace_frames() : ray_trace_from_camera();  // the 'r' key, once or frame after frame
     hrt_scene_destroy(device_scene);
     hrt_multi_destroy(multi);
     hrt_shutdown();

@@ -837,6 +837,70 @@ HRT_API int hrt_render_lens_adaptive(hrt_scene *scene, const hrt_lens *lens, uin
                                      uint64_t seed, uint32_t flags, float *out_rgb, uint32_t *out_tile_spp /* may be NULL */,
                                      hrt_stats *stats /* may be NULL */);
 
+/* ---- Baking: the radiance arriving at caller-supplied surface points (lightmaps, per-vertex irradiance) in one launch.
+ * POINTS: n records of HRT_RAY_FLOATS floats (32 bytes, the array 16-byte aligned), device memory: the layout of a ray record with
+ * the normal in place of the direction and the bias in place of tmax, {P.x, P.y, P.z, time, N.x, N.y, N.z, bias}.  Point i has the
+ * key k = d_keys ? d_keys[i] : i.
+ * THE RULE (the ray of sample s of point i; tests/bake_ref.py states it again in NumPy).  All arithmetic is fp32 without fused
+ * multiply-add, in the order written; sqrtf, sinf, cosf and copysignf are the device's; normalize is the trace path's own (divide
+ * by the length):
+ *   Nn  = normalize(N)
+ *   b0, b1 = draws 0 and 1 of stream (seed, k, s)   -- the slots the camera uses for u, v; a radiance path starts at draw 3
+ *   r   = sqrtf(b0), phi = 6.2831855f * b1
+ *   x   = r * cosf(phi), y = r * sinf(phi), z = sqrtf(1.f - b0)                       -- cosine-weighted about +z
+ *   sg  = copysignf(1.f, Nn.z), a = -1.f / (sg + Nn.z), b = (Nn.x * Nn.y) * a          -- a branch-free frame without a pole
+ *   T   = (1.f + (sg * (Nn.x * Nn.x)) * a, sg * b, (-sg) * Nn.x)
+ *   B   = (b, sg + (Nn.y * Nn.y) * a, -Nn.y)
+ *   d   = normalize((x * T + y * B) + z * Nn)
+ *   O   = P + bias * Nn
+ *   ray = {O, time, d, +inf}
+ * `time` places the scene's moving objects; the point stays where it is.
+ * DEGENERATE: a point is degenerate when one of its eight floats is not finite, bias < 0, N == 0, or Nn has a component that is not
+ * finite or is 0 (a normal whose squared length underflows).  A sample is degenerate when its point is, or when a component of O or
+ * d is not finite, or d == 0.  hrt_bake_rays writes a degenerate sample as {P, time, 0, 0, 0, +inf}: d == 0 is the query layer's own
+ * rule for "not traced", the convention of hrt_lens_rays.  In a bake it adds nothing and still counts in the divisor: a degenerate
+ * point gives 0 in mean mode and leaves its sums as they are under HRT_RADIANCE_ACCUMULATE, exactly as a degenerate ray does in
+ * hrt_trace_radiance.
+ * UNITS: the output is what hrt_trace_radiance gives, the mean over samples of radiance / 6.  The directions have the density
+ * cos(theta) / pi about Nn, so the irradiance at the point is pi times the mean radiance; the calls apply NO factor.
+ * hrt_bake_rays: the ray records of one sample (n records, device, 16-byte aligned) -- the sibling of hrt_camera_rays and
+ * hrt_lens_rays.  No scene: it runs on the calling thread's current device, asynchronously on `stream`.
+ * hrt_bake_device: the fused bake, 3 floats per point at d_out[3i .. 3i+2], with no ray buffer: the mean over samples
+ * [first_sample, first_sample + n_samples), or with HRT_RADIANCE_ACCUMULATE the running sums, exactly as hrt_trace_radiance's
+ * output.  Asynchronous on `stream`; touches none of the scene's per-launch state, so it may overlap a render of the same scene.
+ * CONTRACT A: bit-identical to composing, for s in order, hrt_bake_rays(s) and hrt_trace_radiance(first_sample = s, n_samples = 1,
+ * the same d_keys), summed in fp32 and divided by (float)n_samples -- for every scene and flag set.
+ * Flags: HRT_FLAG_EXACT_ONLY, HRT_FLAG_MESH_BRUTE (with EXACT_ONLY), HRT_FLAG_NO_LDS_TREE, HRT_RADIANCE_ACCUMULATE.  Every other
+ * bit is refused by name; that includes HRT_RAYS_NORMALIZE (the normal is always normalised), HRT_FLAG_GAMMA and the kernel-form
+ * flags.
+ * hrt_bake: the same from and into HOST buffers (`points`, `keys`, `out`; 4-byte aligned), blocking, samples [0, spp); stats as
+ * hrt_render_lens (kernel_ms from events, samples = n * spp; n == 0 zeroes them).  HRT_RADIANCE_ACCUMULATE is refused (the sums
+ * live on the device).
+ * Checked in this order before the scene and the library state, HRT_ERR_INVALID with hrt_last_error() naming the entry point and
+ * the culprit: flags; (n == 0 returns HRT_OK here and launches nothing;) d_points NULL or not 16-byte aligned; d_keys not 4-byte
+ * aligned; n > 2^31 - 1; n_samples == 0; first_sample + n_samples > 2^32; the output NULL or misaligned (d_rays 16 bytes, d_out
+ * 4); then a NULL scene.
+ * POINT GENERATORS (host only: no device, no hrt_init; fp32 in the order written, restated in tests/bake_ref.py):
+ * hrt_bake_quad_points writes tw * th records, row-major, texel (i, j) at index j*tw + i:
+ *   P = (v0 + ((i + .5f)/tw) * (v1 - v0)) + ((j + .5f)/th) * (v3 - v0),  N = side * normalize(cross(v1 - v0, v3 - v0))
+ * with side +1 or -1; +1 is the side the trace path lights (Square::intersect culls d.n > 0 for non-glass quads).
+ * hrt_bake_mesh_points writes one record per vertex (positions: 3 floats per vertex, indices: 3 per triangle): N is the sum, over
+ * the triangles that use the vertex in ascending triangle order, of cross(p1 - p0, p2 - p0), left unnormalised (the bake
+ * normalises it); a vertex that no triangle uses gets N = 0, a degenerate point.  An index >= n_vertices is refused before
+ * anything is written.
+ * Both refuse (HRT_ERR_INVALID, by name) NULL pointers, tw or th zero, tw*th > 2^31 - 1, side other than +1 / -1, and a time or
+ * bias that is not finite.
+ * OUT OF SCOPE (DESIGN.md section 5 "Baking"): spherical-harmonic probes, jitter inside a texel, points that follow a moving quad,
+ * sphere and mesh-texel parametrisations, denoising of lightmaps, the streaming kernel, multi-GPU. */
+HRT_API int hrt_bake_rays(const float *d_points, const uint32_t *d_keys, uint32_t n, uint32_t sample, uint64_t seed, float *d_rays, void *stream);
+HRT_API int hrt_bake_device(hrt_scene *scene, const float *d_points, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
+                            uint32_t n_samples, uint64_t seed, uint32_t flags, float *d_out, void *stream);
+HRT_API int hrt_bake(hrt_scene *scene, const float *points, const uint32_t *keys, uint32_t n, uint32_t spp, uint64_t seed, uint32_t flags,
+                     float *out, hrt_stats *stats /* may be NULL */);
+HRT_API int hrt_bake_quad_points(const hrt_quad *quad, uint32_t tw, uint32_t th, int32_t side, float time, float bias, float *out_points);
+HRT_API int hrt_bake_mesh_points(const float *positions, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles, float time,
+                                 float bias, float *out_points);
+
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
  * format 6: the same integers as bytes (binary PPM; negative values, which P3 prints with a sign, clamp to 0).
