@@ -657,55 +657,65 @@ class DeviceScene:
         earlier samples and is updated in place).  A contiguous float32 torch tensor on the GPU runs on the current torch stream of its
         device and gives a torch tensor there, without synchronising; anything else is taken as NumPy and comes back as NumPy.
         ``flags``: FLAG_EXACT_ONLY, FLAG_MESH_BRUTE, FLAG_NO_LDS_TREE; ``normalize`` adds RAYS_NORMALIZE."""
-        import torch
         flags = int(flags) | (RAYS_NORMALIZE if normalize else 0) | (RADIANCE_ACCUMULATE if accumulate else 0)
-        is_torch = isinstance(rays, torch.Tensor)
+        return DeviceScene._radiance_batch(self, "trace_radiance", "rays", "hrt_trace_radiance", None, rays, spp, first_sample, seed, keys,
+                                           out, accumulate, flags, None)
+
+    def _radiance_batch(self, who: str, noun: str, device_fn: str, blocking_fn: Optional[str], batch, spp, first_sample, seed, keys, out, accumulate, flags, stats):
+        """What trace_radiance and bake share: ``batch`` ((n, RAY_FLOATS) float32, the ``noun`` of the messages), ``keys`` and ``out``
+        checked as torch tensors on one GPU or as NumPy -- before ``self`` is touched -- then the entry point ``device_fn``
+        (hrt_trace_radiance's signature) on the current torch stream; a NumPy batch is uploaded, and its result copied back.
+        ``blocking_fn`` (hrt_bake's signature), if given, takes a NumPy batch of samples [0, spp) without ``out`` instead, and fills
+        ``stats``."""
+        import torch
+        is_torch = isinstance(batch, torch.Tensor)
         if is_torch:
-            if (rays.device.type != "cuda" or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != RAY_FLOATS
-                    or not rays.is_contiguous()):
-                raise ValueError("trace_radiance: a torch tensor must be a contiguous (n, 8) float32 tensor on the GPU")
-            d_rays = rays
+            if (batch.device.type != "cuda" or batch.dtype != torch.float32 or batch.dim() != 2 or batch.shape[1] != RAY_FLOATS
+                    or not batch.is_contiguous()):
+                raise ValueError(f"{who}: a torch tensor must be a contiguous (n, 8) float32 tensor on the GPU")
         else:
-            a = np.ascontiguousarray(rays, dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != RAY_FLOATS:
-                raise ValueError(f"trace_radiance: rays must have shape (n, {RAY_FLOATS}) (got {a.shape})")
-        n = rays.shape[0] if is_torch else a.shape[0]
+            batch = np.ascontiguousarray(batch, dtype=np.float32)
+            if batch.ndim != 2 or batch.shape[1] != RAY_FLOATS:
+                raise ValueError(f"{who}: {noun} must have shape (n, {RAY_FLOATS}) (got {batch.shape})")
+        n = batch.shape[0]
         if n > 0x7FFFFFFF:
-            raise ValueError(f"trace_radiance: at most 2^31 - 1 rays per call (got {n})")
-        if keys is not None and not is_torch:
-            k = np.ascontiguousarray(keys)
-            if k.shape != (n,) or k.dtype not in (np.uint32, np.int32):
-                raise ValueError(f"trace_radiance: keys must be (n,) uint32 (got {k.shape} {k.dtype})")
-        if not is_torch:
-            d_rays = torch.from_numpy(a).to("cuda")
-        dev = d_rays.device
-        d_keys = None
+            raise ValueError(f"{who}: at most 2^31 - 1 {noun} per call (got {n})")
         if keys is not None:
             if is_torch:
-                if (not isinstance(keys, torch.Tensor) or keys.device != dev or keys.dtype not in (torch.int32, torch.uint32)
+                if (not isinstance(keys, torch.Tensor) or keys.device != batch.device or keys.dtype not in (torch.int32, torch.uint32)
                         or keys.shape != (n,) or not keys.is_contiguous()):
-                    raise ValueError("trace_radiance: keys must be a contiguous (n,) int32 tensor on the rays' device")
-                d_keys = keys
+                    raise ValueError(f"{who}: keys must be a contiguous (n,) int32 tensor on the {noun}' device")
             else:
-                d_keys = torch.from_numpy(k.view(np.int32)).to(dev)
+                keys = np.ascontiguousarray(keys)
+                if keys.shape != (n,) or keys.dtype not in (np.uint32, np.int32):
+                    raise ValueError(f"{who}: keys must be (n,) uint32 (got {keys.shape} {keys.dtype})")
         if out is None:
             if accumulate and first_sample != 0:
-                raise ValueError("trace_radiance: accumulate after sample 0 needs the running sums in `out`")
-            d_out = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+                raise ValueError(f"{who}: accumulate after sample 0 needs the running sums in `out`")
         elif is_torch:
-            if (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float32 or out.shape != (n, 3)
+            if (not isinstance(out, torch.Tensor) or out.device != batch.device or out.dtype != torch.float32 or out.shape != (n, 3)
                     or not out.is_contiguous()):
-                raise ValueError("trace_radiance: out must be a contiguous (n, 3) float32 tensor on the rays' device")
-            d_out = out
+                raise ValueError(f"{who}: out must be a contiguous (n, 3) float32 tensor on the {noun}' device")
         else:
             o = np.asarray(out)
             if o.shape != (n, 3) or o.dtype != np.float32:
-                raise ValueError(f"trace_radiance: out must be (n, 3) float32 (got {o.shape} {o.dtype})")
-            d_out = torch.from_numpy(np.ascontiguousarray(o)).to(dev)
-        s = torch.cuda.current_stream(dev)
-        self._check(self._lib.hrt_trace_radiance(self._h, C.c_void_p(d_rays.data_ptr()),
-                                                 None if d_keys is None else C.c_void_p(d_keys.data_ptr()), n, first_sample, spp,
-                                                 seed, flags, C.c_void_p(d_out.data_ptr()), C.c_void_p(s.cuda_stream)))
+                raise ValueError(f"{who}: out must be (n, 3) float32 (got {o.shape} {o.dtype})")
+        if blocking_fn is not None and not is_torch and out is None and not accumulate and first_sample == 0:
+            r = np.empty((n, 3), dtype=np.float32)
+            self._check(getattr(self._lib, blocking_fn)(self._h, batch.ctypes.data, None if keys is None else keys.ctypes.data, n, spp, seed, flags,
+                                                        r.ctypes.data, None if stats is None else C.byref(stats)))
+            return r
+        if is_torch:
+            d_batch, d_keys, d_out = batch, keys, out
+        else:
+            d_batch = torch.from_numpy(batch).to("cuda")
+            d_keys = None if keys is None else torch.from_numpy(keys.view(np.int32)).to(d_batch.device)
+            d_out = None if out is None else torch.from_numpy(np.ascontiguousarray(o)).to(d_batch.device)
+        if d_out is None:
+            d_out = torch.zeros((n, 3), dtype=torch.float32, device=d_batch.device)
+        s = torch.cuda.current_stream(d_batch.device)
+        self._check(getattr(self._lib, device_fn)(self._h, C.c_void_p(d_batch.data_ptr()), None if d_keys is None else C.c_void_p(d_keys.data_ptr()),
+                                                  n, first_sample, spp, seed, flags, C.c_void_p(d_out.data_ptr()), C.c_void_p(s.cuda_stream)))
         if is_torch:
             return d_out
         r = d_out.cpu().numpy()
@@ -725,64 +735,9 @@ class DeviceScene:
         tensor there (``out``, if given, a device tensor), without synchronising (hrt_bake_device).  Anything else is taken as NumPy
         and comes back as NumPy; samples [0, spp) without ``out`` go through the blocking hrt_bake, which fills ``stats`` if given.
         ``flags``: FLAG_EXACT_ONLY, FLAG_MESH_BRUTE, FLAG_NO_LDS_TREE."""
-        import torch
         flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
-        is_torch = isinstance(points, torch.Tensor)
-        if is_torch:
-            if (points.device.type != "cuda" or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != RAY_FLOATS
-                    or not points.is_contiguous()):
-                raise ValueError("bake: a torch tensor must be a contiguous (n, 8) float32 tensor on the GPU")
-        else:
-            a = np.ascontiguousarray(points, dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != RAY_FLOATS:
-                raise ValueError(f"bake: points must have shape (n, {RAY_FLOATS}) (got {a.shape})")
-        n = points.shape[0] if is_torch else a.shape[0]
-        if n > 0x7FFFFFFF:
-            raise ValueError(f"bake: at most 2^31 - 1 points per call (got {n})")
-        k = None
-        if keys is not None:
-            if is_torch:
-                if (not isinstance(keys, torch.Tensor) or keys.device != points.device or keys.dtype not in (torch.int32, torch.uint32)
-                        or keys.shape != (n,) or not keys.is_contiguous()):
-                    raise ValueError("bake: keys must be a contiguous (n,) int32 tensor on the points' device")
-            else:
-                k = np.ascontiguousarray(keys)
-                if k.shape != (n,) or k.dtype not in (np.uint32, np.int32):
-                    raise ValueError(f"bake: keys must be (n,) uint32 (got {k.shape} {k.dtype})")
-        if out is None:
-            if accumulate and first_sample != 0:
-                raise ValueError("bake: accumulate after sample 0 needs the running sums in `out`")
-        elif is_torch:
-            if (not isinstance(out, torch.Tensor) or out.device != points.device or out.dtype != torch.float32 or out.shape != (n, 3)
-                    or not out.is_contiguous()):
-                raise ValueError("bake: out must be a contiguous (n, 3) float32 tensor on the points' device")
-        else:
-            o = np.asarray(out)
-            if o.shape != (n, 3) or o.dtype != np.float32:
-                raise ValueError(f"bake: out must be (n, 3) float32 (got {o.shape} {o.dtype})")
-        if not is_torch and out is None and not accumulate and first_sample == 0:
-            r = np.empty((n, 3), dtype=np.float32)
-            self._check(self._lib.hrt_bake(self._h, a.ctypes.data, None if k is None else k.ctypes.data, n, spp, seed, flags, r.ctypes.data,
-                                           None if stats is None else C.byref(stats)))
-            return r
-        if is_torch:
-            d_points, d_keys = points, keys
-            d_out = torch.zeros((n, 3), dtype=torch.float32, device=points.device) if out is None else out
-        else:
-            d_points = torch.from_numpy(a).to("cuda")
-            d_keys = None if k is None else torch.from_numpy(k.view(np.int32)).to(d_points.device)
-            d_out = (torch.zeros((n, 3), dtype=torch.float32, device=d_points.device) if out is None
-                     else torch.from_numpy(np.ascontiguousarray(o)).to(d_points.device))
-        s = torch.cuda.current_stream(d_points.device)
-        self._check(self._lib.hrt_bake_device(self._h, C.c_void_p(d_points.data_ptr()), None if d_keys is None else C.c_void_p(d_keys.data_ptr()),
-                                              n, first_sample, spp, seed, flags, C.c_void_p(d_out.data_ptr()), C.c_void_p(s.cuda_stream)))
-        if is_torch:
-            return d_out
-        r = d_out.cpu().numpy()
-        if out is not None:
-            out[...] = r
-            return out
-        return r
+        return DeviceScene._radiance_batch(self, "bake", "points", "hrt_bake_device", "hrt_bake", points, spp, first_sample, seed, keys, out,
+                                           accumulate, flags, stats)
 
     def render_views(self, cams, w: int, h: int, spp: int, seeds=None, flags: int = 0, out=None, stats: Optional[Stats] = None):
         """hrt_render_views: every camera of ``cams`` as a w x h frame of ``spp`` samples, in one launch -> (n, h, w, 3) float32;

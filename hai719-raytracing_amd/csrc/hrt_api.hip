@@ -147,6 +147,97 @@ struct Scratch {
     }
 };
 
+// The last launch that read a buffer of a scene's, for whoever writes or frees that buffer next.  Launches on one stream are ordered
+// by the stream; a writer on another stream first waits for `done` there (wait_on), and the host waits for it before the buffer
+// is freed (sync).
+struct LastReader {
+    hipEvent_t done = nullptr;
+    bool used = false;
+    hipStream_t stream = nullptr;  // of the reader
+    int ready() {
+        if (!done) HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        return HRT_OK;
+    }
+    int wait_on(hipStream_t on) {  // before the first write enqueued on `on`
+        if (const int rc = ready()) return rc;
+        if (used && stream != on) HIP_TRY(hipStreamWaitEvent(on, done, 0));
+        return HRT_OK;
+    }
+    int sync() {  // host wait, before the buffer is freed
+        if (used) HIP_TRY(hipEventSynchronize(done));
+        return HRT_OK;
+    }
+    int mark(hipStream_t on) {  // after the launch on `on` that reads the buffer
+        HIP_TRY(hipEventRecord(done, on));
+        used = true;
+        stream = on;
+        return HRT_OK;
+    }
+    void release() {
+        if (done) (void)hipEventDestroy(done);
+        done = nullptr; used = false;
+    }
+};
+
+// A per-launch table of T in device memory that a call fills from the host: a grow-only device table, its pinned staging copy (the
+// caller's entries are free when the call returns) with the event that says the upload has read it, and the table's last reader.
+// T may be incomplete where the table is declared.  stage() is the whole sequence; the trace path (hrt_views.hip) runs its parts
+// itself, because its upload belongs behind launch_trace's own cross-stream wait.
+template <class T>
+struct StagedTable {
+    Scratch dev;
+    T *host = nullptr;
+    size_t host_cap = 0;  // in entries
+    hipEvent_t uploaded = nullptr;
+    bool uploading = false;
+    LastReader reader;
+    const T *table() const { return dev.as<T>(); }
+    // The entries into the staging copy and room for them on the device.  The staging copy is reused by every call: wait until
+    // the previous call's upload has read it (that upload sits in front of its kernel, so this does not wait for the kernel).
+    // sync_reader: the host waits for the table's last reader before a larger table replaces (frees) the old one.  false only where
+    // the caller's launches are ordered behind one another by other means.
+    int fill(const std::vector<T> &entries, bool sync_reader) {
+        const size_t bytes = entries.size() * sizeof(T);
+        if (uploading) { HIP_TRY(hipEventSynchronize(uploaded)); uploading = false; }
+        if (!uploaded) HIP_TRY(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
+        if (const int rc = reader.ready()) return rc;
+        if (host_cap < entries.size()) {
+            if (host) (void)hipHostFree(host);
+            host = nullptr; host_cap = 0;
+            HIP_TRY(hipHostMalloc((void **)&host, bytes, hipHostMallocDefault));
+            host_cap = entries.size();
+        }
+        std::memcpy(host, entries.data(), bytes);
+        if (sync_reader && dev.cap < bytes)
+            if (const int rc = reader.sync()) return rc;
+        return dev.grow(bytes);
+    }
+    // The staged entries to the device on `stream`, behind whatever the caller has made `stream` wait for.
+    int upload(size_t n, hipStream_t stream) {
+        HIP_TRY(hipMemcpyAsync(dev.p, host, n * sizeof(T), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(uploaded, stream));
+        uploading = true;
+        return HRT_OK;
+    }
+    // fill, wait on `stream` for a last reader on another stream, upload: *out is ready for a launch on `stream`, which staged() follows.
+    int stage(const std::vector<T> &entries, hipStream_t stream, const T **out) {
+        int rc = fill(entries, true);
+        if (rc == HRT_OK) rc = reader.wait_on(stream);
+        if (rc == HRT_OK) rc = upload(entries.size(), stream);
+        *out = table();
+        return rc;
+    }
+    int staged(hipStream_t stream) { return reader.mark(stream); }
+    void release() {
+        dev.release();
+        if (host) (void)hipHostFree(host);
+        host = nullptr; host_cap = 0;
+        if (uploaded) (void)hipEventDestroy(uploaded);
+        uploaded = nullptr; uploading = false;
+        reader.release();
+    }
+};
+
 // w x h is a frame of at most max_pixels pixels (2^31 - 1 where pixels are indexed, 2^31 / 16 where 16-byte records of them are).
 int check_frame(const std::string &who, uint32_t w, uint32_t h, uint64_t max_pixels) {
     if (!w || !h) return fail(HRT_ERR_INVALID, who + ": w and h must be positive (got " + std::to_string(w) + " x " + std::to_string(h) + ")");
@@ -263,36 +354,22 @@ struct hrt_scene {
     const KernelBuild *last_build = nullptr;  // the row of k_builds the last trace launch ran (hrt_debug_last_kernel)
     hipStream_t last_stream = nullptr;  // stream of the previous launch on this scene
     int device = 0;                     // the device that holds this scene (current when it was created)
-    // hrt_render_features' own camera block, with its host copy and the event that orders feature launches across streams
+    // hrt_render_features' own camera block, with its host copy and the launch that read it last (feature launches are ordered
+    // across streams)
     DCamera *d_cam_feat = nullptr;
     DCamera h_cam_feat{};
-    hipEvent_t ev_feat = nullptr;
-    bool feat_used = false;
-    hipStream_t feat_stream = nullptr;
-    // Batched views (hrt_views.hip): the per-view blocks of the launch in hand on the device, their pinned host staging copy (the
-    // caller's views are free when the call returns) with the event that says the upload has read it, the item-major tile sums of
-    // all views with the event and stream of the assemble launch that read them last, and the host form's frames.
-    Scratch vw_blocks, vw_tiles, vw_frames;
-    DView *h_views = nullptr;
-    size_t h_views_cap = 0;  // in views
-    hipEvent_t ev_views = nullptr, ev_views_done = nullptr;
-    bool views_uploading = false, views_used = false;
-    hipStream_t views_stream = nullptr;
-    // Batched lens views (hrt_lens.hip): the table of per-view blocks on the device, its pinned host staging copy with the event that
-    // says the upload has read it, and the event and stream of the launch that read the table last.  Nothing of the trace launches.
-    Scratch lv_blocks;
-    DLensView *h_lv = nullptr;
-    size_t h_lv_cap = 0;  // in views
-    hipEvent_t ev_lv = nullptr, ev_lv_done = nullptr;
-    bool lv_uploading = false, lv_used = false;
-    hipStream_t lv_stream = nullptr;
-    // Adaptive lens frames (hrt_lens_adaptive.hip): the tile-major sums of the whole frame, the host form's row-major frame, and the
-    // event and stream of the assemble launch that read the sums last.  The rounds' lists and keep words are ad_compact / ad_words,
-    // shared with hrt_render_adaptive.  Nothing of the trace launches.
+    LastReader feat_reader;
+    // Batched views (hrt_views.hip): the per-view blocks of the launch in hand (its last reader is the assemble launch, which also
+    // read the tile sums last), the item-major tile sums of all views, and the host form's frames.
+    StagedTable<DView> views;
+    Scratch vw_tiles, vw_frames;
+    // Batched lens views (hrt_lens.hip): the table of per-view blocks.  Nothing of the trace launches.
+    StagedTable<DLensView> lens_views;
+    // Adaptive lens frames (hrt_lens_adaptive.hip): the tile-major sums of the whole frame with the assemble launch that read them
+    // last, and the host form's row-major frame.  The rounds' lists and keep words are ad_compact / ad_words, shared with
+    // hrt_render_adaptive.  Nothing of the trace launches.
     Scratch la_tiles, la_frame;
-    hipEvent_t ev_la_done = nullptr;
-    bool la_used = false;
-    hipStream_t la_stream = nullptr;
+    LastReader la_reader;
 };
 
 namespace {
@@ -393,17 +470,11 @@ void hrt_scene_destroy(hrt_scene *s) {
     if (s->d_cam_aov) (void)hipFree(s->d_cam_aov);
     for (Scratch *b : s->scratch()) b->release();
     if (s->d_cam_feat) (void)hipFree(s->d_cam_feat);
-    if (s->ev_feat) (void)hipEventDestroy(s->ev_feat);
-    for (Scratch *b : {&s->vw_blocks, &s->vw_tiles, &s->vw_frames}) b->release();
-    if (s->h_views) (void)hipHostFree(s->h_views);
-    if (s->ev_views) (void)hipEventDestroy(s->ev_views);
-    if (s->ev_views_done) (void)hipEventDestroy(s->ev_views_done);
-    s->lv_blocks.release();
-    if (s->h_lv) (void)hipHostFree(s->h_lv);
-    if (s->ev_lv) (void)hipEventDestroy(s->ev_lv);
-    if (s->ev_lv_done) (void)hipEventDestroy(s->ev_lv_done);
-    for (Scratch *b : {&s->la_tiles, &s->la_frame}) b->release();
-    if (s->ev_la_done) (void)hipEventDestroy(s->ev_la_done);
+    s->feat_reader.release();
+    s->views.release();
+    s->lens_views.release();
+    for (Scratch *b : {&s->vw_tiles, &s->vw_frames, &s->la_tiles, &s->la_frame}) b->release();
+    s->la_reader.release();
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     delete s;
@@ -634,8 +705,8 @@ struct TraceJob {
     // (device, list_n rank slots; adaptive sampling): only those tiles, into a COMPACT d_tiles (entry j of the list at slot j).
     const uint32_t *list = nullptr;
     uint32_t list_n = 0;
-    // != 0 (batched views, hrt_views.hip; rank 0 of world 1, no list, no accumulation): the n_views blocks staged in s->h_views are
-    // uploaded to s->vw_blocks in place of the camera block, and the queue is n_views x the frame's tiles, view-major; cam is view
+    // != 0 (batched views, hrt_views.hip; rank 0 of world 1, no list, no accumulation): the n_views blocks staged in s->views are
+    // uploaded to its device table in place of the camera block, and the queue is n_views x the frame's tiles, view-major; cam is view
     // 0's, seed is not used.  The kernel-form and grid choices see the list's tiles, or all views'.
     uint32_t n_views = 0;
 };
@@ -650,7 +721,7 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, const TraceJob &J) 
         R.tiles_owned = J.list_n;
     }
     if (J.n_views) {
-        R.views = s->vw_blocks.as<DView>();
+        R.views = s->views.table();
         R.tiles_owned = J.n_views * R.tiles_total;
     }
     R.cam = s->d_cam;
@@ -677,9 +748,7 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, const TraceJob &J) 
     if (s->timed && s->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->ev1, 0));
     s->last_stream = stream;
     if (J.n_views) {
-        HIP_TRY(hipMemcpyAsync(s->vw_blocks.p, s->h_views, (size_t)J.n_views * sizeof(DView), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipEventRecord(s->ev_views, stream));
-        s->views_uploading = true;
+        if ((rc = s->views.upload(J.n_views, stream)) != HRT_OK) return rc;
     } else if (!s->cam_valid || std::memcmp(&C, &s->h_cam, sizeof(C)) != 0) {
         s->h_cam = C;
         HIP_TRY(hipMemcpyAsync(s->d_cam, &s->h_cam, sizeof(C), hipMemcpyHostToDevice, stream));

@@ -11,8 +11,8 @@
 //
 // All of it is fp32 without fused multiply-add (the library is built with -ffp-contract=off), in the order the header writes.
 
-// The launch record of the hrt_bake_kernel builds: DRadiance with the point records in place of the rays (query_launch and
-// radiance_body read the fields they share by name).
+// The launch record of the hrt_bake_kernel builds: DRadiance with the point records in place of the rays (radiance_launch,
+// query_launch and radiance_body reach the fields they share by name).
 struct DBake {
     const DScene *scene;
     const float4 *points;  // 2 float4 per point: {P, time} {N, bias}
@@ -93,26 +93,13 @@ extern "C" __global__ void __launch_bounds__(256) hrt_bake_rays_kernel(const flo
     out[2u * i + 1u] = make_float4(r.d.x, r.d.y, r.d.z, __builtin_inff());
 }
 
-// The fused bake: radiance_body over points.  Launch bounds and shape are hrt_lens_kernel's.
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_bake_kernel(const DBake Q) { radiance_body<false, false, BakeRays>(Q); }
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_bake_kernel_lights(const DBake Q) { radiance_body<true, false, BakeRays>(Q); }
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_bake_kernel_exact(const DBake Q) { radiance_body<false, true, BakeRays>(Q); }
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_bake_kernel_lights_exact(const DBake Q) { radiance_body<true, true, BakeRays>(Q); }
+// The fused bake: radiance_body over points.
+HRT_RADIANCE_FAMILY(hrt_bake_kernel, BakeRays, DBake)
 
 // The flags of a bake.
 static int bake_flags_check(const std::string &who, uint32_t flags) {
-    static const struct { uint32_t bit; const char *name; const char *why; } refused[] = {
-        {HRT_FLAG_WAVE_KERNEL, "HRT_FLAG_WAVE_KERNEL", "a bake has one kernel form"},
-        {HRT_FLAG_STREAM_KERNEL, "HRT_FLAG_STREAM_KERNEL", "a bake has one kernel form"},
-        {HRT_FLAG_DUAL_KERNEL, "HRT_FLAG_DUAL_KERNEL", "a bake has one kernel form"},
-        {HRT_FLAG_NO_SHADOW_CULL, "HRT_FLAG_NO_SHADOW_CULL", "the query kernels have no such build"},
-        {HRT_RAYS_NORMALIZE, "HRT_RAYS_NORMALIZE", "the normal of a bake point is always normalised"},
-        {HRT_FLAG_GAMMA, "HRT_FLAG_GAMMA", "a bake is linear radiance, not a frame"}};
-    for (const auto &f : refused)
-        if (flags & f.bit) return fail(HRT_ERR_INVALID, who + ": flags: " + f.name + ": " + f.why);
-    const uint32_t known = HRT_FLAG_EXACT_ONLY | HRT_FLAG_MESH_BRUTE | HRT_FLAG_NO_LDS_TREE | HRT_RADIANCE_ACCUMULATE;
-    if (flags & ~known) return fail(HRT_ERR_INVALID, who + ": flags: unknown bits " + std::to_string(flags & ~known));
-    return check_mesh_brute(who, flags);
+    return fused_flags_check(who, flags, "a bake has one kernel form", "the normal of a bake point is always normalised",
+                             "a bake is linear radiance, not a frame");
 }
 
 // Checks 3..5 of the header's order: the point records, the keys, the count.  `dev`: device pointers (d_ names, 16-byte records).
@@ -130,9 +117,7 @@ int hrt_bake_rays(const float *d_points, const uint32_t *d_keys, uint32_t n, uin
     const std::string who = "hrt_bake_rays";
     if (n == 0u) return HRT_OK;
     { const int prc = bake_points_check(who, d_points, d_keys, n, true); if (prc != HRT_OK) return prc; }
-    if (!d_rays) return fail(HRT_ERR_INVALID, who + ": d_rays is NULL");
-    if ((uintptr_t)d_rays % 16u) return fail(HRT_ERR_INVALID, who + ": d_rays is not 16-byte aligned");
-    if (!g_rt.ready) return fail(HRT_ERR_STATE, who + ": call hrt_init first");
+    { const int rrc = rays_out_check(who, d_rays); if (rrc != HRT_OK) return rrc; }
     hipLaunchKernelGGL(hrt_bake_rays_kernel, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, (const float4 *)d_points, d_keys, n, sample,
                        (uint32_t)seed, (uint32_t)(seed >> 32), (float4 *)d_rays);
     HIP_TRY(hipGetLastError());
@@ -145,18 +130,7 @@ static int bake_launch(hrt_scene *s, const float *d_points, const uint32_t *d_ke
     DBake Q;
     Q.points = (const float4 *)d_points;
     Q.keys = d_keys;
-    Q.out = d_out;
-    Q.n = n;
-    Q.flags = flags;
-    Q.first_sample = first_sample;
-    Q.n_samples = n_samples;
-    Q.seed_lo = (uint32_t)seed;
-    Q.seed_hi = (uint32_t)(seed >> 32);
-    const bool exact = (flags & HRT_FLAG_EXACT_ONLY) != 0u;
-    const bool lights = s->d.n_lights != 0u;
-    void (*const k)(const DBake) = exact ? (lights ? hrt_bake_kernel_lights_exact : hrt_bake_kernel_exact)
-                                         : (lights ? hrt_bake_kernel_lights : hrt_bake_kernel);
-    return query_launch(k, Q, s, HRT_RADIANCE_STAGE_TREE, HRT_RADIANCE_WG, stream);  // the tree from global memory, as hrt_trace_radiance
+    return radiance_launch(hrt_bake_kernel_builds, Q, s, first_sample, n_samples, seed, flags, d_out, n, stream);
 }
 
 int hrt_bake_device(hrt_scene *s, const float *d_points, const uint32_t *d_keys, uint32_t n, uint32_t first_sample, uint32_t n_samples,
@@ -165,13 +139,12 @@ int hrt_bake_device(hrt_scene *s, const float *d_points, const uint32_t *d_keys,
     int rc = bake_flags_check(who, flags);
     if (rc != HRT_OK || n == 0u) return rc;
     if ((rc = bake_points_check(who, d_points, d_keys, n, true)) != HRT_OK) return rc;
-    if ((rc = lens_samples_check(who, first_sample, n_samples, d_out, "d_out")) != HRT_OK) return rc;
+    if ((rc = samples_out_check(who, first_sample, n_samples, d_out, "d_out")) != HRT_OK) return rc;
     if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
     return bake_launch(s, d_points, d_keys, n, first_sample, n_samples, seed, flags, d_out, (hipStream_t)stream);
 }
 
-// Blocking, from and into host memory.  The device buffers and the two events are the call's own, so that this form, too, leaves
-// the scene's state alone.
+// Blocking, from and into host memory (BlockingCall; the points and keys are buffers of the call's, too).
 int hrt_bake(hrt_scene *s, const float *points, const uint32_t *keys, uint32_t n, uint32_t spp, uint64_t seed, uint32_t flags, float *out,
              hrt_stats *stats) {
     const std::string who = "hrt_bake";
@@ -183,45 +156,15 @@ int hrt_bake(hrt_scene *s, const float *points, const uint32_t *keys, uint32_t n
         return HRT_OK;
     }
     if ((rc = bake_points_check(who, points, keys, n, false)) != HRT_OK) return rc;
-    if ((rc = lens_samples_check(who, 0u, spp, out, "out")) != HRT_OK) return rc;
+    if ((rc = samples_out_check(who, 0u, spp, out, "out")) != HRT_OK) return rc;
     if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t pbytes = (size_t)n * HRT_RAY_FLOATS * sizeof(float), kbytes = (size_t)n * sizeof(uint32_t), obytes = (size_t)n * 3u * sizeof(float);
-    float *d_points = nullptr, *d_out = nullptr;
+    BlockingCall call;
+    float *d_points = nullptr;
     uint32_t *d_keys = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float ms = 0.f;
-    auto run = [&]() -> int {
-        HIP_TRY(hipMalloc((void **)&d_points, pbytes));
-        HIP_TRY(hipMalloc((void **)&d_out, obytes));
-        HIP_TRY(hipMemcpy(d_points, points, pbytes, hipMemcpyHostToDevice));
-        if (keys) {
-            HIP_TRY(hipMalloc((void **)&d_keys, kbytes));
-            HIP_TRY(hipMemcpy(d_keys, keys, kbytes, hipMemcpyHostToDevice));
-        }
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
-        HIP_TRY(hipEventRecord(ev0, nullptr));
-        const int lrc = bake_launch(s, d_points, d_keys, n, 0u, spp, seed, flags, d_out, nullptr);
-        if (lrc != HRT_OK) return lrc;
-        HIP_TRY(hipEventRecord(ev1, nullptr));
-        HIP_TRY(hipMemcpy(out, d_out, obytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-        return HRT_OK;
-    };
-    rc = run();
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (d_points) (void)hipFree(d_points);
-    if (d_keys) (void)hipFree(d_keys);
-    if (d_out) (void)hipFree(d_out);
-    if (rc != HRT_OK) return rc;
-    if (stats) {
-        fill_stats(s, stats, t0, (double)ms, (uint64_t)n * spp);
-        stats->lds_bytes = 0u;  // the tree is read from global memory
-        stats->waves_launched = 0u;
-    }
-    return HRT_OK;
+    if ((rc = call.buffer(&d_points, (size_t)n * HRT_RAY_FLOATS * sizeof(float), points)) != HRT_OK) return rc;
+    if (keys && (rc = call.buffer(&d_keys, (size_t)n * sizeof(uint32_t), keys)) != HRT_OK) return rc;
+    return call.run(s, (size_t)n * 3u * sizeof(float), out, (uint64_t)n * spp, stats,
+                    [&](float *d_out) { return bake_launch(s, d_points, d_keys, n, 0u, spp, seed, flags, d_out, nullptr); });
 }
 
 int hrt_bake_quad_points(const hrt_quad *quad, uint32_t tw, uint32_t th, int32_t side, float time, float bias, float *out_points) {

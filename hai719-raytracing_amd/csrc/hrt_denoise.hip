@@ -347,8 +347,7 @@ static int features_launch(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint
     int rc = fill_render(s, cam, w, h, 1, seed, 0, 0, 1, R, C);
     if (rc != HRT_OK) return rc;
     if (!s->d_cam_feat) HIP_TRY(hipMalloc((void **)&s->d_cam_feat, sizeof(DCamera)));
-    if (!s->ev_feat) HIP_TRY(hipEventCreateWithFlags(&s->ev_feat, hipEventDisableTiming));
-    if (s->feat_used && s->feat_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->ev_feat, 0));
+    if ((rc = s->feat_reader.wait_on(stream)) != HRT_OK) return rc;
     s->h_cam_feat = C;
     HIP_TRY(hipMemcpyAsync(s->d_cam_feat, &s->h_cam_feat, sizeof(C), hipMemcpyHostToDevice, stream));
     R.cam = s->d_cam_feat;
@@ -356,10 +355,7 @@ static int features_launch(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint
     const uint32_t npix = w * h;
     hipLaunchKernelGGL(hrt_features_kernel, dim3((npix + 255) / 256), dim3(256), 0, stream, R, n_samples, d_features);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(s->ev_feat, stream));
-    s->feat_used = true;
-    s->feat_stream = stream;
-    return HRT_OK;
+    return s->feat_reader.mark(stream);
 }
 
 int hrt_render_features(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples,

@@ -14,8 +14,8 @@
 // takes the lens and the seed of its item's view from a table in device memory (DLensView) at the point of use -- per LANE: a wave
 // straddles views whenever w*h is no multiple of 64, and lanes take their next item by grid stride on their own, so the view is
 // never wave-uniform.  The item-major store is the view-major, row-major layout of the frames.  hrt_lens_views_features_kernel is
-// features_body over the same items.  The table is the scene's (a grow-only buffer with a pinned staging copy, as hrt_views.hip keeps
-// its view blocks); nothing of the trace launches' state is touched.
+// features_body over the same items.  The table is the scene's (a StagedTable, hrt_api.hip, as the view blocks of
+// hrt_views.hip); nothing of the trace launches' state is touched.
 //
 // Adaptive lens frames (hrt_render_lens_adaptive*, the rounds are in hrt_lens_adaptive.hip): the lens kernel over a LIST OF TILES.  The
 // hrt_lens_tiles_kernel builds are radiance_body with the LensTileRays source over n_active * 64 items, item i being lane i & 63 of
@@ -49,7 +49,7 @@ struct DLensView {
 };
 
 // The launch record of the hrt_lens_kernel builds: DRadiance with the lens and the frame in place of the ray and key arrays
-// (query_launch and radiance_body read the fields they share by name).
+// (radiance_launch, query_launch and radiance_body reach the fields they share by name).
 struct DLensRadiance {
     const DScene *scene;
     float *out;            // 3 floats per pixel
@@ -303,23 +303,14 @@ extern "C" __global__ void __launch_bounds__(256) hrt_lens_rays_kernel(const DLe
     out[2u * pixel + 1u] = make_float4(r.d.x, r.d.y, r.d.z, __builtin_inff());
 }
 
-// The fused frame: radiance_body over pixels.  Launch bounds and shape are hrt_radiance_kernel's.
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_lens_kernel(const DLensRadiance Q) { radiance_body<false, false, LensRays>(Q); }
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_lens_kernel_lights(const DLensRadiance Q) { radiance_body<true, false, LensRays>(Q); }
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_lens_kernel_exact(const DLensRadiance Q) { radiance_body<false, true, LensRays>(Q); }
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_lens_kernel_lights_exact(const DLensRadiance Q) { radiance_body<true, true, LensRays>(Q); }
+// The fused frame: radiance_body over pixels.
+HRT_RADIANCE_FAMILY(hrt_lens_kernel, LensRays, DLensRadiance)
 
-// The fused frames of a batch: radiance_body over the items of all views.  Launch bounds and shape are hrt_lens_kernel's.
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_lens_views_kernel(const DLensViewsRadiance Q) { radiance_body<false, false, LensViewRays>(Q); }
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_lens_views_kernel_lights(const DLensViewsRadiance Q) { radiance_body<true, false, LensViewRays>(Q); }
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_lens_views_kernel_exact(const DLensViewsRadiance Q) { radiance_body<false, true, LensViewRays>(Q); }
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_lens_views_kernel_lights_exact(const DLensViewsRadiance Q) { radiance_body<true, true, LensViewRays>(Q); }
+// The fused frames of a batch: radiance_body over the items of all views.
+HRT_RADIANCE_FAMILY(hrt_lens_views_kernel, LensViewRays, DLensViewsRadiance)
 
-// The fused frame over a list of tiles: radiance_body over the 64 items of every active tile.  Launch bounds and shape are hrt_lens_kernel's.
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_lens_tiles_kernel(const DLensTilesRadiance Q) { radiance_body<false, false, LensTileRays>(Q); }
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_lens_tiles_kernel_lights(const DLensTilesRadiance Q) { radiance_body<true, false, LensTileRays>(Q); }
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_lens_tiles_kernel_exact(const DLensTilesRadiance Q) { radiance_body<false, true, LensTileRays>(Q); }
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_lens_tiles_kernel_lights_exact(const DLensTilesRadiance Q) { radiance_body<true, true, LensTileRays>(Q); }
+// The fused frame over a list of tiles: radiance_body over the 64 items of every active tile.
+HRT_RADIANCE_FAMILY(hrt_lens_tiles_kernel, LensTileRays, DLensTilesRadiance)
 
 // hrt_render_lens_features: hrt_features_kernel with the lens as a kernel argument in place of the scene's camera block.
 extern "C" __global__ void __launch_bounds__(256) hrt_lens_features_kernel(const DRender R, const DLens L, float bound, uint32_t n,
@@ -368,9 +359,7 @@ int hrt_lens_rays(const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t sample,
     DLens L;
     { const int lrc = lens_check(who, lens, L); if (lrc != HRT_OK) return lrc; }
     { const int frc = check_frame(who, w, h, k_max_pixels); if (frc != HRT_OK) return frc; }
-    if (!d_rays) return fail(HRT_ERR_INVALID, who + ": d_rays is NULL");
-    if ((uintptr_t)d_rays % 16u) return fail(HRT_ERR_INVALID, who + ": d_rays is not 16-byte aligned");
-    if (!g_rt.ready) return fail(HRT_ERR_STATE, who + ": call hrt_init first");
+    { const int rrc = rays_out_check(who, d_rays); if (rrc != HRT_OK) return rrc; }
     const uint32_t npix = w * h;
     hipLaunchKernelGGL(hrt_lens_rays_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, L, w, h, sample, (uint32_t)seed,
                        (uint32_t)(seed >> 32), (float4 *)d_rays);
@@ -380,28 +369,7 @@ int hrt_lens_rays(const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t sample,
 
 // The flags of a fused lens launch, one frame or a batch.
 static int lens_flags_check(const std::string &who, uint32_t flags) {
-    static const struct { uint32_t bit; const char *name; } no_form[] = {
-        {HRT_FLAG_WAVE_KERNEL, "HRT_FLAG_WAVE_KERNEL"}, {HRT_FLAG_STREAM_KERNEL, "HRT_FLAG_STREAM_KERNEL"}, {HRT_FLAG_DUAL_KERNEL, "HRT_FLAG_DUAL_KERNEL"}};
-    for (const auto &f : no_form)
-        if (flags & f.bit) return fail(HRT_ERR_INVALID, who + ": flags: " + f.name + ": a lens frame has one kernel form");
-    if (flags & HRT_FLAG_NO_SHADOW_CULL) return fail(HRT_ERR_INVALID, who + ": flags: HRT_FLAG_NO_SHADOW_CULL: the query kernels have no such build");
-    if (flags & HRT_RAYS_NORMALIZE) return fail(HRT_ERR_INVALID, who + ": flags: HRT_RAYS_NORMALIZE: a lens ray is made by the rule, not given");
-    const uint32_t known = HRT_FLAG_EXACT_ONLY | HRT_FLAG_MESH_BRUTE | HRT_FLAG_NO_LDS_TREE | HRT_RADIANCE_ACCUMULATE | HRT_FLAG_GAMMA;
-    if (flags & ~known) return fail(HRT_ERR_INVALID, who + ": flags: unknown bits " + std::to_string(flags & ~known));
-    { const int brc = check_mesh_brute(who, flags); if (brc != HRT_OK) return brc; }
-    if ((flags & HRT_FLAG_GAMMA) && (flags & HRT_RADIANCE_ACCUMULATE))
-        return fail(HRT_ERR_INVALID, who + ": flags: HRT_FLAG_GAMMA cannot be combined with HRT_RADIANCE_ACCUMULATE (running sums are linear)");
-    return HRT_OK;
-}
-
-// The samples and the output of a fused lens launch, one frame or a batch.
-static int lens_samples_check(const std::string &who, uint32_t first_sample, uint32_t n_samples, const float *out, const char *out_name) {
-    if (n_samples == 0u) return fail(HRT_ERR_INVALID, who + ": n_samples must be positive");
-    if ((uint64_t)first_sample + n_samples > 0x100000000ull)
-        return fail(HRT_ERR_INVALID, who + ": first_sample + n_samples must be at most 2^32 (sample indices do not wrap)");
-    if (!out) return fail(HRT_ERR_INVALID, who + ": " + out_name + " is NULL");
-    if ((uintptr_t)out % sizeof(float)) return fail(HRT_ERR_INVALID, who + ": " + out_name + " is not 4-byte aligned");
-    return HRT_OK;
+    return fused_flags_check(who, flags, "a lens frame has one kernel form", "a lens ray is made by the rule, not given", nullptr);
 }
 
 // The checks hrt_render_lens_device and hrt_render_lens share, in the header's order (all before the scene); fills L.
@@ -410,7 +378,7 @@ static int lens_render_check(const std::string &who, const hrt_lens *lens, uint3
     { const int frc = lens_flags_check(who, flags); if (frc != HRT_OK) return frc; }
     { const int lrc = lens_check(who, lens, L); if (lrc != HRT_OK) return lrc; }
     { const int frc = check_frame(who, w, h, k_max_pixels); if (frc != HRT_OK) return frc; }
-    return lens_samples_check(who, first_sample, n_samples, out, out_name);
+    return samples_out_check(who, first_sample, n_samples, out, out_name);
 }
 
 // HRT_FLAG_GAMMA of a fused lens launch: hrt_gamma_kernel, the in-place kernel of the one-shot render (hrt_finalize_kernel's
@@ -429,21 +397,10 @@ static int lens_gamma(float *d_frame, uint64_t total, hipStream_t stream) {
 static int lens_launch(hrt_scene *s, const DLens &L, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples, uint64_t seed,
                        uint32_t flags, float *d_frame, hipStream_t stream) {
     DLensRadiance Q;
-    Q.out = d_frame;
-    Q.n = w * h;
-    Q.flags = flags & ~(uint32_t)HRT_FLAG_GAMMA;
-    Q.first_sample = first_sample;
-    Q.n_samples = n_samples;
-    Q.seed_lo = (uint32_t)seed;
-    Q.seed_hi = (uint32_t)(seed >> 32);
     Q.w = w;
     Q.h = h;
     Q.lens = L;
-    const bool exact = (flags & HRT_FLAG_EXACT_ONLY) != 0u;
-    const bool lights = s->d.n_lights != 0u;
-    void (*const k)(const DLensRadiance) = exact ? (lights ? hrt_lens_kernel_lights_exact : hrt_lens_kernel_exact)
-                                                 : (lights ? hrt_lens_kernel_lights : hrt_lens_kernel);
-    const int rc = query_launch(k, Q, s, HRT_RADIANCE_STAGE_TREE, HRT_RADIANCE_WG, stream);  // the tree from global memory, as hrt_trace_radiance
+    const int rc = radiance_launch(hrt_lens_kernel_builds, Q, s, first_sample, n_samples, seed, flags & ~(uint32_t)HRT_FLAG_GAMMA, d_frame, w * h, stream);
     if (rc != HRT_OK || !(flags & HRT_FLAG_GAMMA)) return rc;
     return lens_gamma(d_frame, (uint64_t)Q.n * 3u, stream);
 }
@@ -458,8 +415,7 @@ int hrt_render_lens_device(hrt_scene *s, const hrt_lens *lens, uint32_t w, uint3
     return lens_launch(s, L, w, h, first_sample, n_samples, seed, flags, d_frame, (hipStream_t)stream);
 }
 
-// Blocking, into host memory.  The device frame and the two events are the call's own, so that this form, too, leaves the scene's
-// state alone.
+// Blocking, into host memory (BlockingCall).
 int hrt_render_lens(hrt_scene *s, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed, uint32_t flags, float *out_rgb,
                     hrt_stats *stats) {
     const std::string who = "hrt_render_lens";
@@ -468,34 +424,9 @@ int hrt_render_lens(hrt_scene *s, const hrt_lens *lens, uint32_t w, uint32_t h, 
     int rc = lens_render_check(who, lens, w, h, 0u, spp, flags, out_rgb, "out_rgb", L);
     if (rc == HRT_OK) rc = enter_scene(who, s);
     if (rc != HRT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t bytes = (size_t)w * h * 3u * sizeof(float);
-    float *d_frame = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float ms = 0.f;
-    auto run = [&]() -> int {
-        HIP_TRY(hipMalloc((void **)&d_frame, bytes));
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
-        HIP_TRY(hipEventRecord(ev0, nullptr));
-        const int lrc = lens_launch(s, L, w, h, 0u, spp, seed, flags, d_frame, nullptr);
-        if (lrc != HRT_OK) return lrc;
-        HIP_TRY(hipEventRecord(ev1, nullptr));
-        HIP_TRY(hipMemcpy(out_rgb, d_frame, bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-        return HRT_OK;
-    };
-    rc = run();
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (d_frame) (void)hipFree(d_frame);
-    if (rc != HRT_OK) return rc;
-    if (stats) {
-        fill_stats(s, stats, t0, (double)ms, (uint64_t)w * h * spp);
-        stats->lds_bytes = 0u;  // the tree is read from global memory
-        stats->waves_launched = 0u;
-    }
-    return HRT_OK;
+    BlockingCall call;
+    return call.run(s, (size_t)w * h * 3u * sizeof(float), out_rgb, (uint64_t)w * h * spp, stats,
+                    [&](float *d_frame) { return lens_launch(s, L, w, h, 0u, spp, seed, flags, d_frame, nullptr); });
 }
 
 int hrt_render_lens_features(hrt_scene *s, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples, uint64_t seed,
@@ -552,44 +483,19 @@ static int lens_views_check(const std::string &who, const hrt_lens_view *views, 
     if (n_views == 0u) return HRT_OK;
     { const int brc = lens_views_blocks(who, views, n_views, blocks); if (brc != HRT_OK) return brc; }
     { const int frc = check_frame(who, w, h, k_max_pixels); if (frc != HRT_OK) return frc; }
-    { const int src = lens_samples_check(who, first_sample, n_samples, out, out_name); if (src != HRT_OK) return src; }
+    { const int src = samples_out_check(who, first_sample, n_samples, out, out_name); if (src != HRT_OK) return src; }
     return lens_views_limit(who, n_views, w, h, k_max_pixels);
 }
 
-// Puts the blocks into the scene's table on `stream` (the scene entered) and returns it.  The pinned staging copy is reused by
-// every call: wait until the previous call's upload has read it (that upload sits in front of its kernel, so this does not wait
-// for the kernel).  The table is read by the previous batch's kernel: one on another stream is waited for on `stream`.
+// Puts the blocks into the scene's table on `stream` (the scene entered) and returns it (StagedTable::stage: the host waits for
+// the table's last reader before a larger table replaces it, nothing else orders these launches); lens_views.staged() follows the
+// launch that reads it.
 static int lens_views_stage(hrt_scene *s, std::vector<DLensView> &blocks, hipStream_t stream, const DLensView **table) {
-    const size_t n_views = blocks.size(), bytes = n_views * sizeof(DLensView);
     for (DLensView &B : blocks) {  // fill_render's margin, per view
         const float *e = B.lens.eye;
         B.err_abs = margin_scale(s->bound, std::sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]));
     }
-    if (s->lv_uploading) { HIP_TRY(hipEventSynchronize(s->ev_lv)); s->lv_uploading = false; }
-    if (!s->ev_lv) HIP_TRY(hipEventCreateWithFlags(&s->ev_lv, hipEventDisableTiming));
-    if (!s->ev_lv_done) HIP_TRY(hipEventCreateWithFlags(&s->ev_lv_done, hipEventDisableTiming));
-    if (s->h_lv_cap < n_views) {
-        if (s->h_lv) (void)hipHostFree(s->h_lv);
-        s->h_lv = nullptr; s->h_lv_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&s->h_lv, bytes, hipHostMallocDefault));
-        s->h_lv_cap = n_views;
-    }
-    std::memcpy(s->h_lv, blocks.data(), bytes);
-    if (s->lv_blocks.cap < bytes && s->lv_used) HIP_TRY(hipEventSynchronize(s->ev_lv_done));  // the old table is freed: its last reader is done
-    { const int grc = s->lv_blocks.grow(bytes); if (grc != HRT_OK) return grc; }
-    if (s->lv_used && s->lv_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->ev_lv_done, 0));
-    HIP_TRY(hipMemcpyAsync(s->lv_blocks.p, s->h_lv, bytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(s->ev_lv, stream));
-    s->lv_uploading = true;
-    *table = s->lv_blocks.as<DLensView>();
-    return HRT_OK;
-}
-// After the launch that reads the table.
-static int lens_views_staged(hrt_scene *s, hipStream_t stream) {
-    HIP_TRY(hipEventRecord(s->ev_lv_done, stream));
-    s->lv_used = true;
-    s->lv_stream = stream;
-    return HRT_OK;
+    return s->lens_views.stage(blocks, stream, table);
 }
 
 // The fused launch over all views into d_frames on `stream` (the scene entered), then the gamma over all frames.
@@ -597,20 +503,12 @@ static int lens_views_launch(hrt_scene *s, std::vector<DLensView> &blocks, uint3
                              uint32_t flags, float *d_frames, hipStream_t stream) {
     DLensViewsRadiance Q;
     { const int src = lens_views_stage(s, blocks, stream, &Q.views); if (src != HRT_OK) return src; }
-    Q.out = d_frames;
-    Q.npix = w * h;
-    Q.n = (uint32_t)blocks.size() * Q.npix;
-    Q.flags = flags & ~(uint32_t)HRT_FLAG_GAMMA;
-    Q.first_sample = first_sample;
-    Q.n_samples = n_samples;
     Q.w = w;
     Q.h = h;
-    const bool exact = (flags & HRT_FLAG_EXACT_ONLY) != 0u;
-    const bool lights = s->d.n_lights != 0u;
-    void (*const k)(const DLensViewsRadiance) = exact ? (lights ? hrt_lens_views_kernel_lights_exact : hrt_lens_views_kernel_exact)
-                                                      : (lights ? hrt_lens_views_kernel_lights : hrt_lens_views_kernel);
-    int rc = query_launch(k, Q, s, HRT_RADIANCE_STAGE_TREE, HRT_RADIANCE_WG, stream);  // as lens_launch
-    if (rc == HRT_OK) rc = lens_views_staged(s, stream);
+    Q.npix = w * h;
+    int rc = radiance_launch(hrt_lens_views_kernel_builds, Q, s, first_sample, n_samples, 0u, flags & ~(uint32_t)HRT_FLAG_GAMMA, d_frames,
+                             (uint32_t)blocks.size() * Q.npix, stream);  // no launch seed: every view has its own
+    if (rc == HRT_OK) rc = s->lens_views.staged(stream);
     if (rc != HRT_OK || !(flags & HRT_FLAG_GAMMA)) return rc;
     return lens_gamma(d_frames, (uint64_t)Q.n * 3u, stream);
 }
@@ -625,7 +523,7 @@ int hrt_render_lens_views_device(hrt_scene *s, const hrt_lens_view *views, uint3
     return lens_views_launch(s, blocks, w, h, first_sample, n_samples, flags, d_frames, (hipStream_t)stream);
 }
 
-// Blocking, into host memory.  The device frames and the two events are the call's own, as hrt_render_lens'.
+// Blocking, into host memory (BlockingCall).
 int hrt_render_lens_views(hrt_scene *s, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h, uint32_t spp, uint32_t flags,
                           float *out_rgb, hrt_stats *stats) {
     const std::string who = "hrt_render_lens_views";
@@ -638,34 +536,9 @@ int hrt_render_lens_views(hrt_scene *s, const hrt_lens_view *views, uint32_t n_v
         return HRT_OK;
     }
     if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t bytes = (size_t)n_views * w * h * 3u * sizeof(float);
-    float *d_frames = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float ms = 0.f;
-    auto run = [&]() -> int {
-        HIP_TRY(hipMalloc((void **)&d_frames, bytes));
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
-        HIP_TRY(hipEventRecord(ev0, nullptr));
-        const int lrc = lens_views_launch(s, blocks, w, h, 0u, spp, flags, d_frames, nullptr);
-        if (lrc != HRT_OK) return lrc;
-        HIP_TRY(hipEventRecord(ev1, nullptr));
-        HIP_TRY(hipMemcpy(out_rgb, d_frames, bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-        return HRT_OK;
-    };
-    rc = run();
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (d_frames) (void)hipFree(d_frames);
-    if (rc != HRT_OK) return rc;
-    if (stats) {
-        fill_stats(s, stats, t0, (double)ms, (uint64_t)n_views * w * h * spp);
-        stats->lds_bytes = 0u;  // the tree is read from global memory
-        stats->waves_launched = 0u;
-    }
-    return HRT_OK;
+    BlockingCall call;
+    return call.run(s, (size_t)n_views * w * h * 3u * sizeof(float), out_rgb, (uint64_t)n_views * w * h * spp, stats,
+                    [&](float *d_frames) { return lens_views_launch(s, blocks, w, h, 0u, spp, flags, d_frames, nullptr); });
 }
 
 int hrt_render_lens_views_features(hrt_scene *s, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h, uint32_t first_sample,
@@ -692,5 +565,5 @@ int hrt_render_lens_views_features(hrt_scene *s, const hrt_lens_view *views, uin
     hipLaunchKernelGGL(hrt_lens_views_features_kernel, dim3((n_items + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, R, table, s->bound, n_items,
                        n_samples, d_features);
     HIP_TRY(hipGetLastError());
-    return lens_views_staged(s, (hipStream_t)stream);
+    return s->lens_views.staged((hipStream_t)stream);
 }

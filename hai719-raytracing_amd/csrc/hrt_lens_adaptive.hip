@@ -21,24 +21,16 @@
 static int lens_tiles_launch(hrt_scene *s, const DLens &L, uint32_t w, uint32_t h, const uint32_t *list, uint32_t n_active, uint32_t first,
                              uint32_t add, uint64_t seed, uint32_t flags, float *sums, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
     DLensTilesRadiance Q;
-    Q.out = sums;
-    Q.n = n_active * 64u;  // n_active <= the frame's tiles, which the entry points hold to (2^31 - 1) / 64
-    Q.flags = (flags & (HRT_FLAG_EXACT_ONLY | HRT_FLAG_MESH_BRUTE | HRT_FLAG_NO_LDS_TREE)) | HRT_RADIANCE_ACCUMULATE;
-    Q.first_sample = first;
-    Q.n_samples = add;
-    Q.seed_lo = (uint32_t)seed;
-    Q.seed_hi = (uint32_t)(seed >> 32);
     Q.w = w;
     Q.h = h;
     Q.tiles_x = (w + HRT_TILE - 1u) / HRT_TILE;
     Q.list = list;
     Q.lens = L;
-    const bool exact = (flags & HRT_FLAG_EXACT_ONLY) != 0u;
-    const bool lights = s->d.n_lights != 0u;
-    void (*const k)(const DLensTilesRadiance) = exact ? (lights ? hrt_lens_tiles_kernel_lights_exact : hrt_lens_tiles_kernel_exact)
-                                                      : (lights ? hrt_lens_tiles_kernel_lights : hrt_lens_tiles_kernel);
     HIP_TRY(hipEventRecord(e0, stream));
-    const int rc = query_launch(k, Q, s, HRT_RADIANCE_STAGE_TREE, HRT_RADIANCE_WG, stream);  // as lens_launch; refuses a launch HIP refused
+    // n_active <= the frame's tiles, which the entry points hold to (2^31 - 1) / 64
+    const int rc = radiance_launch(hrt_lens_tiles_kernel_builds, Q, s, first, add, seed,
+                                   (flags & (HRT_FLAG_EXACT_ONLY | HRT_FLAG_MESH_BRUTE | HRT_FLAG_NO_LDS_TREE)) | HRT_RADIANCE_ACCUMULATE, sums,
+                                   n_active * 64u, stream);  // refuses a launch HIP refused
     if (rc != HRT_OK) return rc;
     HIP_TRY(hipEventRecord(e1, stream));
     return HRT_OK;
@@ -122,24 +114,20 @@ static int lens_adaptive_frame(hrt_scene *s, const DLens &L, uint32_t w, uint32_
                                float *d_frame, uint32_t *d_counts, hipStream_t stream, double *kernel_ms) {
     const uint32_t tiles = hrt_tiles_total(w, h);
     const size_t tile_bytes = (size_t)tiles * 192u * sizeof(float);
-    if (!s->ev_la_done) HIP_TRY(hipEventCreateWithFlags(&s->ev_la_done, hipEventDisableTiming));
-    if (s->la_tiles.cap < tile_bytes && s->la_used) HIP_TRY(hipEventSynchronize(s->ev_la_done));  // the old sums are freed: their last reader is done
-    { const int grc = s->la_tiles.grow(tile_bytes); if (grc != HRT_OK) return grc; }
-    if (s->la_used && s->la_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->ev_la_done, 0));
+    int rc = s->la_tiles.cap < tile_bytes ? s->la_reader.sync() : HRT_OK;  // the old sums are freed: their last reader is done
+    if (rc == HRT_OK) rc = s->la_tiles.grow(tile_bytes);
+    if (rc == HRT_OK) rc = s->la_reader.wait_on(stream);
+    if (rc != HRT_OK) return rc;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     auto run = [&]() -> int {
         for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
-        const int rc = lens_adaptive_run(s, L, w, h, p, seed, flags, s->la_tiles.as<float>(), d_counts, stream, ev, kernel_ms);
-        if (rc != HRT_OK) return rc;
+        const int rrc = lens_adaptive_run(s, L, w, h, p, seed, flags, s->la_tiles.as<float>(), d_counts, stream, ev, kernel_ms);
+        if (rrc != HRT_OK) return rrc;
         return hrt_assemble_frame(s->la_tiles.as<float>(), tiles, w, h, 1, d_frame, stream);
     };
-    int rc = run();
+    rc = run();
     for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    if (rc != HRT_OK) return rc;
-    HIP_TRY(hipEventRecord(s->ev_la_done, stream));
-    s->la_used = true;
-    s->la_stream = stream;
-    return HRT_OK;
+    return rc != HRT_OK ? rc : s->la_reader.mark(stream);
 }
 
 int hrt_render_lens_adaptive_device(hrt_scene *s, const hrt_lens *lens, uint32_t w, uint32_t h, const hrt_adaptive *params, uint64_t seed,

@@ -210,12 +210,129 @@ extern "C" __global__ void __launch_bounds__(256) hrt_camera_rays_kernel(const D
     out[2u * pixel + 1u] = make_float4(r.d.x, r.d.y, r.d.z, __builtin_inff());
 }
 
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_radiance_kernel(const DRadiance Q) { radiance_body<false, false>(Q); }
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) hrt_radiance_kernel_lights(const DRadiance Q) { radiance_body<true, false>(Q); }
-// HRT_FLAG_EXACT_ONLY: the proof builds (no filters, no v_rcp_f32; see CtxT).  Not tuned: 2 waves per SIMD, as trace_body's
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_radiance_kernel_exact(const DRadiance Q) { radiance_body<false, true>(Q); }
-extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) hrt_radiance_kernel_lights_exact(const DRadiance Q) { radiance_body<true, true>(Q); }
+// A family of radiance_body kernels: the four builds of source SRC over launch record QT -- plain, lights, and the two proof builds
+// of HRT_FLAG_EXACT_ONLY (no filters, no v_rcp_f32; see CtxT; not tuned: 2 waves per SIMD, as trace_body's) -- and their table,
+// indexed lights | exact << 1 (radiance_launch).
+#define HRT_RADIANCE_FAMILY(base, SRC, QT)                                                                                                                           \
+    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) base(const QT Q) { radiance_body<false, false, SRC>(Q); }                  \
+    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) base##_lights(const QT Q) { radiance_body<true, false, SRC>(Q); }          \
+    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) base##_exact(const QT Q) { radiance_body<false, true, SRC>(Q); }                                \
+    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) base##_lights_exact(const QT Q) { radiance_body<true, true, SRC>(Q); }                          \
+    static void (*const base##_builds[4])(const QT) = {base, base##_lights, base##_exact, base##_lights_exact};
 
+HRT_RADIANCE_FAMILY(hrt_radiance_kernel, RecordRays, DRadiance)
+
+struct DLensViewsRadiance;  // hrt_lens.hip: the one record without a launch seed (every view has its own)
+
+extern "C++" {
+static void radiance_seed(DLensViewsRadiance &, uint64_t) {}
+template <class QT>
+static void radiance_seed(QT &Q, uint64_t seed) {
+    Q.seed_lo = (uint32_t)seed;
+    Q.seed_hi = (uint32_t)(seed >> 32);
+}
+
+// THE launch of a radiance_body family (the scene entered): fills what every record has -- the caller has set its family's own
+// fields -- picks the build and launches it over n items into `out` on `stream`.
+// The tree prefix is NOT staged by default: measured on MI355X (DESIGN.md section 5 "Radiance queries"), its 36 KiB per workgroup
+// cost a fifth of the resident waves at 5 waves per SIMD and -12..-16 % on the mesh scenes.  HRT_RADIANCE_STAGE_TREE builds keep
+// the staged form for A/B runs (HRT_FLAG_NO_LDS_TREE turns it off there).
+template <class QT>
+static int radiance_launch(void (*const *builds)(const QT), QT &Q, const hrt_scene *s, uint32_t first_sample, uint32_t n_samples, uint64_t seed,
+                           uint32_t flags, float *out, uint32_t n, void *stream) {
+    Q.out = out;
+    Q.n = n;
+    Q.flags = flags;
+    Q.first_sample = first_sample;
+    Q.n_samples = n_samples;
+    radiance_seed(Q, seed);
+    const uint32_t build = (s->d.n_lights != 0u ? 1u : 0u) | ((flags & HRT_FLAG_EXACT_ONLY) ? 2u : 0u);
+    return query_launch(builds[build], Q, s, HRT_RADIANCE_STAGE_TREE, HRT_RADIANCE_WG, stream);
+}
+
+// THE blocking host form of a family (hrt_render_lens, hrt_render_lens_views, hrt_bake): device buffers and two timing events of
+// the call's own, so that this form, too, leaves the scene's state alone; freed on every way out.
+struct BlockingCall {
+    std::vector<void *> buffers;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    ~BlockingCall() {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        for (void *p : buffers) (void)hipFree(p);
+    }
+    // A device buffer of the call's, filled from `from` if given.
+    template <class T>
+    int buffer(T **d, size_t bytes, const void *from = nullptr) {
+        void *p = nullptr;
+        HIP_TRY(hipMalloc(&p, bytes));
+        buffers.push_back(p);
+        if (from) HIP_TRY(hipMemcpy(p, from, bytes, hipMemcpyHostToDevice));
+        *d = (T *)p;
+        return HRT_OK;
+    }
+    // launch(d_out) on the null stream between the events, its `bytes` of result into `out`, and the stats of `samples` samples.
+    template <class F>
+    int run(const hrt_scene *s, size_t bytes, float *out, uint64_t samples, hrt_stats *stats, F launch) {
+        float *d_out = nullptr;
+        float ms = 0.f;
+        if (const int rc = buffer(&d_out, bytes)) return rc;
+        HIP_TRY(hipEventCreate(&ev0));
+        HIP_TRY(hipEventCreate(&ev1));
+        HIP_TRY(hipEventRecord(ev0, nullptr));
+        if (const int rc = launch(d_out)) return rc;
+        HIP_TRY(hipEventRecord(ev1, nullptr));
+        HIP_TRY(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+        if (stats) {
+            fill_stats(s, stats, t0, (double)ms, samples);
+            stats->lds_bytes = 0u;  // the tree is read from global memory
+            stats->waves_launched = 0u;
+        }
+        return HRT_OK;
+    }
+};
+}  // extern "C++"
+
+// The flags of a fused launch (lens frames, bakes).  one_form: why the kernel-form flags are refused; no_normalize: why
+// HRT_RAYS_NORMALIZE is; no_gamma: why HRT_FLAG_GAMMA is, NULL where it is accepted.
+static int fused_flags_check(const std::string &who, uint32_t flags, const char *one_form, const char *no_normalize, const char *no_gamma) {
+    const struct { uint32_t bit; const char *name; const char *why; } refused[] = {
+        {HRT_FLAG_WAVE_KERNEL, "HRT_FLAG_WAVE_KERNEL", one_form},
+        {HRT_FLAG_STREAM_KERNEL, "HRT_FLAG_STREAM_KERNEL", one_form},
+        {HRT_FLAG_DUAL_KERNEL, "HRT_FLAG_DUAL_KERNEL", one_form},
+        {HRT_FLAG_NO_SHADOW_CULL, "HRT_FLAG_NO_SHADOW_CULL", "the query kernels have no such build"},
+        {HRT_RAYS_NORMALIZE, "HRT_RAYS_NORMALIZE", no_normalize},
+        {no_gamma ? HRT_FLAG_GAMMA : 0u, "HRT_FLAG_GAMMA", no_gamma}};
+    for (const auto &f : refused)
+        if (flags & f.bit) return fail(HRT_ERR_INVALID, who + ": flags: " + f.name + ": " + f.why);
+    const uint32_t known = HRT_FLAG_EXACT_ONLY | HRT_FLAG_MESH_BRUTE | HRT_FLAG_NO_LDS_TREE | HRT_RADIANCE_ACCUMULATE | HRT_FLAG_GAMMA;
+    if (flags & ~known) return fail(HRT_ERR_INVALID, who + ": flags: unknown bits " + std::to_string(flags & ~known));
+    { const int brc = check_mesh_brute(who, flags); if (brc != HRT_OK) return brc; }
+    if ((flags & HRT_FLAG_GAMMA) && (flags & HRT_RADIANCE_ACCUMULATE))
+        return fail(HRT_ERR_INVALID, who + ": flags: HRT_FLAG_GAMMA cannot be combined with HRT_RADIANCE_ACCUMULATE (running sums are linear)");
+    return HRT_OK;
+}
+
+// The samples and the output of a fused launch.
+static int samples_out_check(const std::string &who, uint32_t first_sample, uint32_t n_samples, const float *out, const char *out_name) {
+    if (n_samples == 0u) return fail(HRT_ERR_INVALID, who + ": n_samples must be positive");
+    if ((uint64_t)first_sample + n_samples > 0x100000000ull)
+        return fail(HRT_ERR_INVALID, who + ": first_sample + n_samples must be at most 2^32 (sample indices do not wrap)");
+    if (!out) return fail(HRT_ERR_INVALID, who + ": " + out_name + " is NULL");
+    if ((uintptr_t)out % sizeof(float)) return fail(HRT_ERR_INVALID, who + ": " + out_name + " is not 4-byte aligned");
+    return HRT_OK;
+}
+
+// The last checks of an entry point that writes rays as records (hrt_camera_rays, hrt_lens_rays, hrt_bake_rays).
+static int rays_out_check(const std::string &who, const float *d_rays) {
+    if (!d_rays) return fail(HRT_ERR_INVALID, who + ": d_rays is NULL");
+    if ((uintptr_t)d_rays % 16u) return fail(HRT_ERR_INVALID, who + ": d_rays is not 16-byte aligned");
+    if (!g_rt.ready) return fail(HRT_ERR_STATE, who + ": call hrt_init first");
+    return HRT_OK;
+}
+
+// The pointers come before n_samples here (include/hrt.h), and d_out may be NULL for an empty batch: not samples_out_check's order.
 int hrt_trace_radiance(hrt_scene *s, const float *d_rays, const uint32_t *d_keys, uint32_t n, uint32_t first_sample, uint32_t n_samples,
                        uint64_t seed, uint32_t flags, float *d_out, void *stream) {
     const std::string who = "hrt_trace_radiance";
@@ -229,21 +346,7 @@ int hrt_trace_radiance(hrt_scene *s, const float *d_rays, const uint32_t *d_keys
     DRadiance Q;
     Q.rays = (const float4 *)d_rays;
     Q.keys = d_keys;
-    Q.out = d_out;
-    Q.n = n;
-    Q.flags = flags;
-    Q.first_sample = first_sample;
-    Q.n_samples = n_samples;
-    Q.seed_lo = (uint32_t)seed;
-    Q.seed_hi = (uint32_t)(seed >> 32);
-    const bool exact = (flags & HRT_FLAG_EXACT_ONLY) != 0u;
-    const bool lights = s->d.n_lights != 0u;
-    void (*const k)(const DRadiance) = exact ? (lights ? hrt_radiance_kernel_lights_exact : hrt_radiance_kernel_exact)
-                                             : (lights ? hrt_radiance_kernel_lights : hrt_radiance_kernel);
-    // The tree prefix is NOT staged by default: measured on MI355X (DESIGN.md section 5 "Radiance queries"), its 36 KiB per workgroup
-    // cost a fifth of the resident waves at 5 waves per SIMD and -12..-16 % on the mesh scenes.  HRT_RADIANCE_STAGE_TREE builds keep
-    // the staged form for A/B runs (HRT_FLAG_NO_LDS_TREE turns it off there).
-    return query_launch(k, Q, s, HRT_RADIANCE_STAGE_TREE, HRT_RADIANCE_WG, stream);
+    return radiance_launch(hrt_radiance_kernel_builds, Q, s, first_sample, n_samples, seed, flags, d_out, n, stream);
 }
 
 int hrt_camera_rays(const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t sample, uint64_t seed, float *d_rays, void *stream) {
@@ -252,9 +355,7 @@ int hrt_camera_rays(const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t samp
     DCamera C;
     { const int crc = make_camera(cam, C); if (crc != HRT_OK) return crc; }  // refused as hrt_render refuses it
     { const int frc = check_frame(who, w, h, k_max_pixels); if (frc != HRT_OK) return frc; }
-    if (!d_rays) return fail(HRT_ERR_INVALID, who + ": d_rays is NULL");
-    if ((uintptr_t)d_rays % 16u) return fail(HRT_ERR_INVALID, who + ": d_rays is not 16-byte aligned");
-    if (!g_rt.ready) return fail(HRT_ERR_STATE, who + ": call hrt_init first");
+    { const int rrc = rays_out_check(who, d_rays); if (rrc != HRT_OK) return rrc; }
     const uint32_t npix = w * h;
     hipLaunchKernelGGL(hrt_camera_rays_kernel, dim3((npix + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, C, w, h, sample,
                        (uint32_t)seed, (uint32_t)(seed >> 32), (float4 *)d_rays);

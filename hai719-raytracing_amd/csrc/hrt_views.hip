@@ -55,24 +55,14 @@ static int views_launch(hrt_scene *s, const hrt_view *views, std::vector<DView> 
         const float *e = views[v].cam.eye;
         blocks[v].err_abs = margin_scale(s->bound, std::sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]));
     }
-    // The pinned staging copy is reused by every call: wait until the previous call's upload has read it (that upload sits in front
-    // of its launch's kernels, so this does not wait for them).
-    if (s->views_uploading) { HIP_TRY(hipEventSynchronize(s->ev_views)); s->views_uploading = false; }
-    if (!s->ev_views) HIP_TRY(hipEventCreateWithFlags(&s->ev_views, hipEventDisableTiming));
-    if (!s->ev_views_done) HIP_TRY(hipEventCreateWithFlags(&s->ev_views_done, hipEventDisableTiming));
-    if (s->h_views_cap < n_views) {
-        if (s->h_views) (void)hipHostFree(s->h_views);
-        s->h_views = nullptr; s->h_views_cap = 0;
-        HIP_TRY(hipHostMalloc((void **)&s->h_views, (size_t)n_views * sizeof(DView), hipHostMallocDefault));
-        s->h_views_cap = n_views;
-    }
-    std::memcpy(s->h_views, blocks.data(), (size_t)n_views * sizeof(DView));
-    int rc = s->vw_blocks.grow((size_t)n_views * sizeof(DView));
+    // No host wait before a larger table replaces the old one (nor before larger tile sums do): launch_trace orders the launches of
+    // one scene behind its own event, and the upload is its to enqueue, behind that wait (StagedTable::upload).
+    int rc = s->views.fill(blocks, false);
     if (rc == HRT_OK) rc = s->vw_tiles.grow((size_t)n_views * tiles * 64u * 3u * sizeof(float));
-    if (rc != HRT_OK) return rc;
     // The tile sums are read by the assemble launch, behind the event launch_trace orders launches by: a batched launch on another
     // stream waits for the previous one's frames as well.
-    if (s->views_used && s->views_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->ev_views_done, 0));
+    if (rc == HRT_OK) rc = s->views.reader.wait_on(stream);
+    if (rc != HRT_OK) return rc;
     TraceJob job{w, h, 0u, spp, 0u, flags, s->vw_tiles.as<float>(), stream};
     job.n_views = n_views;
     rc = launch_trace(s, &views[0].cam, job);
@@ -81,10 +71,7 @@ static int views_launch(hrt_scene *s, const hrt_view *views, std::vector<DView> 
     hipLaunchKernelGGL(hrt_assemble_views_kernel, dim3((n_pixels + 255u) / 256u), dim3(256), 0, stream, s->vw_tiles.as<float>(), tiles, w, h,
                        n_pixels, d_frames);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(s->ev_views_done, stream));
-    s->views_used = true;
-    s->views_stream = stream;
-    return HRT_OK;
+    return s->views.staged(stream);
 }
 
 int hrt_render_views_device(hrt_scene *s, const hrt_view *views, uint32_t n_views, uint32_t w, uint32_t h, uint32_t spp, uint32_t flags,

@@ -229,6 +229,29 @@ def test_batches_of_one_scene_on_two_streams_keep_their_own_tables(gpu):
     assert np.array_equal(bits(got_a.cpu().numpy()), bits(want_a)) and np.array_equal(bits(got_b.cpu().numpy()), bits(want_b))
 
 
+def test_a_larger_batch_on_a_second_stream_grows_the_table_under_the_previous_batch(gpu):
+    """One view on s1, then at once five on s2: the scene's table of views must grow while the first batch's kernel may still be
+    reading the old one.  Then two views on s1 again: the grown table reused across streams.  Every frame is render_lens' bit for bit."""
+    import torch
+    w, h, spp = 16, 16, 2
+    dev = qr.build(gpu, "cornell_mesh", w, h)[2]  # a scene of its own: its table starts empty (a mesh, and the lamp)
+    lenses, seeds = mixed(gpu, 8, 1.0)  # pinhole | thin, ortho, equirect, two fisheyes | pinhole, thin
+    want = per_view(dev, lenses, seeds, w, h, spp)
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    got = torch.empty((8, h, w, 3), device="cuda")
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s1):
+        dev.render_lens_views(lenses[:1], w, h, spp, seeds[:1], out=got[:1])
+    with torch.cuda.stream(s2):
+        dev.render_lens_views(lenses[1:6], w, h, spp, seeds[1:6], out=got[1:6])
+    torch.cuda.synchronize()
+    assert np.array_equal(bits(got[:6].cpu().numpy()), bits(want[:6])), differing(got[:6].cpu().numpy(), want[:6])
+    with torch.cuda.stream(s1):
+        dev.render_lens_views(lenses[6:], w, h, spp, seeds[6:], out=got[6:])
+    torch.cuda.synchronize()
+    assert np.array_equal(bits(got[6:].cpu().numpy()), bits(want[6:])), differing(got[6:].cpu().numpy(), want[6:])
+
+
 # ----------------------------------------------------------------------------------------------------------------- 7. bindings
 def test_torch_and_numpy_paths_agree(gpu):
     import torch

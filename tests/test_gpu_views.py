@@ -325,6 +325,35 @@ def test_camera_switches_on_one_stream(gpu):
         assert np.array_equal(got, ref), f"launch {k} ({'ABA'[k]}): {describe_difference(got, ref)}"
 
 
+def test_a_larger_batch_of_views_on_a_second_stream_grows_the_blocks_under_the_previous_batch(gpu):
+    """hrt_render_views_device with one view on s1, then at once five on s2, no host wait: the scene's per-view blocks (and tile
+    sums) must grow while the first batch's launch may still be reading the old ones.  Then two views on s1 again: the grown blocks
+    reused across streams.  Every frame is hrt_render's bit for bit."""
+    import torch
+    w, h, spp = 16, 16, 2
+    dev = gpu.DeviceScene(gpu.HostScene().setup("cornell_mesh", 1.0, 1).flatten())  # a scene of its own: its blocks start empty
+    cams = [camera_from_inverse_modelview(gpu, trackball_inverse(15.0 * k, 4.0 * k), 1.0) for k in range(8)]
+    seeds = [5 + 3 * k for k in range(8)]
+    want = np.stack([dev.render(cam, w, h, spp, seed)[0] for cam, seed in zip(cams, seeds)])
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    got = torch.empty((8, h, w, 3), device="cuda")
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s1):
+        dev.render_views(cams[:1], w, h, spp, seeds[:1], out=got[:1])
+    with torch.cuda.stream(s2):
+        dev.render_views(cams[1:6], w, h, spp, seeds[1:6], out=got[1:6])
+    torch.cuda.synchronize()
+    dev.check_last_launch()
+    first = got[:6].cpu().numpy()
+    assert same_bits(first, want[:6]), describe_difference(first.reshape(-1, w, 3), want[:6].reshape(-1, w, 3))
+    with torch.cuda.stream(s1):
+        dev.render_views(cams[6:], w, h, spp, seeds[6:], out=got[6:])
+    torch.cuda.synchronize()
+    dev.check_last_launch()
+    last = got[6:].cpu().numpy()
+    assert same_bits(last, want[6:]), describe_difference(last.reshape(-1, w, 3), want[6:].reshape(-1, w, 3))
+
+
 def test_aov_with_another_camera_while_a_launch_is_in_flight(gpu):
     """hrt_render_aov with camera B while a launch with camera A runs on a non-blocking stream: neither sees the other's camera."""
     import torch
