@@ -359,6 +359,86 @@ def _fp(a):
     return np.ascontiguousarray(a, dtype=np.float32).ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _check(rc: int, last_error, entry: Optional[str] = None, layer: str = "hrt"):
+    """The return code of a library call: ``rc``, or for a negative one HrtError with the library's last error -- "<entry> failed
+    (rc): ..." for a named entry point, "<layer> error rc: ..." otherwise."""
+    if rc < 0:
+        raise HrtError((f"{layer} error {rc}" if entry is None else f"{entry} failed ({rc})") + f": {last_error().decode()}")
+    return rc
+
+
+def _call(entry: str, *args):
+    """``entry`` of libhrt.so on ``args``; HrtError "<entry> failed (rc): ..." if it refuses."""
+    lib = device_lib()
+    return _check(getattr(lib, entry)(*args), lib.hrt_last_error, entry)
+
+
+def _ref(x):
+    """The argument for an optional struct: NULL for None."""
+    return None if x is None else C.byref(x)
+
+
+def _ptr(x):
+    """The ``void*`` argument for a device buffer: a torch tensor, an address (0: NULL) or None."""
+    return None if x is None else C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x)
+
+
+def _stream(device=None):
+    """The ``void*`` argument for the current torch stream of ``device`` (None: of the current device)."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _check_tensor(who: str, name: str, t, shape, dtype: str = "float32", device=None, noun: str = "", shown: Optional[str] = None):
+    """ValueError unless ``t`` is a contiguous torch tensor of ``shape`` (None: any length) and ``dtype`` ("int32" takes uint32 as
+    well) on the GPU -- or, with ``device``, on that device, "the <noun>' device".  ``shown``: the shape as the message states it."""
+    import torch
+    dtypes = (torch.int32, torch.uint32) if dtype == "int32" else (getattr(torch, dtype),)
+    if not (isinstance(t, torch.Tensor) and (t.device.type == "cuda" if device is None else t.device == device) and t.dtype in dtypes
+            and t.dim() == len(shape) and all(a is None or a == b for a, b in zip(shape, t.shape)) and t.is_contiguous()):
+        where = "the GPU" if device is None else f"the {noun}' device"
+        raise ValueError(f"{who}: {name} must be a contiguous {shown or _shape_text(shape)} {dtype} tensor on {where}")
+
+
+def _shape_text(shape) -> str:
+    return "(" + ", ".join(f"{x}" for x in shape) + ")"
+
+
+def _ray_batch(who: str, noun: str, batch, tensor_only: bool = False):
+    """The (n, RAY_FLOATS) float32 batch of ``who`` (its rows the ``noun`` of the messages): a torch tensor on the GPU as it is,
+    anything else -- unless ``tensor_only`` -- as a contiguous NumPy array; at most 2^31 - 1 rows."""
+    import torch
+    if tensor_only or isinstance(batch, torch.Tensor):
+        _check_tensor(who, noun if tensor_only else "a torch tensor", batch, (None, RAY_FLOATS), shown="(n, 8)")
+        return batch
+    batch = np.ascontiguousarray(batch, dtype=np.float32)
+    if batch.ndim != 2 or batch.shape[1] != RAY_FLOATS:
+        raise ValueError(f"{who}: {noun} must have shape (n, {RAY_FLOATS}) (got {batch.shape})")
+    return batch
+
+
+def _row_count(who: str, noun: str, batch) -> int:
+    n = batch.shape[0]
+    if n > 0x7FFFFFFF:
+        raise ValueError(f"{who}: at most 2^31 - 1 {noun} per call (got {n})")
+    return n
+
+
+def _view_table(who: str, noun: str, view_type, items, seeds):
+    """(the ``view_type`` table -- View or LensView -- of ``items`` with their ``seeds`` (default 1 each), its length)."""
+    items = list(items)
+    n = len(items)
+    seeds = [1] * n if seeds is None else [int(x) for x in seeds]
+    if len(seeds) != n:
+        raise ValueError(f"{who}: {n} {noun} but {len(seeds)} seeds")
+    views = (view_type * max(n, 1))()
+    field, item_type = view_type._fields_[0]
+    for v, (item, seed) in enumerate(zip(items, seeds)):
+        C.memmove(C.byref(getattr(views[v], field)), C.byref(item), C.sizeof(item_type))
+        views[v].seed = seed
+    return views, n
+
+
 # ------------------------------------------------------------------ host scene
 class HostScene:
     """Scene of the host layer (mirrors the reference's ``Scene`` set-up API)."""
@@ -371,9 +451,7 @@ class HostScene:
         self._check(rc)
 
     def _check(self, rc: int):
-        if rc < 0:
-            raise HrtError(f"hrt_host error {rc}: {self._lib.hrt_host_last_error().decode()}")
-        return rc
+        return _check(rc, self._lib.hrt_host_last_error, layer="hrt_host")
 
     def close(self):
         if self._h:
@@ -461,15 +539,11 @@ class HostScene:
         keys = ["inner", "leaves", "empty_leaves", "depth", "leaf_tri_refs", "units"]
         return dict(zip(keys, list(out)))
 
-
-def _irregular_stats(self, mesh: int = 0) -> dict:
-    """Triangles kept out of the SAH tree because the reference's own tree treats them specially (host/ref_tree.h)."""
-    out = (C.c_uint32 * 8)()
-    self._check(self._lib.hrt_host_scene_irregular_stats(self._h, mesh, out))
-    return dict(zip(["out_of_tree", "slivers", "dropped", "pairs", "ref_leaves", "ref_depth", "dead", "entries"], list(out)))
-
-
-HostScene.irregular_stats = _irregular_stats
+    def irregular_stats(self, mesh: int = 0) -> dict:
+        """Triangles kept out of the SAH tree because the reference's own tree treats them specially (host/ref_tree.h)."""
+        out = (C.c_uint32 * 8)()
+        self._check(self._lib.hrt_host_scene_irregular_stats(self._h, mesh, out))
+        return dict(zip(["out_of_tree", "slivers", "dropped", "pairs", "ref_leaves", "ref_depth", "dead", "entries"], list(out)))
 
 
 def default_camera(aspect: float) -> Camera:
@@ -485,9 +559,7 @@ _inited = False
 def init(device: int = 0):
     global _inited
     lib = device_lib()
-    rc = lib.hrt_init(device)
-    if rc < 0:
-        raise HrtError(f"hrt_init({device}) failed ({rc}): {lib.hrt_last_error().decode()}")
+    _check(lib.hrt_init(device), lib.hrt_last_error, f"hrt_init({device})")
     _inited = True
 
 
@@ -502,9 +574,7 @@ class DeviceScene:
         self._check(self._lib.hrt_scene_create(desc, C.byref(self._h)))
 
     def _check(self, rc: int):
-        if rc < 0:
-            raise HrtError(f"hrt error {rc}: {self._lib.hrt_last_error().decode()}")
-        return rc
+        return _check(rc, self._lib.hrt_last_error)
 
     def close(self):
         if self._h:
@@ -534,13 +604,13 @@ class DeviceScene:
                      d_tiles_ptr: int, stream_ptr: int = 0):
         """hrt_render_tiles: this rank's tiles into a device buffer (asynchronous)."""
         self._check(self._lib.hrt_render_tiles(self._h, C.byref(cam), w, h, spp, seed, flags, rank, world,
-                                               C.c_void_p(d_tiles_ptr), C.c_void_p(stream_ptr)))
+                                               _ptr(d_tiles_ptr), _ptr(stream_ptr)))
 
     def render_accumulate(self, cam: Camera, w: int, h: int, first_sample: int, n_samples: int, seed: int, flags: int,
                           rank: int, world: int, d_sum_tiles_ptr: int, stream_ptr: int = 0):
         """hrt_render_accumulate: add samples [first_sample, first_sample + n_samples) to the running sums (asynchronous)."""
         self._check(self._lib.hrt_render_accumulate(self._h, C.byref(cam), w, h, first_sample, n_samples, seed, flags, rank,
-                                                    world, C.c_void_p(d_sum_tiles_ptr), C.c_void_p(stream_ptr)))
+                                                    world, _ptr(d_sum_tiles_ptr), _ptr(stream_ptr)))
 
     def render_adaptive(self, cam: Camera, w: int, h: int, min_spp: int, max_spp: int, threshold: float, seed: int = 1,
                         flags: int = 0, stats: Optional[Stats] = None):
@@ -550,7 +620,7 @@ class DeviceScene:
         spp = np.empty(((h + TILE - 1) // TILE, (w + TILE - 1) // TILE), dtype=np.uint32)
         p = Adaptive(min_spp, max_spp, threshold)
         self._check(self._lib.hrt_render_adaptive(self._h, C.byref(cam), w, h, C.byref(p), seed, flags, out.ctypes.data,
-                                                   spp.ctypes.data, None if stats is None else C.byref(stats)))
+                                                   spp.ctypes.data, _ref(stats)))
         return out, spp
 
     def render_adaptive_tiles(self, cam: Camera, w: int, h: int, min_spp: int, max_spp: int, threshold: float, seed: int,
@@ -558,16 +628,20 @@ class DeviceScene:
         """hrt_render_adaptive_tiles: this rank's tiles (means) and their counts (uint32 per owned tile) into device buffers."""
         p = Adaptive(min_spp, max_spp, threshold)
         self._check(self._lib.hrt_render_adaptive_tiles(self._h, C.byref(cam), w, h, C.byref(p), seed, flags, rank, world,
-                                                        C.c_void_p(d_tiles_ptr), C.c_void_p(d_tile_spp_ptr), C.c_void_p(stream_ptr)))
+                                                        _ptr(d_tiles_ptr), _ptr(d_tile_spp_ptr), _ptr(stream_ptr)))
 
     def render_features(self, cam: Camera, w: int, h: int, first_sample: int, n_samples: int, seed: int = 1) -> np.ndarray:
         """hrt_render_features: first-hit features of samples [first_sample, first_sample + n_samples) (n_samples 0: pixel centres)
         -> (h, w, FEATURE_FLOATS) float32.  The device buffer is a torch tensor on the scene's device; the call waits for it."""
+        return DeviceScene._features(self, "hrt_render_features", (h, w), C.byref(cam), w, h, first_sample, n_samples, seed)
+
+    def _features(self, entry: str, frames: tuple, *args) -> np.ndarray:
+        """What the three feature wrappers share: ``entry`` on ``args``, a fresh ``frames`` + (FEATURE_FLOATS,) device tensor and the
+        current torch stream; waits, and returns the tensor as NumPy."""
         import torch
-        d = torch.empty((h, w, FEATURE_FLOATS), dtype=torch.float32, device="cuda")
+        d = torch.empty(frames + (FEATURE_FLOATS,), dtype=torch.float32, device="cuda")
         s = torch.cuda.current_stream()
-        self._check(self._lib.hrt_render_features(self._h, C.byref(cam), w, h, first_sample, n_samples, seed, C.c_void_p(d.data_ptr()),
-                                                  C.c_void_p(s.cuda_stream)))
+        self._check(getattr(self._lib, entry)(self._h, *args, _ptr(d), C.c_void_p(s.cuda_stream)))
         s.synchronize()
         return d.cpu().numpy()
 
@@ -578,7 +652,7 @@ class DeviceScene:
         out = np.empty((h, w, 3), dtype=np.float32)
         p = DenoiseParams() if params is None else params
         self._check(self._lib.hrt_render_denoised(self._h, C.byref(cam), w, h, spp, feature_spp, seed, flags, C.byref(p), out.ctypes.data,
-                                                  None if stats is None else C.byref(stats)))
+                                                  _ref(stats)))
         return out
 
     def render_denoised_var(self, cam: Camera, w: int, h: int, spp: int, feature_spp: int, seed: int = 1, flags: int = 0,
@@ -591,7 +665,7 @@ class DeviceScene:
         p = DenoiseVarParams() if params is None else params
         self._check(self._lib.hrt_render_denoised_var(self._h, C.byref(cam), w, h, spp, feature_spp, seed, flags, C.byref(p),
                                                       out.ctypes.data, None if var is None else var.ctypes.data,
-                                                      None if stats is None else C.byref(stats)))
+                                                      _ref(stats)))
         return (out, var) if variance else out
 
     def render_temporal(self, history: "History", cam: Camera, w: int, h: int, spp: int, feature_spp: int, seed: int = 1, flags: int = 0,
@@ -605,8 +679,8 @@ class DeviceScene:
         hist = np.empty((h, w), dtype=np.float32)
         tp = TemporalParams() if tparams is None else tparams
         self._check(self._lib.hrt_render_temporal(self._h, history._h, C.byref(cam), w, h, spp, feature_spp, seed, flags, C.byref(tp),
-                                                  None if dparams is None else C.byref(dparams), out.ctypes.data, hist.ctypes.data,
-                                                  None if stats is None else C.byref(stats)))
+                                                  _ref(dparams), out.ctypes.data, hist.ctypes.data,
+                                                  _ref(stats)))
         return out, hist
 
     def trace_rays(self, rays, mode: str = "closest", flags: int = 0, normalize: bool = False):
@@ -623,26 +697,14 @@ class DeviceScene:
         q = _QUERY_MODES[mode]
         flags = int(flags) | (RAYS_NORMALIZE if normalize else 0)
         is_torch = isinstance(rays, torch.Tensor)
-        if is_torch:
-            if (rays.device.type != "cuda" or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != RAY_FLOATS
-                    or not rays.is_contiguous()):
-                raise ValueError("trace_rays: a torch tensor must be a contiguous (n, 8) float32 tensor on the GPU")
-            d_rays = rays
-        else:
-            a = np.ascontiguousarray(rays, dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != RAY_FLOATS:
-                raise ValueError(f"trace_rays: rays must have shape (n, {RAY_FLOATS}) (got {a.shape})")
-            d_rays = torch.from_numpy(a).to("cuda")
-        n, dev = d_rays.shape[0], d_rays.device
-        if n > 0x7FFFFFFF:
-            raise ValueError(f"trace_rays: at most 2^31 - 1 rays per call (got {n})")
+        rays = _ray_batch("trace_rays", "rays", rays)
+        d_rays = rays if is_torch else torch.from_numpy(rays).to("cuda")
+        n, dev = _row_count("trace_rays", "rays", d_rays), d_rays.device
         if q == QUERY_OCCLUDED:
             out = torch.empty((n,), dtype=torch.int32, device=dev)
         else:
             out = torch.empty((n, SHADE_FLOATS if q == QUERY_SHADE else CLOSEST_FLOATS), dtype=torch.float32, device=dev)
-        s = torch.cuda.current_stream(dev)
-        self._check(self._lib.hrt_trace_rays(self._h, C.c_void_p(d_rays.data_ptr()), n, q, flags, C.c_void_p(out.data_ptr()),
-                                             C.c_void_p(s.cuda_stream)))
+        self._check(self._lib.hrt_trace_rays(self._h, _ptr(d_rays), n, q, flags, _ptr(out), _stream(dev)))
         if is_torch:
             return out
         r = out.cpu().numpy()
@@ -669,22 +731,11 @@ class DeviceScene:
         ``stats``."""
         import torch
         is_torch = isinstance(batch, torch.Tensor)
-        if is_torch:
-            if (batch.device.type != "cuda" or batch.dtype != torch.float32 or batch.dim() != 2 or batch.shape[1] != RAY_FLOATS
-                    or not batch.is_contiguous()):
-                raise ValueError(f"{who}: a torch tensor must be a contiguous (n, 8) float32 tensor on the GPU")
-        else:
-            batch = np.ascontiguousarray(batch, dtype=np.float32)
-            if batch.ndim != 2 or batch.shape[1] != RAY_FLOATS:
-                raise ValueError(f"{who}: {noun} must have shape (n, {RAY_FLOATS}) (got {batch.shape})")
-        n = batch.shape[0]
-        if n > 0x7FFFFFFF:
-            raise ValueError(f"{who}: at most 2^31 - 1 {noun} per call (got {n})")
+        batch = _ray_batch(who, noun, batch)
+        n = _row_count(who, noun, batch)
         if keys is not None:
             if is_torch:
-                if (not isinstance(keys, torch.Tensor) or keys.device != batch.device or keys.dtype not in (torch.int32, torch.uint32)
-                        or keys.shape != (n,) or not keys.is_contiguous()):
-                    raise ValueError(f"{who}: keys must be a contiguous (n,) int32 tensor on the {noun}' device")
+                _check_tensor(who, "keys", keys, (n,), "int32", batch.device, noun, "(n,)")
             else:
                 keys = np.ascontiguousarray(keys)
                 if keys.shape != (n,) or keys.dtype not in (np.uint32, np.int32):
@@ -693,9 +744,7 @@ class DeviceScene:
             if accumulate and first_sample != 0:
                 raise ValueError(f"{who}: accumulate after sample 0 needs the running sums in `out`")
         elif is_torch:
-            if (not isinstance(out, torch.Tensor) or out.device != batch.device or out.dtype != torch.float32 or out.shape != (n, 3)
-                    or not out.is_contiguous()):
-                raise ValueError(f"{who}: out must be a contiguous (n, 3) float32 tensor on the {noun}' device")
+            _check_tensor(who, "out", out, (n, 3), "float32", batch.device, noun, "(n, 3)")
         else:
             o = np.asarray(out)
             if o.shape != (n, 3) or o.dtype != np.float32:
@@ -703,7 +752,7 @@ class DeviceScene:
         if blocking_fn is not None and not is_torch and out is None and not accumulate and first_sample == 0:
             r = np.empty((n, 3), dtype=np.float32)
             self._check(getattr(self._lib, blocking_fn)(self._h, batch.ctypes.data, None if keys is None else keys.ctypes.data, n, spp, seed, flags,
-                                                        r.ctypes.data, None if stats is None else C.byref(stats)))
+                                                        r.ctypes.data, _ref(stats)))
             return r
         if is_torch:
             d_batch, d_keys, d_out = batch, keys, out
@@ -713,9 +762,8 @@ class DeviceScene:
             d_out = None if out is None else torch.from_numpy(np.ascontiguousarray(o)).to(d_batch.device)
         if d_out is None:
             d_out = torch.zeros((n, 3), dtype=torch.float32, device=d_batch.device)
-        s = torch.cuda.current_stream(d_batch.device)
-        self._check(getattr(self._lib, device_fn)(self._h, C.c_void_p(d_batch.data_ptr()), None if d_keys is None else C.c_void_p(d_keys.data_ptr()),
-                                                  n, first_sample, spp, seed, flags, C.c_void_p(d_out.data_ptr()), C.c_void_p(s.cuda_stream)))
+        self._check(getattr(self._lib, device_fn)(self._h, _ptr(d_batch), _ptr(d_keys), n, first_sample, spp, seed, flags, _ptr(d_out),
+                                                  _stream(d_batch.device)))
         if is_torch:
             return d_out
         r = d_out.cpu().numpy()
@@ -745,28 +793,45 @@ class DeviceScene:
         ``render``).  With ``out`` a contiguous (n, h, w, 3) float32 torch tensor on the GPU the call runs on the current torch
         stream of its device without synchronising and returns ``out`` (hrt_render_views_device; ``check_last_launch`` before the
         frames are trusted).  Without it the frames come back as a NumPy array; ``stats``: a Stats to fill, if wanted."""
-        cams = list(cams)
-        n = len(cams)
-        seeds = [1] * n if seeds is None else [int(x) for x in seeds]
-        if len(seeds) != n:
-            raise ValueError(f"render_views: {n} cameras but {len(seeds)} seeds")
-        views = (View * max(n, 1))()
-        for v, (cam, seed) in enumerate(zip(cams, seeds)):
-            views[v].cam = cam
-            views[v].seed = seed
+        views, n = _view_table("render_views", "cameras", View, cams, seeds)
         if out is not None:
-            import torch
-            if (not isinstance(out, torch.Tensor) or out.device.type != "cuda" or out.dtype != torch.float32
-                    or tuple(out.shape) != (n, h, w, 3) or not out.is_contiguous()):
-                raise ValueError(f"render_views: out must be a contiguous ({n}, {h}, {w}, 3) float32 tensor on the GPU")
-            s = torch.cuda.current_stream(out.device)
-            self._check(self._lib.hrt_render_views_device(self._h, views, n, w, h, spp, flags, C.c_void_p(out.data_ptr()),
-                                                          C.c_void_p(s.cuda_stream)))
-            return out
-        frames = np.empty((n, h, w, 3), dtype=np.float32)
-        self._check(self._lib.hrt_render_views(self._h, views, n, w, h, spp, flags, frames.ctypes.data,
-                                               None if stats is None else C.byref(stats)))
+            return DeviceScene._frames_device(self, "render_views", "hrt_render_views_device", (views, n, w, h, spp, flags), out, (n, h, w, 3))
+        return DeviceScene._frames_blocking(self, "hrt_render_views", (views, n, w, h, spp, flags), (n, h, w, 3), stats)
+
+    def _frames_device(self, who: str, entry: str, args: tuple, out, shape: tuple):
+        """The device form ``entry`` on ``args`` into ``out``, a contiguous float32 torch tensor of ``shape`` on the GPU, on the
+        current torch stream of its device, without synchronising; returns ``out``."""
+        _check_tensor(who, "out", out, shape)
+        self._check(getattr(self._lib, entry)(self._h, *args, _ptr(out), _stream(out.device)))
+        return out
+
+    def _frames_blocking(self, entry: str, args: tuple, shape: tuple, stats: Optional[Stats]):
+        """The blocking form ``entry`` on ``args`` -> a NumPy array of ``shape``; fills ``stats`` if given."""
+        frames = np.empty(shape, dtype=np.float32)
+        self._check(getattr(self._lib, entry)(self._h, *args, frames.ctypes.data, _ref(stats)))
         return frames
+
+    def _frames(self, who: str, shape: tuple, device: tuple, blocking: tuple, first_sample: int, out, accumulate: bool, stats: Optional[Stats]):
+        """The frame call behind render_lens and render_lens_views; ``device`` and ``blocking``: (entry, args) of the two forms.
+        ``out`` a torch tensor: the device form into it.  ``out`` NumPy, ``accumulate`` or a ``first_sample``: uploaded (or zeros),
+        the device form, the result copied back (into ``out``).  Otherwise the blocking form, which fills ``stats``."""
+        import torch
+        if isinstance(out, torch.Tensor):
+            return DeviceScene._frames_device(self, who, *device, out, shape)
+        if out is not None:
+            o = np.asarray(out)
+            if o.shape != shape or o.dtype != np.float32:
+                raise ValueError(f"{who}: out must be {_shape_text(shape)} float32 (got {o.shape} {o.dtype})")
+        elif accumulate and first_sample != 0:
+            raise ValueError(f"{who}: accumulate after sample 0 needs the running sums in `out`")
+        if out is None and not accumulate and first_sample == 0:
+            return DeviceScene._frames_blocking(self, *blocking, shape, stats)
+        d = torch.zeros(shape, dtype=torch.float32, device="cuda") if out is None else torch.from_numpy(np.ascontiguousarray(o)).to("cuda")
+        r = DeviceScene._frames_device(self, who, *device, d, shape).cpu().numpy()
+        if out is not None:
+            out[...] = r
+            return out
+        return r
 
     def render_lens(self, lens: Lens, w: int, h: int, spp: int, seed: int = 1, flags: int = 0, first_sample: int = 0, out=None,
                     accumulate: bool = False, stats: Optional[Stats] = None):
@@ -776,35 +841,9 @@ class DeviceScene:
         synchronising and returns ``out`` (hrt_render_lens_device).  Otherwise the frame comes back as NumPy and the call blocks;
         ``stats``: a Stats to fill, if wanted (the blocking form of samples [0, spp) without ``out``: hrt_render_lens).
         ``flags``: FLAG_EXACT_ONLY, FLAG_MESH_BRUTE, FLAG_NO_LDS_TREE, FLAG_GAMMA (not with ``accumulate``)."""
-        import torch
         flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
-        if isinstance(out, torch.Tensor):
-            if out.device.type != "cuda" or out.dtype != torch.float32 or tuple(out.shape) != (h, w, 3) or not out.is_contiguous():
-                raise ValueError(f"render_lens: out must be a contiguous ({h}, {w}, 3) float32 tensor on the GPU")
-            s = torch.cuda.current_stream(out.device)
-            self._check(self._lib.hrt_render_lens_device(self._h, C.byref(lens), w, h, first_sample, spp, seed, flags,
-                                                         C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)))
-            return out
-        if out is not None:
-            o = np.asarray(out)
-            if o.shape != (h, w, 3) or o.dtype != np.float32:
-                raise ValueError(f"render_lens: out must be ({h}, {w}, 3) float32 (got {o.shape} {o.dtype})")
-        elif accumulate and first_sample != 0:
-            raise ValueError("render_lens: accumulate after sample 0 needs the running sums in `out`")
-        if out is None and not accumulate and first_sample == 0:
-            frame = np.empty((h, w, 3), dtype=np.float32)
-            self._check(self._lib.hrt_render_lens(self._h, C.byref(lens), w, h, spp, seed, flags, frame.ctypes.data,
-                                                  None if stats is None else C.byref(stats)))
-            return frame
-        d = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda") if out is None else torch.from_numpy(np.ascontiguousarray(o)).to("cuda")
-        s = torch.cuda.current_stream(d.device)
-        self._check(self._lib.hrt_render_lens_device(self._h, C.byref(lens), w, h, first_sample, spp, seed, flags, C.c_void_p(d.data_ptr()),
-                                                     C.c_void_p(s.cuda_stream)))
-        r = d.cpu().numpy()
-        if out is not None:
-            out[...] = r
-            return out
-        return r
+        return DeviceScene._frames(self, "render_lens", (h, w, 3), ("hrt_render_lens_device", (C.byref(lens), w, h, first_sample, spp, seed, flags)),
+                                   ("hrt_render_lens", (C.byref(lens), w, h, spp, seed, flags)), first_sample, out, accumulate, stats)
 
     def render_lens_adaptive(self, lens: Lens, w: int, h: int, min_spp: int, max_spp: int, threshold: float, seed: int = 1,
                              flags: int = 0, out=None, stats: Optional[Stats] = None):
@@ -819,46 +858,23 @@ class DeviceScene:
         ty, tx = (h + TILE - 1) // TILE, (w + TILE - 1) // TILE
         if out is not None:
             import torch
-            if (not isinstance(out, torch.Tensor) or out.device.type != "cuda" or out.dtype != torch.float32
-                    or tuple(out.shape) != (h, w, 3) or not out.is_contiguous()):
-                raise ValueError(f"render_lens_adaptive: out must be a contiguous ({h}, {w}, 3) float32 tensor on the GPU")
+            _check_tensor("render_lens_adaptive", "out", out, (h, w, 3))
             if stats is not None:
                 raise ValueError("render_lens_adaptive: stats are the blocking form's (no `out`)")
-            s = torch.cuda.current_stream(out.device)
             counts = torch.empty((ty, tx), dtype=torch.int32, device=out.device)
-            self._check(self._lib.hrt_render_lens_adaptive_device(self._h, C.byref(lens), w, h, C.byref(p), seed, int(flags),
-                                                                  C.c_void_p(out.data_ptr()), C.c_void_p(counts.data_ptr()),
-                                                                  C.c_void_p(s.cuda_stream)))
+            self._check(self._lib.hrt_render_lens_adaptive_device(self._h, C.byref(lens), w, h, C.byref(p), seed, int(flags), _ptr(out),
+                                                                  _ptr(counts), _stream(out.device)))
             return out, counts
         frame = np.empty((h, w, 3), dtype=np.float32)
         spp = np.empty((ty, tx), dtype=np.uint32)
         self._check(self._lib.hrt_render_lens_adaptive(self._h, C.byref(lens), w, h, C.byref(p), seed, int(flags), frame.ctypes.data,
-                                                       spp.ctypes.data, None if stats is None else C.byref(stats)))
+                                                       spp.ctypes.data, _ref(stats)))
         return frame, spp
 
     def render_lens_features(self, lens: Lens, w: int, h: int, first_sample: int, n_samples: int, seed: int = 1) -> np.ndarray:
         """hrt_render_lens_features: ``render_features`` through ``lens`` -> (h, w, FEATURE_FLOATS) float32.  The device buffer is a
         torch tensor on the scene's device; the call waits for it."""
-        import torch
-        d = torch.empty((h, w, FEATURE_FLOATS), dtype=torch.float32, device="cuda")
-        s = torch.cuda.current_stream()
-        self._check(self._lib.hrt_render_lens_features(self._h, C.byref(lens), w, h, first_sample, n_samples, seed, C.c_void_p(d.data_ptr()),
-                                                       C.c_void_p(s.cuda_stream)))
-        s.synchronize()
-        return d.cpu().numpy()
-
-    @staticmethod
-    def _lens_views(who: str, lenses, seeds):
-        lenses = list(lenses)
-        n = len(lenses)
-        seeds = [1] * n if seeds is None else [int(x) for x in seeds]
-        if len(seeds) != n:
-            raise ValueError(f"{who}: {n} lenses but {len(seeds)} seeds")
-        views = (LensView * max(n, 1))()
-        for v, (lens, seed) in enumerate(zip(lenses, seeds)):
-            C.memmove(C.byref(views[v].lens), C.byref(lens), C.sizeof(Lens))
-            views[v].seed = seed
-        return views, n
+        return DeviceScene._features(self, "hrt_render_lens_features", (h, w), C.byref(lens), w, h, first_sample, n_samples, seed)
 
     def render_lens_views(self, lenses, w: int, h: int, spp: int, seeds=None, flags: int = 0, first_sample: int = 0, out=None,
                           accumulate: bool = False, stats: Optional[Stats] = None):
@@ -869,48 +885,16 @@ class DeviceScene:
         without synchronising and returns ``out`` (hrt_render_lens_views_device).  Otherwise the frames come back as NumPy and the
         call blocks; ``stats``: a Stats to fill, if wanted (the blocking form of samples [0, spp) without ``out``:
         hrt_render_lens_views).  ``flags``: as ``render_lens``."""
-        import torch
-        views, n = DeviceScene._lens_views("render_lens_views", lenses, seeds)
+        views, n = _view_table("render_lens_views", "lenses", LensView, lenses, seeds)
         flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
-        if isinstance(out, torch.Tensor):
-            if out.device.type != "cuda" or out.dtype != torch.float32 or tuple(out.shape) != (n, h, w, 3) or not out.is_contiguous():
-                raise ValueError(f"render_lens_views: out must be a contiguous ({n}, {h}, {w}, 3) float32 tensor on the GPU")
-            s = torch.cuda.current_stream(out.device)
-            self._check(self._lib.hrt_render_lens_views_device(self._h, views, n, w, h, first_sample, spp, flags, C.c_void_p(out.data_ptr()),
-                                                               C.c_void_p(s.cuda_stream)))
-            return out
-        if out is not None:
-            o = np.asarray(out)
-            if o.shape != (n, h, w, 3) or o.dtype != np.float32:
-                raise ValueError(f"render_lens_views: out must be ({n}, {h}, {w}, 3) float32 (got {o.shape} {o.dtype})")
-        elif accumulate and first_sample != 0:
-            raise ValueError("render_lens_views: accumulate after sample 0 needs the running sums in `out`")
-        if out is None and not accumulate and first_sample == 0:
-            frames = np.empty((n, h, w, 3), dtype=np.float32)
-            self._check(self._lib.hrt_render_lens_views(self._h, views, n, w, h, spp, flags, frames.ctypes.data,
-                                                        None if stats is None else C.byref(stats)))
-            return frames
-        d = torch.zeros((n, h, w, 3), dtype=torch.float32, device="cuda") if out is None else torch.from_numpy(np.ascontiguousarray(o)).to("cuda")
-        s = torch.cuda.current_stream(d.device)
-        self._check(self._lib.hrt_render_lens_views_device(self._h, views, n, w, h, first_sample, spp, flags, C.c_void_p(d.data_ptr()),
-                                                           C.c_void_p(s.cuda_stream)))
-        r = d.cpu().numpy()
-        if out is not None:
-            out[...] = r
-            return out
-        return r
+        return DeviceScene._frames(self, "render_lens_views", (n, h, w, 3), ("hrt_render_lens_views_device", (views, n, w, h, first_sample, spp, flags)),
+                                   ("hrt_render_lens_views", (views, n, w, h, spp, flags)), first_sample, out, accumulate, stats)
 
     def render_lens_views_features(self, lenses, w: int, h: int, first_sample: int, n_samples: int, seeds=None) -> np.ndarray:
         """hrt_render_lens_views_features: ``render_lens_features`` of every lens of ``lenses`` with its seed, in one launch ->
         (n, h, w, FEATURE_FLOATS) float32.  The device buffer is a torch tensor on the scene's device; the call waits for it."""
-        import torch
-        views, n = DeviceScene._lens_views("render_lens_views_features", lenses, seeds)
-        d = torch.empty((n, h, w, FEATURE_FLOATS), dtype=torch.float32, device="cuda")
-        s = torch.cuda.current_stream()
-        self._check(self._lib.hrt_render_lens_views_features(self._h, views, n, w, h, first_sample, n_samples, C.c_void_p(d.data_ptr()),
-                                                             C.c_void_p(s.cuda_stream)))
-        s.synchronize()
-        return d.cpu().numpy()
+        views, n = _view_table("render_lens_views_features", "lenses", LensView, lenses, seeds)
+        return DeviceScene._features(self, "hrt_render_lens_views_features", (n, h, w), views, n, w, h, first_sample, n_samples)
 
     def check_last_launch(self):
         """hrt_check_last_launch: waits for the last launch; raises if the trace kernel gave up (incomplete tiles)."""
@@ -956,25 +940,18 @@ def pick_kernel(n_meshes: int, n_lights: int, n_spheres: int, tab_rows: int, til
                 n_views: int = 0, kernel: str = "") -> str:
     """hrt_debug_pick_kernel: the name of the trace kernel build a launch with these traits runs (``kernel``: the value of
     HRT_KERNEL); raises HrtError where the launch would be refused.  Needs neither ``init`` nor a GPU."""
-    lib = device_lib()
     name = C.create_string_buffer(64)
-    rc = lib.hrt_debug_pick_kernel(C.byref(PickInput(n_meshes, n_lights, n_spheres, tab_rows, tiles, spp, flags, int(has_list), n_views,
+    _call("hrt_debug_pick_kernel", C.byref(PickInput(n_meshes, n_lights, n_spheres, tab_rows, tiles, spp, flags, int(has_list), n_views,
                                                      kernel.encode())), name, len(name))
-    if rc < 0:
-        raise HrtError(f"hrt_debug_pick_kernel failed ({rc}): {lib.hrt_last_error().decode()}")
     return name.value.decode()
 
 
 def debug_kat(which: int, inp, prim=None, cam: Optional[Camera] = None) -> np.ndarray:
     """hrt_debug_kat: the DEVICE functions of the trace path on caller vectors (include/hrt.h); returns (n, out width)."""
-    lib = device_lib()
     a = np.ascontiguousarray(inp, dtype=np.float32).reshape(-1, _KAT_IN[which])
     out = np.empty((a.shape[0], _KAT_OUT[which]), dtype=np.float32)
     pr = None if prim is None else np.ascontiguousarray(prim, dtype=np.float32)
-    rc = lib.hrt_debug_kat(which, None if cam is None else C.byref(cam), None if pr is None else pr.ctypes.data, a.ctypes.data,
-                           a.shape[0], out.ctypes.data)
-    if rc < 0:
-        raise HrtError(f"hrt_debug_kat failed ({rc}): {lib.hrt_last_error().decode()}")
+    _call("hrt_debug_kat", which, _ref(cam), None if pr is None else pr.ctypes.data, a.ctypes.data, a.shape[0], out.ctypes.data)
     return out
 
 
@@ -986,9 +963,7 @@ class MultiScene:
         self._lib = device_lib()
         self._h = C.c_void_p()
         arr = (C.c_int * len(devices))(*devices)
-        rc = self._lib.hrt_multi_create(desc, len(devices), arr, C.byref(self._h))
-        if rc < 0:
-            raise HrtError(f"hrt error {rc}: {self._lib.hrt_last_error().decode()}")
+        _check(self._lib.hrt_multi_create(desc, len(devices), arr, C.byref(self._h)), self._lib.hrt_last_error)
         self.note = self._lib.hrt_last_error().decode()  # what creation fell back from, if anything
         _inited = True
 
@@ -1011,9 +986,7 @@ class MultiScene:
     def render(self, cam: Camera, w: int, h: int, spp: int, seed: int = 1, flags: int = 0):
         out = np.empty((h, w, 3), dtype=np.float32)
         st = Stats()
-        rc = self._lib.hrt_multi_render(self._h, C.byref(cam), w, h, spp, seed, flags, out.ctypes.data, C.byref(st))
-        if rc < 0:
-            raise HrtError(f"hrt error {rc}: {self._lib.hrt_last_error().decode()}")
+        _check(self._lib.hrt_multi_render(self._h, C.byref(cam), w, h, spp, seed, flags, out.ctypes.data, C.byref(st)), self._lib.hrt_last_error)
         return out, st
 
 
@@ -1023,9 +996,7 @@ def render_multi(desc, cam: Camera, w: int, h: int, spp: int, seed: int, flags: 
     out = np.empty((h, w, 3), dtype=np.float32)
     st = Stats()
     arr = (C.c_int * len(devices))(*devices)
-    rc = lib.hrt_render_multi(desc, C.byref(cam), w, h, spp, seed, flags, len(devices), arr, out.ctypes.data, C.byref(st))
-    if rc < 0:
-        raise HrtError(f"hrt error {rc}: {lib.hrt_last_error().decode()}")
+    _check(lib.hrt_render_multi(desc, C.byref(cam), w, h, spp, seed, flags, len(devices), arr, out.ctypes.data, C.byref(st)), lib.hrt_last_error)
     return out, st
 
 
@@ -1033,13 +1004,15 @@ def camera_rays(cam: Camera, w: int, h: int, sample: int = 0, seed: int = 1):
     """hrt_camera_rays: the render's camera rays of sample ``sample`` of a w x h frame as a (w*h, RAY_FLOATS) float32 torch tensor
     on the current device (pixel y*w + x), written on the current torch stream.  Traced with trace_radiance(first_sample=sample)
     they give the render's samples."""
+    return _frame_rays("hrt_camera_rays", cam, w, h, sample, seed)
+
+
+def _frame_rays(entry: str, view, w: int, h: int, sample: int, seed: int):
+    """camera_rays and lens_rays: ``entry`` on the camera or lens into a fresh (w*h, RAY_FLOATS) tensor, on the current torch stream."""
     import torch
-    lib = device_lib()
+    device_lib()  # a missing library is reported before the GPU is asked for anything
     out = torch.empty((w * h, RAY_FLOATS), dtype=torch.float32, device="cuda")
-    rc = lib.hrt_camera_rays(C.byref(cam), w, h, sample, seed, C.c_void_p(out.data_ptr()),
-                             C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc < 0:
-        raise HrtError(f"hrt_camera_rays failed ({rc}): {lib.hrt_last_error().decode()}")
+    _call(entry, C.byref(view), w, h, sample, seed, _ptr(out), _stream())
     return out
 
 
@@ -1047,14 +1020,7 @@ def lens_rays(lens: Lens, w: int, h: int, sample: int = 0, seed: int = 1):
     """hrt_lens_rays: the rays of sample ``sample`` of a w x h frame of ``lens`` as a (w*h, RAY_FLOATS) float32 torch tensor on the
     current device (pixel y*w + x), written on the current torch stream; a degenerate sample has direction 0.  Traced with
     trace_radiance(first_sample=sample) they give the samples of ``DeviceScene.render_lens``."""
-    import torch
-    lib = device_lib()
-    out = torch.empty((w * h, RAY_FLOATS), dtype=torch.float32, device="cuda")
-    rc = lib.hrt_lens_rays(C.byref(lens), w, h, sample, seed, C.c_void_p(out.data_ptr()),
-                           C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc < 0:
-        raise HrtError(f"hrt_lens_rays failed ({rc}): {lib.hrt_last_error().decode()}")
-    return out
+    return _frame_rays("hrt_lens_rays", lens, w, h, sample, seed)
 
 
 def bake_rays(points, sample: int = 0, seed: int = 1, keys=None):
@@ -1063,20 +1029,14 @@ def bake_rays(points, sample: int = 0, seed: int = 1, keys=None):
     sample has direction 0.  ``keys``: (n,) int32 on the same device.  Traced with trace_radiance(first_sample=sample, keys=keys)
     they give the samples of ``DeviceScene.bake``."""
     import torch
-    lib = device_lib()
-    if (not isinstance(points, torch.Tensor) or points.device.type != "cuda" or points.dtype != torch.float32 or points.dim() != 2
-            or points.shape[1] != RAY_FLOATS or not points.is_contiguous()):
-        raise ValueError("bake_rays: points must be a contiguous (n, 8) float32 tensor on the GPU")
+    device_lib()
+    _ray_batch("bake_rays", "points", points, tensor_only=True)
     n = points.shape[0]
-    if keys is not None and (not isinstance(keys, torch.Tensor) or keys.device != points.device or keys.dtype not in (torch.int32, torch.uint32)
-                             or keys.shape != (n,) or not keys.is_contiguous()):
-        raise ValueError("bake_rays: keys must be a contiguous (n,) int32 tensor on the points' device")
+    if keys is not None:
+        _check_tensor("bake_rays", "keys", keys, (n,), "int32", points.device, "points", "(n,)")
     out = torch.empty((n, RAY_FLOATS), dtype=torch.float32, device=points.device)
     with torch.cuda.device(points.device):
-        rc = lib.hrt_bake_rays(C.c_void_p(points.data_ptr()), None if keys is None else C.c_void_p(keys.data_ptr()), n, sample, seed,
-                               C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(points.device).cuda_stream))
-    if rc < 0:
-        raise HrtError(f"hrt_bake_rays failed ({rc}): {lib.hrt_last_error().decode()}")
+        _call("hrt_bake_rays", _ptr(points), _ptr(keys), n, sample, seed, _ptr(out), _stream(points.device))
     return out
 
 
@@ -1096,12 +1056,9 @@ def quad_points(quad: Quad, tw: int, th: int, side: int = 1, time: float = 0.0, 
     """hrt_bake_quad_points: the (tw * th, RAY_FLOATS) float32 bake points of a tw x th lightmap over ``quad``, row-major (texel
     (i, j) at j * tw + i), at the texel centres with the quad's normal times ``side`` (+1: the side the trace path lights).  Host
     only: needs no GPU."""
-    lib = device_lib()
     n = int(tw) * int(th)
     out = np.empty((n if 0 < n <= 0x7FFFFFFF else 1, RAY_FLOATS), dtype=np.float32)  # a frame the library refuses writes nothing
-    rc = lib.hrt_bake_quad_points(C.byref(quad), tw, th, side, time, bias, out.ctypes.data)
-    if rc < 0:
-        raise HrtError(f"hrt_bake_quad_points failed ({rc}): {lib.hrt_last_error().decode()}")
+    _call("hrt_bake_quad_points", C.byref(quad), tw, th, side, time, bias, out.ctypes.data)
     return out
 
 
@@ -1109,7 +1066,6 @@ def mesh_points(positions, indices, time: float = 0.0, bias: float = 1e-4) -> np
     """hrt_bake_mesh_points: one bake point per vertex of a triangle mesh -- ``positions`` (n_vertices, 3) float32, ``indices``
     (n_triangles, 3) uint32 -- with the unnormalised sum of the cross products of its triangles as the normal (0 for a vertex no
     triangle uses: a degenerate point).  Host only: needs no GPU."""
-    lib = device_lib()
     p = np.ascontiguousarray(positions, dtype=np.float32)
     ix = np.ascontiguousarray(indices, dtype=np.uint32)
     if p.ndim != 2 or p.shape[1] != 3:
@@ -1117,9 +1073,7 @@ def mesh_points(positions, indices, time: float = 0.0, bias: float = 1e-4) -> np
     if ix.size and (ix.ndim != 2 or ix.shape[1] != 3):
         raise ValueError(f"mesh_points: indices must have shape (n_triangles, 3) (got {ix.shape})")
     out = np.empty((p.shape[0], RAY_FLOATS), dtype=np.float32)
-    rc = lib.hrt_bake_mesh_points(p.ctypes.data, p.shape[0], ix.ctypes.data, ix.shape[0] if ix.size else 0, time, bias, out.ctypes.data)
-    if rc < 0:
-        raise HrtError(f"hrt_bake_mesh_points failed ({rc}): {lib.hrt_last_error().decode()}")
+    _call("hrt_bake_mesh_points", p.ctypes.data, p.shape[0], ix.ctypes.data, ix.shape[0] if ix.size else 0, time, bias, out.ctypes.data)
     return out
 
 
@@ -1134,11 +1088,7 @@ def tiles_owned(w: int, h: int, rank: int, world: int) -> int:
 
 def assemble_frame(d_gathered_ptr: int, tiles_per_rank_padded: int, w: int, h: int, world: int, d_frame_ptr: int,
                    stream_ptr: int = 0):
-    lib = device_lib()
-    rc = lib.hrt_assemble_frame(C.c_void_p(d_gathered_ptr), tiles_per_rank_padded, w, h, world,
-                                C.c_void_p(d_frame_ptr), C.c_void_p(stream_ptr))
-    if rc < 0:
-        raise HrtError(f"hrt_assemble_frame failed ({rc}): {lib.hrt_last_error().decode()}")
+    _call("hrt_assemble_frame", _ptr(d_gathered_ptr), tiles_per_rank_padded, w, h, world, _ptr(d_frame_ptr), _ptr(stream_ptr))
 
 
 def assemble_frame_host(gathered: np.ndarray, w: int, h: int, world: int) -> np.ndarray:
@@ -1158,11 +1108,7 @@ def assemble_frame_host(gathered: np.ndarray, w: int, h: int, world: int) -> np.
 
 def finalize_tiles(d_sum_tiles_ptr: int, n_tiles: int, total_samples: int, flags: int, d_tiles_ptr: int, stream_ptr: int = 0):
     """hrt_finalize_tiles: running sums -> pixel means (+ gamma with FLAG_GAMMA); the two pointers may be equal."""
-    lib = device_lib()
-    rc = lib.hrt_finalize_tiles(C.c_void_p(d_sum_tiles_ptr), n_tiles, total_samples, flags, C.c_void_p(d_tiles_ptr),
-                                C.c_void_p(stream_ptr))
-    if rc < 0:
-        raise HrtError(f"hrt_finalize_tiles failed ({rc}): {lib.hrt_last_error().decode()}")
+    _call("hrt_finalize_tiles", _ptr(d_sum_tiles_ptr), n_tiles, total_samples, flags, _ptr(d_tiles_ptr), _ptr(stream_ptr))
 
 
 def denoise_scratch_bytes(w: int, h: int) -> int:
@@ -1174,12 +1120,8 @@ def denoise(d_color_ptr: int, d_features_ptr: int, w: int, h: int, params: Optio
             d_out_ptr: int, stream_ptr: int = 0):
     """hrt_denoise on device pointers (asynchronous on the stream): linear colour (h, w, 3) and features (h, w, FEATURE_FLOATS)
     -> d_out (h, w, 3).  ``params`` None: the default DenoiseParams; ``flags``: FLAG_GAMMA or 0."""
-    lib = device_lib()
     p = DenoiseParams() if params is None else params
-    rc = lib.hrt_denoise(C.c_void_p(d_color_ptr), C.c_void_p(d_features_ptr), w, h, C.byref(p), flags, C.c_void_p(d_scratch_ptr),
-                         C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr))
-    if rc < 0:
-        raise HrtError(f"hrt_denoise failed ({rc}): {lib.hrt_last_error().decode()}")
+    _call("hrt_denoise", _ptr(d_color_ptr), _ptr(d_features_ptr), w, h, C.byref(p), flags, _ptr(d_scratch_ptr), _ptr(d_out_ptr), _ptr(stream_ptr))
 
 
 def denoise_var_scratch_bytes(w: int, h: int) -> int:
@@ -1192,12 +1134,9 @@ def denoise_var(d_color_ptr: int, d_color_half_ptr: int, d_features_ptr: int, w:
     """hrt_denoise_var on device pointers (asynchronous on the stream): linear means of all samples and of their first half
     (h, w, 3) and features (h, w, FEATURE_FLOATS) -> d_out (h, w, 3) and, if its pointer is not 0, the variance map (h, w).
     ``params`` None: the default DenoiseVarParams; ``flags``: FLAG_GAMMA or 0."""
-    lib = device_lib()
     p = DenoiseVarParams() if params is None else params
-    rc = lib.hrt_denoise_var(C.c_void_p(d_color_ptr), C.c_void_p(d_color_half_ptr), C.c_void_p(d_features_ptr), w, h, C.byref(p), flags,
-                             C.c_void_p(d_scratch_ptr), C.c_void_p(d_out_ptr), C.c_void_p(d_variance_out_ptr), C.c_void_p(stream_ptr))
-    if rc < 0:
-        raise HrtError(f"hrt_denoise_var failed ({rc}): {lib.hrt_last_error().decode()}")
+    _call("hrt_denoise_var", _ptr(d_color_ptr), _ptr(d_color_half_ptr), _ptr(d_features_ptr), w, h, C.byref(p), flags, _ptr(d_scratch_ptr),
+          _ptr(d_out_ptr), _ptr(d_variance_out_ptr), _ptr(stream_ptr))
 
 
 def temporal_accumulate(cam: Camera, prev_cam: Optional[Camera], w: int, h: int, d_color_ptr: int, d_color_half_ptr: int, d_features_ptr: int,
@@ -1206,25 +1145,17 @@ def temporal_accumulate(cam: Camera, prev_cam: Optional[Camera], w: int, h: int,
     """hrt_temporal_accumulate on device pointers (asynchronous on the stream): the current frame's linear means, first-half means
     (0: none) and features, the previous call's outputs with the features and camera of that frame (``prev_cam`` None and 0s: the
     first frame) -> accumulated colour, half colour and history lengths.  ``params`` None: the default TemporalParams."""
-    lib = device_lib()
     p = TemporalParams() if params is None else params
-    ptr = lambda v: C.c_void_p(v) if v else None
-    rc = lib.hrt_temporal_accumulate(C.byref(cam), None if prev_cam is None else C.byref(prev_cam), w, h, ptr(d_color_ptr),
-                                     ptr(d_color_half_ptr), ptr(d_features_ptr), ptr(d_prev_color_ptr), ptr(d_prev_color_half_ptr),
-                                     ptr(d_prev_features_ptr), ptr(d_prev_history_ptr), C.byref(p), ptr(d_out_ptr), ptr(d_out_half_ptr),
-                                     ptr(d_history_out_ptr), C.c_void_p(stream_ptr))
-    if rc < 0:
-        raise HrtError(f"hrt_temporal_accumulate failed ({rc}): {lib.hrt_last_error().decode()}")
+    _call("hrt_temporal_accumulate", C.byref(cam), _ref(prev_cam), w, h, _ptr(d_color_ptr), _ptr(d_color_half_ptr), _ptr(d_features_ptr),
+          _ptr(d_prev_color_ptr), _ptr(d_prev_color_half_ptr), _ptr(d_prev_features_ptr), _ptr(d_prev_history_ptr), C.byref(p), _ptr(d_out_ptr),
+          _ptr(d_out_half_ptr), _ptr(d_history_out_ptr), _ptr(stream_ptr))
 
 
 def encode_ppm(d_frame_ptr: int, w: int, h: int, fmt: int, d_out_ptr: int, capacity: int, stream_ptr: int = 0) -> int:
     """hrt_encode_ppm: the reference's PPM file (fmt 3, byte for byte) or its binary form (fmt 6), encoded on the
     device into d_out; returns the file size in bytes."""
-    lib = device_lib()
     n = C.c_size_t(0)
-    rc = lib.hrt_encode_ppm(C.c_void_p(d_frame_ptr), w, h, fmt, C.c_void_p(d_out_ptr), capacity, C.byref(n), C.c_void_p(stream_ptr))
-    if rc < 0:
-        raise HrtError(f"hrt_encode_ppm failed ({rc}): {lib.hrt_last_error().decode()}")
+    _call("hrt_encode_ppm", _ptr(d_frame_ptr), w, h, fmt, _ptr(d_out_ptr), capacity, C.byref(n), _ptr(stream_ptr))
     return int(n.value)
 
 
@@ -1244,7 +1175,4 @@ def ppm_text_reference(rgb: np.ndarray) -> bytes:
 def write_ppm(path: str, rgb: np.ndarray):
     """P3 dump with the reference's quantisation (main.cpp:258-261)."""
     rgb = np.ascontiguousarray(rgb, dtype=np.float32)
-    lib = device_lib()
-    rc = lib.hrt_write_ppm(path.encode(), rgb.ctypes.data, rgb.shape[1], rgb.shape[0])
-    if rc < 0:
-        raise HrtError(f"hrt_write_ppm failed ({rc}): {lib.hrt_last_error().decode()}")
+    _call("hrt_write_ppm", path.encode(), rgb.ctypes.data, rgb.shape[1], rgb.shape[0])

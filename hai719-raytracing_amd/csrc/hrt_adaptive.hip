@@ -132,33 +132,43 @@ static int adaptive_trace_done(hrt_scene *s, double *kernel_ms) {
     return HRT_OK;
 }
 
-// The rounds over this rank's tiles: d_sums (tiles_owned tiles, tile-major) ends with the means, d_counts with each tile's count
-// (NULL: the scene's own count map, ad_words + 3 x tiles_owned).
-static int adaptive_run(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, const hrt_adaptive *p, uint64_t seed, uint32_t flags,
-                        uint32_t rank, uint32_t world, float *d_sums, uint32_t *d_counts, hipStream_t stream, double *kernel_ms) {
-    *kernel_ms = 0.0;
-    DRender R;
-    DCamera C;
-    int rc = fill_render(s, cam, w, h, p->min_spp, seed, flags, rank, world, R, C);  // the frame, the partition; the scene's device
-    if (rc != HRT_OK) return rc;
-    const uint32_t n_tiles = R.tiles_owned;
-    if (n_tiles == 0u) return HRT_OK;
+// The scene's ad_words as a call over n tiles carves it: two tile lists, the judge's keep flags and the count map (n words each),
+// then the length of the next list.
+struct AdWords {
+    uint32_t *lists[2], *keep, *counts, *counter;
+    AdWords(hrt_scene *s, size_t n) {
+        lists[0] = s->ad_words.as<uint32_t>(); lists[1] = lists[0] + n; keep = lists[1] + n; counts = keep + n; counter = counts + n;
+    }
+    static size_t bytes(size_t n) { return (4u * n + 1u) * sizeof(uint32_t); }
+};
+
+// What the rounds run over: the frame, and the n_tiles tiles that rank of world owns (the lens path: every tile, 0 of 1).
+struct AdFrame { uint32_t w, h, tiles_x, n_tiles, rank, world; };
+
+// The rounds, for the camera path (adaptive_run) and the lens path (lens_adaptive_run, hrt_lens_adaptive.hip) alike: d_sums
+// (n_tiles tiles, tile-major) ends with the means, d_counts with each tile's count (NULL: the scene's own count map).
+//   trace(list, n, first, add, sums, round)   adds samples [first, first + add) of the n tiles of list (NULL: all) onto sums
+//   synced(round)                             the round's synchronise has happened
+// The HIP calls, in order, all on `stream`: ad_compact and ad_words grown; the sums zeroed; trace of round 0, [0, min/2) onto
+// d_sums.  Then per round from 1, while the list is not empty: gather -> trace onto the compact buffer -> judge -> compact -> the
+// 4-byte length of the next list copied back -> hipStreamSynchronize -> synced -> done += add, the lists swap.  At length 0 the
+// finalize kernel.  Whatever else a path does per round (the camera path waits for its trace launch and reads its time, so a
+// kernel that gave up ends the call before the judge; the lens path records events) it does inside its two callables.
+extern "C++" {
+template <class Trace, class Synced>
+static int adaptive_rounds(hrt_scene *s, const AdFrame &F, const hrt_adaptive *p, bool gamma, float *d_sums, uint32_t *d_counts,
+                           hipStream_t stream, Trace trace, Synced synced) {
+    const uint32_t n_tiles = F.n_tiles;
     const size_t sum_bytes = (size_t)n_tiles * 192u * sizeof(float);
-    if ((rc = s->ad_compact.grow(sum_bytes)) != HRT_OK || (rc = s->ad_words.grow((4u * (size_t)n_tiles + 1u) * sizeof(uint32_t))) != HRT_OK) return rc;
+    int rc;
+    if ((rc = s->ad_compact.grow(sum_bytes)) != HRT_OK || (rc = s->ad_words.grow(AdWords::bytes(n_tiles))) != HRT_OK) return rc;
     float *const compact = s->ad_compact.as<float>();
-    uint32_t *const words = s->ad_words.as<uint32_t>();
-    uint32_t *const lists[2] = {words, words + n_tiles};
-    uint32_t *const keep = words + 2u * (size_t)n_tiles;
-    uint32_t *const counter = words + 4u * (size_t)n_tiles;
-    if (!d_counts) d_counts = words + 3u * (size_t)n_tiles;
+    const AdWords A(s, n_tiles);
+    if (!d_counts) d_counts = A.counts;
     const uint32_t half = p->min_spp / 2u;
 
     HIP_TRY(hipMemsetAsync(d_sums, 0, sum_bytes, stream));
-    TraceJob job{w, h, 0u, half, seed, flags, d_sums, stream};  // round 0
-    job.rank = rank; job.world = world; job.accumulate = true;
-    rc = launch_trace(s, cam, job);
-    if (rc == HRT_OK) rc = adaptive_trace_done(s, kernel_ms);
-    if (rc != HRT_OK) return rc;
+    if ((rc = trace(nullptr, n_tiles, 0u, half, d_sums, 0u)) != HRT_OK) return rc;  // round 0
     uint32_t done = half, n = n_tiles, next = 0;
     const uint32_t *active = nullptr;  // round 1: every tile
     for (uint32_t round = 1; n != 0u; ++round) {
@@ -166,25 +176,62 @@ static int adaptive_run(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
         const dim3 grid((n + HRT_AD_WG / 64u - 1u) / (HRT_AD_WG / 64u));
         hipLaunchKernelGGL(hrt_ad_gather_kernel, grid, dim3(HRT_AD_WG), 0, stream, d_sums, active, n, compact);
         HIP_TRY(hipGetLastError());
-        job.s0 = done; job.spp = add; job.d_tiles = compact; job.list = active; job.list_n = n;
-        rc = launch_trace(s, cam, job);
-        if (rc == HRT_OK) rc = adaptive_trace_done(s, kernel_ms);
-        if (rc != HRT_OK) return rc;
+        if ((rc = trace(active, n, done, add, compact, round)) != HRT_OK) return rc;
         hipLaunchKernelGGL(hrt_ad_judge_kernel, grid, dim3(HRT_AD_WG), 0, stream, compact, d_sums, active, n, done, done + add,
-                           p->threshold, p->max_spp, w, h, rank, world, R.tiles_x, d_counts, keep);
+                           p->threshold, p->max_spp, F.w, F.h, F.rank, F.world, F.tiles_x, d_counts, A.keep);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(hrt_ad_compact_kernel, dim3(1), dim3(1024), 0, stream, keep, active, n, lists[round & 1u], counter);
+        hipLaunchKernelGGL(hrt_ad_compact_kernel, dim3(1), dim3(1024), 0, stream, A.keep, active, n, A.lists[round & 1u], A.counter);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&next, counter, sizeof(next), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&next, A.counter, sizeof(next), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
+        if ((rc = synced(round)) != HRT_OK) return rc;
         done += add;
-        active = lists[round & 1u];
+        active = A.lists[round & 1u];
         n = next;
     }
     hipLaunchKernelGGL(hrt_ad_finalize_kernel, dim3((n_tiles + HRT_AD_WG / 64u - 1u) / (HRT_AD_WG / 64u)), dim3(HRT_AD_WG), 0, stream, d_sums, d_sums,
-                       n_tiles, d_counts, (flags & HRT_FLAG_GAMMA) ? 1u : 0u);
+                       n_tiles, d_counts, gamma ? 1u : 0u);
     HIP_TRY(hipGetLastError());
     return HRT_OK;
+}
+}  // extern "C++"
+
+// The tail of the two blocking forms: the scene's count map of a whole w x h frame to the host and, if wanted, on to
+// out_tile_spp; *samples (if wanted): the in-image samples, every in-image pixel having its tile's count.
+static int adaptive_counts_to_host(hrt_scene *s, uint32_t w, uint32_t h, uint32_t *out_tile_spp, uint64_t *samples) {
+    const uint32_t tiles = hrt_tiles_total(w, h), tx = (w + HRT_TILE - 1) / HRT_TILE;
+    std::vector<uint32_t> counts(tiles);
+    HIP_TRY(hipMemcpy(counts.data(), AdWords(s, tiles).counts, (size_t)tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_tile_spp) std::memcpy(out_tile_spp, counts.data(), (size_t)tiles * sizeof(uint32_t));
+    if (!samples) return HRT_OK;
+    *samples = 0;
+    for (uint32_t t = 0; t < tiles; ++t) {
+        const uint32_t x0 = (t % tx) * HRT_TILE, y0 = (t / tx) * HRT_TILE;
+        *samples += (uint64_t)std::min<uint32_t>(HRT_TILE, w - x0) * std::min<uint32_t>(HRT_TILE, h - y0) * counts[t];
+    }
+    return HRT_OK;
+}
+
+// The rounds over this rank's tiles with the trace kernels.  fill_render comes first (the frame, the partition; the scene's
+// device), and a rank without tiles is done before anything is grown or touched.  Every trace launch is waited for at once.
+static int adaptive_run(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, const hrt_adaptive *p, uint64_t seed, uint32_t flags,
+                        uint32_t rank, uint32_t world, float *d_sums, uint32_t *d_counts, hipStream_t stream, double *kernel_ms) {
+    *kernel_ms = 0.0;
+    DRender R;
+    DCamera C;
+    const int rc = fill_render(s, cam, w, h, p->min_spp, seed, flags, rank, world, R, C);
+    if (rc != HRT_OK) return rc;
+    if (R.tiles_owned == 0u) return HRT_OK;
+    TraceJob job{w, h, 0u, 0u, seed, flags, d_sums, stream};
+    job.rank = rank; job.world = world; job.accumulate = true;
+    return adaptive_rounds(
+        s, AdFrame{w, h, R.tiles_x, R.tiles_owned, rank, world}, p, (flags & HRT_FLAG_GAMMA) != 0u, d_sums, d_counts, stream,
+        [&](const uint32_t *list, uint32_t n, uint32_t first, uint32_t add, float *sums, uint32_t) -> int {
+            job.s0 = first; job.spp = add; job.d_tiles = sums; job.list = list; job.list_n = n;  // list_n counts only with a list
+            const int trc = launch_trace(s, cam, job);
+            return trc != HRT_OK ? trc : adaptive_trace_done(s, kernel_ms);
+        },
+        [](uint32_t) -> int { return HRT_OK; });
 }
 
 int hrt_render_adaptive_tiles(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, const hrt_adaptive *params, uint64_t seed,
@@ -212,21 +259,10 @@ int hrt_render_adaptive(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_
     double ms = 0.0;
     rc = adaptive_run(s, cam, w, h, params, seed, flags, 0, 1, s->tiles.as<float>(), nullptr, nullptr, &ms);  // the count map: the scene's
     if (rc == HRT_OK) rc = hrt_assemble_frame(s->tiles.as<float>(), tiles, w, h, 1, s->frame.as<float>(), nullptr);
-    std::vector<uint32_t> counts(tiles);
-    hipError_t e = hipSuccess;
-    if (rc == HRT_OK) e = hipMemcpy(out_rgb, s->frame.p, frame_bytes, hipMemcpyDeviceToHost);
-    if (rc == HRT_OK && e == hipSuccess) e = hipMemcpy(counts.data(), s->ad_words.as<uint32_t>() + 3u * (size_t)tiles, (size_t)tiles * sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (rc != HRT_OK) return rc;
-    if (e != hipSuccess) return fail(HRT_ERR_DEVICE, std::string("hrt_render_adaptive: ") + hipGetErrorString(e));
-    if (out_tile_spp) std::memcpy(out_tile_spp, counts.data(), (size_t)tiles * sizeof(uint32_t));
-    if (stats) {
-        const uint32_t tx = (w + HRT_TILE - 1) / HRT_TILE;
-        uint64_t samples = 0;
-        for (uint32_t t = 0; t < tiles; ++t) {
-            const uint32_t x0 = (t % tx) * HRT_TILE, y0 = (t / tx) * HRT_TILE;
-            samples += (uint64_t)std::min<uint32_t>(HRT_TILE, w - x0) * std::min<uint32_t>(HRT_TILE, h - y0) * counts[t];
-        }
-        fill_stats(s, stats, t0, ms, samples);
-    }
+    HIP_TRY(hipMemcpy(out_rgb, s->frame.p, frame_bytes, hipMemcpyDeviceToHost));
+    uint64_t samples = 0;
+    if ((rc = adaptive_counts_to_host(s, w, h, out_tile_spp, stats ? &samples : nullptr)) != HRT_OK) return rc;
+    if (stats) fill_stats(s, stats, t0, ms, samples);
     return HRT_OK;
 }

@@ -2,15 +2,11 @@
 // Included by hrt_api.hip inside its extern "C" block, after hrt_adaptive.hip (the rounds' kernels and parameter checks) and
 // hrt_lens.hip (the tile-list lens kernel and the lens checks).
 //
-// The rounds are adaptive_run's with the fused lens kernel in place of the trace kernels:
-//   round 0   samples [0, min/2) of every tile, added straight onto the zeroed tile-major sums           (hrt_lens_tiles_kernel, no list)
-//   round 1   gather every tile -> compact; samples [min/2, min) added onto compact; judge; compact the list; read its length
-//   round k   gather the active tiles -> compact; min(n, max - n) more samples onto compact over the list; judge; compact; length
-// and at length 0 the sums become means by each tile's own count (and gamma).  The gather, judge, compact and finalize kernels are
-// hrt_adaptive.hip's, unchanged, with rank 0 of world 1: the lens kernel's item i is lane i & 63 of active tile i >> 6, which is
-// exactly the compact buffer they read and write, so nothing is scattered.  Every lens launch passes HRT_RADIANCE_ACCUMULATE: a
-// round continues the stored sums in sample order, and since a sample depends only on (seed, pixel, sample) every tile ends with
-// the bits of hrt_render_lens at its count.
+// The rounds are adaptive_rounds' (hrt_adaptive.hip) with the fused lens kernel, hrt_lens_tiles_kernel, in place of the trace
+// kernels.  The gather, judge, compact and finalize kernels run unchanged, with rank 0 of world 1: the lens kernel's item i is lane
+// i & 63 of active tile i >> 6, which is exactly the compact buffer they read and write, so nothing is scattered.  Every lens launch
+// passes HRT_RADIANCE_ACCUMULATE: a round continues the stored sums in sample order, and since a sample depends only on (seed,
+// pixel, sample) every tile ends with the bits of hrt_render_lens at its count.
 //
 // The lens travels as a kernel argument, the lists and keep words are ad_compact / ad_words (shared with hrt_render_adaptive: the
 // two may not overlap on one scene), the sums are la_tiles; the work-queue head, the path pool, the camera blocks and the trace
@@ -36,58 +32,30 @@ static int lens_tiles_launch(hrt_scene *s, const DLens &L, uint32_t w, uint32_t 
     return HRT_OK;
 }
 
-// The rounds over all tiles of the frame: d_sums (tile-major, every tile) ends with the means, d_counts with each tile's count
-// (NULL: the scene's own count map, ad_words + 3 x tiles).  ev: two pairs of timing events, the call's own.  The stream is
-// synchronised once per round from round 1 on; a fault of a round's kernels ends the call there, before the length of the next
+// The rounds (adaptive_rounds, hrt_adaptive.hip) over all tiles of the frame with the lens kernel: d_sums (tile-major, every
+// tile) ends with the means, d_counts with each tile's count (NULL: the scene's own count map).  ev: two pairs of timing events,
+// the call's own: pair 0 around round 0's launch, pair 1 around every later one.  The stream is synchronised once per round from
+// round 1 on, and the times are read after it; a fault of a round's kernels ends the call there, before the length of the next
 // list is believed.
 static int lens_adaptive_run(hrt_scene *s, const DLens &L, uint32_t w, uint32_t h, const hrt_adaptive *p, uint64_t seed, uint32_t flags,
                              float *d_sums, uint32_t *d_counts, hipStream_t stream, hipEvent_t ev[4], double *kernel_ms) {
     *kernel_ms = 0.0;
-    const uint32_t tiles_x = (w + HRT_TILE - 1u) / HRT_TILE, n_tiles = hrt_tiles_total(w, h);
-    const size_t sum_bytes = (size_t)n_tiles * 192u * sizeof(float);
-    int rc;
-    if ((rc = s->ad_compact.grow(sum_bytes)) != HRT_OK || (rc = s->ad_words.grow((4u * (size_t)n_tiles + 1u) * sizeof(uint32_t))) != HRT_OK) return rc;
-    float *const compact = s->ad_compact.as<float>();
-    uint32_t *const words = s->ad_words.as<uint32_t>();
-    uint32_t *const lists[2] = {words, words + n_tiles};
-    uint32_t *const keep = words + 2u * (size_t)n_tiles;
-    uint32_t *const counter = words + 4u * (size_t)n_tiles;
-    if (!d_counts) d_counts = words + 3u * (size_t)n_tiles;
-    const uint32_t half = p->min_spp / 2u;
     auto add_time = [&](hipEvent_t e0, hipEvent_t e1) -> int {  // after the synchronisation that covers e1
         float f = 0.f;
         HIP_TRY(hipEventElapsedTime(&f, e0, e1));
         *kernel_ms += (double)f;
         return HRT_OK;
     };
-
-    HIP_TRY(hipMemsetAsync(d_sums, 0, sum_bytes, stream));
-    if ((rc = lens_tiles_launch(s, L, w, h, nullptr, n_tiles, 0u, half, seed, flags, d_sums, stream, ev[0], ev[1])) != HRT_OK) return rc;  // round 0
-    uint32_t done = half, n = n_tiles, next = 0;
-    const uint32_t *active = nullptr;  // round 1: every tile
-    for (uint32_t round = 1; n != 0u; ++round) {
-        const uint32_t add = round == 1u ? half : std::min(done, p->max_spp - done);
-        const dim3 grid((n + HRT_AD_WG / 64u - 1u) / (HRT_AD_WG / 64u));
-        hipLaunchKernelGGL(hrt_ad_gather_kernel, grid, dim3(HRT_AD_WG), 0, stream, d_sums, active, n, compact);
-        HIP_TRY(hipGetLastError());
-        if ((rc = lens_tiles_launch(s, L, w, h, active, n, done, add, seed, flags, compact, stream, ev[2], ev[3])) != HRT_OK) return rc;
-        hipLaunchKernelGGL(hrt_ad_judge_kernel, grid, dim3(HRT_AD_WG), 0, stream, compact, d_sums, active, n, done, done + add,
-                           p->threshold, p->max_spp, w, h, 0u, 1u, tiles_x, d_counts, keep);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(hrt_ad_compact_kernel, dim3(1), dim3(1024), 0, stream, keep, active, n, lists[round & 1u], counter);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&next, counter, sizeof(next), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (round == 1u && (rc = add_time(ev[0], ev[1])) != HRT_OK) return rc;
-        if ((rc = add_time(ev[2], ev[3])) != HRT_OK) return rc;
-        done += add;
-        active = lists[round & 1u];
-        n = next;
-    }
-    hipLaunchKernelGGL(hrt_ad_finalize_kernel, dim3((n_tiles + HRT_AD_WG / 64u - 1u) / (HRT_AD_WG / 64u)), dim3(HRT_AD_WG), 0, stream, d_sums, d_sums,
-                       n_tiles, d_counts, (flags & HRT_FLAG_GAMMA) ? 1u : 0u);
-    HIP_TRY(hipGetLastError());
-    return HRT_OK;
+    return adaptive_rounds(
+        s, AdFrame{w, h, (w + HRT_TILE - 1u) / HRT_TILE, hrt_tiles_total(w, h), 0u, 1u}, p, (flags & HRT_FLAG_GAMMA) != 0u, d_sums, d_counts, stream,
+        [&](const uint32_t *list, uint32_t n, uint32_t first, uint32_t add, float *sums, uint32_t round) -> int {
+            hipEvent_t *const e = ev + (round == 0u ? 0 : 2);
+            return lens_tiles_launch(s, L, w, h, list, n, first, add, seed, flags, sums, stream, e[0], e[1]);
+        },
+        [&](uint32_t round) -> int {
+            const int rc = round == 1u ? add_time(ev[0], ev[1]) : HRT_OK;
+            return rc != HRT_OK ? rc : add_time(ev[2], ev[3]);
+        });
 }
 
 // The checks of both entry points, in the header's order (all before the scene and the library state); fills L.
@@ -150,22 +118,14 @@ int hrt_render_lens_adaptive(hrt_scene *s, const hrt_lens *lens, uint32_t w, uin
     if (rc == HRT_OK) rc = enter_scene(who, s);
     if (rc != HRT_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
-    const uint32_t tiles = hrt_tiles_total(w, h);
     const size_t frame_bytes = (size_t)w * h * 3u * sizeof(float);
     if ((rc = s->la_frame.grow(frame_bytes)) != HRT_OK) return rc;
     double ms = 0.0;
     if ((rc = lens_adaptive_frame(s, L, w, h, params, seed, flags, s->la_frame.as<float>(), nullptr, nullptr, &ms)) != HRT_OK) return rc;
-    std::vector<uint32_t> counts(tiles);
     HIP_TRY(hipMemcpy(out_rgb, s->la_frame.p, frame_bytes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(counts.data(), s->ad_words.as<uint32_t>() + 3u * (size_t)tiles, (size_t)tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_tile_spp) std::memcpy(out_tile_spp, counts.data(), (size_t)tiles * sizeof(uint32_t));
+    uint64_t samples = 0;  // degenerate samples count: every in-image pixel has its tile's count
+    if ((rc = adaptive_counts_to_host(s, w, h, out_tile_spp, stats ? &samples : nullptr)) != HRT_OK) return rc;
     if (stats) {
-        const uint32_t tx = (w + HRT_TILE - 1) / HRT_TILE;
-        uint64_t samples = 0;  // degenerate samples count: every in-image pixel has its tile's count
-        for (uint32_t t = 0; t < tiles; ++t) {
-            const uint32_t x0 = (t % tx) * HRT_TILE, y0 = (t / tx) * HRT_TILE;
-            samples += (uint64_t)std::min<uint32_t>(HRT_TILE, w - x0) * std::min<uint32_t>(HRT_TILE, h - y0) * counts[t];
-        }
         fill_stats(s, stats, t0, ms, samples);
         stats->lds_bytes = 0u;  // the tree is read from global memory
         stats->waves_launched = 0u;

@@ -228,3 +228,54 @@ def test_device_form_on_its_own_stream_beside_a_render_of_the_same_scene(gpu):
     assert torch.equal(t.view(torch.int32), want_t.view(torch.int32)), "the render changed beside an adaptive lens frame"
     again, again_counts = dev.render_lens_adaptive(lens, W, H, MN, MX, thr, seed=SEED, flags=GAMMA, out=torch.empty_like(out))  # default stream, after s2
     assert np.array_equal(bits(again.cpu().numpy()), bits(want)) and np.array_equal(again_counts.cpu().numpy().astype(np.uint32), want_counts)
+
+
+# ------------------------------------------------------------------------------------------------- the scene's shared scratch
+def test_camera_and_lens_rounds_share_one_scenes_scratch(gpu):
+    """hrt_render_adaptive and hrt_render_lens_adaptive carve one grow-only pair of buffers of the scene (the compact sums; two
+    lists, keep flags, count map and counter) by the tile count of their own call.  Alternating the two on ONE scene over frames
+    that shrink and grow, each (frame, counts) has the bits of the same call on a fresh scene of the same description: at
+    threshold 0 (every round runs), +inf (round 1 ends it) and the median tile error of that frame (lists of mixed length).
+    Then the binding's refusals that need a tensor on the GPU, text for text (tests/test_python_refusals.py)."""
+    import json
+    import torch
+    import test_python_refusals as refusals
+    mn, mx = 4, 16
+    desc = gpu.HostScene().setup("cornell_mesh", 40 / 24, 1).flatten()
+    big, small = gpu.default_camera(40 / 24), gpu.default_camera(24 / 16)
+    fish = gpu.Lens(small, "fisheye", extent=180.0)
+    thin = gpu.Lens(big, "perspective", aperture=0.05, focus=6.7)
+    calls = [("render_adaptive", big, 40, 24), ("render_lens_adaptive", fish, 24, 16), ("render_adaptive", small, 24, 16),
+             ("render_lens_adaptive", thin, 40, 24)]
+    ref = gpu.DeviceScene(desc)
+    medians = []
+    for fn, view, w, h in calls:
+        plain = ref.render if fn == "render_adaptive" else ref.render_lens
+        frames = {c: plain(view, w, h, c, SEED) for c in sequence(mn, mx)}
+        frames = {c: f[0] if isinstance(f, tuple) else f for c, f in frames.items()}  # render also returns its Stats
+        medians.append(threshold_of(errors_from(frames, mn, mx), mn))
+    ref.close()
+    shared = gpu.DeviceScene(desc)
+    for which in ("zero", "inf", "median"):
+        for (fn, view, w, h), median in zip(calls, medians):
+            thr = {"zero": 0.0, "inf": float("inf"), "median": median}[which]
+            frame, counts = getattr(shared, fn)(view, w, h, mn, mx, thr, seed=SEED)
+            fresh = gpu.DeviceScene(desc)
+            want, want_counts = getattr(fresh, fn)(view, w, h, mn, mx, thr, seed=SEED)
+            fresh.close()
+            print(f"{fn} {w}x{h} threshold {thr:.6g}: counts {dict(zip(*np.unique(counts, return_counts=True)))}")
+            assert counts.shape == ((h + 7) // 8, (w + 7) // 8)
+            assert np.array_equal(counts, want_counts), f"{fn} {w}x{h} threshold {thr}: other counts than on a fresh scene"
+            assert np.array_equal(bits(frame), bits(want)), f"{fn} {w}x{h} threshold {thr}: other pixels than on a fresh scene"
+            if which == "zero":
+                assert (counts == mx).all()
+            elif which == "inf":
+                assert (counts == mn).all()
+            else:
+                assert len(np.unique(counts)) > 1, f"{fn} {w}x{h}: threshold {thr} gave no spread of counts"
+    shared.close()
+    golden = json.load(open(refusals.GOLDEN))
+    cases = refusals.gpu_cases(gpu, torch)
+    assert {"gpu_rad_keys", "gpu_rad_out", "gpu_bake_rays_keys", "gpu_la_stats"} <= set(cases)
+    for name, call in cases.items():
+        assert refusals.refusal(call) == golden[name], name
