@@ -36,6 +36,9 @@
 #define HRT_QUAD_ROWS 7
 #define HRT_SPHERE_ROWS 2
 #define HRT_MAT_ROWS 8
+// Internal, set per ray by the query kernels (hrt_rays.hip query_margin) and never accepted from a caller: the origin is far outside the
+// scene, HRT_FLAG_MESH_BRUTE is on for this segment, and an exact tie between triangles goes to the lower triangle id (mesh_brute).
+#define HRT_FLAG_FAR_ORIGIN (1u << 30)
 #define HRT_TRI_ROWS 4   // {c0, d11} {e1, d00} {e2, d01} {id}: one 64-byte line per triangle; the plane {n, D} lives in DScene::tri_planes
 #define HRT_EXC_INNER 0xFFFFFFFFu  // first word of a bounding entry of a mesh's exception list (DScene::exceptions)
 #define HRT_QUAD_FLAG_GLASS 1u

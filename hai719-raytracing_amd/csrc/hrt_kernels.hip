@@ -484,6 +484,27 @@ __device__ __forceinline__ bool mesh_brute(const CX &cx, cmesh M, const Ray &ray
     const uint32_t first = M->tri_base, cnt = M->n_soup;
     best_t = HRT_FLT_MAX;
     bool found = mesh_exceptions<true>(cx, M, ray, mk(0.f, 0.f, 0.f), best_t, best_tri, bu, bv);
+    if (CX::far_brute && (cx.flags & HRT_FLAG_FAR_ORIGIN)) {
+        // From 1e6 away one ulp of t is 0.0625: triangles that are not neighbours tie exactly, and soup order (leaf order) would keep
+        // another one than the reference, whose leaves hold their triangles in ascending id and keep the first (KDTree.cpp:44).
+        // An exact tie goes to the lower triangle id.
+        uint32_t best_id = found ? __float_as_uint(ld(sp.rows, HRT_TRI_ROWS * best_tri + 3u).x) : 0xFFFFFFFFu;
+        for (uint32_t k = 0; k < cnt; ++k) {
+            const uint32_t slot = first + k;
+            const float4 pl = ld(sp.planes, slot);
+            const f3 n = mk(pl);
+            const float dotRN = dot(ray.d, n);
+            if (!(dotRN < 0.f)) continue;                          // tri_plane_t, but a t equal to the best so far goes on
+            const float t = (pl.w - dot(ray.o, n)) / dotRN;
+            if (t < 0.f || !(t <= best_t)) continue;
+            gf4 tr = sp.rows + HRT_TRI_ROWS * slot;
+            float u, v;
+            if (!tri_inside(ld(tr, 0), ld(tr, 1), ld(tr, 2), ray, t, u, v)) continue;
+            const uint32_t id = __float_as_uint(ld(sp.rows, HRT_TRI_ROWS * slot + 3u).x);
+            if (t < best_t || id < best_id) { best_t = t; bu = u; bv = v; best_tri = slot; best_id = id; found = true; }
+        }
+        return found;
+    }
     for (uint32_t k = 0; k < cnt;) k = tri_test_run(sp, first, cnt, k, ray, best_t, best_tri, bu, bv, found);
     return found;
 }

@@ -67,7 +67,7 @@ __device__ __forceinline__ float query_far(float bound) { return HRT_RAYS_FAR * 
 __device__ __forceinline__ void query_margin(const Ray &ray, float bound, float far, uint32_t flags, float &err_abs, uint32_t &ray_flags) {
     const float olen = length(ray.o);
     err_abs = fabsf(dot(ray.d, ray.d) - 1.f) <= 1e-5f ? margin_scale(bound, olen) : __builtin_inff();
-    ray_flags = olen > far ? (flags | HRT_FLAG_MESH_BRUTE) : flags;
+    ray_flags = olen > far ? (flags | HRT_FLAG_MESH_BRUTE | HRT_FLAG_FAR_ORIGIN) : flags;
 }
 
 // The context of a query kernel: tables from global memory, the leading lds_units nodelets staged into LDS by the whole workgroup

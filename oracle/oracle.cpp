@@ -275,6 +275,7 @@ struct OMesh {
     };
     std::vector<Node> nodes;
     int root = -1;
+    float far_origin = FLT_MAX;  // MESH_ROPE_TREE: see rope_far_origin()
 };
 
 struct TriBox { float lo[3], hi[3]; };
@@ -439,7 +440,17 @@ TriHit mesh_intersect(const OMesh &m, const Ray &ray, int mode, Counters *cnt) {
     }
     if (cnt) cnt->node_visits++;
     if (!aabb_intersects(m.src->aabb_min, m.src->aabb_max, ray)) return TriHit();  // KDTree.cpp:82
-    if (mode == MESH_ROPE_TREE) return rope_tree_intersect(m, ray, cnt);
+    if (mode == MESH_ROPE_TREE) {
+        if (length(ray.o) > m.far_origin) {  // the product's far-origin rule: no walk, every triangle (rope_far_origin below)
+            TriHit best;
+            for (uint32_t t = 0; t < m.src->n_triangles; ++t) {
+                TriHit h = leaf_triangle(m, t, ray, cnt);
+                if (h.hit && h.t < best.t) { best = h; best.tIndex = t; }
+            }
+            return best;
+        }
+        return rope_tree_intersect(m, ray, cnt);
+    }
     if (m.root < 0) return TriHit();
     return ref_node_intersect(m, m.root, ray, cnt);
 }
@@ -623,8 +634,11 @@ V3 skybox_texture(const OScene &S, V3 dir, int remaining, Counters *cnt) {
     }
     float u = (float)(0.5 + std::atan2((double)dir.z, (double)dir.x) / (2 * M_PI));
     float v = (float)(0.5 - std::asin((double)dir.y) / M_PI);
-    int x = (int)(u * sky->w);
-    int y = (int)(v * sky->h);
+    // A caller's ray is traced as given (oracle_radiance), so dir need not be unit: |dir.y| > 1 leaves asin's domain, v is NaN and
+    // the reference's index is undefined (it never sees such a direction).  The device converts a NaN to 0, the first row; stated
+    // here so that the oracle reads inside the image.  Unit directions are untouched: u and v lie in [0, 1].
+    int x = u * sky->w >= 0.f ? (int)(u * sky->w) : 0;
+    int y = v * sky->h >= 0.f ? (int)(v * sky->h) : 0;
     if (x >= sky->w) x = sky->w - 1;  // the reference reads out of bounds at u == 1; clamped here
     if (y >= sky->h) y = sky->h - 1;
     const uint8_t *px = sky->rgb + 3 * ((size_t)y * sky->w + x);
@@ -819,13 +833,50 @@ struct Prepared {
     OScene scene;
 };
 
+// The other half of "what the device picks" in MESH_ROPE_TREE mode.  The rope walk finds its cells at o + t d; from 1e6 away that
+// point is ulp(1e6) = 0.06 off the line, more than a cell, and the walk above goes astray exactly as the device's did.  The product
+// therefore does not walk for such a ray (csrc/hrt_rays.hip query_margin, DESIGN.md section 5 "Ray queries"): an origin farther than
+// HRT_RAYS_FAR = 16 times (bound + 1) from the world origin tests every triangle of each mesh whose box the ray enters.  `bound` is
+// the product's scene extent, restated from csrc/hrt_pack.h scene_bound: the largest distance from the world origin of any point of
+// the scene (spheres with radius and motion, square corners with motion, mesh vertices, lights with radius).  Camera, bounce and
+// shadow rays start inside the scene and are never far, so renders and the other entry points are untouched.
+float rope_far_origin(const hrt_scene_desc &D) {
+    double b = 0.0;
+    auto grow = [&](double x, double y, double z, double extra) { b = std::max(b, std::sqrt(x * x + y * y + z * z) + extra); };
+    auto mlen = [&](const hrt_material &m) {
+        return std::sqrt((double)m.motion[0] * m.motion[0] + (double)m.motion[1] * m.motion[1] + (double)m.motion[2] * m.motion[2]);
+    };
+    for (uint32_t i = 0; i < D.n_spheres; ++i) {
+        const hrt_sphere &sp = D.spheres[i];
+        grow(sp.center[0], sp.center[1], sp.center[2], std::fabs((double)sp.radius) + mlen(D.materials[sp.material]));
+    }
+    for (uint32_t i = 0; i < D.n_quads; ++i) {
+        const hrt_quad &q = D.quads[i];
+        const double ml = mlen(D.materials[q.material]);
+        grow(q.v0[0], q.v0[1], q.v0[2], ml);
+        grow(q.v1[0], q.v1[1], q.v1[2], ml);
+        grow(q.v3[0], q.v3[1], q.v3[2], ml);
+        grow((double)q.v1[0] + q.v3[0] - q.v0[0], (double)q.v1[1] + q.v3[1] - q.v0[1], (double)q.v1[2] + q.v3[2] - q.v0[2], ml);
+    }
+    for (uint32_t mi = 0; mi < D.n_meshes; ++mi)
+        for (uint32_t v = 0; v < D.meshes[mi].n_vertices; ++v) {
+            const float *p = D.meshes[mi].positions + 3 * (size_t)v;
+            grow(p[0] * 1.00001, p[1] * 1.00001, p[2] * 1.00001, 0.0);
+        }
+    for (uint32_t i = 0; i < D.n_lights; ++i)
+        grow(D.lights[i].pos[0], D.lights[i].pos[1], D.lights[i].pos[2], std::fabs((double)D.lights[i].radius));
+    return 16.f * ((float)b + 1.f);
+}
+
 void prepare(OScene &S, const hrt_scene_desc *d, int mesh_mode) {
     S.d = d;
     S.mesh_mode = mesh_mode;
     S.meshes.resize(d->n_meshes);
+    const float far_origin = mesh_mode == MESH_ROPE_TREE ? rope_far_origin(*d) : FLT_MAX;
     for (uint32_t i = 0; i < d->n_meshes; ++i) {
         OMesh &m = S.meshes[i];
         m.src = &d->meshes[i];
+        m.far_origin = far_origin;
         m.scaled.resize(m.src->n_vertices);
         for (uint32_t v = 0; v < m.src->n_vertices; ++v)
             m.scaled[v] = v3(m.src->positions + 3 * (size_t)v) * HRT_TRIANGLE_SCALING;
@@ -1061,6 +1112,52 @@ void oracle_kat_random(uint32_t seed, uint32_t n, float *out) {
 void oracle_path_stream(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t n, float *out) {
     PathRng rng(seed, pixel, sample, nullptr);
     for (uint32_t i = 0; i < n; ++i) out[i] = rng.next();
+}
+// Radiance queries (include/hrt.h hrt_trace_radiance) of the caller's own rays: records of HRT_RAY_FLOATS floats {o, time, d, tmax},
+// tmax not read.  Ray i has the key k = keys ? keys[i] : i; for sample s in [0, n_samples) the path is ray_trace on Ray{o, d, time}
+// AS GIVEN (no make_ray: nothing is normalised) with PathRng(seed, k, first_sample + s) from draw 3 on (draws 0..2 are the camera's
+// u, v, time).  out[(i * n_samples + s) * 3 ..] = that one sample's value, radiance / HRT_MAXBOUNCES: nothing is summed, divided or
+// filtered here -- the degenerate-ray rule, the ordered sums and the mean are tests/oracle_lib.py's (OracleScene.radiance).
+// threads: the number of workers over the rays (>= 1; the caller chooses, there is no "all cores" default).
+int oracle_radiance(const oracle_scene *o, const float *rays, const uint32_t *keys, uint32_t n, uint32_t first_sample,
+                    uint32_t n_samples, uint64_t seed, int threads, float *out) {
+    if (!o || (n && (!rays || !out)) || threads < 1) return -1;
+    const OScene &S = o->S;
+    std::atomic<uint32_t> next{0};
+    auto worker = [&]() {
+        for (;;) {
+            const uint32_t i = next.fetch_add(1);
+            if (i >= n) break;
+            const float *r = rays + (size_t)HRT_RAY_FLOATS * i;
+            const Ray ray{v3(r), v3(r + 4), r[3]};
+            for (uint32_t s = 0; s < n_samples; ++s) {
+                PathRng rng(seed, keys ? keys[i] : i, first_sample + s, nullptr);
+                rng.i = 3;
+                const V3 c = ray_trace(S, ray, rng, nullptr);
+                float *px = out + 3 * ((size_t)i * n_samples + s);
+                px[0] = c.x; px[1] = c.y; px[2] = c.z;
+            }
+        }
+    };
+    const unsigned nt = std::min<unsigned>((unsigned)threads, std::max(1u, n));
+    if (nt == 1) worker();
+    else {
+        std::vector<std::thread> pool;
+        for (unsigned t = 0; t < nt; ++t) pool.emplace_back(worker);
+        for (auto &t : pool) t.join();
+    }
+    return 0;
+}
+// Debug instrument, the sibling of oracle_trace_path for a caller's ray: the closest-hit queries of the path oracle_radiance runs
+// for (ray, key, sample), same records.  Returns the number of records.
+uint32_t oracle_trace_ray_path(const oracle_scene *o, const float *ray, uint32_t key, uint32_t sample, uint64_t seed, float *out,
+                               uint32_t cap) {
+    PathRng rng(seed, key, sample, nullptr);
+    rng.i = 3;
+    g_trace = out; g_trace_n = 0; g_trace_cap = cap;
+    (void)ray_trace(o->S, Ray{v3(ray), v3(ray + 4), ray[3]}, rng, nullptr);
+    g_trace = nullptr;
+    return g_trace_n;
 }
 // Debug instrument: the closest-hit queries of ONE path (pixel x,y, sample s) in order -- up to `cap` records of 12 floats
 // {ray o, d, time, hit kind, object index, t, triangle id, 0}.  Returns the number of records.

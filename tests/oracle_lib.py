@@ -1,6 +1,12 @@
 """ctypes access to the CPU oracle (oracle/liboracle.so) and, when it was built in
 the build container, to the glut-free reference parts (oracle/_ref/libref_parts.so).
 
+Besides the renders, AOVs and features of a camera, the oracle answers for a caller's own ray: OracleScene.radiance_samples is
+oracle_radiance (one value per ray and sample: the ray as given, RNG stream (seed, key, sample) from draw 3, the oracle's own
+ray_trace), OracleScene.radiance restates the rest of include/hrt.h "radiance queries" in NumPy (degenerate rays, ordered fp32
+sums, the mean), and OracleScene.trace_ray_path records the closest-hit queries of one such path.  In MESH_ROPE_TREE mode a ray
+whose origin is far outside the scene tests every triangle instead of walking, as the device does (oracle.cpp rope_far_origin).
+
 TEST INFRASTRUCTURE: imported only by tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg -- never by the product package.
 """
@@ -60,6 +66,9 @@ def lib() -> C.CDLL:
         L.oracle_kat_normalize.restype = None
         L.oracle_trace_path.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 5 + [C.c_uint64, C.c_void_p, C.c_uint32]
         L.oracle_trace_path.restype = C.c_uint32
+        L.oracle_radiance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint32] * 3 + [C.c_uint64, C.c_int, C.c_void_p]
+        L.oracle_trace_ray_path.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32]
+        L.oracle_trace_ray_path.restype = C.c_uint32
         L.oracle_features.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
         _lib = L
     return _lib
@@ -140,6 +149,59 @@ class OracleScene:
                                      out.ctypes.data)
         assert rc == 0
         return out.reshape(h, w, 12) if whole else out
+
+    def radiance_samples(self, rays, keys=None, first_sample=0, n_samples=1, seed=1, threads=1):
+        """oracle_radiance as it is: one value per (ray, sample) -> (n, n_samples, 3) float32.  Ray i is Ray{o, d, time} of record i
+        ({o, time, d, tmax}, tmax not read) AS GIVEN -- nothing is normalised, nothing is filtered: the rays must be traceable --
+        its key is keys[i] (None: i), and sample s runs the oracle's own ray_trace with RNG stream (seed, key, first_sample + s) from
+        draw 3 on, the stream position at which a camera path starts tracing.  `threads`: workers over the rays."""
+        rays = _f32(rays).reshape(-1, 8)
+        n = rays.shape[0]
+        k = None if keys is None else np.ascontiguousarray(keys).astype(np.uint32)
+        assert k is None or k.shape == (n,)
+        assert 0 <= first_sample and n_samples >= 1 and first_sample + n_samples <= 2 ** 32
+        out = np.empty((n, n_samples, 3), dtype=np.float32)
+        rc = self._L.oracle_radiance(self._h, rays.ctypes.data, None if k is None else k.ctypes.data, n, first_sample, n_samples, seed,
+                                     threads, out.ctypes.data)
+        assert rc == 0
+        return out
+
+    def radiance(self, rays, keys=None, first_sample=0, n_samples=1, seed=1, accumulate=None, normalize=False, threads=1):
+        """include/hrt.h "radiance queries" (hrt_trace_radiance) on the CPU -> (n, 3) float32.  The paths are radiance_samples';
+        the rest of the rule is restated here: `normalize` (HRT_RAYS_NORMALIZE) passes d through the Ray constructor's
+        normalisation (kat_normalize) first; a DEGENERATE ray -- a component of o, d or time not finite, d == 0, or with `normalize`
+        a normalised d that is not finite or is 0 -- is not traced and adds nothing; the samples are added in order, in fp32, to +0
+        or, with `accumulate` (the (n, 3) running sums, HRT_RADIANCE_ACCUMULATE; not modified), to what is there; without
+        `accumulate` the sum is divided by float32(n_samples).  tmax is never read."""
+        rays = _f32(rays).reshape(-1, 8)
+        n = rays.shape[0]
+        o, time, d = rays[:, 0:3], rays[:, 3], rays[:, 4:7]
+        bad = ~np.isfinite(o).all(axis=1) | ~np.isfinite(time) | ~np.isfinite(d).all(axis=1) | (d == 0).all(axis=1)
+        if normalize:
+            d = kat_normalize(d)
+            bad |= ~np.isfinite(d).all(axis=1) | (d == 0).all(axis=1)
+        good = np.flatnonzero(~bad)
+        traced = rays[good].copy()
+        traced[:, 4:7] = d[good]
+        k = np.arange(n, dtype=np.uint32) if keys is None else np.ascontiguousarray(keys).astype(np.uint32)
+        per = self.radiance_samples(traced, k[good], first_sample, n_samples, seed, threads)
+        total = np.zeros((n, 3), np.float32) if accumulate is None else _f32(accumulate).reshape(n, 3).copy()
+        s = total[good]
+        for j in range(n_samples):
+            s = s + per[:, j]
+        if accumulate is None:
+            s = s / np.float32(n_samples)
+        total[good] = s
+        return total
+
+    def trace_ray_path(self, ray, key, sample, seed, cap=8):
+        """Debug, the sibling of trace_path for a caller's ray: the closest-hit queries of the path radiance_samples runs for
+        (ray record, key, sample), rows of {o, d, time, kind, index, t, triangle, 0} -- the segments to hand to hrt_trace_rays when a
+        radiance value disagrees."""
+        ray = _f32(ray).reshape(8)
+        out = np.zeros((cap, 12), np.float32)
+        n = self._L.oracle_trace_ray_path(self._h, ray.ctypes.data, key, sample, seed, out.ctypes.data, cap)
+        return out[:n]
 
     def ref_tree_stats(self, mesh=0):
         out = (C.c_uint32 * 4)()
