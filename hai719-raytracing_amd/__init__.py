@@ -931,9 +931,11 @@ class History:
             pass
 
 
-KAT_CAMERA, KAT_TRIANGLE, KAT_AABB, KAT_SPHERE, KAT_QUAD, KAT_OPTICS, KAT_NORMALIZE, KAT_HITWORD = range(8)
-_KAT_IN = {KAT_CAMERA: 2, KAT_TRIANGLE: 7, KAT_AABB: 7, KAT_SPHERE: 7, KAT_QUAD: 7, KAT_OPTICS: 8, KAT_NORMALIZE: 3, KAT_HITWORD: 3}
-_KAT_OUT = {KAT_CAMERA: 12, KAT_TRIANGLE: 8, KAT_AABB: 2, KAT_SPHERE: 9, KAT_QUAD: 8, KAT_OPTICS: 8, KAT_NORMALIZE: 3, KAT_HITWORD: 4}
+KAT_CAMERA, KAT_TRIANGLE, KAT_AABB, KAT_SPHERE, KAT_QUAD, KAT_OPTICS, KAT_NORMALIZE, KAT_HITWORD, KAT_DIV_KNOWN, KAT_NORMALIZE_SHARED, KAT_QUAD_RCP = range(11)
+_KAT_IN = {KAT_CAMERA: 2, KAT_TRIANGLE: 7, KAT_AABB: 7, KAT_SPHERE: 7, KAT_QUAD: 7, KAT_OPTICS: 8, KAT_NORMALIZE: 3, KAT_HITWORD: 3, KAT_DIV_KNOWN: 2,
+           KAT_NORMALIZE_SHARED: 3, KAT_QUAD_RCP: 7}
+_KAT_OUT = {KAT_CAMERA: 12, KAT_TRIANGLE: 8, KAT_AABB: 2, KAT_SPHERE: 9, KAT_QUAD: 8, KAT_OPTICS: 8, KAT_NORMALIZE: 3, KAT_HITWORD: 4, KAT_DIV_KNOWN: 1,
+            KAT_NORMALIZE_SHARED: 3, KAT_QUAD_RCP: 8}
 
 
 def pick_kernel(n_meshes: int, n_lights: int, n_spheres: int, tab_rows: int, tiles: int, spp: int, flags: int = 0, has_list: bool = False,

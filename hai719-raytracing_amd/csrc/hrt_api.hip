@@ -636,6 +636,9 @@ static int size_stream(hrt_scene *s, const KernelBuild &b, DRender &R, uint32_t 
     const uint32_t fixed = (uint32_t)(HRT_SP_NQ * HRT_SP_POOL * 2 + HRT_SP_STREAMS * sizeof(SpCtl) + sizeof(SpShared) + HRT_SP_UNITS * sizeof(SpUnit) + HRT_SP_UNITS * HRT_SP_MAXG * 4) +
                            ((b.bits & KB_VIEWS) ? HRT_SP_UNITS * HRT_SP_MAXG * 16u : 0u) +  // the VIEWS builds' table of view rows
                            2048u + s->d.tab_rows * 16u  // + the scene's per-object tables (stream_tables_fit)
+#if HRT_DIV_QUAD
+                           + (s->d.n_quads + 1u) / 2u * 16u  // + the squares' side-length reciprocals, 8 bytes each (hrt_stream.hip), out of the nodelets' room
+#endif
 #ifdef HRT_WALK_SEG
                            + 2048u  // diagnostic build: 16 accumulators per wave
 #endif
@@ -987,9 +990,10 @@ int hrt_debug_path_stream(uint64_t seed, uint32_t pixel, uint32_t sample, uint32
 int hrt_debug_kat(uint32_t which, const hrt_camera *cam, const float *prim, const float *in, uint32_t n, float *out) {
     if (!g_rt.ready) return fail(HRT_ERR_STATE, "hrt_debug_kat: call hrt_init first");
     if (!in || !out || !n) return fail(HRT_ERR_INVALID, "hrt_debug_kat: bad argument");
-    static const uint32_t in_w[] = {2, 7, 7, 7, 7, 8, 3, 3}, out_w[] = {12, 8, 2, 9, 8, 8, 3, 4};
-    if (which > HRT_KAT_HITWORD) return fail(HRT_ERR_INVALID, "hrt_debug_kat: unknown instrument");
-    if ((which == HRT_KAT_CAMERA) != (cam != nullptr) || ((which >= HRT_KAT_TRIANGLE && which <= HRT_KAT_QUAD) != (prim != nullptr)))
+    static const uint32_t in_w[] = {2, 7, 7, 7, 7, 8, 3, 3, 2, 3, 7}, out_w[] = {12, 8, 2, 9, 8, 8, 3, 4, 1, 3, 8};
+    if (which > HRT_KAT_QUAD_RCP) return fail(HRT_ERR_INVALID, "hrt_debug_kat: unknown instrument");
+    const bool quad = which == HRT_KAT_QUAD || which == HRT_KAT_QUAD_RCP;
+    if ((which == HRT_KAT_CAMERA) != (cam != nullptr) || (((which >= HRT_KAT_TRIANGLE && which <= HRT_KAT_QUAD) || quad) != (prim != nullptr)))
         return fail(HRT_ERR_INVALID, "hrt_debug_kat: cam is for HRT_KAT_CAMERA, prim for the primitive instruments");
     std::vector<float4> rows, kat_qf;
     std::vector<float> box;
@@ -1011,7 +1015,7 @@ int hrt_debug_kat(uint32_t which, const hrt_camera *cam, const float *prim, cons
     } else if (which == HRT_KAT_SPHERE) {    // prim: centre, radius, motion
         rows.push_back(make_float4(prim[0], prim[1], prim[2], prim[3]));
         rows.push_back(make_float4(prim[4], prim[5], prim[6], as_float(0u)));
-    } else if (which == HRT_KAT_QUAD) {      // prim: v0, v1, v3, motion, glass flag
+    } else if (quad) {                       // prim: v0, v1, v3, motion, glass flag
         hrt_quad q;
         std::memset(&q, 0, sizeof(q));
         hrt_material m;
@@ -1044,15 +1048,19 @@ int hrt_debug_kat(uint32_t which, const hrt_camera *cam, const float *prim, cons
             case HRT_KAT_AABB: hipLaunchKernelGGL(hrt_kat_aabb_kernel, grid, block, 0, 0, (const float *)d_prim, d_in, n, d_out); break;
             case HRT_KAT_SPHERE: hipLaunchKernelGGL(hrt_kat_sphere_kernel, grid, block, 0, 0, (const float4 *)d_prim, d_in, n, d_out); break;
             case HRT_KAT_QUAD:
+            case HRT_KAT_QUAD_RCP:
                 e = hipMalloc((void **)&d_qf, kat_qf.size() * sizeof(float4));
                 if (e == hipSuccess) e = hipMemcpy(d_qf, kat_qf.data(), kat_qf.size() * sizeof(float4), hipMemcpyHostToDevice);
                 kat_scene.qfilter = d_qf;
                 if (e == hipSuccess) e = hipMalloc((void **)&d_scene, sizeof(DScene));
                 if (e == hipSuccess) e = hipMemcpy(d_scene, &kat_scene, sizeof(DScene), hipMemcpyHostToDevice);
-                if (e == hipSuccess) hipLaunchKernelGGL(hrt_kat_quad_kernel, grid, block, 0, 0, (const float4 *)d_prim, (const DScene *)d_scene, d_in, n, err_abs, d_out);
+                if (e == hipSuccess && which == HRT_KAT_QUAD) hipLaunchKernelGGL(hrt_kat_quad_kernel, grid, block, 0, 0, (const float4 *)d_prim, (const DScene *)d_scene, d_in, n, err_abs, d_out);
+                else if (e == hipSuccess) hipLaunchKernelGGL(hrt_kat_quad_rcp_kernel, grid, block, 0, 0, (const float4 *)d_prim, (const DScene *)d_scene, d_in, n, err_abs, d_out);
                 break;
             case HRT_KAT_OPTICS: hipLaunchKernelGGL(hrt_kat_optics_kernel, grid, block, 0, 0, d_in, n, d_out); break;
             case HRT_KAT_HITWORD: hipLaunchKernelGGL(hrt_kat_hitword_kernel, grid, block, 0, 0, d_in, n, d_out); break;
+            case HRT_KAT_DIV_KNOWN: hipLaunchKernelGGL(hrt_kat_div_known_kernel, grid, block, 0, 0, d_in, n, d_out); break;
+            case HRT_KAT_NORMALIZE_SHARED: hipLaunchKernelGGL(hrt_kat_normalize_shared_kernel, grid, block, 0, 0, d_in, n, d_out); break;
             default: hipLaunchKernelGGL(hrt_kat_normalize_kernel, grid, block, 0, 0, d_in, n, d_out); break;
         }
         if (e == hipSuccess) e = hipGetLastError();

@@ -74,14 +74,23 @@ extern "C" __global__ void hrt_kat_sphere_kernel(const float4 *rows, const float
 }
 
 // rows: the 11 rows of one square.  out n x 8: hit, t, u, v, normal (Square.h:65-126; oracle_kat_quad), then whether the
-// shipped no-division filter lets the square through (it must whenever hit is set)
-extern "C" __global__ void hrt_kat_quad_kernel(const float4 *rows, const DScene *filter_scene, const float *__restrict__ rays, uint32_t n, float err_abs,
-                                               float *__restrict__ out) {
+// shipped no-division filter lets the square through (it must whenever hit is set).  RCP: quad_t_rcp, the form of the shipped
+// streaming builds, with the two reciprocals taken here as stream_body's staging takes them.
+template <bool RCP>
+__device__ __forceinline__ void kat_quad_body(const float4 *rows, const DScene *filter_scene, const float *__restrict__ rays, uint32_t n, float err_abs,
+                                              float *__restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const Ray ray = kat_ray(rays, i);
     float t = 0.f, u = 0.f, v = 0.f;
-    const bool hit = hrtk::quad_t((gf4)rows, ray, HRT_FLT_MAX, t, u, v);
+    bool hit;
+    if (RCP) {
+        v2f rc;
+        rc.x = 1.f / ld((gf4)rows, 2).w; rc.y = 1.f / ld((gf4)rows, 3).w;
+        hit = hrtk::quad_t_rcp((gf4)rows, rc, ray, HRT_FLT_MAX, t, u, v);
+    } else {
+        hit = hrtk::quad_t((gf4)rows, ray, HRT_FLT_MAX, t, u, v);
+    }
     const float4 q1 = ld((gf4)rows, 1);
     Ctx cx;
     cx.S = (cscene)filter_scene; cx.tq = cx.tm = cx.ts = cx.texc = (gf4) nullptr; cx.tmesh = (gmesh) nullptr; cx.lut = (gf1) nullptr; cx.lds = (lu4) nullptr; cx.lds_n = 0; cx.err_abs = err_abs; cx.flags = 0; cx.st = nullptr;
@@ -90,6 +99,30 @@ extern "C" __global__ void hrt_kat_quad_kernel(const float4 *rows, const DScene 
     o[0] = hit ? 1.f : 0.f; o[1] = hit ? t : 0.f; o[2] = hit ? u : 0.f; o[3] = hit ? v : 0.f;
     o[4] = hit ? q1.x : 0.f; o[5] = hit ? q1.y : 0.f; o[6] = hit ? q1.z : 0.f;
     o[7] = (cand & 1u) ? 1.f : 0.f;
+}
+extern "C" __global__ void hrt_kat_quad_kernel(const float4 *rows, const DScene *filter_scene, const float *__restrict__ rays, uint32_t n, float err_abs,
+                                               float *__restrict__ out) {
+    kat_quad_body<false>(rows, filter_scene, rays, n, err_abs, out);
+}
+extern "C" __global__ void hrt_kat_quad_rcp_kernel(const float4 *rows, const DScene *filter_scene, const float *__restrict__ rays, uint32_t n, float err_abs,
+                                                   float *__restrict__ out) {
+    kat_quad_body<true>(rows, filter_scene, rays, n, err_abs, out);
+}
+
+// in n x 2 = a, c -> out n = a / c by hrt_div.h div_known, with the IEEE 1.f / c taken here
+extern "C" __global__ void hrt_kat_div_known_kernel(const float *__restrict__ in, uint32_t n, float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float a = in[2 * i], c = in[2 * i + 1];
+    out[i] = hrtdiv::div_known(a, c, 1.f / c);
+}
+
+// in n x 3 -> out n x 3: the normalisation of the shipped streaming builds (normalize_t<true>: hrt_div.h normalize_shared)
+extern "C" __global__ void hrt_kat_normalize_shared_kernel(const float *__restrict__ in, uint32_t n, float *__restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f3 v = normalize_t<true>(mk(in[3 * i], in[3 * i + 1], in[3 * i + 2]));
+    out[3 * i] = v.x; out[3 * i + 1] = v.y; out[3 * i + 2] = v.z;
 }
 
 // in n x 8 = d(3), n(3), eta, cosine; out n x 8 = reflect(3), refract(3), reflectance, gamma(|cosine|)  (Functions.cpp:38-60)

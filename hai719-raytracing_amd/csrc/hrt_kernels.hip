@@ -30,6 +30,19 @@
 // (throughput form instead of the recursion's inside-out order, ~1e-7 relative) and fp64 libm calls
 // (acos/atan2/asin/pow: other implementations, equal after rounding to fp32 except on rare ties).
 #include "hrt_device.h"
+#include "hrt_div.h"
+
+// Exact divisions by known and shared divisors as a reciprocal and two FMAs (hrt_div.h), in the shipped streaming builds only
+// (CtxT::div_*).  Each part is a switch of its own for A/B builds (tools/variants.sh); DESIGN.md section 5 has what each measured.
+#ifndef HRT_DIV_QUAD
+#define HRT_DIV_QUAD 1     // squares: 1 / |R| and 1 / |U| staged in LDS once per workgroup (quad_t_rcp); sp_hit_uv_square uses the stored t
+#endif
+#ifndef HRT_DIV_NORM
+#define HRT_DIV_NORM 1     // normalisations of scatter and shade and Rng::unit_vector: one 1 / L shared by the three components
+#endif
+#ifndef HRT_DIV_UNI
+#define HRT_DIV_UNI 1      // wave-uniform divisors (image width and height, the 6 of Scene.h:348): reciprocal taken once per launch
+#endif
 
 #ifndef HRT_MESH_BATCH
 #define HRT_MESH_BATCH 16  // parked lanes that trigger a mesh stage (A/B on MI355X: 1 -> 45.4 ms, 16 -> 43.3, 32 -> 53.4)
@@ -79,6 +92,7 @@ __constant__ float c_u8_lut[512];
 //               stores to out_tiles, so plain pointers would not be provably unclobbered.
 // global   (1): per-lane indexed rows -> global_load (not flat_load).
 // local    (3): nodelets staged in LDS -> ds_read_b128.
+typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 typedef const v4f __attribute__((address_space(4))) *cf4;
@@ -116,6 +130,14 @@ __device__ __forceinline__ f3 normalize(f3 a) {  // Vec3.h:46: divide by the len
     const float L = length(a);
     return mk(a.x / L, a.y / L, a.z / L);
 }
+// FD: the same quotients through hrt_div.h normalize_shared (one IEEE 1 / L, then two FMAs per component); same bits.
+template <bool FD>
+__device__ __forceinline__ f3 normalize_t(f3 a) {
+    if (!FD) return normalize(a);
+    f3 r;
+    hrtdiv::normalize_shared(a.x, a.y, a.z, r.x, r.y, r.z);
+    return r;
+}
 __device__ __forceinline__ float comp(f3 a, uint32_t axis) { return axis == 0 ? a.x : (axis == 1 ? a.y : a.z); }
 
 // ------------------------------------------------------------------ RNG stream
@@ -136,9 +158,10 @@ struct Rng {
         x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x ^= k1; x *= 0x846ca68bu; x ^= x >> 16;
         return (float)(x >> 8) * (1.0f / 16777216.0f);
     }
+    template <bool FD = false>
     __device__ __forceinline__ f3 unit_vector() {  // Functions.cpp:10-18: min + (max-min)*u, normalised cube sample
         const float a = -1.f + 2.f * next(), b = -1.f + 2.f * next(), c = -1.f + 2.f * next();
-        return normalize(mk(a, b, c));
+        return normalize_t<FD>(mk(a, b, c));
     }
 };
 
@@ -175,8 +198,16 @@ template <> struct TabPtr<true> { typedef lf4 f4; typedef lmesh mesh; typedef lf
 // the scenes without a crowd of spheres -- every wall-and-mesh scene -- then pay for in spills (measured: Cornell+mesh -17 %).
 // FARB: HRT_FLAG_MESH_BRUTE is honoured in a build that is not EXACT too (the ray queries, hrt_rays.hip, set it per ray for origins
 // far outside the scene, where the walk's entry point o + t d is off the line by more than a cell can absorb).
-template <bool EXACT, bool LTAB = false, bool SPHF = false, bool FARB = false>
-struct CtxT {
+// DIVK: the build divides by known and shared divisors with hrt_div.h (the shipped streaming builds; never EXACT, so the proof
+// builds keep `/` everywhere and tests compare the two forms bit for bit).  Only such a context carries qrcp.
+typedef const v2f __attribute__((address_space(3))) *lf2;
+template <bool ON> struct QuadRcp { };
+template <> struct QuadRcp<true> { lf2 qrcp; };  // {RN(1 / |R|), RN(1 / |U|)} per square, behind the staged tables (hrt_stream.hip)
+template <bool EXACT, bool LTAB = false, bool SPHF = false, bool FARB = false, bool DIVK = false>
+struct CtxT : QuadRcp<DIVK && !EXACT && HRT_DIV_QUAD> {
+    static constexpr bool div_quad = DIVK && !EXACT && HRT_DIV_QUAD;
+    static constexpr bool div_norm = DIVK && !EXACT && HRT_DIV_NORM;
+    static constexpr bool div_uni = DIVK && !EXACT && HRT_DIV_UNI;
     static constexpr bool exact = EXACT;
     static constexpr bool far_brute = FARB;
     static constexpr bool sphf = SPHF && !EXACT;
@@ -242,6 +273,33 @@ __device__ __forceinline__ bool quad_t(Q q, const Ray &ray, float tmax, float &t
     if (!((proj1 <= q2.w && proj1 >= 0.f) && (proj2 <= q3.w && proj2 >= 0.f))) return false;
     u = proj1 / q2.w;
     v = proj2 / q3.w;
+    return true;
+}
+
+// quad_t with RN(1 / |R|) and RN(1 / |U|) at hand (rc; CtxT::qrcp): the four quotients by the square's side lengths through
+// hrt_div.h div_known -- the same bits.  t stays an IEEE division: its divisor is the ray's.
+template <class Q>
+__device__ __forceinline__ bool quad_t_rcp(Q q, const v2f rc, const Ray &ray, float tmax, float &t, float &u, float &v) {
+    const float4 q0 = ld(q, 0), q1 = ld(q, 1);
+    const uint32_t flags = __float_as_uint(q1.w);
+    const f3 n = mk(q1);
+    const float dotRN = dot(ray.d, n);
+    if (dotRN == 0.f) return false;
+    if (dotRN > 0.f && !(flags & HRT_QUAD_FLAG_GLASS)) return false;
+    f3 p0 = mk(q0);
+    float D = q0.w;
+    if (flags & HRT_QUAD_FLAG_MOVING) {
+        p0 = p0 + ray.time * mk(ld(q, 4));
+        D = dot(p0, n);
+    }
+    t = (D - dot(ray.o, n)) / dotRN;
+    if (!HRT_T_ACCEPT(t) || !(t < tmax)) return false;
+    const float4 q2 = ld(q, 2), q3 = ld(q, 3);
+    const f3 qq = (ray.o + t * ray.d) - p0;
+    float proj1, proj2;
+    hrtdiv::div_known_pair(dot(qq, mk(q2)), q2.w, rc.x, dot(qq, mk(q3)), q3.w, rc.y, proj1, proj2);
+    if (!((proj1 <= q2.w && proj1 >= 0.f) && (proj2 <= q3.w && proj2 >= 0.f))) return false;
+    hrtdiv::div_known_pair(proj1, q2.w, rc.x, proj2, q3.w, rc.y, u, v);
     return true;
 }
 
@@ -712,7 +770,6 @@ __device__ __forceinline__ M quad_filter(const CX &cx, const Ray &ray, float tsu
 // (A ray that starts inside a sphere -- cc < 0 -- is not rejected here; the exact test sends it away.)
 // Rows, 4 per pair (DScene::tab_sfilter): {c.x A, c.x B, c.y A, c.y B} {c.z A, c.z B, r^2 A, r^2 B} {motion.x A, B, motion.y A, B}
 // {motion.z A, B, -, -}; an odd last sphere is paired with itself.
-typedef float v2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2f pk(float x) { v2f r; r.x = x; r.y = x; return r; }
 __device__ __forceinline__ v2f pkfma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
 #ifndef HRT_SPHERE_FILTER_MIN
@@ -826,7 +883,10 @@ __device__ __forceinline__ Hit prims_hit(const CX &cx, const Ray &ray) {
             const uint32_t i = (uint32_t)__builtin_ctzll(cand);
             cand &= cand - 1ull;
             float t, u, v;
-            if (quad_t(gq + HRT_QUAD_ROWS * i, ray, h.t, t, u, v)) { h.kind = 2; h.index = i; h.t = t; h.a0 = u; h.a1 = v; }
+            bool hit;
+            if constexpr (CX::div_quad) hit = quad_t_rcp(gq + HRT_QUAD_ROWS * i, cx.qrcp[i], ray, h.t, t, u, v);
+            else hit = quad_t(gq + HRT_QUAD_ROWS * i, ray, h.t, t, u, v);
+            if (hit) { h.kind = 2; h.index = i; h.t = t; h.a0 = u; h.a1 = v; }
         }
     } else {
         for (uint32_t i = 0; i < nq; ++i) {
@@ -1114,7 +1174,7 @@ __device__ __forceinline__ Surface shade(const CX &cx, const Ray &ray, const Hit
         const uint32_t tex_type = __float_as_uint(m1.z);
         const bool emissive = __float_as_uint(m1.w) != 0u;
         const f3 c = mk(r0) + ray.time * mk(r1);
-        sf.n = normalize(p - c);
+        sf.n = normalize_t<CX::div_norm>(p - c);
         sf.albedo = mk(m0);
         if (tex_type != 0u || emissive) {  // Sphere.h:129-130, Scene.h:275-277 (fp64 libm as the reference)
             float theta, phi;
@@ -1152,7 +1212,7 @@ __device__ __forceinline__ Surface shade(const CX &cx, const Ray &ray, const Hit
         sf.albedo = tex;
         if (nmap >= 0) {  // Material::get_normal, Material.cpp:114-130
             const float nx = cx.lut[256u + (px_n & 255u)], ny = cx.lut[256u + ((px_n >> 8) & 255u)], nz = cx.lut[256u + ((px_n >> 16) & 255u)];
-            sf.n = normalize(nx * mk(ld(q, 5)) + ny * mk(ld(q, 6)) + nz * sf.n);
+            sf.n = normalize_t<CX::div_norm>(nx * mk(ld(q, 5)) + ny * mk(ld(q, 6)) + nz * sf.n);
         }
         if (emissive) {  // mat_emit: the light colour, or the texture value at the same (u, v) -- the texel fetched above -- times the intensity
             const float4 lc = ld(m, 4);
@@ -1201,7 +1261,8 @@ __device__ __forceinline__ float reflectance(float cosine, float ref_idx) {
     return (float)((double)r0 + (double)(1 - r0) * (m2 * m2 * m));  // pow(x, 5) in double
 }
 
-// Material::scatter, Material.cpp:26-60
+// Material::scatter, Material.cpp:26-60.  FD: its three normalisations through normalize_shared (CtxT::div_norm).
+template <bool FD = false>
 __device__ __forceinline__ void scatter(const Surface &sf, Ray &ray, Rng &rng) {
     f3 dir;
     if (sf.type == 1u) {  // glass (the reference's inverted convention, N7)
@@ -1212,14 +1273,14 @@ __device__ __forceinline__ void scatter(const Surface &sf, Ray &ray, Rng &rng) {
         if (cannot_refract || reflectance(cos_theta, ri) > rng.next()) dir = reflect(ray.d, sf.n);
         else dir = refract(ray.d, sf.n, ri);
     } else if (sf.type == 0u) {  // diffuse
-        dir = sf.n + rng.unit_vector();
+        dir = sf.n + rng.template unit_vector<FD>();
         if (!(length(dir) > HRT_EPS)) dir = sf.n;  // (double)len <= 1e-5
     } else {  // mirror
         dir = reflect(ray.d, sf.n);
     }
-    dir = normalize(dir);
+    dir = normalize_t<FD>(dir);
     ray.o = sf.p + HRT_EPS * dir;
-    ray.d = normalize(dir);  // Ray's constructor normalises again (Line.h:15)
+    ray.d = normalize_t<FD>(dir);  // Ray's constructor normalises again (Line.h:15)
 }
 
 // Scene::skyboxTexture, Scene.h:149-161

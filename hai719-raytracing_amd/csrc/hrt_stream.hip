@@ -264,10 +264,30 @@ __device__ __forceinline__ uint4 sp_g1(const Ray &ray, const Hit &h) {
 // Square: quad_t (the same t, the same u, v: it depends on the ray -- its time included -- and the square alone), rows per lane
 // from the staged tables.  Triangle: tri_inside on the triangle's rows with the stored t, which is the t the walk gave it
 // (tri_test_plane); the rows share a 64-byte line with the id row shade() fetches.
+//
+// CX::div_quad: the STORED t instead of the division that gave it, and no accept tests.  h.t is what quad_t (quad_t_rcp) returned
+// for this square when the ray was intersected: t = (D - o.n) / d.n with D = p0(time).n, a function of the ray's origin, direction
+// and time and of the square's rows alone.  The record holds origin and direction as the floats they were, the time is the same
+// draw 2 of the path's stream (a moving square implies DScene::any_motion, so the visit has recomputed it), and the rows are the
+// staged ones the refine read: redoing the division would give these bits again, and a hit that was accepted passes the same
+// tests again.  From t on the expressions are quad_t's: p0 moved by the same time, qq, the two projections and (u, v) -- the four
+// quotients by |R| and |U| through div_known with the staged reciprocals, bit for bit the divisions.
 template <class CX>
 __device__ __forceinline__ void sp_hit_uv_square(const CX &cx, const Ray &ray, Hit &h) {
-    float t, u = 0.f, v = 0.f;
-    if (quad_t(cx.tq + HRT_QUAD_ROWS * h.index, ray, HRT_FLT_MAX, t, u, v)) { h.a0 = u; h.a1 = v; }
+    if constexpr (CX::div_quad) {
+        const typename CX::tab4 q = cx.tq + HRT_QUAD_ROWS * h.index;
+        const float4 q0 = ld(q, 0), q2 = ld(q, 2), q3 = ld(q, 3);
+        const v2f rc = cx.qrcp[h.index];
+        f3 p0 = mk(q0);
+        if (__float_as_uint(ld(q, 1).w) & HRT_QUAD_FLAG_MOVING) p0 = p0 + ray.time * mk(ld(q, 4));
+        const f3 qq = (ray.o + h.t * ray.d) - p0;
+        float proj1, proj2;
+        hrtdiv::div_known_pair(dot(qq, mk(q2)), q2.w, rc.x, dot(qq, mk(q3)), q3.w, rc.y, proj1, proj2);
+        hrtdiv::div_known_pair(proj1, q2.w, rc.x, proj2, q3.w, rc.y, h.a0, h.a1);
+    } else {
+        float t, u = 0.f, v = 0.f;
+        if (quad_t(cx.tq + HRT_QUAD_ROWS * h.index, ray, HRT_FLT_MAX, t, u, v)) { h.a0 = u; h.a1 = v; }
+    }
 }
 template <class CX>
 __device__ __forceinline__ void sp_hit_uv_triangle(const CX &cx, const Ray &ray, Hit &h) {
@@ -330,10 +350,15 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
     float *s_lut = VIEWS ? reinterpret_cast<float *>(tile_vw + HRT_SP_UNITS * HRT_SP_MAXG)
                          : reinterpret_cast<float *>(tile_xy + HRT_SP_UNITS * HRT_SP_MAXG);  // the u8 -> float tables (512 floats)
     float4 *s_tabs = reinterpret_cast<float4 *>(s_lut + 512);            // 16-byte aligned: every size above is a multiple of 16
-    CtxT<EXACT, true, SPHF> cx;
+    typedef CtxT<EXACT, true, SPHF, false, true> CX;  // (DIVK: the proof builds, EXACT, keep `/` everywhere all the same)
+    CX cx;
     cx.S = (cscene)R.scene;
     const uint32_t tab_rows = cx.S->tab_rows;  // the scene's per-object tables: staged once, read per lane from LDS (CtxT)
-    uint4 *s_units = reinterpret_cast<uint4 *>(s_tabs + tab_rows);
+    // {RN(1 / |R|), RN(1 / |U|)} per square behind the tables, 8 bytes each in whole 16-byte rows (hrt_api.hip size_stream takes them
+    // from the room of the nodelets, in every build: one LDS layout)
+    const uint32_t n_sq = cx.S->n_quads, qr_rows = HRT_DIV_QUAD ? (n_sq + 1u) / 2u : 0u;
+    uint4 *s_units = reinterpret_cast<uint4 *>(s_tabs + tab_rows + qr_rows);
+    if constexpr (CX::div_quad) cx.qrcp = (lf2)(s_tabs + tab_rows);
     cx.set_tables((lf4)s_tabs, (lf1)s_lut, cx.S);
     cx.lds = (lu4)s_units;
     cx.lds_n = R.lds_units;
@@ -356,6 +381,18 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
         gf4 g_tabs = (gf4)cx.S->tabs;
         for (uint32_t i = tid; i < tab_rows; i += HRT_SP_WG) s_tabs[i] = ld(g_tabs, i);
         if (tid < 512u) s_lut[tid] = c_u8_lut[tid];
+        if constexpr (CX::div_quad) {  // one IEEE division per side length and workgroup; a degenerate side's inf is never used (div_known's window)
+            float2 *s_qrcp = reinterpret_cast<float2 *>(s_tabs + tab_rows);
+            const uint32_t tq = cx.S->tab_quads;
+            for (uint32_t i = tid; i < n_sq; i += HRT_SP_WG)
+                s_qrcp[i] = make_float2(1.f / ld(g_tabs, tq + HRT_QUAD_ROWS * i + 2u).w, 1.f / ld(g_tabs, tq + HRT_QUAD_ROWS * i + 3u).w);
+        }
+    }
+    // wave-uniform divisors: the reciprocal once per launch, in scalar registers
+    float inv_w = 0.f, inv_h = 0.f;
+    if constexpr (CX::div_uni) {
+        inv_w = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(1.f / (float)R.w)));
+        inv_h = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(1.f / (float)R.h)));
     }
     uint16_t *const q_all = L.q;
     if (tid < HRT_SP_STREAMS) {
@@ -803,8 +840,9 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                         if (VIEWS) { vw = view_row(n | (gs << 30)); cx.err_abs = __uint_as_float(vw.w); }
                         Rng rng;
                         rng.start(vw.y, vw.z, py * R.w + px, R.s0 + s);
-                        const float u = ((float)px + rng.next()) / (float)R.w;
-                        const float v = ((float)py + rng.next()) / (float)R.h;
+                        const float un = (float)px + rng.next(), vn = (float)py + rng.next();
+                        const float u = CX::div_uni ? hrtdiv::div_known(un, (float)R.w, inv_w) : un / (float)R.w;
+                        const float v = CX::div_uni ? hrtdiv::div_known(vn, (float)R.h, inv_h) : vn / (float)R.h;
                         const float tm = rng.next();
                         if (VIEWS) {
                             // The camera block by SCALAR loads, as in the one-camera builds: one pass per distinct view among the chunk's
@@ -880,7 +918,7 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                         SEG(8);  // direct light (shadow rays)
                         rad = rad + thr * (direct + sf.emission);
                         thr = thr * sf.albedo;
-                        scatter(sf, ray, rng);
+                        scatter<CX::div_norm>(sf, ray, rng);
                         SEG(2);  // scatter
                         --remaining;
                         ended = (remaining == 0);
@@ -926,7 +964,8 @@ __device__ __forceinline__ void stream_body(const DRender &R) {
                     const uint32_t n = min(pnum & 0x3FFFFFFFu, (uint32_t)HRT_SP_UNIT - 1u);  // the path's number; stays inside the scratch
                     fin_unit = pnum >> 30;
                     float *o = scratch + (size_t)fin_unit * ((size_t)HRT_SP_UNIT * 3u) + (size_t)n * 3u;
-                    o[0] = rad.x / 6.f; o[1] = rad.y / 6.f; o[2] = rad.z / 6.f;
+                    if (CX::div_uni) { o[0] = hrtdiv::div_known(rad.x, 6.f, 1.f / 6.f); o[1] = hrtdiv::div_known(rad.y, 6.f, 1.f / 6.f); o[2] = hrtdiv::div_known(rad.z, 6.f, 1.f / 6.f); }
+                    else { o[0] = rad.x / 6.f; o[1] = rad.y / 6.f; o[2] = rad.z / 6.f; }
                     freed = true;
                 }
                 if (trace) {

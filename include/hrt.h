@@ -353,9 +353,14 @@ HRT_API int hrt_debug_path_stream(uint64_t seed, uint32_t pixel, uint32_t sample
  *   HRT_KAT_NORMALIZE -                                         v        3: v / |v| (Vec3.h:46)
  *   HRT_KAT_HITWORD   -                                         kind, index, soup slot (u32 bit patterns)   4: the hit word of a
  *                     path record of the streaming kernel (kind | index, or kind | mesh | soup slot), then the kind, index and
- *                     soup slot read back from it (u32 bit patterns) */
+ *                     soup slot read back from it (u32 bit patterns)
+ *   HRT_KAT_DIV_KNOWN -                                         a, c     1: a / c by the shipped streaming builds' division by a known
+ *                                                                        divisor (two FMAs; 1.f / c taken on the device, as their staging does)
+ *   HRT_KAT_NORMALIZE_SHARED -                                  v        3: v / |v| with one reciprocal shared by the components
+ *   HRT_KAT_QUAD_RCP  as HRT_KAT_QUAD                           ray 7    8: as HRT_KAT_QUAD, the quotients by |R| and |U| through their
+ *                                                                        reciprocals (taken on the device) */
 enum { HRT_KAT_CAMERA = 0, HRT_KAT_TRIANGLE = 1, HRT_KAT_AABB = 2, HRT_KAT_SPHERE = 3, HRT_KAT_QUAD = 4, HRT_KAT_OPTICS = 5,
-       HRT_KAT_NORMALIZE = 6, HRT_KAT_HITWORD = 7 };
+       HRT_KAT_NORMALIZE = 6, HRT_KAT_HITWORD = 7, HRT_KAT_DIV_KNOWN = 8, HRT_KAT_NORMALIZE_SHARED = 9, HRT_KAT_QUAD_RCP = 10 };
 HRT_API int hrt_debug_kat(uint32_t which, const hrt_camera *cam, const float *prim, const float *in, uint32_t n, float *out);
 
 /* Cycle counters per kernel stage of the last launch; all zero unless libhrt.so was built with
