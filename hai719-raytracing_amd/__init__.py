@@ -351,6 +351,8 @@ def device_lib() -> C.CDLL:
         lib.hrt_bake_mesh_points.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_void_p]
         lib.hrt_debug_pick_kernel.argtypes = [C.POINTER(PickInput), C.c_char_p, C.c_size_t]
         lib.hrt_debug_last_kernel.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+        lib.hrt_debug_live_resources.argtypes = [C.POINTER(C.c_uint64 * 4)]
+        lib.hrt_debug_live_resources.restype = None
         _dev = lib
     return _dev
 
@@ -946,6 +948,13 @@ def pick_kernel(n_meshes: int, n_lights: int, n_spheres: int, tab_rows: int, til
     _call("hrt_debug_pick_kernel", C.byref(PickInput(n_meshes, n_lights, n_spheres, tab_rows, tiles, spp, flags, int(has_list), n_views,
                                                      kernel.encode())), name, len(name))
     return name.value.decode()
+
+
+def live_resources() -> tuple:
+    """hrt_debug_live_resources: the (device buffers, pinned host buffers, events, streams) libhrt.so holds at this moment."""
+    out = (C.c_uint64 * 4)()
+    device_lib().hrt_debug_live_resources(C.byref(out))
+    return tuple(out)
 
 
 def debug_kat(which: int, inp, prim=None, cam: Optional[Camera] = None) -> np.ndarray:

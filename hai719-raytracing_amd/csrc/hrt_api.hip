@@ -13,6 +13,7 @@
 #include <rccl/rccl.h>  // types and prototypes only: librccl.so is opened with dlopen by hrt_multi_create (hrt_multi.hip)
 
 #include <array>
+#include <atomic>
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -119,30 +120,107 @@ bool host_invert4(const double m[16], double out[16]) {
     return true;
 }
 
-template <class T>
-int upload(const std::vector<T> &v, T **dptr) {
-    *dptr = nullptr;
-    size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    HIP_TRY(hipMalloc((void **)dptr, bytes));
-    if (!v.empty()) HIP_TRY(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return HRT_OK;
-}
+// ---- The owners.  Every HIP resource the library holds belongs to exactly one of these four, which acquires it, frees it in its
+// destructor (or in release(), for whoever must choose the device that is current at that moment: hrt_multi_destroy) and counts it
+// in g_live (hrt_debug_live_resources).  All are move-only.  An error return (HIP_TRY) may therefore leave any scope that holds
+// them.  NONE MAY HAVE STATIC STORAGE DURATION: the HIP runtime may be gone by the time static destructors run.
+enum { LIVE_DEVICE, LIVE_PINNED, LIVE_EVENT, LIVE_STREAM };
+std::atomic<uint64_t> g_live[4];  // plain counters: nothing to destroy
 
-// A device scratch buffer that grows on demand and never shrinks; the capacity is in bytes.  The old block is freed before the
-// larger one is asked for (its contents are never wanted), so a frame size that only just fits does not need both at once.
+// A device buffer that grows on demand and never shrinks; the capacity is in bytes.  The old block is freed before the larger one
+// is asked for (its contents are never wanted), so a frame size that only just fits does not need both at once.
 struct Scratch {
     void *p = nullptr;
     size_t cap = 0;
+    Scratch() = default;
+    Scratch(Scratch &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch() { release(); }
     template <class T> T *as() const { return (T *)p; }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) { (void)hipFree(p); --g_live[LIVE_DEVICE]; }
         p = nullptr; cap = 0;
     }
     int grow(size_t bytes) {
         if (cap >= bytes) return HRT_OK;
         release();
         HIP_TRY(hipMalloc(&p, bytes));
+        ++g_live[LIVE_DEVICE];
         cap = bytes;
+        return HRT_OK;
+    }
+    // Room for n elements of T, and for one where n is 0: an empty array still has an address.
+    template <class T> int need(size_t n) { return grow(std::max<size_t>(n, 1) * sizeof(T)); }
+    // Room for `bytes` (need's rule is the caller's), filled from host memory with a blocking copy.
+    int from_host(const void *src, size_t bytes) {
+        if (const int rc = grow(bytes)) return rc;
+        if (bytes) HIP_TRY(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
+        return HRT_OK;
+    }
+};
+
+// A pinned host buffer, grown as Scratch grows.
+struct Pinned {
+    void *p = nullptr;
+    size_t cap = 0;
+    Pinned() = default;
+    Pinned(Pinned &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    Pinned(const Pinned &) = delete;
+    Pinned &operator=(const Pinned &) = delete;
+    ~Pinned() { release(); }
+    void release() {
+        if (p) { (void)hipHostFree(p); --g_live[LIVE_PINNED]; }
+        p = nullptr; cap = 0;
+    }
+    int grow(size_t bytes) {
+        if (cap >= bytes) return HRT_OK;
+        release();
+        HIP_TRY(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+        ++g_live[LIVE_PINNED];
+        cap = bytes;
+        return HRT_OK;
+    }
+};
+
+// An event, created by the first ready(flags) and handed to HIP as the handle it holds.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { release(); }
+    operator hipEvent_t() const { return e; }
+    void release() {
+        if (e) { (void)hipEventDestroy(e); --g_live[LIVE_EVENT]; }
+        e = nullptr;
+    }
+    int ready(unsigned flags = hipEventDefault) {  // the default times (a timing pair); hipEventDisableTiming orders only
+        if (e) return HRT_OK;
+        HIP_TRY(hipEventCreateWithFlags(&e, flags));
+        ++g_live[LIVE_EVENT];
+        return HRT_OK;
+    }
+};
+
+// A stream of the library's own.
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream &&o) noexcept : s(o.s) { o.s = nullptr; }
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream() { release(); }
+    operator hipStream_t() const { return s; }
+    void release() {
+        if (s) { (void)hipStreamDestroy(s); --g_live[LIVE_STREAM]; }
+        s = nullptr;
+    }
+    int ready(unsigned flags) {
+        if (s) return HRT_OK;
+        HIP_TRY(hipStreamCreateWithFlags(&s, flags));
+        ++g_live[LIVE_STREAM];
         return HRT_OK;
     }
 };
@@ -151,13 +229,10 @@ struct Scratch {
 // by the stream; a writer on another stream first waits for `done` there (wait_on), and the host waits for it before the buffer
 // is freed (sync).
 struct LastReader {
-    hipEvent_t done = nullptr;
+    Event done;
     bool used = false;
     hipStream_t stream = nullptr;  // of the reader
-    int ready() {
-        if (!done) HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-        return HRT_OK;
-    }
+    int ready() { return done.ready(hipEventDisableTiming); }
     int wait_on(hipStream_t on) {  // before the first write enqueued on `on`
         if (const int rc = ready()) return rc;
         if (used && stream != on) HIP_TRY(hipStreamWaitEvent(on, done, 0));
@@ -173,10 +248,6 @@ struct LastReader {
         stream = on;
         return HRT_OK;
     }
-    void release() {
-        if (done) (void)hipEventDestroy(done);
-        done = nullptr; used = false;
-    }
 };
 
 // A per-launch table of T in device memory that a call fills from the host: a grow-only device table, its pinned staging copy (the
@@ -186,9 +257,8 @@ struct LastReader {
 template <class T>
 struct StagedTable {
     Scratch dev;
-    T *host = nullptr;
-    size_t host_cap = 0;  // in entries
-    hipEvent_t uploaded = nullptr;
+    Pinned host;
+    Event uploaded;
     bool uploading = false;
     LastReader reader;
     const T *table() const { return dev.as<T>(); }
@@ -199,22 +269,17 @@ struct StagedTable {
     int fill(const std::vector<T> &entries, bool sync_reader) {
         const size_t bytes = entries.size() * sizeof(T);
         if (uploading) { HIP_TRY(hipEventSynchronize(uploaded)); uploading = false; }
-        if (!uploaded) HIP_TRY(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
+        if (const int rc = uploaded.ready(hipEventDisableTiming)) return rc;
         if (const int rc = reader.ready()) return rc;
-        if (host_cap < entries.size()) {
-            if (host) (void)hipHostFree(host);
-            host = nullptr; host_cap = 0;
-            HIP_TRY(hipHostMalloc((void **)&host, bytes, hipHostMallocDefault));
-            host_cap = entries.size();
-        }
-        std::memcpy(host, entries.data(), bytes);
+        if (const int rc = host.grow(bytes)) return rc;
+        std::memcpy(host.p, entries.data(), bytes);
         if (sync_reader && dev.cap < bytes)
             if (const int rc = reader.sync()) return rc;
         return dev.grow(bytes);
     }
     // The staged entries to the device on `stream`, behind whatever the caller has made `stream` wait for.
     int upload(size_t n, hipStream_t stream) {
-        HIP_TRY(hipMemcpyAsync(dev.p, host, n * sizeof(T), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(dev.p, host.p, n * sizeof(T), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipEventRecord(uploaded, stream));
         uploading = true;
         return HRT_OK;
@@ -228,14 +293,6 @@ struct StagedTable {
         return rc;
     }
     int staged(hipStream_t stream) { return reader.mark(stream); }
-    void release() {
-        dev.release();
-        if (host) (void)hipHostFree(host);
-        host = nullptr; host_cap = 0;
-        if (uploaded) (void)hipEventDestroy(uploaded);
-        uploaded = nullptr; uploading = false;
-        reader.release();
-    }
 };
 
 // w x h is a frame of at most max_pixels pixels (2^31 - 1 where pixels are indexed, 2^31 / 16 where 16-byte records of them are).
@@ -330,17 +387,17 @@ struct DLensView;  // hrt_lens.hip
 
 struct hrt_scene {
     DScene d{};                  // host copy of the device scene header
-    DScene *d_scene = nullptr;   // the header in HBM (read by the kernels through a constant-space pointer)
-    DCamera *d_cam = nullptr;    // camera block in HBM, re-uploaded only when the camera changes
-    DCamera *d_cam_aov = nullptr;  // hrt_render_aov's own camera block (it takes no part in the trace launches' ordering)
+    Scratch d_scene;             // the header in HBM (read by the kernels through a constant-space pointer)
+    Scratch d_cam;               // camera block in HBM, re-uploaded only when the camera changes
+    Scratch d_cam_aov;           // hrt_render_aov's own camera block (it takes no part in the trace launches' ordering)
     DCamera h_cam{};
     bool cam_valid = false;
     uint32_t lds_units = 0;
     uint32_t max_leaf = 0;       // most triangles in one KD leaf (the resumable walk keeps a 16-bit leaf cursor)
-    std::vector<void *> allocations;
-    uint32_t *tile_counter = nullptr;
-    unsigned long long *stamps = nullptr;  // diagnostic cycle counters (HRT_STAMPS builds)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::vector<Scratch> allocations;  // the packed arrays the header points at
+    Scratch tile_counter;        // one uint32_t: the work-queue head
+    Scratch stamps;              // 16 x unsigned long long: diagnostic cycle counters (HRT_STAMPS builds)
+    Event ev0, ev1;              // around the last trace launch
     bool timed = false;
     float bound = 0.f;  // largest distance of any scene point from the origin (filter margins)
     // Scratch, grown on demand.  The streaming kernel's: per-workgroup samples (floats), and its path records (words) when they
@@ -349,14 +406,13 @@ struct hrt_scene {
     // hrt_render_adaptive (tiles each), then the list counter.  The denoisers' (hrt_denoise.hip): the linear frame, the features,
     // the filter's scratch, the result; and for the variance-guided one the first half's sums and frame, and the variance map.
     Scratch sp_scratch, sp_pool, tiles, frame, ad_compact, ad_words, dn_frame, dn_feat, dn_scratch, dn_out, dnv_half_tiles, dnv_frame_half, dnv_var;
-    std::array<Scratch *, 13> scratch() { return {&sp_scratch, &sp_pool, &tiles, &frame, &ad_compact, &ad_words, &dn_frame, &dn_feat, &dn_scratch, &dn_out, &dnv_half_tiles, &dnv_frame_half, &dnv_var}; }
     uint32_t last_grid = 0, last_waves = 0, last_lds = 0;
     const KernelBuild *last_build = nullptr;  // the row of k_builds the last trace launch ran (hrt_debug_last_kernel)
     hipStream_t last_stream = nullptr;  // stream of the previous launch on this scene
     int device = 0;                     // the device that holds this scene (current when it was created)
     // hrt_render_features' own camera block, with its host copy and the launch that read it last (feature launches are ordered
     // across streams)
-    DCamera *d_cam_feat = nullptr;
+    Scratch d_cam_feat;
     DCamera h_cam_feat{};
     LastReader feat_reader;
     // Batched views (hrt_views.hip): the per-view blocks of the launch in hand (its last reader is the assemble launch, which also
@@ -401,10 +457,11 @@ void fill_stats(const hrt_scene *s, hrt_stats *stats, std::chrono::steady_clock:
 // Uploads one packed array; the scene owns the allocation, `field` (of its header) points at it.
 template <class T>
 int upload_owned(hrt_scene *s, const std::vector<T> &v, const T *&field) {
-    T *ptr = nullptr;
-    if (const int rc = upload(v, &ptr)) return rc;
-    s->allocations.push_back(ptr);
-    field = ptr;
+    Scratch b;
+    if (const int rc = b.need<T>(v.size())) return rc;
+    if (const int rc = b.from_host(v.data(), v.size() * sizeof(T))) return rc;
+    field = b.as<T>();
+    s->allocations.push_back(std::move(b));
     return HRT_OK;
 }
 
@@ -462,22 +519,7 @@ void hrt_shutdown(void) { g_rt.ready = false; g_rt.dev_cus.clear(); }
 void hrt_scene_destroy(hrt_scene *s) {
     if (!s) return;
     if (g_rt.ready) (void)use_device(s->device);
-    for (void *p : s->allocations) (void)hipFree(p);
-    if (s->tile_counter) (void)hipFree(s->tile_counter);
-    if (s->stamps) (void)hipFree(s->stamps);
-    if (s->d_scene) (void)hipFree(s->d_scene);
-    if (s->d_cam) (void)hipFree(s->d_cam);
-    if (s->d_cam_aov) (void)hipFree(s->d_cam_aov);
-    for (Scratch *b : s->scratch()) b->release();
-    if (s->d_cam_feat) (void)hipFree(s->d_cam_feat);
-    s->feat_reader.release();
-    s->views.release();
-    s->lens_views.release();
-    for (Scratch *b : {&s->vw_tiles, &s->vw_frames, &s->la_tiles, &s->la_frame}) b->release();
-    s->la_reader.release();
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    delete s;
+    delete s;  // everything it holds frees itself (the owners above)
 }
 
 // Pack on the host (hrt_pack.h: every check of the description is there), upload, then the scene's own allocations.
@@ -508,16 +550,14 @@ static int scene_create_impl(const hrt_scene_desc *desc, hrt_scene *s) {
     // the two things that are not the description's alone: the LDS budget and the measurement override of the pruning
     s->lds_units = std::min<uint32_t>(d.n_kd_units, g_rt.lds_budget / 16u) & ~3u;  // whole 64-byte lines: no treelet or leaf straddles
     if (const char *e = std::getenv("HRT_PRUNE")) if (e[0] == '0') d.prune_ok = 0u;  // measurement aid: the same kernels without the pruning (bench.py reports both rates)
-    HIP_TRY(hipMalloc((void **)&s->tile_counter, sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&s->stamps, 16 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(s->stamps, 0, 16 * sizeof(unsigned long long)));
-    HIP_TRY(hipEventCreate(&s->ev0));
-    HIP_TRY(hipEventCreate(&s->ev1));
-    HIP_TRY(hipMalloc((void **)&s->d_scene, sizeof(DScene)));
-    HIP_TRY(hipMemcpy(s->d_scene, &s->d, sizeof(DScene), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc((void **)&s->d_cam, sizeof(DCamera)));
-    HIP_TRY(hipMalloc((void **)&s->d_cam_aov, sizeof(DCamera)));
-    return HRT_OK;
+    if (const int rc = s->tile_counter.grow(sizeof(uint32_t))) return rc;
+    if (const int rc = s->stamps.grow(16 * sizeof(unsigned long long))) return rc;
+    HIP_TRY(hipMemset(s->stamps.p, 0, 16 * sizeof(unsigned long long)));
+    if (const int rc = s->ev0.ready()) return rc;
+    if (const int rc = s->ev1.ready()) return rc;
+    if (const int rc = s->d_scene.from_host(&s->d, sizeof(DScene))) return rc;
+    if (const int rc = s->d_cam.grow(sizeof(DCamera))) return rc;
+    return s->d_cam_aov.grow(sizeof(DCamera));
 }
 
 int hrt_scene_create(const hrt_scene_desc *desc, hrt_scene **out) {
@@ -611,7 +651,7 @@ static int fill_render(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t
     if (!spp) return fail(HRT_ERR_INVALID, "render: spp must be positive");
     if (w > 65535u || h > 65535u) return fail(HRT_ERR_INVALID, "render: w and h must be below 65536 (tile origins are packed in 16 + 16 bits)");
     if (!world || rank >= world) return fail(HRT_ERR_INVALID, "render: bad rank/world");
-    R.scene = s->d_scene;
+    R.scene = s->d_scene.as<DScene>();
     R.lds_units = (flags & HRT_FLAG_NO_LDS_TREE) ? 0u : s->lds_units;
     R.err_abs = margin_scale(s->bound, std::sqrt(cam->eye[0] * cam->eye[0] + cam->eye[1] * cam->eye[1] + cam->eye[2] * cam->eye[2]));
     {
@@ -625,8 +665,8 @@ static int fill_render(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t
     R.tiles_x = (w + HRT_TILE - 1) / HRT_TILE;
     R.tiles_total = hrt_tiles_total(w, h);
     R.tiles_owned = hrt_tiles_owned(w, h, rank, world);
-    R.tile_counter = s->tile_counter;
-    R.stamps = s->stamps;
+    R.tile_counter = s->tile_counter.as<uint32_t>();
+    R.stamps = s->stamps.as<unsigned long long>();
     R.tile_list = nullptr;
     return HRT_OK;
 }
@@ -727,7 +767,7 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, const TraceJob &J) 
         R.views = s->views.table();
         R.tiles_owned = J.n_views * R.tiles_total;
     }
-    R.cam = s->d_cam;
+    R.cam = s->d_cam.as<DCamera>();
     if (!J.d_tiles) return fail(HRT_ERR_INVALID, "render: NULL tile buffer");
     if ((uint64_t)J.s0 + J.spp > 0xffffffffull) return fail(HRT_ERR_INVALID, "render: sample index overflows 32 bits");
     R.out_tiles = J.d_tiles;
@@ -754,11 +794,11 @@ static int launch_trace(hrt_scene *s, const hrt_camera *cam, const TraceJob &J) 
         if ((rc = s->views.upload(J.n_views, stream)) != HRT_OK) return rc;
     } else if (!s->cam_valid || std::memcmp(&C, &s->h_cam, sizeof(C)) != 0) {
         s->h_cam = C;
-        HIP_TRY(hipMemcpyAsync(s->d_cam, &s->h_cam, sizeof(C), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(s->d_cam.p, &s->h_cam, sizeof(C), hipMemcpyHostToDevice, stream));
         s->cam_valid = true;
     }
-    HIP_TRY(hipMemsetAsync(s->tile_counter, 0, sizeof(uint32_t), stream));
-    HIP_TRY(hipMemsetAsync(s->stamps, 0, 16 * sizeof(unsigned long long), stream));  // [15] = give-up code of the streaming kernel
+    HIP_TRY(hipMemsetAsync(s->tile_counter.p, 0, sizeof(uint32_t), stream));
+    HIP_TRY(hipMemsetAsync(s->stamps.p, 0, 16 * sizeof(unsigned long long), stream));  // [15] = give-up code of the streaming kernel
     HIP_TRY(hipEventRecord(s->ev0, stream));
     hipLaunchKernelGGL(build->fn, dim3(grid), dim3(build->wg()), lds_bytes, stream, R);
     s->last_build = build;
@@ -829,33 +869,26 @@ int hrt_encode_ppm(const float *d_frame, uint32_t w, uint32_t h, int format, uns
     // offsets, pass 2 writes the digits.  Blocks of 1024 pixels; block totals are scanned on the host side of
     // the launch (n/1024 words) to keep the device code to two simple kernels.
     const uint32_t nblocks = (npix + 1023u) / 1024u;
-    uint32_t *d_len = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_len, ((size_t)npix + nblocks) * sizeof(uint32_t)));
-    uint32_t *d_block = d_len + npix;
+    Scratch len, d_base;  // every pixel's length, then the blocks' totals; the blocks' offsets
+    if (const int rc = len.grow(((size_t)npix + nblocks) * sizeof(uint32_t))) return rc;
+    uint32_t *const d_len = len.as<uint32_t>(), *const d_block = d_len + npix;
     hipLaunchKernelGGL(hrt_ppm3_measure_kernel, dim3(nblocks), dim3(256), 0, stream, d_frame, npix, d_len, d_block);
     std::vector<uint32_t> block(nblocks);
-    hipError_t e = hipMemcpyAsync(block.data(), d_block, nblocks * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) { (void)hipFree(d_len); return fail(HRT_ERR_DEVICE, std::string("hrt_encode_ppm: ") + hipGetErrorString(e)); }
+    HIP_TRY(hipMemcpyAsync(block.data(), d_block, nblocks * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     std::vector<unsigned long long> base(nblocks);
     unsigned long long run = (unsigned long long)hl;
     for (uint32_t b = 0; b < nblocks; ++b) { base[b] = run; run += block[b]; }
     const size_t total = (size_t)run + 1u;  // the closing endl
-    if (capacity < total) { (void)hipFree(d_len); return fail(HRT_ERR_INVALID, "hrt_encode_ppm: output buffer too small (need " + std::to_string(total) + ")"); }
-    unsigned long long *d_base = nullptr;
-    e = hipMalloc((void **)&d_base, nblocks * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_base, base.data(), nblocks * sizeof(unsigned long long), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out, head, (size_t)hl, hipMemcpyHostToDevice, stream);
+    if (capacity < total) return fail(HRT_ERR_INVALID, "hrt_encode_ppm: output buffer too small (need " + std::to_string(total) + ")");
+    if (const int rc = d_base.grow(nblocks * sizeof(unsigned long long))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_base.p, base.data(), nblocks * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_out, head, (size_t)hl, hipMemcpyHostToDevice, stream));
     const unsigned char nl = '\n';
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out + run, &nl, 1, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(hrt_ppm3_write_kernel, dim3(nblocks), dim3(256), 0, stream, d_frame, npix, d_len, d_base, d_out);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_len);
-    if (d_base) (void)hipFree(d_base);
-    if (e != hipSuccess) return fail(HRT_ERR_DEVICE, std::string("hrt_encode_ppm: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(d_out + run, &nl, 1, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(hrt_ppm3_write_kernel, dim3(nblocks), dim3(256), 0, stream, d_frame, npix, d_len, d_base.as<unsigned long long>(), d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));  // `head`, `nl` and `base` are the call's own
     *bytes = total;
     return HRT_OK;
 }
@@ -866,7 +899,7 @@ int hrt_check_last_launch(hrt_scene *s) {
     { const int drc = use_device(s->device); if (drc != HRT_OK) return drc; }
     HIP_TRY(hipEventSynchronize(s->ev1));
     unsigned long long gave_up = 0;
-    HIP_TRY(hipMemcpy(&gave_up, s->stamps + 15, sizeof(gave_up), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&gave_up, s->stamps.as<unsigned long long>() + 15, sizeof(gave_up), hipMemcpyDeviceToHost));
     if (gave_up) return fail(HRT_ERR_DEVICE, "trace kernel gave up (scheduler cycle bound exceeded): the frame of the last launch is incomplete");
     return HRT_OK;
 }
@@ -900,7 +933,7 @@ int hrt_debug_read_stamps(hrt_scene *s, uint64_t out[16]) {
     if (!s || !out) return fail(HRT_ERR_INVALID, "hrt_debug_read_stamps: NULL argument");
     { const int drc = use_device(s->device); if (drc != HRT_OK) return drc; }
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, s->stamps, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, s->stamps.p, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return HRT_OK;
 }
 
@@ -960,30 +993,30 @@ int hrt_render_aov(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, 
     if (rc != HRT_OK) return rc;
     // A camera block of its own: a trace launch on another stream may still be reading s->d_cam.  The AOV kernel runs on the
     // null stream and hipMemcpy below waits for it, so the block is free again when this returns.
-    HIP_TRY(hipMemcpy(s->d_cam_aov, &C, sizeof(C), hipMemcpyHostToDevice));
-    R.cam = s->d_cam_aov;
-    float *d = nullptr;
+    HIP_TRY(hipMemcpy(s->d_cam_aov.p, &C, sizeof(C), hipMemcpyHostToDevice));
+    R.cam = s->d_cam_aov.as<DCamera>();
+    Scratch d;
     const size_t bytes = (size_t)w * h * 3 * sizeof(float);
-    HIP_TRY(hipMalloc((void **)&d, bytes));
-    hipLaunchKernelGGL(hrt_aov_kernel, dim3((w * h + 255) / 256), dim3(256), 0, 0, R, which, d);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(out_rgb, d, bytes, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(HRT_ERR_DEVICE, std::string("hrt_render_aov: ") + hipGetErrorString(e));
+    if ((rc = d.grow(bytes)) != HRT_OK) return rc;
+    hipLaunchKernelGGL(hrt_aov_kernel, dim3((w * h + 255) / 256), dim3(256), 0, 0, R, which, d.as<float>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out_rgb, d.p, bytes, hipMemcpyDeviceToHost));
     return HRT_OK;
 }
 
 int hrt_debug_path_stream(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t n, float *out) {
     if (!out || !n) return fail(HRT_ERR_INVALID, "hrt_debug_path_stream: bad argument");
     if (!g_rt.ready) return fail(HRT_ERR_STATE, "hrt_debug_path_stream: call hrt_init first");
-    float *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, n * sizeof(float)));
-    hipLaunchKernelGGL(hrt_stream_kernel, dim3(1), dim3(64), 0, 0, (uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample, n, d);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(out, d, n * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(HRT_ERR_DEVICE, std::string("hrt_debug_path_stream: ") + hipGetErrorString(e));
+    Scratch d;
+    if (const int rc = d.grow(n * sizeof(float))) return rc;
+    hipLaunchKernelGGL(hrt_stream_kernel, dim3(1), dim3(64), 0, 0, (uint32_t)seed, (uint32_t)(seed >> 32), pixel, sample, n, d.as<float>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d.p, n * sizeof(float), hipMemcpyDeviceToHost));
     return HRT_OK;
+}
+
+void hrt_debug_live_resources(uint64_t out[4]) {
+    for (int k = 0; k < 4; ++k) out[k] = g_live[k].load();
 }
 
 // Known-answer instrument: device functions on caller vectors (include/hrt.h).
@@ -1000,8 +1033,6 @@ int hrt_debug_kat(uint32_t which, const hrt_camera *cam, const float *prim, cons
     float err_abs = 0.f;
     DCamera C;
     DScene kat_scene{};   // HRT_KAT_QUAD: carries nothing but the square's filter rows
-    float4 *d_qf = nullptr;
-    DScene *d_scene = nullptr;
     if (which == HRT_KAT_CAMERA) {
         const int rc = make_camera(cam, C);
         if (rc != HRT_OK) return rc;
@@ -1029,49 +1060,38 @@ int hrt_debug_kat(uint32_t which, const hrt_camera *cam, const float *prim, cons
         for (size_t k = 0; k < (size_t)n * 7; ++k) if (k % 7 < 3) b = std::max(b, (double)std::fabs(in[k]));
         err_abs = margin_scale((float)(b * 4.0), 0.f);  // as fill_render derives it from the scene extent (x + 0.f is x)
     }
-    void *d_prim = nullptr;
-    float *d_in = nullptr, *d_out = nullptr;
-    hipError_t e = hipSuccess;
+    Scratch prim_buf, in_buf, out_buf, qf_buf, scene_buf;
     const size_t in_bytes = (size_t)n * in_w[which] * sizeof(float), out_bytes = (size_t)n * out_w[which] * sizeof(float);
     const void *h_prim = which == HRT_KAT_CAMERA ? (const void *)&C : (which == HRT_KAT_AABB ? (const void *)box.data() : (const void *)rows.data());
     const size_t prim_bytes = which == HRT_KAT_CAMERA ? sizeof(C) : (which == HRT_KAT_AABB ? 6 * sizeof(float) : rows.size() * sizeof(float4));
-    if (prim_bytes) e = hipMalloc(&d_prim, prim_bytes);
-    if (e == hipSuccess && prim_bytes) e = hipMemcpy(d_prim, h_prim, prim_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_in, in_bytes);
-    if (e == hipSuccess) e = hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, out_bytes);
-    if (e == hipSuccess) {
-        const dim3 grid((n + 255u) / 256u), block(256);
-        switch (which) {
-            case HRT_KAT_CAMERA: hipLaunchKernelGGL(hrt_kat_camera_kernel, grid, block, 0, 0, (const DCamera *)d_prim, d_in, n, d_out); break;
-            case HRT_KAT_TRIANGLE: hipLaunchKernelGGL(hrt_kat_triangle_kernel, grid, block, 0, 0, (const float4 *)d_prim, d_in, n, d_out); break;
-            case HRT_KAT_AABB: hipLaunchKernelGGL(hrt_kat_aabb_kernel, grid, block, 0, 0, (const float *)d_prim, d_in, n, d_out); break;
-            case HRT_KAT_SPHERE: hipLaunchKernelGGL(hrt_kat_sphere_kernel, grid, block, 0, 0, (const float4 *)d_prim, d_in, n, d_out); break;
-            case HRT_KAT_QUAD:
-            case HRT_KAT_QUAD_RCP:
-                e = hipMalloc((void **)&d_qf, kat_qf.size() * sizeof(float4));
-                if (e == hipSuccess) e = hipMemcpy(d_qf, kat_qf.data(), kat_qf.size() * sizeof(float4), hipMemcpyHostToDevice);
-                kat_scene.qfilter = d_qf;
-                if (e == hipSuccess) e = hipMalloc((void **)&d_scene, sizeof(DScene));
-                if (e == hipSuccess) e = hipMemcpy(d_scene, &kat_scene, sizeof(DScene), hipMemcpyHostToDevice);
-                if (e == hipSuccess && which == HRT_KAT_QUAD) hipLaunchKernelGGL(hrt_kat_quad_kernel, grid, block, 0, 0, (const float4 *)d_prim, (const DScene *)d_scene, d_in, n, err_abs, d_out);
-                else if (e == hipSuccess) hipLaunchKernelGGL(hrt_kat_quad_rcp_kernel, grid, block, 0, 0, (const float4 *)d_prim, (const DScene *)d_scene, d_in, n, err_abs, d_out);
-                break;
-            case HRT_KAT_OPTICS: hipLaunchKernelGGL(hrt_kat_optics_kernel, grid, block, 0, 0, d_in, n, d_out); break;
-            case HRT_KAT_HITWORD: hipLaunchKernelGGL(hrt_kat_hitword_kernel, grid, block, 0, 0, d_in, n, d_out); break;
-            case HRT_KAT_DIV_KNOWN: hipLaunchKernelGGL(hrt_kat_div_known_kernel, grid, block, 0, 0, d_in, n, d_out); break;
-            case HRT_KAT_NORMALIZE_SHARED: hipLaunchKernelGGL(hrt_kat_normalize_shared_kernel, grid, block, 0, 0, d_in, n, d_out); break;
-            default: hipLaunchKernelGGL(hrt_kat_normalize_kernel, grid, block, 0, 0, d_in, n, d_out); break;
-        }
-        if (e == hipSuccess) e = hipGetLastError();
+    if (const int rc = prim_buf.from_host(h_prim, prim_bytes)) return rc;  // nothing where the instrument has no primitive
+    if (const int rc = in_buf.from_host(in, in_bytes)) return rc;
+    if (const int rc = out_buf.grow(out_bytes)) return rc;
+    const void *const d_prim = prim_buf.p;
+    const float *const d_in = in_buf.as<float>();
+    float *const d_out = out_buf.as<float>();
+    const dim3 grid((n + 255u) / 256u), block(256);
+    switch (which) {
+        case HRT_KAT_CAMERA: hipLaunchKernelGGL(hrt_kat_camera_kernel, grid, block, 0, 0, (const DCamera *)d_prim, d_in, n, d_out); break;
+        case HRT_KAT_TRIANGLE: hipLaunchKernelGGL(hrt_kat_triangle_kernel, grid, block, 0, 0, (const float4 *)d_prim, d_in, n, d_out); break;
+        case HRT_KAT_AABB: hipLaunchKernelGGL(hrt_kat_aabb_kernel, grid, block, 0, 0, (const float *)d_prim, d_in, n, d_out); break;
+        case HRT_KAT_SPHERE: hipLaunchKernelGGL(hrt_kat_sphere_kernel, grid, block, 0, 0, (const float4 *)d_prim, d_in, n, d_out); break;
+        case HRT_KAT_QUAD:
+        case HRT_KAT_QUAD_RCP:
+            if (const int rc = qf_buf.from_host(kat_qf.data(), kat_qf.size() * sizeof(float4))) return rc;
+            kat_scene.qfilter = qf_buf.as<float4>();
+            if (const int rc = scene_buf.from_host(&kat_scene, sizeof(DScene))) return rc;
+            if (which == HRT_KAT_QUAD) hipLaunchKernelGGL(hrt_kat_quad_kernel, grid, block, 0, 0, (const float4 *)d_prim, scene_buf.as<const DScene>(), d_in, n, err_abs, d_out);
+            else hipLaunchKernelGGL(hrt_kat_quad_rcp_kernel, grid, block, 0, 0, (const float4 *)d_prim, scene_buf.as<const DScene>(), d_in, n, err_abs, d_out);
+            break;
+        case HRT_KAT_OPTICS: hipLaunchKernelGGL(hrt_kat_optics_kernel, grid, block, 0, 0, d_in, n, d_out); break;
+        case HRT_KAT_HITWORD: hipLaunchKernelGGL(hrt_kat_hitword_kernel, grid, block, 0, 0, d_in, n, d_out); break;
+        case HRT_KAT_DIV_KNOWN: hipLaunchKernelGGL(hrt_kat_div_known_kernel, grid, block, 0, 0, d_in, n, d_out); break;
+        case HRT_KAT_NORMALIZE_SHARED: hipLaunchKernelGGL(hrt_kat_normalize_shared_kernel, grid, block, 0, 0, d_in, n, d_out); break;
+        default: hipLaunchKernelGGL(hrt_kat_normalize_kernel, grid, block, 0, 0, d_in, n, d_out); break;
     }
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost);
-    if (d_qf) (void)hipFree(d_qf);
-    if (d_scene) (void)hipFree(d_scene);
-    if (d_prim) (void)hipFree(d_prim);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(HRT_ERR_DEVICE, std::string("hrt_debug_kat: ") + hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
     return HRT_OK;
 }
 

@@ -144,7 +144,7 @@ int hrt_bake_device(hrt_scene *s, const float *d_points, const uint32_t *d_keys,
     return bake_launch(s, d_points, d_keys, n, first_sample, n_samples, seed, flags, d_out, (hipStream_t)stream);
 }
 
-// Blocking, from and into host memory (BlockingCall; the points and keys are buffers of the call's, too).
+// Blocking, from and into host memory (BlockingCall; the points and keys are device buffers of the call's, too).
 int hrt_bake(hrt_scene *s, const float *points, const uint32_t *keys, uint32_t n, uint32_t spp, uint64_t seed, uint32_t flags, float *out,
              hrt_stats *stats) {
     const std::string who = "hrt_bake";
@@ -159,12 +159,12 @@ int hrt_bake(hrt_scene *s, const float *points, const uint32_t *keys, uint32_t n
     if ((rc = samples_out_check(who, 0u, spp, out, "out")) != HRT_OK) return rc;
     if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
     BlockingCall call;
-    float *d_points = nullptr;
-    uint32_t *d_keys = nullptr;
-    if ((rc = call.buffer(&d_points, (size_t)n * HRT_RAY_FLOATS * sizeof(float), points)) != HRT_OK) return rc;
-    if (keys && (rc = call.buffer(&d_keys, (size_t)n * sizeof(uint32_t), keys)) != HRT_OK) return rc;
-    return call.run(s, (size_t)n * 3u * sizeof(float), out, (uint64_t)n * spp, stats,
-                    [&](float *d_out) { return bake_launch(s, d_points, d_keys, n, 0u, spp, seed, flags, d_out, nullptr); });
+    Scratch d_points, d_keys;
+    if ((rc = d_points.from_host(points, (size_t)n * HRT_RAY_FLOATS * sizeof(float))) != HRT_OK) return rc;
+    if (keys && (rc = d_keys.from_host(keys, (size_t)n * sizeof(uint32_t))) != HRT_OK) return rc;
+    return call.run(s, (size_t)n * 3u * sizeof(float), out, (uint64_t)n * spp, stats, [&](float *d_out) {
+        return bake_launch(s, d_points.as<float>(), d_keys.as<uint32_t>(), n, 0u, spp, seed, flags, d_out, nullptr);
+    });
 }
 
 int hrt_bake_quad_points(const hrt_quad *quad, uint32_t tw, uint32_t th, int32_t side, float time, float bias, float *out_points) {

@@ -346,11 +346,11 @@ static int features_launch(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint
     DCamera C;
     int rc = fill_render(s, cam, w, h, 1, seed, 0, 0, 1, R, C);
     if (rc != HRT_OK) return rc;
-    if (!s->d_cam_feat) HIP_TRY(hipMalloc((void **)&s->d_cam_feat, sizeof(DCamera)));
+    if ((rc = s->d_cam_feat.grow(sizeof(DCamera))) != HRT_OK) return rc;
     if ((rc = s->feat_reader.wait_on(stream)) != HRT_OK) return rc;
     s->h_cam_feat = C;
-    HIP_TRY(hipMemcpyAsync(s->d_cam_feat, &s->h_cam_feat, sizeof(C), hipMemcpyHostToDevice, stream));
-    R.cam = s->d_cam_feat;
+    HIP_TRY(hipMemcpyAsync(s->d_cam_feat.p, &s->h_cam_feat, sizeof(C), hipMemcpyHostToDevice, stream));
+    R.cam = s->d_cam_feat.as<DCamera>();
     R.s0 = first_sample;
     const uint32_t npix = w * h;
     hipLaunchKernelGGL(hrt_features_kernel, dim3((npix + 255) / 256), dim3(256), 0, stream, R, n_samples, d_features);

@@ -139,21 +139,6 @@ extern "C" __global__ void __launch_bounds__(256) kd_partition(const uint32_t *_
     }
 }
 
-template <class T>
-struct DevBuf {   // a device array that only grows
-    T *p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        const hipError_t e = hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace hrtkd
 
 // The level loop.  (g_rt / fail / HIP_TRY come from hrt_api.hip, which includes this file inside its anonymous-namespace scope's
@@ -167,15 +152,11 @@ static int kd_build_gpu_impl(const hrt_kd_build_input *in, hrt_kd_build_output *
     const uint32_t n0 = in->n_refs;
 
     // level arrays on the device, ping-pong
-    DevBuf<uint32_t> ids[2], counts, cursors;
-    DevBuf<float> lo[2], hi[2];
-    DevBuf<DNode> d_nodes;
-    DevBuf<Work> d_work;
-    DevBuf<Best> d_best;
+    Scratch ids[2], counts, cursors, lo[2], hi[2], d_nodes, d_work, d_best;  // of uint32_t; of float; of DNode, Work, Best
     size_t cap[2] = {std::max<size_t>(n0, 1), 0};
-    HIP_TRY(ids[0].need(cap[0]));
-    HIP_TRY(lo[0].need(3 * cap[0]));
-    HIP_TRY(hi[0].need(3 * cap[0]));
+    if (const int rc = ids[0].need<uint32_t>(cap[0])) return rc;
+    if (const int rc = lo[0].need<float>(3 * cap[0])) return rc;
+    if (const int rc = hi[0].need<float>(3 * cap[0])) return rc;
     {
         std::vector<float> soa(3 * cap[0]);
         HIP_TRY(hipMemcpy(ids[0].p, in->ids, n0 * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -216,14 +197,14 @@ static int kd_build_gpu_impl(const hrt_kd_build_input *in, hrt_kd_build_output *
         }
         first_work[level.size()] = (uint32_t)work.size();
         std::vector<Best> best(work.size());
-        HIP_TRY(d_nodes.need(dn.size()));
+        if (const int rc = d_nodes.need<DNode>(dn.size())) return rc;
         HIP_TRY(hipMemcpy(d_nodes.p, dn.data(), dn.size() * sizeof(DNode), hipMemcpyHostToDevice));
         if (!work.empty()) {
-            HIP_TRY(d_work.need(work.size()));
-            HIP_TRY(d_best.need(work.size()));
+            if (const int rc = d_work.need<Work>(work.size())) return rc;
+            if (const int rc = d_best.need<Best>(work.size())) return rc;
             HIP_TRY(hipMemcpy(d_work.p, work.data(), work.size() * sizeof(Work), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(kd_split_search, dim3((uint32_t)work.size()), dim3(256), 0, 0, lo[cur].p, hi[cur].p, (uint32_t)cap[cur], d_nodes.p, d_work.p,
-                               d_best.p, in->cost_traverse, in->cost_intersect, in->empty_bonus);
+            hipLaunchKernelGGL(kd_split_search, dim3((uint32_t)work.size()), dim3(256), 0, 0, lo[cur].as<float>(), hi[cur].as<float>(), (uint32_t)cap[cur], d_nodes.as<DNode>(), d_work.as<Work>(),
+                               d_best.as<Best>(), in->cost_traverse, in->cost_intersect, in->empty_bonus);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpy(best.data(), d_best.p, work.size() * sizeof(Best), hipMemcpyDeviceToHost));
         }
@@ -260,13 +241,13 @@ static int kd_build_gpu_impl(const hrt_kd_build_input *in, hrt_kd_build_output *
         if (split_work.empty()) break;
         // ---- children: sizes, ranges, cells
         HIP_TRY(hipMemcpy(d_nodes.p, dn.data(), dn.size() * sizeof(DNode), hipMemcpyHostToDevice));
-        HIP_TRY(d_work.need(split_work.size()));
+        if (const int rc = d_work.need<Work>(split_work.size())) return rc;
         HIP_TRY(hipMemcpy(d_work.p, split_work.data(), split_work.size() * sizeof(Work), hipMemcpyHostToDevice));
-        HIP_TRY(counts.need(2 * level.size()));
-        HIP_TRY(cursors.need(2 * level.size()));
+        if (const int rc = counts.need<uint32_t>(2 * level.size())) return rc;
+        if (const int rc = cursors.need<uint32_t>(2 * level.size())) return rc;
         HIP_TRY(hipMemset(counts.p, 0, 2 * level.size() * sizeof(uint32_t)));
         HIP_TRY(hipMemset(cursors.p, 0, 2 * level.size() * sizeof(uint32_t)));
-        hipLaunchKernelGGL(kd_count, dim3((uint32_t)split_work.size()), dim3(256), 0, 0, lo[cur].p, hi[cur].p, (uint32_t)cap[cur], d_nodes.p, d_work.p, counts.p);
+        hipLaunchKernelGGL(kd_count, dim3((uint32_t)split_work.size()), dim3(256), 0, 0, lo[cur].as<float>(), hi[cur].as<float>(), (uint32_t)cap[cur], d_nodes.as<DNode>(), d_work.as<Work>(), counts.as<uint32_t>());
         HIP_TRY(hipGetLastError());
         std::vector<uint32_t> h_counts(2 * level.size());
         HIP_TRY(hipMemcpy(h_counts.data(), counts.p, h_counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -291,13 +272,13 @@ static int kd_build_gpu_impl(const hrt_kd_build_input *in, hrt_kd_build_output *
         if (run > 0x7fffffffull) return fail(HRT_ERR_INVALID, "hrt_kd_build_gpu: more than 2^31 triangle references in one level");
         const int nxt = cur ^ 1;
         cap[nxt] = std::max<size_t>((size_t)run, 1);
-        HIP_TRY(ids[nxt].need(cap[nxt]));
-        HIP_TRY(lo[nxt].need(3 * cap[nxt]));
-        HIP_TRY(hi[nxt].need(3 * cap[nxt]));
-        cap[nxt] = std::min(ids[nxt].cap, std::min(lo[nxt].cap, hi[nxt].cap) / 3);  // (the arrays only grow: the axis stride is the capacity)
+        if (const int rc = ids[nxt].need<uint32_t>(cap[nxt])) return rc;
+        if (const int rc = lo[nxt].need<float>(3 * cap[nxt])) return rc;
+        if (const int rc = hi[nxt].need<float>(3 * cap[nxt])) return rc;
+        cap[nxt] = std::min(ids[nxt].cap, std::min(lo[nxt].cap, hi[nxt].cap) / 3) / 4;  // (the arrays only grow: the axis stride is the capacity, which is in bytes: 4 per id or float)
         HIP_TRY(hipMemcpy(d_nodes.p, dn.data(), dn.size() * sizeof(DNode), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(kd_partition, dim3((uint32_t)split_work.size()), dim3(256), 0, 0, ids[cur].p, lo[cur].p, hi[cur].p, (uint32_t)cap[cur], d_nodes.p, d_work.p,
-                           cursors.p, ids[nxt].p, lo[nxt].p, hi[nxt].p, (uint32_t)cap[nxt]);
+        hipLaunchKernelGGL(kd_partition, dim3((uint32_t)split_work.size()), dim3(256), 0, 0, ids[cur].as<uint32_t>(), lo[cur].as<float>(), hi[cur].as<float>(), (uint32_t)cap[cur], d_nodes.as<DNode>(), d_work.as<Work>(),
+                           cursors.as<uint32_t>(), ids[nxt].as<uint32_t>(), lo[nxt].as<float>(), hi[nxt].as<float>(), (uint32_t)cap[nxt]);
         HIP_TRY(hipGetLastError());
         level.swap(next);
         cur = nxt;

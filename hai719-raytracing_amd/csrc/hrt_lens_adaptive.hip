@@ -38,7 +38,7 @@ static int lens_tiles_launch(hrt_scene *s, const DLens &L, uint32_t w, uint32_t 
 // round 1 on, and the times are read after it; a fault of a round's kernels ends the call there, before the length of the next
 // list is believed.
 static int lens_adaptive_run(hrt_scene *s, const DLens &L, uint32_t w, uint32_t h, const hrt_adaptive *p, uint64_t seed, uint32_t flags,
-                             float *d_sums, uint32_t *d_counts, hipStream_t stream, hipEvent_t ev[4], double *kernel_ms) {
+                             float *d_sums, uint32_t *d_counts, hipStream_t stream, const Event ev[4], double *kernel_ms) {
     *kernel_ms = 0.0;
     auto add_time = [&](hipEvent_t e0, hipEvent_t e1) -> int {  // after the synchronisation that covers e1
         float f = 0.f;
@@ -49,7 +49,7 @@ static int lens_adaptive_run(hrt_scene *s, const DLens &L, uint32_t w, uint32_t 
     return adaptive_rounds(
         s, AdFrame{w, h, (w + HRT_TILE - 1u) / HRT_TILE, hrt_tiles_total(w, h), 0u, 1u}, p, (flags & HRT_FLAG_GAMMA) != 0u, d_sums, d_counts, stream,
         [&](const uint32_t *list, uint32_t n, uint32_t first, uint32_t add, float *sums, uint32_t round) -> int {
-            hipEvent_t *const e = ev + (round == 0u ? 0 : 2);
+            const Event *const e = ev + (round == 0u ? 0 : 2);
             return lens_tiles_launch(s, L, w, h, list, n, first, add, seed, flags, sums, stream, e[0], e[1]);
         },
         [&](uint32_t round) -> int {
@@ -86,16 +86,12 @@ static int lens_adaptive_frame(hrt_scene *s, const DLens &L, uint32_t w, uint32_
     if (rc == HRT_OK) rc = s->la_tiles.grow(tile_bytes);
     if (rc == HRT_OK) rc = s->la_reader.wait_on(stream);
     if (rc != HRT_OK) return rc;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    auto run = [&]() -> int {
-        for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
-        const int rrc = lens_adaptive_run(s, L, w, h, p, seed, flags, s->la_tiles.as<float>(), d_counts, stream, ev, kernel_ms);
-        if (rrc != HRT_OK) return rrc;
-        return hrt_assemble_frame(s->la_tiles.as<float>(), tiles, w, h, 1, d_frame, stream);
-    };
-    rc = run();
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    return rc != HRT_OK ? rc : s->la_reader.mark(stream);
+    Event ev[4];
+    for (Event &e : ev)
+        if ((rc = e.ready()) != HRT_OK) return rc;
+    if ((rc = lens_adaptive_run(s, L, w, h, p, seed, flags, s->la_tiles.as<float>(), d_counts, stream, ev, kernel_ms)) != HRT_OK) return rc;
+    if ((rc = hrt_assemble_frame(s->la_tiles.as<float>(), tiles, w, h, 1, d_frame, stream)) != HRT_OK) return rc;
+    return s->la_reader.mark(stream);
 }
 
 int hrt_render_lens_adaptive_device(hrt_scene *s, const hrt_lens *lens, uint32_t w, uint32_t h, const hrt_adaptive *params, uint64_t seed,

@@ -61,8 +61,8 @@ struct hrt_multi {
     uint32_t n = 0;
     std::vector<int> ordinal;
     std::vector<hrt_scene *> replica;
-    std::vector<hipStream_t> stream;
-    std::vector<hipEvent_t> done;
+    std::vector<Stream> stream;
+    std::vector<Event> done;
     std::vector<bool> busy;            // `done` of the slot has been recorded by a render (and may still be pending)
     std::vector<Scratch> tiles;         // slots 1..n-1: this slot's tiles on its own device
     std::vector<ncclComm_t> comm;      // gather == rccl: one communicator per slot
@@ -95,8 +95,8 @@ void hrt_multi_destroy(hrt_multi *m) {
         if (!m->replica[i]) continue;  // a slot hrt_multi_create never reached (e.g. a bad ordinal): nothing on it
         if (use_device(m->ordinal[i]) != HRT_OK) continue;
         if (i < m->comm.size() && m->comm[i]) (void)rccl_api().CommDestroy(m->comm[i]);
-        if (i < m->stream.size() && m->stream[i]) (void)hipStreamDestroy(m->stream[i]);
-        if (i < m->done.size() && m->done[i]) (void)hipEventDestroy(m->done[i]);
+        m->stream[i].release();  // here, with the slot's device current: the destructors then find nothing
+        m->done[i].release();
         hrt_scene_destroy(m->replica[i]);
     }
     if (m->n && g_rt.ready && m->replica[0]) (void)use_device(m->ordinal[0]);
@@ -120,17 +120,17 @@ int hrt_multi_create(const hrt_scene_desc *desc, uint32_t n_devices, const int *
     m->n = n_devices;
     m->ordinal.assign(device_ordinals, device_ordinals + n_devices);
     m->replica.assign(n_devices, nullptr);
-    m->stream.assign(n_devices, nullptr);
-    m->done.assign(n_devices, nullptr);
+    m->stream.resize(n_devices);
+    m->done.resize(n_devices);
     m->busy.assign(n_devices, false);
-    m->tiles.assign(n_devices, Scratch());
+    m->tiles.resize(n_devices);
     m->comm.assign(n_devices, nullptr);
     int rc = HRT_OK;
     for (uint32_t i = 0; i < n_devices && rc == HRT_OK; ++i) {
         rc = hrt_init(m->ordinal[i]);  // prepares the device on first use, makes it current
         if (rc == HRT_OK) rc = hrt_scene_create(desc, &m->replica[i]);
-        if (rc == HRT_OK && hipStreamCreateWithFlags(&m->stream[i], hipStreamNonBlocking) != hipSuccess) rc = fail(HRT_ERR_DEVICE, "hrt_multi_create: hipStreamCreate failed");
-        if (rc == HRT_OK && hipEventCreateWithFlags(&m->done[i], hipEventDisableTiming) != hipSuccess) rc = fail(HRT_ERR_DEVICE, "hrt_multi_create: hipEventCreate failed");
+        if (rc == HRT_OK) rc = m->stream[i].ready(hipStreamNonBlocking);
+        if (rc == HRT_OK) rc = m->done[i].ready(hipEventDisableTiming);
     }
     if (rc == HRT_OK && want != "peer" && distinct) {  // the collective
         RcclApi &api = rccl_api();
@@ -204,7 +204,7 @@ int hrt_multi_render(hrt_multi *m, const hrt_camera *cam, uint32_t w, uint32_t h
     // render: every slot at once, blocks of `per` floats in the gather buffer
     for (uint32_t i = 0; i < n; ++i) {
         float *tiles = i == 0 ? d_gathered : m->tiles[i].as<float>();
-        rc = hrt_render_tiles(m->replica[i], cam, w, h, spp, seed, flags, i, n, tiles, (void *)m->stream[i]);  // switches to the slot's device
+        rc = hrt_render_tiles(m->replica[i], cam, w, h, spp, seed, flags, i, n, tiles, (void *)m->stream[i].s);  // switches to the slot's device
         if (rc != HRT_OK) return rc;
     }
     // gather: behind each slot's kernel, on the slot's stream
@@ -232,7 +232,7 @@ int hrt_multi_render(hrt_multi *m, const hrt_camera *cam, uint32_t w, uint32_t h
     }
     if ((rc = use_device(m->ordinal[0])) != HRT_OK) return rc;
     for (uint32_t i = 1; i < n; ++i) HIP_TRY(hipStreamWaitEvent(m->stream[0], m->done[i], 0));
-    rc = hrt_assemble_frame(d_gathered, (uint32_t)(per / 192u), w, h, n, m->frame.as<float>(), (void *)m->stream[0]);
+    rc = hrt_assemble_frame(d_gathered, (uint32_t)(per / 192u), w, h, n, m->frame.as<float>(), (void *)m->stream[0].s);
     if (rc != HRT_OK) return rc;
     HIP_TRY(hipMemcpyAsync(out_rgb, m->frame.p, frame_bytes, hipMemcpyDeviceToHost, m->stream[0]));
     HIP_TRY(hipStreamSynchronize(m->stream[0]));

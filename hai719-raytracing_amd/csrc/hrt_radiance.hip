@@ -250,39 +250,23 @@ static int radiance_launch(void (*const *builds)(const QT), QT &Q, const hrt_sce
     return query_launch(builds[build], Q, s, HRT_RADIANCE_STAGE_TREE, HRT_RADIANCE_WG, stream);
 }
 
-// THE blocking host form of a family (hrt_render_lens, hrt_render_lens_views, hrt_bake): device buffers and two timing events of
-// the call's own, so that this form, too, leaves the scene's state alone; freed on every way out.
+// THE blocking host form of a family (hrt_render_lens, hrt_render_lens_views, hrt_bake): a result buffer and two timing events of
+// the call's own (owners: gone on every way out), so that this form, too, leaves the scene's state alone.
 struct BlockingCall {
-    std::vector<void *> buffers;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    ~BlockingCall() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        for (void *p : buffers) (void)hipFree(p);
-    }
-    // A device buffer of the call's, filled from `from` if given.
-    template <class T>
-    int buffer(T **d, size_t bytes, const void *from = nullptr) {
-        void *p = nullptr;
-        HIP_TRY(hipMalloc(&p, bytes));
-        buffers.push_back(p);
-        if (from) HIP_TRY(hipMemcpy(p, from, bytes, hipMemcpyHostToDevice));
-        *d = (T *)p;
-        return HRT_OK;
-    }
     // launch(d_out) on the null stream between the events, its `bytes` of result into `out`, and the stats of `samples` samples.
     template <class F>
     int run(const hrt_scene *s, size_t bytes, float *out, uint64_t samples, hrt_stats *stats, F launch) {
-        float *d_out = nullptr;
+        Scratch d_out;
+        Event ev0, ev1;
         float ms = 0.f;
-        if (const int rc = buffer(&d_out, bytes)) return rc;
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
+        if (const int rc = d_out.grow(bytes)) return rc;
+        if (const int rc = ev0.ready()) return rc;
+        if (const int rc = ev1.ready()) return rc;
         HIP_TRY(hipEventRecord(ev0, nullptr));
-        if (const int rc = launch(d_out)) return rc;
+        if (const int rc = launch(d_out.as<float>())) return rc;
         HIP_TRY(hipEventRecord(ev1, nullptr));
-        HIP_TRY(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out, d_out.p, bytes, hipMemcpyDeviceToHost));
         HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
         if (stats) {
             fill_stats(s, stats, t0, (double)ms, samples);

@@ -208,7 +208,7 @@ static int query_check(const std::string &who, uint32_t flags, uint32_t extra, c
 extern "C++" {
 template <class QT>
 static int query_launch(void (*k)(const QT), QT &Q, const hrt_scene *s, bool stage_tree, uint32_t wg, void *stream) {
-    Q.scene = s->d_scene;
+    Q.scene = s->d_scene.as<DScene>();
     Q.bound = s->bound;
     Q.lds_units = (stage_tree && !(Q.flags & HRT_FLAG_NO_LDS_TREE)) ? std::min<uint32_t>(s->lds_units, 4096u) : 0u;
     const size_t lds_bytes = (size_t)Q.lds_units * 16u;

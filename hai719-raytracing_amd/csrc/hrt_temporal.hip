@@ -239,12 +239,11 @@ void hrt_history_reset(hrt_history *hist) {
     if (hist) hist->valid = false;
 }
 
+// After hrt_shutdown the buffers are freed all the same, on whatever device is current, as hrt_scene_destroy frees a scene's (they
+// used to be left behind).
 void hrt_history_destroy(hrt_history *hist) {
     if (!hist) return;
-    if (g_rt.ready && hist->scene && use_device(hist->scene->device) == HRT_OK)
-        for (int k = 0; k < 2; ++k) {
-            hist->color[k].release(); hist->half[k].release(); hist->feat[k].release(); hist->len[k].release();
-        }
+    if (g_rt.ready && hist->scene) (void)use_device(hist->scene->device);
     delete hist;
 }
 

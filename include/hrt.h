@@ -382,6 +382,11 @@ typedef struct hrt_pick_input {
 HRT_API int hrt_debug_pick_kernel(const hrt_pick_input *in, char *name, size_t cap);
 /* The name of the build the scene's last trace launch ran ("" before any). */
 HRT_API int hrt_debug_last_kernel(hrt_scene *scene, char *name, size_t cap);
+/* The HIP resources the library holds at this moment, in every scene, history and multi handle and in calls under way:
+ * out[0] device buffers, out[1] pinned host buffers, out[2] events, out[3] streams.  Each is counted where it is acquired and
+ * where it is freed, so a handle's destroy call brings the numbers back to what they were before its creation.  Needs no hrt_init,
+ * makes no HIP call and cannot fail. */
+HRT_API void hrt_debug_live_resources(uint64_t out[4]);
 
 /* Output stage of main.cpp:252-262: P3 ASCII with (int)(255*min(1,c)). */
 /* The tree build's split search and partition on the GPU (a hrt_kd_builder_fn; `user` is ignored): level by level, every
@@ -598,6 +603,8 @@ HRT_API int hrt_temporal_accumulate(const hrt_camera *cam, const hrt_camera *pre
 typedef struct hrt_history hrt_history;
 HRT_API int hrt_history_create(hrt_scene *scene, hrt_history **out);
 HRT_API void hrt_history_reset(hrt_history *hist);      /* the next frame restarts everywhere */
+/* Frees the history's device buffers, also when called after hrt_shutdown (as hrt_scene_destroy frees a scene's; before the
+ * buffers owned themselves, a history destroyed after hrt_shutdown left its eight buffers behind). */
 HRT_API void hrt_history_destroy(hrt_history *hist);
 HRT_API int hrt_render_temporal(hrt_scene *scene, hrt_history *hist, const hrt_camera *cam, uint32_t w, uint32_t h,
                                 uint32_t spp, uint32_t feature_spp, uint64_t seed, uint32_t flags,
