@@ -172,6 +172,10 @@ SHADE_FLOATS = 16
 KIND_MISS, KIND_SPHERE, KIND_SQUARE, KIND_MESH = 0, 1, 2, 3
 NO_PRIM = 0xFFFFFFFF  # index and prim of a miss, prim of a sphere or square hit
 RADIANCE_ACCUMULATE = 512  # HRT_RADIANCE_ACCUMULATE: add to the running sums in the output instead of storing means
+# Light probes (include/hrt.h "Light probes").  A probe record is PROBE_FLOATS float32: position, time; a result PROBE_COEFFS x 3.
+PROBE_FLOATS = 4    # HRT_PROBE_FLOATS
+PROBE_COEFFS = 9    # HRT_PROBE_COEFFS
+PROBE_BLOCK = 64    # HRT_PROBE_BLOCK: samples per block of the fixed-order sum (tests/test_probe_abi.py holds it to the header)
 
 
 class DenoiseParams(C.Structure):
@@ -349,6 +353,10 @@ def device_lib() -> C.CDLL:
                                  C.POINTER(Stats)]
         lib.hrt_bake_quad_points.argtypes = [C.POINTER(Quad), C.c_uint32, C.c_uint32, C.c_int32, C.c_float, C.c_float, C.c_void_p]
         lib.hrt_bake_mesh_points.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_void_p]
+        lib.hrt_probe_rays.argtypes = lib.hrt_bake_rays.argtypes
+        lib.hrt_probes_device.argtypes = lib.hrt_bake_device.argtypes
+        lib.hrt_probes.argtypes = lib.hrt_bake.argtypes
+        lib.hrt_probe_grid_points.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]
         lib.hrt_debug_pick_kernel.argtypes = [C.POINTER(PickInput), C.c_char_p, C.c_size_t]
         lib.hrt_debug_last_kernel.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         lib.hrt_debug_live_resources.argtypes = [C.POINTER(C.c_uint64 * 4)]
@@ -416,6 +424,18 @@ def _ray_batch(who: str, noun: str, batch, tensor_only: bool = False):
     batch = np.ascontiguousarray(batch, dtype=np.float32)
     if batch.ndim != 2 or batch.shape[1] != RAY_FLOATS:
         raise ValueError(f"{who}: {noun} must have shape (n, {RAY_FLOATS}) (got {batch.shape})")
+    return batch
+
+
+def _probe_batch(who: str, noun: str, batch, tensor_only: bool = False):
+    """``_ray_batch`` for probe records: (n, PROBE_FLOATS) float32."""
+    import torch
+    if tensor_only or isinstance(batch, torch.Tensor):
+        _check_tensor(who, noun if tensor_only else "a torch tensor", batch, (None, PROBE_FLOATS), shown=f"(n, {PROBE_FLOATS})")
+        return batch
+    batch = np.ascontiguousarray(batch, dtype=np.float32)
+    if batch.ndim != 2 or batch.shape[1] != PROBE_FLOATS:
+        raise ValueError(f"{who}: {noun} must be probe records of shape (n, {PROBE_FLOATS}) (got {batch.shape})")
     return batch
 
 
@@ -725,16 +745,19 @@ class DeviceScene:
         return DeviceScene._radiance_batch(self, "trace_radiance", "rays", "hrt_trace_radiance", None, rays, spp, first_sample, seed, keys,
                                            out, accumulate, flags, None)
 
-    def _radiance_batch(self, who: str, noun: str, device_fn: str, blocking_fn: Optional[str], batch, spp, first_sample, seed, keys, out, accumulate, flags, stats):
-        """What trace_radiance and bake share: ``batch`` ((n, RAY_FLOATS) float32, the ``noun`` of the messages), ``keys`` and ``out``
+    def _radiance_batch(self, who: str, noun: str, device_fn: str, blocking_fn: Optional[str], batch, spp, first_sample, seed, keys, out, accumulate, flags, stats,
+                        rows=None, cell: tuple = (3,)):
+        """What trace_radiance, bake and probes share: ``batch`` ((n, RAY_FLOATS) float32, the ``noun`` of the messages -- or what
+        ``rows(who, noun, batch)`` accepts in place of ``_ray_batch``), ``keys`` and ``out`` ((n,) + ``cell``)
         checked as torch tensors on one GPU or as NumPy -- before ``self`` is touched -- then the entry point ``device_fn``
         (hrt_trace_radiance's signature) on the current torch stream; a NumPy batch is uploaded, and its result copied back.
         ``blocking_fn`` (hrt_bake's signature), if given, takes a NumPy batch of samples [0, spp) without ``out`` instead, and fills
         ``stats``."""
         import torch
         is_torch = isinstance(batch, torch.Tensor)
-        batch = _ray_batch(who, noun, batch)
+        batch = (rows or _ray_batch)(who, noun, batch)
         n = _row_count(who, noun, batch)
+        shape, shown = (n,) + tuple(cell), "(n, " + ", ".join(str(c) for c in cell) + ")"
         if keys is not None:
             if is_torch:
                 _check_tensor(who, "keys", keys, (n,), "int32", batch.device, noun, "(n,)")
@@ -746,13 +769,13 @@ class DeviceScene:
             if accumulate and first_sample != 0:
                 raise ValueError(f"{who}: accumulate after sample 0 needs the running sums in `out`")
         elif is_torch:
-            _check_tensor(who, "out", out, (n, 3), "float32", batch.device, noun, "(n, 3)")
+            _check_tensor(who, "out", out, shape, "float32", batch.device, noun, shown)
         else:
             o = np.asarray(out)
-            if o.shape != (n, 3) or o.dtype != np.float32:
-                raise ValueError(f"{who}: out must be (n, 3) float32 (got {o.shape} {o.dtype})")
+            if o.shape != shape or o.dtype != np.float32:
+                raise ValueError(f"{who}: out must be {shown} float32 (got {o.shape} {o.dtype})")
         if blocking_fn is not None and not is_torch and out is None and not accumulate and first_sample == 0:
-            r = np.empty((n, 3), dtype=np.float32)
+            r = np.empty(shape, dtype=np.float32)
             self._check(getattr(self._lib, blocking_fn)(self._h, batch.ctypes.data, None if keys is None else keys.ctypes.data, n, spp, seed, flags,
                                                         r.ctypes.data, _ref(stats)))
             return r
@@ -763,7 +786,7 @@ class DeviceScene:
             d_keys = None if keys is None else torch.from_numpy(keys.view(np.int32)).to(d_batch.device)
             d_out = None if out is None else torch.from_numpy(np.ascontiguousarray(o)).to(d_batch.device)
         if d_out is None:
-            d_out = torch.zeros((n, 3), dtype=torch.float32, device=d_batch.device)
+            d_out = torch.zeros(shape, dtype=torch.float32, device=d_batch.device)
         self._check(getattr(self._lib, device_fn)(self._h, _ptr(d_batch), _ptr(d_keys), n, first_sample, spp, seed, flags, _ptr(d_out),
                                                   _stream(d_batch.device)))
         if is_torch:
@@ -788,6 +811,24 @@ class DeviceScene:
         flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
         return DeviceScene._radiance_batch(self, "bake", "points", "hrt_bake_device", "hrt_bake", points, spp, first_sample, seed, keys, out,
                                            accumulate, flags, stats)
+
+    def probes(self, points, spp: int = 1, first_sample: int = 0, seed: int = 1, keys=None, out=None, accumulate: bool = False,
+               flags: int = 0, stats: Optional[Stats] = None):
+        """hrt_probes*: the radiance arriving at points in space from every direction, (n, PROBE_FLOATS) float32 rows {P, time},
+        projected onto the 9 spherical-harmonic basis functions of bands 0..2: samples [first_sample, first_sample + spp) of RNG
+        stream (seed, key, sample), uniform on the sphere; key i unless ``keys`` (n uint32 / int32).
+
+        Returns (n, PROBE_COEFFS, 3) float32: per coefficient and colour channel the mean over the samples of basis x radiance in
+        the units of ``trace_radiance`` (the SH coefficients of the incoming radiance are 4 pi x 6 x the mean; no factor is applied),
+        or with ``accumulate`` the running sums (``out`` then holds the sums of the earlier samples and is updated in place).  The
+        sum has a fixed order (include/hrt.h "Light probes"), in blocks of PROBE_BLOCK samples.  A contiguous float32 torch tensor
+        on the GPU runs on the current torch stream of its device and gives a torch tensor there (``out``, if given, a device
+        tensor), without synchronising (hrt_probes_device).  Anything else is taken as NumPy and comes back as NumPy; samples
+        [0, spp) without ``out`` go through the blocking hrt_probes, which fills ``stats`` if given.  Probe calls of one scene must
+        not overlap each other.  ``flags``: FLAG_EXACT_ONLY, FLAG_MESH_BRUTE, FLAG_NO_LDS_TREE."""
+        flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
+        return DeviceScene._radiance_batch(self, "probes", "points", "hrt_probes_device", "hrt_probes", points, spp, first_sample, seed, keys, out,
+                                           accumulate, flags, stats, rows=_probe_batch, cell=(PROBE_COEFFS, 3))
 
     def render_views(self, cams, w: int, h: int, spp: int, seeds=None, flags: int = 0, out=None, stats: Optional[Stats] = None):
         """hrt_render_views: every camera of ``cams`` as a w x h frame of ``spp`` samples, in one launch -> (n, h, w, 3) float32;
@@ -1048,6 +1089,35 @@ def bake_rays(points, sample: int = 0, seed: int = 1, keys=None):
     out = torch.empty((n, RAY_FLOATS), dtype=torch.float32, device=points.device)
     with torch.cuda.device(points.device):
         _call("hrt_bake_rays", _ptr(points), _ptr(keys), n, sample, seed, _ptr(out), _stream(points.device))
+    return out
+
+
+def probe_rays(points, sample: int = 0, seed: int = 1, keys=None):
+    """hrt_probe_rays: the rays of sample ``sample`` of light probes -- a contiguous (n, PROBE_FLOATS) float32 torch tensor on the
+    GPU, rows {P, time} -- as an (n, RAY_FLOATS) tensor on the same device, written on the current torch stream; a degenerate
+    sample has direction 0.  ``keys``: (n,) int32 on the same device.  Traced with trace_radiance(first_sample=sample, keys=keys)
+    they give the samples ``DeviceScene.probes`` projects."""
+    import torch
+    device_lib()
+    _probe_batch("probe_rays", "points", points, tensor_only=True)
+    n = points.shape[0]
+    if keys is not None:
+        _check_tensor("probe_rays", "keys", keys, (n,), "int32", points.device, "points", "(n,)")
+    out = torch.empty((n, RAY_FLOATS), dtype=torch.float32, device=points.device)
+    with torch.cuda.device(points.device):
+        _call("hrt_probe_rays", _ptr(points), _ptr(keys), n, sample, seed, _ptr(out), _stream(points.device))
+    return out
+
+
+def probe_grid(lo, hi, nx: int, ny: int, nz: int, time: float = 0.0) -> np.ndarray:
+    """hrt_probe_grid_points: the (nx * ny * nz, PROBE_FLOATS) float32 probe records of a regular grid in the box ``lo`` .. ``hi``,
+    probe (i, j, k) at index (k * ny + j) * nx + i, at the centre of its cell.  Host only: needs no GPU."""
+    lo3, hi3 = (np.ascontiguousarray(v, dtype=np.float32) for v in (lo, hi))
+    if lo3.shape != (3,) or hi3.shape != (3,):
+        raise ValueError(f"probe_grid: lo and hi must have 3 components (got {lo3.shape} and {hi3.shape})")
+    n = int(nx) * int(ny) * int(nz)
+    out = np.empty((n if 0 < n <= 0x7FFFFFFF else 1, PROBE_FLOATS), dtype=np.float32)  # a grid the library refuses writes nothing
+    _call("hrt_probe_grid_points", lo3.ctypes.data, hi3.ctypes.data, nx, ny, nz, time, out.ctypes.data)
     return out
 
 

@@ -8,6 +8,7 @@
 #include "hrt_kat.hip"
 #include "hrt_pack.h"  // hrt_scene_desc -> host arrays (pack_scene): everything of scene creation that needs no device
 #include "hrt_bake_points.h"  // the host-only bake point generators (hrt_bake_quad_points, hrt_bake_mesh_points)
+#include "hrt_probe_points.h"  // the host-only probe grid generator (hrt_probe_grid_points)
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types and prototypes only: librccl.so is opened with dlopen by hrt_multi_create (hrt_multi.hip)
@@ -426,6 +427,9 @@ struct hrt_scene {
     // hrt_render_adaptive.  Nothing of the trace launches.
     Scratch la_tiles, la_frame;
     LastReader la_reader;
+    // Light probes (hrt_probes.hip): the block values of the launch in hand, allocated by the first probe call.  Nothing of the
+    // trace launches.
+    Scratch pr_blocks;
 };
 
 namespace {
@@ -1120,6 +1124,7 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 #include "hrt_radiance.hip"
 #include "hrt_lens.hip"
 #include "hrt_bake.hip"
+#include "hrt_probes.hip"
 #include "hrt_lens_adaptive.hip"
 #include "hrt_views.hip"
 

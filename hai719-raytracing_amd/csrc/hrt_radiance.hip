@@ -47,8 +47,20 @@ struct RecordRays {
     static constexpr bool per_sample = false;
 };
 
+// A per-sample source with wave_items (ProbeRays, hrt_probes.hip) spreads the samples of one item over the 64 lanes of a WAVE and
+// keeps what a finished sample is added to itself.  Q.n then counts lanes (64 per item), lane i works for item i / 64, and the
+// source says which samples are the lane's -- s = SRC::first(Q, i), then every 64th below SRC::end(Q, i), counted from first_sample
+// --, takes every finished sample (SRC::add) and, once no lane of the wave has a sample left, closes the item (SRC::finish, in
+// which all 64 lanes take part) before the wave takes its next one (SRC::begin).  Every other source is untouched by this: all of
+// it is behind `if constexpr`.
+template <class SRC, class = void>
+struct src_wave_items { static constexpr bool value = false; };
+template <class SRC>
+struct src_wave_items<SRC, std::enable_if_t<SRC::wave_items>> { static constexpr bool value = true; };
+
 template <bool LIGHTS, bool EXACT, class SRC = RecordRays, class QT = DRadiance>
 __device__ __forceinline__ void radiance_body(const QT &Q) {
+    constexpr bool WAVE = src_wave_items<SRC>::value;
     CtxT<EXACT, false, false, true> cx;
     unsigned long long stamps_local[17] = {0};
     query_context(cx, Q.scene, Q.lds_units, Q.flags, stamps_local);
@@ -64,6 +76,7 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
     uint32_t first_flags = Q.flags;  // cx.flags of its first segments (+ MESH_BRUTE for a far origin)
     f3 sum = mk(0.f, 0.f, 0.f);
     uint32_t s = 0;          // next sample of this lane's ray
+    [[maybe_unused]] uint32_t count = 0;  // a wave_items source: where the samples of the wave's item end (s runs in steps of 64)
     int remaining = 0;       // bounces left on the current path; 0 = needs a new path
     Ray ray;
     ray.o = mk(0.f, 0.f, 0.f); ray.d = mk(0.f, 0.f, 1.f); ray.time = 0.f;
@@ -82,6 +95,16 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
     // A per-sample source has no ray yet: every pixel is live, and a sample that is not traced is skipped where it is made.
     auto next_ray = [&]() {
         live = false;
+        if constexpr (WAVE) {  // the wave's next item: this lane's share of its samples, nothing of `sum` or Q.out
+            if (i < Q.n) {
+                SRC::begin(Q, i);
+                key = SRC::key(Q, i);
+                s = SRC::first(Q, i);
+                count = SRC::end(Q, i);
+                live = s < count;
+            }
+            return;
+        }
         if constexpr (SRC::per_sample) {
             live = i < Q.n;
         } else {
@@ -106,8 +129,22 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
         }
     };
 
+    // Whether the wave has work.  A wave_items source: the item boundary -- the wave meets here once none of its lanes has a
+    // sample left, closes the item with all 64 lanes and takes the next one by a wave-granular grid stride (Q.n and the stride are
+    // multiples of 64, so i < Q.n holds for a whole wave or for none of it).
+    auto more = [&]() -> bool {
+        if constexpr (WAVE) {
+            while (__ballot(live) == 0ull && __ballot(i < Q.n) != 0ull) {
+                SRC::finish(Q, i);
+                i += stride;
+                next_ray();
+            }
+        }
+        return __ballot(live) != 0ull;
+    };
+
     next_ray();
-    while (__ballot(live) != 0ull) {
+    while (more()) {
         // ---- stage A: (re)start a path, spheres + squares, mesh gates
         if (live && stage == 0u) {
             bool traced = true;    // a per-sample source may make a sample that is not traced: it ends at once, nothing is added
@@ -181,9 +218,16 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
                 ended = (remaining == 0) || (prune && thr.x == 0.f && thr.y == 0.f && thr.z == 0.f);
             }
             if (ended) {
-                if (!(SRC::per_sample && stage == 4u)) sum = sum + mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f);  // Scene.h:348
+                if constexpr (WAVE) {  // the sink is the source's: it gets what a one-sample query stores, 0 + rad / 6
+                    if (stage != 4u) SRC::add(Q, i, Q.first_sample + s, mk(0.f, 0.f, 0.f) + mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f));
+                } else if (!(SRC::per_sample && stage == 4u)) {
+                    sum = sum + mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f);  // Scene.h:348
+                }
                 remaining = 0;
-                if (++s == Q.n_samples) {  // the ray is done: its mean (or running sum), then the lane's next ray
+                if constexpr (WAVE) {
+                    if (count - s <= 64u) live = false;  // out of samples: idle until the wave meets in more()
+                    else s += 64u;
+                } else if (++s == Q.n_samples) {  // the ray is done: its mean (or running sum), then the lane's next ray
                     const float ns = accumulate ? 1.f : (float)Q.n_samples;  // x / 1.f is exact
                     float *o = Q.out + (size_t)i * 3u;
                     o[0] = sum.x / ns; o[1] = sum.y / ns; o[2] = sum.z / ns;

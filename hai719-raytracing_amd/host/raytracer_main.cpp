@@ -34,6 +34,11 @@
 //                                                  the side, +1 the lit one), --spp cosine-weighted samples per texel; written
 //                                                  row-major in the frame's linear units, radiance / 6, without gamma (one GPU,
 //                                                  no other mode)
+//             [--probe-grid NX,NY,NZ --probe-box x0,y0,z0,x1,y1,z1] light probes (hrt_probes): an NX x NY x NZ grid of probes at the
+//                                                  cell centres of the box (hrt_probe_grid_points), --spp uniform directions per
+//                                                  probe; --out is TEXT, one line per probe: its position, then the 27 means
+//                                                  (9 SH coefficients x rgb, radiance / 6, no factor), %.9g (one GPU, not with
+//                                                  --lens, --bake-quad, --views or --adaptive)
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -69,6 +74,9 @@ static hrt_lens lens_params = {{}, HRT_LENS_PERSPECTIVE, 0.f, 1.f, 0.f};
 static long bake_quad = -1;             // --bake-quad: hrt_bake over the texels of that quad of the flattened scene
 static int32_t bake_side = 1;
 static float bake_bias = 1e-4f;
+static bool probe_grid_given = false, probe_box_given = false;  // --probe-grid with --probe-box: hrt_probes over a grid of probes
+static uint32_t probe_n[3] = {0u, 0u, 0u};
+static float probe_box[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 static hrt_temporal_params temporal_params = {0.02f, 64.f, 0.05f, 0.1f, 0.05f};  // the Python TemporalParams()
 
 // Drop-in for ray_trace_from_camera(): same inputs (current scene, nsamples, window size, camera),
@@ -215,6 +223,50 @@ static int bake_lightmap(const hrt_scene_desc &desc) {
     return rc;
 }
 
+// --probe-grid: the SH coefficients of a grid of light probes, as text
+static int light_probes() {
+    const size_t n = (size_t)probe_n[0] * probe_n[1] * probe_n[2];
+    std::vector<float> probes(n * HRT_PROBE_FLOATS), sh(n * 3u * HRT_PROBE_COEFFS, 0.f);
+    int rc = hrt_probe_grid_points(probe_box, probe_box + 3, probe_n[0], probe_n[1], probe_n[2], 0.f, probes.data());
+    if (rc != HRT_OK) {
+        std::cout << "hrt_probe_grid_points failed: " << hrt_last_error() << std::endl;
+        return rc;
+    }
+    std::cout << "Tracing " << probe_n[0] << " x " << probe_n[1] << " x " << probe_n[2] << " light probes on the GPU using " << nsamples
+              << " samples per probe" << std::endl;
+    hrt_stats st;
+    rc = hrt_probes(device_scene, probes.data(), nullptr, (uint32_t)n, nsamples, seed, 0u, sh.data(), &st);
+    if (rc != HRT_OK) {
+        std::cout << "hrt_probes failed: " << hrt_last_error() << std::endl;
+        return rc;
+    }
+    std::cout << "  Done in " << st.total_ms / 1000.0 << " seconds (kernel " << st.kernel_ms << " ms, " << (double)st.samples / st.kernel_ms / 1e3
+              << " Msamples/s)" << std::endl;
+    FILE *f = std::fopen(out_path.c_str(), "w");
+    if (!f) {
+        std::cout << "cannot write " << out_path << std::endl;
+        return HRT_ERR_INVALID;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        std::fprintf(f, "%.9g %.9g %.9g", probes[i * HRT_PROBE_FLOATS], probes[i * HRT_PROBE_FLOATS + 1], probes[i * HRT_PROBE_FLOATS + 2]);
+        for (unsigned k = 0; k < 3u * HRT_PROBE_COEFFS; ++k) std::fprintf(f, " %.9g", sh[i * 3u * HRT_PROBE_COEFFS + k]);
+        std::fprintf(f, "\n");
+    }
+    return std::fclose(f) == 0 ? HRT_OK : HRT_ERR_INVALID;
+}
+
+// "a,b,c" as exactly `count` numbers; false otherwise
+static bool parse_list(const std::string &v, int count, double *out) {
+    const char *p = v.c_str();
+    for (int i = 0; i < count; ++i) {
+        char *end = nullptr;
+        out[i] = std::strtod(p, &end);
+        if (end == p || *end != (i + 1 < count ? ',' : '\0')) return false;
+        p = end + 1;
+    }
+    return true;
+}
+
 static int ray_trace_from_camera() {
     const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
     std::vector<float> image((size_t)w * h * 3, 0.f);
@@ -285,6 +337,28 @@ int main(int argc, char **argv) {
         else if (k == "--bake-quad") bake_quad = strtol(v.c_str(), nullptr, 10);
         else if (k == "--bake-side") bake_side = (int32_t)strtol(v.c_str(), nullptr, 10);
         else if (k == "--bake-bias") bake_bias = strtof(v.c_str(), nullptr);
+        else if (k == "--probe-grid") {
+            double g[3];
+            if (!parse_list(v, 3, g) || !(g[0] >= 1 && g[1] >= 1 && g[2] >= 1) || g[0] > 4294967295. || g[1] > 4294967295. || g[2] > 4294967295.) {
+                std::cerr << "--probe-grid takes NX,NY,NZ, three positive counts (got " << v << ")" << std::endl;
+                return 2;
+            }
+            if (g[0] * g[1] * g[2] > 2147483647.) {  // exact in double wherever it is near the bound; refused before anything is sized by it
+                std::cerr << "--probe-grid " << v << ": NX * NY * NZ must be at most 2^31 - 1" << std::endl;
+                return 2;
+            }
+            for (int a = 0; a < 3; ++a) probe_n[a] = (uint32_t)g[a];
+            probe_grid_given = true;
+        }
+        else if (k == "--probe-box") {
+            double b[6];
+            if (!parse_list(v, 6, b)) {
+                std::cerr << "--probe-box takes x0,y0,z0,x1,y1,z1, the two corners of the box (got " << v << ")" << std::endl;
+                return 2;
+            }
+            for (int a = 0; a < 6; ++a) probe_box[a] = (float)b[a];
+            probe_box_given = true;
+        }
         else if (k == "--gpus") { devices.clear(); for (int d = 0; d < atoi(v.c_str()); ++d) devices.push_back(d); }
         else if (k == "--devices") {
             devices.clear();
@@ -345,6 +419,20 @@ int main(int argc, char **argv) {
         std::cerr << "--orbit turns the camera over the frames of --temporal or the cameras of --views: give --temporal FRAMES or --views N" << std::endl;
         return 2;
     }
+    if (probe_grid_given != probe_box_given) {
+        std::cerr << (probe_grid_given ? "--probe-grid NX,NY,NZ needs the box of the grid: give --probe-box x0,y0,z0,x1,y1,z1"
+                                       : "--probe-box x0,y0,z0,x1,y1,z1 needs the counts of the grid: give --probe-grid NX,NY,NZ") << std::endl;
+        return 2;
+    }
+    const bool probes = probe_grid_given;
+    if (probes) {
+        const char *other = use_lens ? "--lens" : bake_quad != -1 ? "--bake-quad" : n_views != 0u ? "--views" : adaptive ? "--adaptive" : denoise ? "--denoise"
+                            : denoise_var ? "--denoise-var" : temporal ? "--temporal" : !devices.empty() ? "--gpus / --devices" : nullptr;
+        if (other) {
+            std::cerr << "--probe-grid traces light probes on one GPU: it cannot be combined with " << other << std::endl;
+            return 2;
+        }
+    }
     const bool bake = bake_quad != -1;
     if (bake && (adaptive || denoise || denoise_var || temporal || n_views != 0u || use_lens || !devices.empty())) {
         std::cerr << "--bake-quad bakes a lightmap on one GPU: it cannot be combined with a render mode or --gpus / --devices" << std::endl;
@@ -379,7 +467,7 @@ int main(int argc, char **argv) {
         std::cout << "Image tiles across " << devices.size() << " GPU slot(s), gather: " << hrt_multi_gather(multi)
                   << (note.empty() ? "" : " (" + note + ")") << std::endl;
     }
-    int rc = bake ? bake_lightmap(flat->desc) : n_views ? ray_trace_views() : use_lens ? ray_trace_lens() : temporal ? ray_trace_frames() : ray_trace_from_camera();  // the 'r' key, once or frame after frame
+    int rc = probes ? light_probes() : bake ? bake_lightmap(flat->desc) : n_views ? ray_trace_views() : use_lens ? ray_trace_lens() : temporal ? ray_trace_frames() : ray_trace_from_camera();  // the 'r' key, once or frame after frame
     hrt_scene_destroy(device_scene);
     hrt_multi_destroy(multi);
     hrt_shutdown();

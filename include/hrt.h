@@ -902,8 +902,8 @@ HRT_API int hrt_render_lens_adaptive(hrt_scene *scene, const hrt_lens *lens, uin
  * anything is written.
  * Both refuse (HRT_ERR_INVALID, by name) NULL pointers, tw or th zero, tw*th > 2^31 - 1, side other than +1 / -1, and a time or
  * bias that is not finite.
- * OUT OF SCOPE (DESIGN.md section 5 "Baking"): spherical-harmonic probes, jitter inside a texel, points that follow a moving quad,
- * sphere and mesh-texel parametrisations, denoising of lightmaps, the streaming kernel, multi-GPU. */
+ * OUT OF SCOPE (DESIGN.md section 5 "Baking"): jitter inside a texel, points that follow a moving quad, sphere and mesh-texel
+ * parametrisations, denoising of lightmaps, the streaming kernel, multi-GPU.  Spherical-harmonic probes are "Light probes" below. */
 HRT_API int hrt_bake_rays(const float *d_points, const uint32_t *d_keys, uint32_t n, uint32_t sample, uint64_t seed, float *d_rays, void *stream);
 HRT_API int hrt_bake_device(hrt_scene *scene, const float *d_points, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
                             uint32_t n_samples, uint64_t seed, uint32_t flags, float *d_out, void *stream);
@@ -912,6 +912,76 @@ HRT_API int hrt_bake(hrt_scene *scene, const float *points, const uint32_t *keys
 HRT_API int hrt_bake_quad_points(const hrt_quad *quad, uint32_t tw, uint32_t th, int32_t side, float time, float bias, float *out_points);
 HRT_API int hrt_bake_mesh_points(const float *positions, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles, float time,
                                  float bias, float *out_points);
+
+/* ---- Light probes: the radiance arriving at caller-supplied points in space from EVERY direction, projected onto the 9 real
+ * spherical-harmonic (SH) basis functions of bands 0..2, per colour channel, in one launch.
+ * PROBES: n records of HRT_PROBE_FLOATS floats (16 bytes, the array 16-byte aligned), device memory: {P.x, P.y, P.z, time}.  Probe i
+ * has the key k = d_keys ? d_keys[i] : i.  A probe is DEGENERATE when one of its four floats is not finite.
+ * THE RULE (tests/probe_ref.py states it again in NumPy).  All arithmetic is fp32 without fused multiply-add, in the order written;
+ * sqrtf, sinf and cosf are the device's; normalize is the trace path's own (divide by the length).
+ * Direction of sample s of probe i, uniform on the sphere:
+ *   b0, b1 = draws 0 and 1 of stream (seed, k, s)   -- the slots a bake uses; a radiance path starts at draw 3
+ *   z = 1.f - 2.f * b0, r = sqrtf(fmaxf(0.f, 1.f - z * z)), phi = 6.2831855f * b1
+ *   d = normalize((r * cosf(phi), r * sinf(phi), z))
+ *   ray = {P, time, d, +inf}
+ * A sample is degenerate when its probe is, or when a component of d is not finite, or d == 0.  hrt_probe_rays writes it as
+ * {P, time, 0, 0, 0, +inf}; it adds nothing and still counts in the divisor -- the convention of hrt_bake_rays.
+ * Basis, with (x, y, z) = d:
+ *   Y0 = 0.2820948f
+ *   Y1 = 0.48860251f * y        Y2 = 0.48860251f * z        Y3 = 0.48860251f * x
+ *   Y4 = 1.0925485f * (x * y)   Y5 = 1.0925485f * (y * z)
+ *   Y6 = 0.31539157f * (3.f * (z * z) - 1.f)
+ *   Y7 = 1.0925485f * (x * z)   Y8 = 0.54627422f * (x * x - y * y)
+ * The sum.  Its order is fixed and does not depend on how the device schedules it.  v(s) is the three floats
+ * hrt_trace_radiance(first_sample = s, n_samples = 1) returns for the ray above (that path's radiance / 6), j = s - first_sample:
+ *   sample j belongs to block j / HRT_PROBE_BLOCK and to lane j % 64 of that block;
+ *   lane partial: a[k][c] = 0.f, then for the lane's samples in ascending j: a[k][c] = a[k][c] + Y_k * v_c (one multiply and one
+ *     add per term; a degenerate sample adds nothing; a lane with no samples holds 0.f);
+ *   block value: halving over the 64 lane partials: for m = 32, 16, 8, 4, 2, 1: a_l = a_l + a_{l+m} for l < m; the value is a_0;
+ *   total: t = 0.f, then t = t + block_b for b ascending;
+ *   output: 27 floats per probe, d_out[27 i + 3 k + c]: t / (float)n_samples, or with HRT_RADIANCE_ACCUMULATE d_out (on entry) + t.
+ * UNITS: the output is the mean over uniform directions of Y_k(d) times what hrt_trace_radiance gives (radiance / 6); the calls
+ * apply NO factor, as the bakes.  The SH coefficients of the incoming radiance are 4 pi * 6 * the mean.  (An irradiance evaluator
+ * is nine multiplies in the caller's shader: convolve with the clamped cosine by scaling band 0 by pi, band 1 by 2 pi / 3 and band 2
+ * by pi / 4 -- Ramamoorthi and Hanrahan 2001 -- and evaluate the basis at the normal.)
+ * hrt_probe_rays: the ray records of one sample (n records of HRT_RAY_FLOATS floats, device, 16-byte aligned) -- the sibling of
+ * hrt_bake_rays.  No scene: it runs on the calling thread's current device, asynchronously on `stream`.
+ * hrt_probes_device: the fused form, with no ray buffer, asynchronous on `stream`.  One wave of the device works on one (probe,
+ * block) pair, its lane the rule's lane; a second small launch on the same stream adds the block values.
+ * CONTRACT A: bit-identical to the sum above over the per-sample outputs of hrt_probe_rays(s) and hrt_trace_radiance(first_sample = s,
+ * n_samples = 1, the same d_keys) -- for every scene and flag set.
+ * Flags: a bake's -- HRT_FLAG_EXACT_ONLY, HRT_FLAG_MESH_BRUTE (with EXACT_ONLY), HRT_FLAG_NO_LDS_TREE, HRT_RADIANCE_ACCUMULATE.  Every
+ * other bit is refused by name; that includes HRT_RAYS_NORMALIZE (a probe has no direction to normalise), HRT_FLAG_GAMMA and the
+ * kernel-form flags.
+ * hrt_probes: the same from and into HOST buffers (`probes`, `keys`, `out`; 4-byte aligned), blocking, samples [0, spp); stats as
+ * hrt_bake (samples = n * spp; n == 0 zeroes them).  HRT_RADIANCE_ACCUMULATE is refused (the sums live on the device).
+ * LIMIT: n * ceil(n_samples / HRT_PROBE_BLOCK) <= HRT_PROBE_MAX_BLOCKS: the block values stay below 453 MB and a work item times
+ * 64 fits 32 bits.
+ * Checked in this order before the scene and the library state, HRT_ERR_INVALID with hrt_last_error() naming the entry point and
+ * the culprit: flags; (n == 0 returns HRT_OK here and launches nothing;) d_probes NULL or not 16-byte aligned; d_keys not 4-byte
+ * aligned; n > 2^31 - 1; n_samples == 0; first_sample + n_samples > 2^32; the limit above; the output NULL or misaligned (d_rays
+ * 16 bytes, d_out 4); then a NULL scene.
+ * CONCURRENCY: the block values are a grow-only scratch buffer of the scene's, allocated by its first probe call and freed with
+ * the scene, so probe launches of ONE scene must not overlap each other.  Nothing of the trace launches' per-launch state is
+ * touched: a probe launch may overlap a render or a query of the same scene on another stream.
+ * hrt_probe_grid_points (host only: no device, no hrt_init; fp32 in the order written) writes nx * ny * nz records, probe (i, j, k)
+ * at index (k*ny + j)*nx + i, per axis at lo + ((i + .5f)/nx) * (hi - lo); lo > hi on an axis runs it backwards.  It refuses
+ * (HRT_ERR_INVALID, by name) NULL pointers, a zero count, nx*ny*nz > 2^31 - 1 and a lo, hi or time that is not finite.
+ * OUT OF SCOPE (DESIGN.md section 5 "Light probes"): higher SH orders, stratified or low-discrepancy directions, an irradiance
+ * evaluator, probes that move, visibility or depth moments per probe, the streaming kernel, multi-GPU (a caller splits the probes;
+ * the keys keep every probe's random numbers). */
+#define HRT_PROBE_FLOATS 4
+#define HRT_PROBE_COEFFS 9
+#ifndef HRT_PROBE_BLOCK
+#define HRT_PROBE_BLOCK 64u           /* samples per block of the sum; a multiple of 64 (-DHRT_PROBE_BLOCK: the A/B builds) */
+#endif
+#define HRT_PROBE_MAX_BLOCKS (1u << 22)
+HRT_API int hrt_probe_rays(const float *d_probes, const uint32_t *d_keys, uint32_t n, uint32_t sample, uint64_t seed, float *d_rays, void *stream);
+HRT_API int hrt_probes_device(hrt_scene *scene, const float *d_probes, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
+                              uint32_t n_samples, uint64_t seed, uint32_t flags, float *d_out, void *stream);
+HRT_API int hrt_probes(hrt_scene *scene, const float *probes, const uint32_t *keys, uint32_t n, uint32_t spp, uint64_t seed, uint32_t flags,
+                       float *out, hrt_stats *stats /* may be NULL */);
+HRT_API int hrt_probe_grid_points(const float *lo, const float *hi, uint32_t nx, uint32_t ny, uint32_t nz, float time, float *out_probes);
 
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");

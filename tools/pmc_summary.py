@@ -12,8 +12,15 @@ Fabric bytes: the guide's factor of 2 on FETCH_SIZE is for wide coalesced stream
 uncalibrated.  This kernel's traffic is a gather of 16-byte groups from 128-byte path records, so the bytes are taken from the
 request-size counters instead -- 32 x RDREQ_32B + 64 x RDREQ_64B + 128 x RDREQ_128B, and 64 x WRREQ_64B + 32 x the other write
 requests -- which tools/calibrate_traffic.sh checks against a known byte count on exactly that pattern
-(profiles/<tag>_traffic_calibration.json; `fetch_factor` below is the resulting ratio to FETCH_SIZE, reported, not assumed)."""
-import collections, csv, glob, hashlib, json, os, shutil, sys
+(profiles/<tag>_traffic_calibration.json; `fetch_factor` below is the resulting ratio to FETCH_SIZE, reported, not assumed).
+
+    python tools/pmc_summary.py --carry-over <tag> <parent.s> <this.s>
+
+for a change that leaves the measured kernels alone: given the gfx950 device assembly of the parent commit and of this tree
+(hipcc with the Makefile's DEV_FLAGS and NOPK, --cuda-device-only -S, of csrc/hrt_api.hip), it compares every kernel of the parent
+instruction for instruction (comments dropped, the function ordinal in local labels .LBB<n>_<m> normalised) and, only if none
+differs or is missing, writes this tree's source hash into profiles/<tag>_*_pmc.json; nothing else in them changes."""
+import collections, csv, glob, hashlib, json, os, re, shutil, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -28,7 +35,38 @@ def source_sha16():
     return h.hexdigest()[:16]
 
 
+def kernels_of(path):
+    """name -> instruction lines of every function of a device assembly file."""
+    out, cur, name = {}, None, None
+    for line in open(path):
+        m = re.match(r"^([A-Za-z_][\w$.]*):\s*(;.*)?$", line)
+        if cur is None and m and not m.group(1).startswith(".L"):
+            name, cur = m.group(1), []
+        elif cur is not None and line.startswith(".Lfunc_end"):
+            out[name], cur = cur, None
+        elif cur is not None and line.split(";")[0].strip():
+            cur.append(re.sub(r"\.LBB\d+_", ".LBB_", line.split(";")[0].rstrip()))
+    return out
+
+
+def carry_over(tag, parent_s, this_s):
+    parent, this = kernels_of(parent_s), kernels_of(this_s)
+    changed = sorted(k for k in parent if parent[k] != this.get(k))
+    if not parent or changed:
+        raise SystemExit(f"not carried over: {len(changed)} of {len(parent)} kernels of the parent differ or are missing: {changed[:8]}")
+    sha, paths = source_sha16(), sorted(glob.glob(os.path.join(ROOT, "profiles", f"{tag}_*_pmc.json")))
+    for path in paths:
+        text, n = re.subn(r'("source_sha16": ")[0-9a-f]{16}(")', r"\g<1>" + sha + r"\2", open(path).read())
+        if n != 1:
+            raise SystemExit(f"{path}: no single source_sha16 field")
+        open(path, "w").write(text)
+    print(f"{len(parent)} kernels of the parent are instruction-identical ({len(this) - len(parent)} new); source_sha16 {sha} written to {len(paths)} profiles")
+
+
 if __name__ == "__main__":
+    if sys.argv[1] == "--carry-over":
+        carry_over(*sys.argv[2:5])
+        sys.exit(0)
     cfg_dir, tag, cfg, scene, spp, w, h = sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4], int(sys.argv[5]), int(sys.argv[6]), int(sys.argv[7])
     out_dir = os.path.dirname(os.path.abspath(cfg_dir))
     acc = collections.defaultdict(lambda: collections.defaultdict(float))
