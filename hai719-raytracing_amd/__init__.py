@@ -176,6 +176,10 @@ RADIANCE_ACCUMULATE = 512  # HRT_RADIANCE_ACCUMULATE: add to the running sums in
 PROBE_FLOATS = 4    # HRT_PROBE_FLOATS
 PROBE_COEFFS = 9    # HRT_PROBE_COEFFS
 PROBE_BLOCK = 64    # HRT_PROBE_BLOCK: samples per block of the fixed-order sum (tests/test_probe_abi.py holds it to the header)
+PROBE_RECORD_FLOATS = 32      # HRT_PROBE_RECORD_FLOATS: a probe's packed record inside a ProbeVolume, 27 coefficients + 5 zeros
+PROBE_VOLUME_MAX = 1 << 24    # HRT_PROBE_VOLUME_MAX: probes per volume
+PROBE_EVAL_RADIANCE = 1       # HRT_PROBE_EVAL_RADIANCE: SH radiance in direction N instead of the cosine-convolved irradiance / pi
+PROBE_EVAL_FACING = 2         # HRT_PROBE_EVAL_FACING: weight probes by how far they face the surface
 
 
 class DenoiseParams(C.Structure):
@@ -357,6 +361,15 @@ def device_lib() -> C.CDLL:
         lib.hrt_probes_device.argtypes = lib.hrt_bake_device.argtypes
         lib.hrt_probes.argtypes = lib.hrt_bake.argtypes
         lib.hrt_probe_grid_points.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]
+        lib.hrt_probe_volume_create.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+        lib.hrt_probe_volume_update_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.hrt_probe_volume_update.argtypes = [C.c_void_p, C.c_void_p]
+        lib.hrt_probe_volume_destroy.argtypes = [C.c_void_p]
+        lib.hrt_probe_volume_destroy.restype = None
+        lib.hrt_probe_eval_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.hrt_probe_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_probe_volume_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                 C.c_void_p]
         lib.hrt_debug_pick_kernel.argtypes = [C.POINTER(PickInput), C.c_char_p, C.c_size_t]
         lib.hrt_debug_last_kernel.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         lib.hrt_debug_live_resources.argtypes = [C.POINTER(C.c_uint64 * 4)]
@@ -974,6 +987,97 @@ class History:
             pass
 
 
+def _box(who: str, lo, hi):
+    """``lo`` and ``hi`` of a probe grid as (3,) float32 arrays."""
+    lo3, hi3 = (np.ascontiguousarray(v, dtype=np.float32) for v in (lo, hi))
+    if lo3.shape != (3,) or hi3.shape != (3,):
+        raise ValueError(f"{who}: lo and hi must have 3 components (got {lo3.shape} and {hi3.shape})")
+    return lo3, hi3
+
+
+class ProbeVolume:
+    """``hrt_probe_volume``: an nx x ny x nz grid of SH9 light probes in the box ``lo`` .. ``hi`` -- the grid of ``probe_grid`` --
+    that lives on the current device, to be looked up at surface points (include/hrt.h "Probe volumes").  It needs no scene."""
+
+    def __init__(self, lo, hi, nx: int, ny: int, nz: int):
+        lo3, hi3 = _box("ProbeVolume", lo, hi)
+        self._h = C.c_void_p()
+        self._lib = device_lib()
+        self.shape = (int(nx), int(ny), int(nz))
+        self.count = self.shape[0] * self.shape[1] * self.shape[2]
+        _call("hrt_probe_volume_create", lo3.ctypes.data, hi3.ctypes.data, nx, ny, nz, C.byref(self._h))
+
+    def update(self, coeffs):
+        """hrt_probe_volume_update*: the coefficients of every probe, (count, PROBE_COEFFS, 3) float32 as ``DeviceScene.probes``
+        returns them for ``probe_grid`` of the same box and counts.  A contiguous torch tensor on the GPU is repacked on the
+        current torch stream of its device, without synchronising; anything else is taken as NumPy and uploaded."""
+        import torch
+        who = "ProbeVolume.update"
+        is_torch = isinstance(coeffs, torch.Tensor)
+        if is_torch:
+            _check_tensor(who, "a torch tensor", coeffs, (None, PROBE_COEFFS, 3), shown=f"(n, {PROBE_COEFFS}, 3)")
+        else:
+            coeffs = np.ascontiguousarray(coeffs, dtype=np.float32)
+            if coeffs.ndim != 3 or coeffs.shape[1:] != (PROBE_COEFFS, 3):
+                raise ValueError(f"{who}: coeffs must have shape (n, {PROBE_COEFFS}, 3) (got {coeffs.shape})")
+        if coeffs.shape[0] != self.count:
+            raise ValueError(f"{who}: the volume has {self.count} probes (got coefficients of {coeffs.shape[0]})")
+        if is_torch:
+            with torch.cuda.device(coeffs.device):
+                _call("hrt_probe_volume_update_device", self._h, _ptr(coeffs), _stream(coeffs.device))
+        else:
+            _call("hrt_probe_volume_update", self._h, coeffs.ctypes.data)
+        return self
+
+    def eval(self, points, radiance: bool = False, facing: bool = False, out=None, stats: Optional[Stats] = None):
+        """hrt_probe_eval*: the volume at surface points, (n, RAY_FLOATS) float32 rows {P, time, N, bias} as ``quad_points`` and
+        ``mesh_points`` write them (time and bias are not read): trilinear interpolation between the eight probes round P -- with
+        ``facing``, weighted by how far each probe faces the surface -- then the irradiance / pi about N, the quantity
+        ``DeviceScene.bake`` returns for the same rows, or with ``radiance`` the SH radiance arriving from direction N.
+
+        Returns (n, 3) float32; a degenerate point gives zeros.  A contiguous float32 torch tensor on the GPU runs on the current
+        torch stream of its device and gives a torch tensor there (``out``, if given, a device tensor), without synchronising
+        (hrt_probe_eval_device).  Anything else is taken as NumPy and goes through the blocking hrt_probe_eval, which fills
+        ``stats`` if given."""
+        import torch
+        who = "ProbeVolume.eval"
+        is_torch = isinstance(points, torch.Tensor)
+        points = _ray_batch(who, "points", points)
+        n = _row_count(who, "points", points)
+        flags = (PROBE_EVAL_RADIANCE if radiance else 0) | (PROBE_EVAL_FACING if facing else 0)
+        if is_torch:
+            if out is None:
+                out = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+            else:
+                _check_tensor(who, "out", out, (n, 3), "float32", points.device, "points", "(n, 3)")
+            with torch.cuda.device(points.device):
+                _call("hrt_probe_eval_device", self._h, _ptr(points), n, flags, _ptr(out), _stream(points.device))
+            return out
+        if out is None:
+            out = np.empty((n, 3), dtype=np.float32)
+        elif not (isinstance(out, np.ndarray) and out.shape == (n, 3) and out.dtype == np.float32 and out.flags.c_contiguous):
+            raise ValueError(f"{who}: out must be a contiguous (n, 3) float32 array (got {getattr(out, 'shape', None)} {getattr(out, 'dtype', None)})")
+        _call("hrt_probe_eval", self._h, points.ctypes.data, n, flags, out.ctypes.data, _ref(stats))
+        return out
+
+    def close(self):
+        if self._h:
+            self._lib.hrt_probe_volume_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 KAT_CAMERA, KAT_TRIANGLE, KAT_AABB, KAT_SPHERE, KAT_QUAD, KAT_OPTICS, KAT_NORMALIZE, KAT_HITWORD, KAT_DIV_KNOWN, KAT_NORMALIZE_SHARED, KAT_QUAD_RCP = range(11)
 _KAT_IN = {KAT_CAMERA: 2, KAT_TRIANGLE: 7, KAT_AABB: 7, KAT_SPHERE: 7, KAT_QUAD: 7, KAT_OPTICS: 8, KAT_NORMALIZE: 3, KAT_HITWORD: 3, KAT_DIV_KNOWN: 2,
            KAT_NORMALIZE_SHARED: 3, KAT_QUAD_RCP: 7}
@@ -1112,13 +1216,25 @@ def probe_rays(points, sample: int = 0, seed: int = 1, keys=None):
 def probe_grid(lo, hi, nx: int, ny: int, nz: int, time: float = 0.0) -> np.ndarray:
     """hrt_probe_grid_points: the (nx * ny * nz, PROBE_FLOATS) float32 probe records of a regular grid in the box ``lo`` .. ``hi``,
     probe (i, j, k) at index (k * ny + j) * nx + i, at the centre of its cell.  Host only: needs no GPU."""
-    lo3, hi3 = (np.ascontiguousarray(v, dtype=np.float32) for v in (lo, hi))
-    if lo3.shape != (3,) or hi3.shape != (3,):
-        raise ValueError(f"probe_grid: lo and hi must have 3 components (got {lo3.shape} and {hi3.shape})")
+    lo3, hi3 = _box("probe_grid", lo, hi)
     n = int(nx) * int(ny) * int(nz)
     out = np.empty((n if 0 < n <= 0x7FFFFFFF else 1, PROBE_FLOATS), dtype=np.float32)  # a grid the library refuses writes nothing
     _call("hrt_probe_grid_points", lo3.ctypes.data, hi3.ctypes.data, nx, ny, nz, time, out.ctypes.data)
     return out
+
+
+def probe_volume_weights(lo, hi, nx: int, ny: int, nz: int, point, facing: bool = False):
+    """hrt_probe_volume_weights: for one point record {P, time, N, bias} (8 floats) the indices of the eight probes of an
+    nx x ny x nz ``ProbeVolume`` in the box ``lo`` .. ``hi`` that ``eval`` interpolates between, and their final weights:
+    ((8,) uint32, (8,) float32), both zero for a degenerate point.  Host only: needs no GPU."""
+    lo3, hi3 = _box("probe_volume_weights", lo, hi)
+    p = np.ascontiguousarray(point, dtype=np.float32)
+    if p.shape != (RAY_FLOATS,):
+        raise ValueError(f"probe_volume_weights: point must be one record of {RAY_FLOATS} floats (got {p.shape})")
+    index, weight = np.zeros(8, dtype=np.uint32), np.zeros(8, dtype=np.float32)
+    _call("hrt_probe_volume_weights", lo3.ctypes.data, hi3.ctypes.data, nx, ny, nz, p.ctypes.data, PROBE_EVAL_FACING if facing else 0,
+          index.ctypes.data, weight.ctypes.data)
+    return index, weight
 
 
 class _SceneDescHead(C.Structure):

@@ -9,6 +9,7 @@
 #include "hrt_pack.h"  // hrt_scene_desc -> host arrays (pack_scene): everything of scene creation that needs no device
 #include "hrt_bake_points.h"  // the host-only bake point generators (hrt_bake_quad_points, hrt_bake_mesh_points)
 #include "hrt_probe_points.h"  // the host-only probe grid generator (hrt_probe_grid_points)
+#include "hrt_probe_volume_cell.h"  // the cell and the weights of a probe volume, for the host and the device
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types and prototypes only: librccl.so is opened with dlopen by hrt_multi_create (hrt_multi.hip)
@@ -447,15 +448,16 @@ int enter_render(const std::string &who, hrt_scene *s, const hrt_camera *cam) {
     return enter_scene(who, s);
 }
 
-// The stats block of a render that took kernel_ms on the device and `samples` samples, started at t0.
+// The stats block of a render that took kernel_ms on the device and `samples` samples, started at t0.  s may be NULL for a call
+// that has no scene (hrt_probe_eval).
 void fill_stats(const hrt_scene *s, hrt_stats *stats, std::chrono::steady_clock::time_point t0, double kernel_ms, uint64_t samples) {
     std::memset(stats, 0, sizeof(*stats));
     stats->kernel_ms = kernel_ms;
     stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     stats->samples = samples;
     stats->vgprs = (uint32_t)g_rt.attr.numRegs;
-    stats->lds_bytes = s->last_lds;
-    stats->waves_launched = s->last_waves;
+    stats->lds_bytes = s ? s->last_lds : 0u;
+    stats->waves_launched = s ? s->last_waves : 0u;
 }
 
 // Uploads one packed array; the scene owns the allocation, `field` (of its header) points at it.
@@ -1125,6 +1127,7 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 #include "hrt_lens.hip"
 #include "hrt_bake.hip"
 #include "hrt_probes.hip"
+#include "hrt_probe_volume.hip"
 #include "hrt_lens_adaptive.hip"
 #include "hrt_views.hip"
 

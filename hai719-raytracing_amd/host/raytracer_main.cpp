@@ -39,6 +39,11 @@
 //                                                  probe; --out is TEXT, one line per probe: its position, then the 27 means
 //                                                  (9 SH coefficients x rgb, radiance / 6, no factor), %.9g (one GPU, not with
 //                                                  --lens, --bake-quad, --views or --adaptive)
+//             [--probe-quad INDEX [--probe-side 1|-1] [--probe-facing]] with --probe-grid and --probe-box: a lightmap from the
+//                                                  probes (hrt_probe_eval) instead of the text: the grid is traced as above,
+//                                                  loaded into a probe volume and evaluated at the --w x --h texel centres of
+//                                                  quad INDEX (hrt_bake_quad_points, bias 0; --probe-facing weights the probes
+//                                                  by how far they face the surface); written as --bake-quad writes its own
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -77,6 +82,9 @@ static float bake_bias = 1e-4f;
 static bool probe_grid_given = false, probe_box_given = false;  // --probe-grid with --probe-box: hrt_probes over a grid of probes
 static uint32_t probe_n[3] = {0u, 0u, 0u};
 static float probe_box[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+static bool probe_quad_given = false, probe_side_given = false, probe_facing = false;  // --probe-quad: hrt_probe_eval over the texels of that quad
+static long probe_quad = -1;
+static int32_t probe_side = 1;
 static hrt_temporal_params temporal_params = {0.02f, 64.f, 0.05f, 0.1f, 0.05f};  // the Python TemporalParams()
 
 // Drop-in for ray_trace_from_camera(): same inputs (current scene, nsamples, window size, camera),
@@ -223,8 +231,8 @@ static int bake_lightmap(const hrt_scene_desc &desc) {
     return rc;
 }
 
-// --probe-grid: the SH coefficients of a grid of light probes, as text
-static int light_probes() {
+// --probe-grid: the SH coefficients of a grid of light probes, as text -- or with --probe-quad the lightmap they give on a quad
+static int light_probes(const hrt_scene_desc &desc) {
     const size_t n = (size_t)probe_n[0] * probe_n[1] * probe_n[2];
     std::vector<float> probes(n * HRT_PROBE_FLOATS), sh(n * 3u * HRT_PROBE_COEFFS, 0.f);
     int rc = hrt_probe_grid_points(probe_box, probe_box + 3, probe_n[0], probe_n[1], probe_n[2], 0.f, probes.data());
@@ -242,6 +250,30 @@ static int light_probes() {
     }
     std::cout << "  Done in " << st.total_ms / 1000.0 << " seconds (kernel " << st.kernel_ms << " ms, " << (double)st.samples / st.kernel_ms / 1e3
               << " Msamples/s)" << std::endl;
+    if (probe_quad_given) {
+        const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
+        std::vector<float> points((size_t)w * h * HRT_RAY_FLOATS), map((size_t)w * h * 3, 0.f);
+        rc = hrt_bake_quad_points(&desc.quads[probe_quad], w, h, probe_side, 0.f, 0.f, points.data());
+        if (rc != HRT_OK) {
+            std::cout << "hrt_bake_quad_points failed: " << hrt_last_error() << std::endl;
+            return rc;
+        }
+        std::cout << "Evaluating the probes over a " << w << " x " << h << " lightmap of quad " << probe_quad << " (side " << probe_side
+                  << (probe_facing ? ", facing weights" : "") << ")" << std::endl;
+        hrt_probe_volume *volume = nullptr;
+        rc = hrt_probe_volume_create(probe_box, probe_box + 3, probe_n[0], probe_n[1], probe_n[2], &volume);
+        if (rc == HRT_OK) rc = hrt_probe_volume_update(volume, sh.data());
+        if (rc == HRT_OK) rc = hrt_probe_eval(volume, points.data(), w * h, probe_facing ? HRT_PROBE_EVAL_FACING : 0u, map.data(), &st);
+        hrt_probe_volume_destroy(volume);
+        if (rc != HRT_OK) {
+            std::cout << "the probe volume failed: " << hrt_last_error() << std::endl;
+            return rc;
+        }
+        std::cout << "  Done (kernel " << st.kernel_ms << " ms)" << std::endl;
+        rc = hrt_write_ppm(out_path.c_str(), map.data(), w, h);
+        if (rc != HRT_OK) std::cout << hrt_last_error() << std::endl;
+        return rc;
+    }
     FILE *f = std::fopen(out_path.c_str(), "w");
     if (!f) {
         std::cout << "cannot write " << out_path << std::endl;
@@ -304,8 +336,15 @@ int main(int argc, char **argv) {
     int gpu = 0;
     bool kd_on_gpu = false;
     std::vector<int> devices;
-    for (int i = 1; i + 1 < argc; i += 2) {
-        const std::string k = argv[i], v = argv[i + 1];
+    for (int i = 1; i < argc; i += 2) {
+        const std::string k = argv[i];
+        if (k == "--probe-facing") {  // the one option without a value
+            probe_facing = true;
+            --i;
+            continue;
+        }
+        if (i + 1 >= argc) break;
+        const std::string v = argv[i + 1];
         if (k == "--scene") name = v;
         else if (k == "--w") SCREENWIDTH = (unsigned)atoi(v.c_str());
         else if (k == "--h") SCREENHEIGHT = (unsigned)atoi(v.c_str());
@@ -359,6 +398,8 @@ int main(int argc, char **argv) {
             for (int a = 0; a < 6; ++a) probe_box[a] = (float)b[a];
             probe_box_given = true;
         }
+        else if (k == "--probe-quad") { probe_quad = strtol(v.c_str(), nullptr, 10); probe_quad_given = true; }
+        else if (k == "--probe-side") { probe_side = (int32_t)strtol(v.c_str(), nullptr, 10); probe_side_given = true; }
         else if (k == "--gpus") { devices.clear(); for (int d = 0; d < atoi(v.c_str()); ++d) devices.push_back(d); }
         else if (k == "--devices") {
             devices.clear();
@@ -424,6 +465,18 @@ int main(int argc, char **argv) {
                                        : "--probe-box x0,y0,z0,x1,y1,z1 needs the counts of the grid: give --probe-grid NX,NY,NZ") << std::endl;
         return 2;
     }
+    if (probe_quad_given && !probe_grid_given) {
+        std::cerr << "--probe-quad looks a probe grid up over a quad: give --probe-grid NX,NY,NZ and --probe-box x0,y0,z0,x1,y1,z1" << std::endl;
+        return 2;
+    }
+    if (!probe_quad_given && (probe_side_given || probe_facing)) {
+        std::cerr << (probe_side_given ? "--probe-side" : "--probe-facing") << " describes the look-up of a probe grid over a quad: give --probe-quad INDEX" << std::endl;
+        return 2;
+    }
+    if (probe_side != 1 && probe_side != -1) {
+        std::cerr << "--probe-side takes 1 or -1 (got " << probe_side << ")" << std::endl;
+        return 2;
+    }
     const bool probes = probe_grid_given;
     if (probes) {
         const char *other = use_lens ? "--lens" : bake_quad != -1 ? "--bake-quad" : n_views != 0u ? "--views" : adaptive ? "--adaptive" : denoise ? "--denoise"
@@ -456,6 +509,10 @@ int main(int argc, char **argv) {
         std::cerr << "--bake-quad " << bake_quad << ": the scene has " << flat->desc.n_quads << " quads" << std::endl;
         return 2;
     }
+    if (probe_quad_given && (probe_quad < 0 || (unsigned long)probe_quad >= flat->desc.n_quads)) {  // before any device is touched
+        std::cerr << "--probe-quad " << probe_quad << ": the scene has " << flat->desc.n_quads << " quads" << std::endl;
+        return 2;
+    }
     const int up = devices.empty() ? (hrt_init(gpu) != HRT_OK ? HRT_ERR_DEVICE : hrt_scene_create(&flat->desc, &device_scene))
                                    : hrt_multi_create(&flat->desc, (uint32_t)devices.size(), devices.data(), &multi);
     if (up != HRT_OK) {
@@ -467,7 +524,7 @@ int main(int argc, char **argv) {
         std::cout << "Image tiles across " << devices.size() << " GPU slot(s), gather: " << hrt_multi_gather(multi)
                   << (note.empty() ? "" : " (" + note + ")") << std::endl;
     }
-    int rc = probes ? light_probes() : bake ? bake_lightmap(flat->desc) : n_views ? ray_trace_views() : use_lens ? ray_trace_lens() : temporal ? ray_trace_frames() : ray_trace_from_camera();  // the 'r' key, once or frame after frame
+    int rc = probes ? light_probes(flat->desc) : bake ? bake_lightmap(flat->desc) : n_views ? ray_trace_views() : use_lens ? ray_trace_lens() : temporal ? ray_trace_frames() : ray_trace_from_camera();  // the 'r' key, once or frame after frame
     hrt_scene_destroy(device_scene);
     hrt_multi_destroy(multi);
     hrt_shutdown();

@@ -941,9 +941,9 @@ HRT_API int hrt_bake_mesh_points(const float *positions, uint32_t n_vertices, co
  *   total: t = 0.f, then t = t + block_b for b ascending;
  *   output: 27 floats per probe, d_out[27 i + 3 k + c]: t / (float)n_samples, or with HRT_RADIANCE_ACCUMULATE d_out (on entry) + t.
  * UNITS: the output is the mean over uniform directions of Y_k(d) times what hrt_trace_radiance gives (radiance / 6); the calls
- * apply NO factor, as the bakes.  The SH coefficients of the incoming radiance are 4 pi * 6 * the mean.  (An irradiance evaluator
- * is nine multiplies in the caller's shader: convolve with the clamped cosine by scaling band 0 by pi, band 1 by 2 pi / 3 and band 2
- * by pi / 4 -- Ramamoorthi and Hanrahan 2001 -- and evaluate the basis at the normal.)
+ * apply NO factor, as the bakes.  The SH coefficients of the incoming radiance are 4 pi * 6 * the mean.  (The irradiance evaluator
+ * is "Probe volumes" below: it convolves with the clamped cosine by scaling band 0 by pi, band 1 by 2 pi / 3 and band 2 by pi / 4
+ * -- Ramamoorthi and Hanrahan 2001 -- and evaluates the basis at the normal, between the eight probes round a point.)
  * hrt_probe_rays: the ray records of one sample (n records of HRT_RAY_FLOATS floats, device, 16-byte aligned) -- the sibling of
  * hrt_bake_rays.  No scene: it runs on the calling thread's current device, asynchronously on `stream`.
  * hrt_probes_device: the fused form, with no ray buffer, asynchronous on `stream`.  One wave of the device works on one (probe,
@@ -967,9 +967,9 @@ HRT_API int hrt_bake_mesh_points(const float *positions, uint32_t n_vertices, co
  * hrt_probe_grid_points (host only: no device, no hrt_init; fp32 in the order written) writes nx * ny * nz records, probe (i, j, k)
  * at index (k*ny + j)*nx + i, per axis at lo + ((i + .5f)/nx) * (hi - lo); lo > hi on an axis runs it backwards.  It refuses
  * (HRT_ERR_INVALID, by name) NULL pointers, a zero count, nx*ny*nz > 2^31 - 1 and a lo, hi or time that is not finite.
- * OUT OF SCOPE (DESIGN.md section 5 "Light probes"): higher SH orders, stratified or low-discrepancy directions, an irradiance
- * evaluator, probes that move, visibility or depth moments per probe, the streaming kernel, multi-GPU (a caller splits the probes;
- * the keys keep every probe's random numbers). */
+ * OUT OF SCOPE (DESIGN.md section 5 "Light probes"): higher SH orders, stratified or low-discrepancy directions, probes that move,
+ * visibility or depth moments per probe, the streaming kernel, multi-GPU (a caller splits the probes; the keys keep every probe's
+ * random numbers).  The irradiance evaluator is "Probe volumes" below. */
 #define HRT_PROBE_FLOATS 4
 #define HRT_PROBE_COEFFS 9
 #ifndef HRT_PROBE_BLOCK
@@ -982,6 +982,77 @@ HRT_API int hrt_probes_device(hrt_scene *scene, const float *d_probes, const uin
 HRT_API int hrt_probes(hrt_scene *scene, const float *probes, const uint32_t *keys, uint32_t n, uint32_t spp, uint64_t seed, uint32_t flags,
                        float *out, hrt_stats *stats /* may be NULL */);
 HRT_API int hrt_probe_grid_points(const float *lo, const float *hi, uint32_t nx, uint32_t ny, uint32_t nz, float time, float *out_probes);
+
+/* ---- Probe volumes: a regular grid of the SH9 probes above that lives on the device, evaluated at caller-supplied SURFACE POINTS
+ * (lightmap texels, mesh vertices, the first hits of a frame) in one launch: each point is interpolated between the eight probes
+ * round it and gives the irradiance -- or the radiance -- in the direction of its normal, in the units of hrt_bake.
+ * GRID: that of hrt_probe_grid_points.  Probe (i, j, k) is at index (k*ny + j)*nx + i, per axis at lo + ((i + .5f)/n) * (hi - lo);
+ * lo > hi on an axis runs it backwards.  hrt_probe_volume_create computes per axis, on the host in fp32, e = hi - lo and
+ * s = (float)n / e (s is not used on an axis with n == 1) and refuses (HRT_ERR_INVALID, by name) NULL pointers, a zero count,
+ * nx*ny*nz > HRT_PROBE_VOLUME_MAX, a lo or hi that is not finite, e == 0 on an axis with n > 1, and an s that is not finite.
+ * COEFFICIENTS: nx*ny*nz * 27 floats, the layout hrt_probes* writes (d_out[27 i + 3 k + c]), taken unscaled.  An update repacks
+ * them (hrt_probe_pack_kernel) into records of HRT_PROBE_RECORD_FLOATS floats -- the 27 followed by 5 zeros, 128 bytes on a
+ * 128-byte boundary -- so that each corner of a look-up is one aligned line; the caller's buffer is free when the launch has run
+ * (hrt_probe_volume_update_device, asynchronous on `stream`) or on return (hrt_probe_volume_update, host buffer, blocking).
+ * POINTS: the bake's records, n * HRT_RAY_FLOATS floats {P.x, P.y, P.z, time, N.x, N.y, N.z, bias}, 16-byte aligned on the device:
+ * the output of hrt_bake_quad_points and hrt_bake_mesh_points goes in as it is.  `time` and `bias` are not read.  A point is
+ * DEGENERATE when a float of P or N is not finite, when N == 0, or when Nn = normalize(N) has a component that is not finite (a
+ * normal whose squared length underflows); it gives three zeros.
+ * THE RULE (tests/probe_volume_ref.py states it again in NumPy).  All arithmetic is fp32 without fused multiply-add, in the order
+ * written; it uses only + - * /, sqrtf, floorf, fminf and fmaxf (of which a NaN operand is dropped); normalize is the trace path's
+ * own (divide by the length):
+ *   1. per axis with n > 1: g = fminf(fmaxf((P - lo) * s - .5f, 0.f), (float)(n - 1)), i0 = (uint32_t)floorf(g), f = g - (float)i0,
+ *      i1 = min(i0 + 1, n - 1); with n == 1: i0 = i1 = 0, f = 0.f.  Points outside the box clamp to the outermost probes.
+ *   2. corner m = 0..7: bit 0 of m chooses x, bit 1 y, bit 2 z; the per-axis weight is 1.f - f for the 0 side and f for the 1
+ *      side; w_m = (wx * wy) * wz.
+ *   3. with HRT_PROBE_EVAL_FACING (the back-face term of dynamic diffuse global illumination, Majercik et al. 2019): C_m the
+ *      corner's centre by the grid formula, v = C_m - P, l = sqrtf((v.x*v.x + v.y*v.y) + v.z*v.z),
+ *      c = l > 0.f ? ((v.x*Nn.x + v.y*Nn.y) + v.z*Nn.z) / l : 0.f, t = (c + 1.f) * .5f, w_m = w_m * (t * t + .2f); then
+ *      W = ((((((w_0 + w_1) + w_2) + w_3) + w_4) + w_5) + w_6) + w_7 and w_m = w_m / W.  W > 0: every factor is at least .2 and
+ *      some trilinear weight is positive.  (A P so far away that l overflows gives NaN.)
+ *   4. for each of the 27 slots j = 3k + ch: a_j = 0.f, then for m ascending a_j = a_j + w_m * p_m[j], p_m the corner's
+ *      coefficients.
+ *   5. Y_k: the basis of "Light probes", the same constants and expressions, at (x, y, z) = Nn.
+ *   6. out[ch] = 0.f, then for k ascending out[ch] = out[ch] + (F_k * a_{3k+ch}) * Y_k, with F per band:
+ *        irradiance (default):            12.566371f (4 pi) for k = 0, 8.3775804f (8 pi / 3) for k = 1..3, 3.1415927f (pi) for k = 4..8;
+ *        with HRT_PROBE_EVAL_RADIANCE:    12.566371f for every k.
+ * The result does not depend on how the device maps points to lanes.
+ * UNITS: the default output is the irradiance divided by pi in hrt_trace_radiance's units (radiance / 6) -- exactly what hrt_bake
+ * returns for the same record; a constant environment of value L gives L.  Derivation: a probe holds the means
+ * c_k = (1 / 4 pi) x the integral of Y_k L over the sphere, so the SH coefficients of L are L_k = 4 pi c_k; convolving with the
+ * clamped cosine scales band 0 by pi, band 1 by 2 pi / 3 and band 2 by pi / 4 (Ramamoorthi and Hanrahan 2001); dividing by pi
+ * gives F = 4 pi, 8 pi / 3, pi.  With HRT_PROBE_EVAL_RADIANCE the output is the SH reconstruction of the radiance arriving from
+ * direction Nn, in the same units.
+ * hrt_probe_eval_device: 3 floats per point at d_out[3i .. 3i+2], asynchronous on `stream`.  hrt_probe_eval: the same from and into
+ * HOST buffers (4-byte aligned), blocking; stats as hrt_bake (kernel_ms from events, samples = n; n == 0 zeroes them).
+ * hrt_probe_volume_weights (host only: no device, no hrt_init): steps 1-3 for ONE point record -- the eight probe indices and the
+ * final weights, by the code the kernel runs (csrc/hrt_probe_volume_cell.h); both zeroed, and HRT_OK, for a degenerate point.  It
+ * refuses what create refuses, unknown flags, and NULL point, index or weight.
+ * Checked in this order, HRT_ERR_INVALID with hrt_last_error() naming the entry point and the culprit: flags (every bit beyond the
+ * two refused by name); (n == 0 returns HRT_OK here and launches nothing;) the volume NULL; a volume never updated ("has no
+ * coefficients yet"); the points NULL or misaligned (16 bytes on the device, 4 on the host); n > 2^31 - 1; the output NULL or not
+ * 4-byte aligned.  The updates: the volume NULL, the coefficients NULL or not 4-byte aligned.  The library state comes after these,
+ * as for hrt_denoise: HRT_ERR_STATE before hrt_init -- which create needs too, since it allocates.
+ * CONCURRENCY AND LIFETIME: an evaluation only reads the volume, so evaluations may overlap each other and any launch of any scene.
+ * An update must not overlap an evaluation of the same volume; on one stream they are ordered.  The volume needs no scene: it
+ * belongs to the device that was current at create (one hrt_init has prepared), every call on it makes that device current, and
+ * its buffer is counted by hrt_debug_live_resources until hrt_probe_volume_destroy, which waits for the launches that read it.
+ * OUT OF SCOPE (DESIGN.md section 5 "Probe volumes"): visibility or depth moments per probe (Chebyshev leak tests), probes that
+ * move, higher SH orders, a probe-lit frame mode of the renderer, multi-GPU. */
+typedef struct hrt_probe_volume hrt_probe_volume;
+#define HRT_PROBE_VOLUME_MAX (1u << 24)   /* probes: the packed copy stays at or below 2 GiB */
+#define HRT_PROBE_RECORD_FLOATS 32        /* packed record: 27 coefficients + 5 zeros, 128 bytes, 128-byte aligned */
+#define HRT_PROBE_EVAL_RADIANCE 1u        /* SH radiance in direction N instead of cosine-convolved */
+#define HRT_PROBE_EVAL_FACING 2u          /* weight probes by how far they face the surface */
+HRT_API int hrt_probe_volume_create(const float *lo, const float *hi, uint32_t nx, uint32_t ny, uint32_t nz, hrt_probe_volume **out);
+HRT_API int hrt_probe_volume_update_device(hrt_probe_volume *volume, const float *d_coeffs, void *stream);
+HRT_API int hrt_probe_volume_update(hrt_probe_volume *volume, const float *coeffs);
+HRT_API void hrt_probe_volume_destroy(hrt_probe_volume *volume);
+HRT_API int hrt_probe_eval_device(const hrt_probe_volume *volume, const float *d_points, uint32_t n, uint32_t flags, float *d_out, void *stream);
+HRT_API int hrt_probe_eval(const hrt_probe_volume *volume, const float *points, uint32_t n, uint32_t flags, float *out,
+                           hrt_stats *stats /* may be NULL */);
+HRT_API int hrt_probe_volume_weights(const float *lo, const float *hi, uint32_t nx, uint32_t ny, uint32_t nz, const float *point, uint32_t flags,
+                                     uint32_t index[8], float weight[8]);
 
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
