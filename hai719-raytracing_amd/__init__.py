@@ -180,6 +180,11 @@ PROBE_RECORD_FLOATS = 32      # HRT_PROBE_RECORD_FLOATS: a probe's packed record
 PROBE_VOLUME_MAX = 1 << 24    # HRT_PROBE_VOLUME_MAX: probes per volume
 PROBE_EVAL_RADIANCE = 1       # HRT_PROBE_EVAL_RADIANCE: SH radiance in direction N instead of the cosine-convolved irradiance / pi
 PROBE_EVAL_FACING = 2         # HRT_PROBE_EVAL_FACING: weight probes by how far they face the surface
+PROBE_DEPTH_RES = 8                 # HRT_PROBE_DEPTH_RES: a probe's octahedral depth map is RES x RES texels
+PROBE_DEPTH_TEXELS = 64             # HRT_PROBE_DEPTH_TEXELS
+PROBE_DEPTH_FLOATS = 192            # HRT_PROBE_DEPTH_FLOATS: the sums {W, A, B} per texel
+PROBE_DEPTH_MAX_BLOCKS = 1 << 20    # HRT_PROBE_DEPTH_MAX_BLOCKS: (probe, block of 64 samples) pairs per depth launch
+PROBE_DEPTH_VOLUME_MAX = 1 << 22    # HRT_PROBE_DEPTH_VOLUME_MAX: probes of a volume with depth
 
 
 class DenoiseParams(C.Structure):
@@ -370,6 +375,16 @@ def device_lib() -> C.CDLL:
         lib.hrt_probe_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
         lib.hrt_probe_volume_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
                                                  C.c_void_p]
+        lib.hrt_probe_depth_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_float,
+                                               C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.hrt_probe_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_float, C.c_uint32, C.c_void_p,
+                                        C.POINTER(Stats)]
+        lib.hrt_probe_volume_update_depth_device.argtypes = lib.hrt_probe_volume_update_device.argtypes
+        lib.hrt_probe_volume_update_depth.argtypes = lib.hrt_probe_volume_update.argtypes
+        lib.hrt_probe_eval_visible_device.argtypes = lib.hrt_probe_eval_device.argtypes
+        lib.hrt_probe_eval_visible.argtypes = lib.hrt_probe_eval.argtypes
+        lib.hrt_probe_depth_texel.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        lib.hrt_probe_depth_direction.argtypes = [C.c_uint32, C.c_void_p]
         lib.hrt_debug_pick_kernel.argtypes = [C.POINTER(PickInput), C.c_char_p, C.c_size_t]
         lib.hrt_debug_last_kernel.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         lib.hrt_debug_live_resources.argtypes = [C.POINTER(C.c_uint64 * 4)]
@@ -759,13 +774,13 @@ class DeviceScene:
                                            out, accumulate, flags, None)
 
     def _radiance_batch(self, who: str, noun: str, device_fn: str, blocking_fn: Optional[str], batch, spp, first_sample, seed, keys, out, accumulate, flags, stats,
-                        rows=None, cell: tuple = (3,)):
+                        rows=None, cell: tuple = (3,), extra: tuple = ()):
         """What trace_radiance, bake and probes share: ``batch`` ((n, RAY_FLOATS) float32, the ``noun`` of the messages -- or what
         ``rows(who, noun, batch)`` accepts in place of ``_ray_batch``), ``keys`` and ``out`` ((n,) + ``cell``)
         checked as torch tensors on one GPU or as NumPy -- before ``self`` is touched -- then the entry point ``device_fn``
         (hrt_trace_radiance's signature) on the current torch stream; a NumPy batch is uploaded, and its result copied back.
         ``blocking_fn`` (hrt_bake's signature), if given, takes a NumPy batch of samples [0, spp) without ``out`` instead, and fills
-        ``stats``."""
+        ``stats``.  ``extra``: the arguments an entry point takes between the seed and the flags (hrt_probe_depth*: r_max)."""
         import torch
         is_torch = isinstance(batch, torch.Tensor)
         batch = (rows or _ray_batch)(who, noun, batch)
@@ -789,7 +804,7 @@ class DeviceScene:
                 raise ValueError(f"{who}: out must be {shown} float32 (got {o.shape} {o.dtype})")
         if blocking_fn is not None and not is_torch and out is None and not accumulate and first_sample == 0:
             r = np.empty(shape, dtype=np.float32)
-            self._check(getattr(self._lib, blocking_fn)(self._h, batch.ctypes.data, None if keys is None else keys.ctypes.data, n, spp, seed, flags,
+            self._check(getattr(self._lib, blocking_fn)(self._h, batch.ctypes.data, None if keys is None else keys.ctypes.data, n, spp, seed, *extra, flags,
                                                         r.ctypes.data, _ref(stats)))
             return r
         if is_torch:
@@ -800,7 +815,7 @@ class DeviceScene:
             d_out = None if out is None else torch.from_numpy(np.ascontiguousarray(o)).to(d_batch.device)
         if d_out is None:
             d_out = torch.zeros(shape, dtype=torch.float32, device=d_batch.device)
-        self._check(getattr(self._lib, device_fn)(self._h, _ptr(d_batch), _ptr(d_keys), n, first_sample, spp, seed, flags, _ptr(d_out),
+        self._check(getattr(self._lib, device_fn)(self._h, _ptr(d_batch), _ptr(d_keys), n, first_sample, spp, seed, *extra, flags, _ptr(d_out),
                                                   _stream(d_batch.device)))
         if is_torch:
             return d_out
@@ -842,6 +857,21 @@ class DeviceScene:
         flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
         return DeviceScene._radiance_batch(self, "probes", "points", "hrt_probes_device", "hrt_probes", points, spp, first_sample, seed, keys, out,
                                            accumulate, flags, stats, rows=_probe_batch, cell=(PROBE_COEFFS, 3))
+
+    def probe_depth(self, points, spp: int = 1, first_sample: int = 0, seed: int = 1, keys=None, r_max: float = 1.0, out=None,
+                    accumulate: bool = False, flags: int = 0, stats: Optional[Stats] = None):
+        """hrt_probe_depth*: per probe, (n, PROBE_FLOATS) float32 rows {P, time}, an 8 x 8 octahedral map of filtered depth sums
+        over the directions ``probes`` uses for the same seed, keys and samples: the distance to the closest hit, at most ``r_max``
+        (a miss gives ``r_max``), weighted per texel by the 32nd power of the cosine to the texel's centre direction.
+
+        Returns (n, PROBE_DEPTH_TEXELS, 3) float32 {W, A, B}: the sums of the weights, of weight x depth and of weight x depth^2 --
+        sums, not means, so that calls over further samples add up with ``accumulate`` (``out`` then holds the sums of the earlier
+        samples and is updated in place).  ``ProbeVolume.update_depth`` takes them.  The sum has a fixed order (include/hrt.h
+        "Probe visibility").  Torch and NumPy batches, ``out`` and ``stats`` as ``probes``.  Depth calls of one scene must not
+        overlap each other.  ``flags``: FLAG_EXACT_ONLY, FLAG_MESH_BRUTE, FLAG_NO_LDS_TREE."""
+        flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
+        return DeviceScene._radiance_batch(self, "probe_depth", "points", "hrt_probe_depth_device", "hrt_probe_depth", points, spp, first_sample, seed,
+                                           keys, out, accumulate, flags, stats, rows=_probe_batch, cell=(PROBE_DEPTH_TEXELS, 3), extra=(float(r_max),))
 
     def render_views(self, cams, w: int, h: int, spp: int, seeds=None, flags: int = 0, out=None, stats: Optional[Stats] = None):
         """hrt_render_views: every camera of ``cams`` as a w x h frame of ``spp`` samples, in one launch -> (n, h, w, 3) float32;
@@ -1029,6 +1059,35 @@ class ProbeVolume:
             _call("hrt_probe_volume_update", self._h, coeffs.ctypes.data)
         return self
 
+    def update_depth(self, sums):
+        """hrt_probe_volume_update_depth*: the depth sums of every probe, (count, PROBE_DEPTH_TEXELS, 3) float32 as
+        ``DeviceScene.probe_depth`` returns them for ``probe_grid`` of the same box and counts; the volume keeps the two moments
+        per texel that ``eval_visible`` reads.  Torch and NumPy as ``update``."""
+        import torch
+        who = "ProbeVolume.update_depth"
+        is_torch = isinstance(sums, torch.Tensor)
+        if is_torch:
+            _check_tensor(who, "a torch tensor", sums, (None, PROBE_DEPTH_TEXELS, 3), shown=f"(n, {PROBE_DEPTH_TEXELS}, 3)")
+        else:
+            sums = np.ascontiguousarray(sums, dtype=np.float32)
+            if sums.ndim != 3 or sums.shape[1:] != (PROBE_DEPTH_TEXELS, 3):
+                raise ValueError(f"{who}: sums must have shape (n, {PROBE_DEPTH_TEXELS}, 3) (got {sums.shape})")
+        if sums.shape[0] != self.count:
+            raise ValueError(f"{who}: the volume has {self.count} probes (got sums of {sums.shape[0]})")
+        if is_torch:
+            with torch.cuda.device(sums.device):
+                _call("hrt_probe_volume_update_depth_device", self._h, _ptr(sums), _stream(sums.device))
+        else:
+            _call("hrt_probe_volume_update_depth", self._h, sums.ctypes.data)
+        return self
+
+    def eval_visible(self, points, radiance: bool = False, facing: bool = False, out=None, stats: Optional[Stats] = None):
+        """hrt_probe_eval_visible*: ``eval`` with every one of the eight probes also weighted by whether it can see the point --
+        a Chebyshev test of the distance from the probe to P + bias x N against the two depth moments of the probe's texel in that
+        direction (``update_depth``) -- so that a probe behind a wall gives at most a thousandth of its weight.  The rows' bias is
+        read here; a bias that is not finite makes the point degenerate.  Arguments, result and streams as ``eval``."""
+        return ProbeVolume._lookup(self, "ProbeVolume.eval_visible", "hrt_probe_eval_visible", points, radiance, facing, out, stats)
+
     def eval(self, points, radiance: bool = False, facing: bool = False, out=None, stats: Optional[Stats] = None):
         """hrt_probe_eval*: the volume at surface points, (n, RAY_FLOATS) float32 rows {P, time, N, bias} as ``quad_points`` and
         ``mesh_points`` write them (time and bias are not read): trilinear interpolation between the eight probes round P -- with
@@ -1039,8 +1098,12 @@ class ProbeVolume:
         torch stream of its device and gives a torch tensor there (``out``, if given, a device tensor), without synchronising
         (hrt_probe_eval_device).  Anything else is taken as NumPy and goes through the blocking hrt_probe_eval, which fills
         ``stats`` if given."""
+        return ProbeVolume._lookup(self, "ProbeVolume.eval", "hrt_probe_eval", points, radiance, facing, out, stats)
+
+    def _lookup(self, who: str, entry: str, points, radiance, facing, out, stats):
+        """What eval and eval_visible share: the arguments checked before ``self`` is touched, then ``entry`` + "_device" on the
+        current torch stream or the blocking ``entry``."""
         import torch
-        who = "ProbeVolume.eval"
         is_torch = isinstance(points, torch.Tensor)
         points = _ray_batch(who, "points", points)
         n = _row_count(who, "points", points)
@@ -1051,13 +1114,13 @@ class ProbeVolume:
             else:
                 _check_tensor(who, "out", out, (n, 3), "float32", points.device, "points", "(n, 3)")
             with torch.cuda.device(points.device):
-                _call("hrt_probe_eval_device", self._h, _ptr(points), n, flags, _ptr(out), _stream(points.device))
+                _call(entry + "_device", self._h, _ptr(points), n, flags, _ptr(out), _stream(points.device))
             return out
         if out is None:
             out = np.empty((n, 3), dtype=np.float32)
         elif not (isinstance(out, np.ndarray) and out.shape == (n, 3) and out.dtype == np.float32 and out.flags.c_contiguous):
             raise ValueError(f"{who}: out must be a contiguous (n, 3) float32 array (got {getattr(out, 'shape', None)} {getattr(out, 'dtype', None)})")
-        _call("hrt_probe_eval", self._h, points.ctypes.data, n, flags, out.ctypes.data, _ref(stats))
+        _call(entry, self._h, points.ctypes.data, n, flags, out.ctypes.data, _ref(stats))
         return out
 
     def close(self):
@@ -1235,6 +1298,24 @@ def probe_volume_weights(lo, hi, nx: int, ny: int, nz: int, point, facing: bool 
     _call("hrt_probe_volume_weights", lo3.ctypes.data, hi3.ctypes.data, nx, ny, nz, p.ctypes.data, PROBE_EVAL_FACING if facing else 0,
           index.ctypes.data, weight.ctypes.data)
     return index, weight
+
+
+def probe_depth_texel(v) -> int:
+    """hrt_probe_depth_texel: the texel e = 8 j + i of a probe's octahedral depth map that the vector ``v`` (3 floats, any length
+    but 0) points through, by the code the kernels run.  Needs neither ``init`` nor a GPU."""
+    v3 = np.ascontiguousarray(v, dtype=np.float32)
+    if v3.shape != (3,):
+        raise ValueError(f"probe_depth_texel: v must have 3 components (got {v3.shape})")
+    e = C.c_uint32()
+    _call("hrt_probe_depth_texel", v3.ctypes.data, C.byref(e))
+    return e.value
+
+
+def probe_depth_direction(texel: int) -> np.ndarray:
+    """hrt_probe_depth_direction: the unit centre direction of ``texel`` (below PROBE_DEPTH_TEXELS), (3,) float32."""
+    out = np.empty(3, dtype=np.float32)
+    _call("hrt_probe_depth_direction", int(texel), out.ctypes.data)
+    return out
 
 
 class _SceneDescHead(C.Structure):

@@ -9,7 +9,7 @@
 #include "hrt_pack.h"  // hrt_scene_desc -> host arrays (pack_scene): everything of scene creation that needs no device
 #include "hrt_bake_points.h"  // the host-only bake point generators (hrt_bake_quad_points, hrt_bake_mesh_points)
 #include "hrt_probe_points.h"  // the host-only probe grid generator (hrt_probe_grid_points)
-#include "hrt_probe_volume_cell.h"  // the cell and the weights of a probe volume, for the host and the device
+#include "hrt_probe_volume_cell.h"  // the cell and the weights of a probe volume, for the host and the device (with hrt_probe_depth_oct.h, the octahedral depth map)
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types and prototypes only: librccl.so is opened with dlopen by hrt_multi_create (hrt_multi.hip)
@@ -431,6 +431,9 @@ struct hrt_scene {
     // Light probes (hrt_probes.hip): the block values of the launch in hand, allocated by the first probe call.  Nothing of the
     // trace launches.
     Scratch pr_blocks;
+    // Probe depth (hrt_probe_depth.hip): the block values of the launch in hand, allocated by the first depth call.  Nothing of
+    // the trace launches.
+    Scratch pd_blocks;
 };
 
 namespace {
@@ -1127,6 +1130,7 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 #include "hrt_lens.hip"
 #include "hrt_bake.hip"
 #include "hrt_probes.hip"
+#include "hrt_probe_depth.hip"
 #include "hrt_probe_volume.hip"
 #include "hrt_lens_adaptive.hip"
 #include "hrt_views.hip"

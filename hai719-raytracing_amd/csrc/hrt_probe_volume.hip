@@ -30,6 +30,8 @@ struct hrt_probe_volume {
     int device = -1;      // the device that was current at hrt_probe_volume_create
     bool loaded = false;  // an update has been enqueued
     Scratch packed;       // count records of HRT_PROBE_RECORD_FLOATS floats
+    bool has_depth = false;  // a depth update has been enqueued
+    Scratch depth;        // count x HRT_PROBE_DEPTH_TEXELS moment pairs {m1, m2} ("Probe visibility"), allocated by the first depth update
 };
 
 extern "C++" {
@@ -164,6 +166,67 @@ extern "C" __global__ void __launch_bounds__(HRT_PV_WG) hrt_probe_eval_kernel(co
 #define HRT_PV_POINTS_PER_WG HRT_PV_WG
 #endif
 
+// ---- Probe visibility (include/hrt.h): the moments of a volume's depth maps and the look-up that weighs every corner by them.
+
+// One lane per texel: the sums {W, A, B} to the moments {A / W, B / W}; a texel nobody looked through hides nothing.
+extern "C" __global__ void __launch_bounds__(HRT_PV_WG) hrt_probe_depth_pack_kernel(const float *__restrict__ sums, uint32_t n_texels,
+                                                                                     float2 *__restrict__ moments) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;  // n_texels <= 2^28
+    if (i >= n_texels) return;
+    const float W = sums[3u * (size_t)i], A = sums[3u * (size_t)i + 1u], B = sums[3u * (size_t)i + 2u];
+    moments[i] = W > 0.f ? make_float2(A / W, B / W) : make_float2(__builtin_inff(), 0.f);
+}
+
+// hrt_probe_eval_kernel's eight lanes to a point, with step 3 of the visible look-up: lane q, which owns corner q of steps 2 and 3,
+// additionally works out v, l and the texel of its corner, loads that texel's 8 bytes and scales its weight; the division by W
+// is then unconditional.  The one mapping of this kernel: both builds of the library compile it.
+#define HRT_PVV_POINTS_PER_WG (HRT_PV_WG / HRT_PV_PIECES)
+extern "C" __global__ void __launch_bounds__(HRT_PV_WG) hrt_probe_eval_visible_kernel(const probevol::Grid g, const float4 *__restrict__ packed,
+                                                                                       const float2 *__restrict__ moments,
+                                                                                       const float4 *__restrict__ points, uint32_t n, uint32_t flags,
+                                                                                       float *__restrict__ out) {
+    const uint32_t group = blockIdx.x * HRT_PVV_POINTS_PER_WG + threadIdx.x / HRT_PV_PIECES, q = threadIdx.x % HRT_PV_PIECES;
+    const uint32_t i = min(group, n - 1u);  // n >= 1
+    const float4 r0 = points[2u * (size_t)i], r1 = points[2u * (size_t)i + 1u];
+    const float P[3] = {r0.x, r0.y, r0.z}, N[3] = {r1.x, r1.y, r1.z};
+    float Nn[3], Pb[3];
+    bool ok = probevol::normal(P, N, Nn);
+    ok = probevol::biased(P, Nn, r1.w, Pb) && ok;
+    probevol::Axes ax;
+    probevol::axes(g, P, ax);  // whatever P holds, every coordinate is inside the grid
+    uint32_t my_index, my_texel;
+    float my_w = probevol::corner(g, ax, P, Nn, flags, q, my_index);
+    {
+        const float l = probevol::toward(g, ax, Pb, q, my_texel);  // a texel below HRT_PROBE_DEPTH_TEXELS whatever Pb holds
+        const float2 mm = moments[(size_t)my_index * HRT_PROBE_DEPTH_TEXELS + my_texel];
+        my_w = my_w * probedepth::visibility(l, mm.x, mm.y);
+        float w[8];
+#pragma unroll
+        for (uint32_t m = 0; m < 8u; ++m) w[m] = __shfl(my_w, (int)m, (int)HRT_PV_PIECES);
+        my_w = my_w / probevol::total(w);
+    }
+    if (!ok) my_w = 0.f;  // a degenerate point: its result is 0 below, whatever is loaded
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    float4 p[8];
+#pragma unroll
+    for (uint32_t m = 0; m < 8u; ++m) p[m] = packed[(size_t)__shfl(my_index, (int)m, (int)HRT_PV_PIECES) * HRT_PV_PIECES + q];  // an index < nx * ny * nz
+#pragma unroll
+    for (uint32_t m = 0; m < 8u; ++m) pv_fold_corner(a, __shfl(my_w, (int)m, (int)HRT_PV_PIECES), p[m]);
+    const uint32_t ch = min(q, 2u);
+    float mine[HRT_PROBE_COEFFS];
+#pragma unroll
+    for (uint32_t k = 0; k < HRT_PROBE_COEFFS; ++k) {
+        const uint32_t j = 3u * k + ch, from = j >> 2, c = j & 3u;
+        const float t0 = __shfl(a[0], (int)from, (int)HRT_PV_PIECES), t1 = __shfl(a[1], (int)from, (int)HRT_PV_PIECES);
+        const float t2 = __shfl(a[2], (int)from, (int)HRT_PV_PIECES), t3 = __shfl(a[3], (int)from, (int)HRT_PV_PIECES);
+        mine[k] = c == 0u ? t0 : c == 1u ? t1 : c == 2u ? t2 : t3;
+    }
+    if (group >= n || q >= 3u) return;
+    float Y[HRT_PROBE_COEFFS];
+    pv_basis(Nn[0], Nn[1], Nn[2], Y);
+    out[3u * (size_t)i + q] = ok ? pv_channel(mine, Y, (flags & HRT_PROBE_EVAL_RADIANCE) != 0u) : 0.f;
+}
+
 // The flags of an evaluation: the two of the header; every other bit is refused, by name where the library has one for it.
 static int pv_flags_check(const std::string &who, uint32_t flags) {
     const struct { uint32_t bit; const char *name; } named[] = {
@@ -180,11 +243,13 @@ static int pv_flags_check(const std::string &who, uint32_t flags) {
 }
 
 // Checks 3..7 of the header's order.  `dev`: device pointers (d_ names, 16-byte records).
-static int pv_eval_check(const std::string &who, const hrt_probe_volume *v, const float *points, uint32_t n, const float *out, bool dev) {
+static int pv_eval_check(const std::string &who, const hrt_probe_volume *v, const float *points, uint32_t n, const float *out, bool dev,
+                         bool needs_depth = false) {
     const std::string pn = dev ? "d_points" : "points", on = dev ? "d_out" : "out";
     const uintptr_t align = dev ? 16u : 4u;
     if (!v) return fail(HRT_ERR_INVALID, who + ": volume is NULL");
     if (!v->loaded) return fail(HRT_ERR_INVALID, who + ": the volume has no coefficients yet (hrt_probe_volume_update)");
+    if (needs_depth && !v->has_depth) return fail(HRT_ERR_INVALID, who + ": the volume has no depth moments yet (hrt_probe_volume_update_depth)");
     if (!points) return fail(HRT_ERR_INVALID, who + ": " + pn + " is NULL");
     if ((uintptr_t)points % align) return fail(HRT_ERR_INVALID, who + ": " + pn + " is not " + std::to_string(align) + "-byte aligned");
     if (n > 0x7fffffffu) return fail(HRT_ERR_INVALID, who + ": n must be at most 2^31 - 1 (got " + std::to_string(n) + ")");
@@ -306,4 +371,74 @@ int hrt_probe_volume_weights(const float *lo, const float *hi, uint32_t nx, uint
     float Nn[3];
     (void)probevol::cell(g, point, point + 4, flags, index, weight, Nn);  // a degenerate point: both zeroed
     return HRT_OK;
+}
+
+// ---- Probe visibility: the depth updates and the visible look-up.
+
+static int pv_depth_check(const std::string &who, const hrt_probe_volume *v, const float *sums, const char *name) {
+    if (!v) return fail(HRT_ERR_INVALID, who + ": volume is NULL");
+    if (!sums) return fail(HRT_ERR_INVALID, who + ": " + name + " is NULL");
+    if ((uintptr_t)sums % sizeof(float)) return fail(HRT_ERR_INVALID, who + ": " + name + " is not 4-byte aligned");
+    if (v->count > HRT_PROBE_DEPTH_VOLUME_MAX)
+        return fail(HRT_ERR_INVALID, who + ": depth needs a volume of at most HRT_PROBE_DEPTH_VOLUME_MAX = " + std::to_string(HRT_PROBE_DEPTH_VOLUME_MAX) +
+                                         " probes (this one has " + std::to_string(v->count) + ")");
+    return pv_enter(who, v);
+}
+
+static int pv_depth_pack(hrt_probe_volume *v, const float *d_sums, hipStream_t stream) {
+    const uint32_t texels = v->count * HRT_PROBE_DEPTH_TEXELS;  // <= 2^28
+    if (const int rc = v->depth.grow((size_t)texels * sizeof(float2))) return rc;
+    hipLaunchKernelGGL(hrt_probe_depth_pack_kernel, dim3((texels + HRT_PV_WG - 1u) / HRT_PV_WG), dim3(HRT_PV_WG), 0, stream, d_sums, texels, v->depth.as<float2>());
+    HIP_TRY(hipGetLastError());
+    v->has_depth = true;
+    return HRT_OK;
+}
+
+int hrt_probe_volume_update_depth_device(hrt_probe_volume *v, const float *d_sums, void *stream) {
+    if (const int rc = pv_depth_check("hrt_probe_volume_update_depth_device", v, d_sums, "d_sums")) return rc;
+    return pv_depth_pack(v, d_sums, (hipStream_t)stream);
+}
+
+int hrt_probe_volume_update_depth(hrt_probe_volume *v, const float *sums) {
+    if (const int rc = pv_depth_check("hrt_probe_volume_update_depth", v, sums, "sums")) return rc;
+    Scratch d_sums;
+    if (const int rc = d_sums.from_host(sums, (size_t)v->count * HRT_PROBE_DEPTH_FLOATS * sizeof(float))) return rc;
+    if (const int rc = pv_depth_pack(v, d_sums.as<float>(), nullptr)) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));  // before the staging copy goes
+    return HRT_OK;
+}
+
+static int pv_launch_visible(const hrt_probe_volume *v, const float *d_points, uint32_t n, uint32_t flags, float *d_out, hipStream_t stream) {
+    const uint32_t grid = (uint32_t)(((uint64_t)n + HRT_PVV_POINTS_PER_WG - 1u) / HRT_PVV_POINTS_PER_WG);
+    hipLaunchKernelGGL(hrt_probe_eval_visible_kernel, dim3(grid), dim3(HRT_PV_WG), 0, stream, v->grid, v->packed.as<float4>(), v->depth.as<float2>(),
+                       (const float4 *)d_points, n, flags, d_out);
+    HIP_TRY(hipGetLastError());
+    return HRT_OK;
+}
+
+int hrt_probe_eval_visible_device(const hrt_probe_volume *v, const float *d_points, uint32_t n, uint32_t flags, float *d_out, void *stream) {
+    const std::string who = "hrt_probe_eval_visible_device";
+    int rc = pv_flags_check(who, flags);
+    if (rc != HRT_OK || n == 0u) return rc;
+    if ((rc = pv_eval_check(who, v, d_points, n, d_out, true, true)) != HRT_OK) return rc;
+    if ((rc = pv_enter(who, v)) != HRT_OK) return rc;
+    return pv_launch_visible(v, d_points, n, flags, d_out, (hipStream_t)stream);
+}
+
+// Blocking, from and into host memory, as hrt_probe_eval.
+int hrt_probe_eval_visible(const hrt_probe_volume *v, const float *points, uint32_t n, uint32_t flags, float *out, hrt_stats *stats) {
+    const std::string who = "hrt_probe_eval_visible";
+    int rc = pv_flags_check(who, flags);
+    if (rc != HRT_OK) return rc;
+    if (n == 0u) {
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        return HRT_OK;
+    }
+    if ((rc = pv_eval_check(who, v, points, n, out, false, true)) != HRT_OK) return rc;
+    if ((rc = pv_enter(who, v)) != HRT_OK) return rc;
+    BlockingCall call;
+    Scratch d_points;
+    if ((rc = d_points.from_host(points, (size_t)n * HRT_RAY_FLOATS * sizeof(float))) != HRT_OK) return rc;
+    return call.run(nullptr, (size_t)n * 3u * sizeof(float), out, (uint64_t)n, stats,
+                    [&](float *d_out) { return pv_launch_visible(v, d_points.as<float>(), n, flags, d_out, nullptr); });
 }

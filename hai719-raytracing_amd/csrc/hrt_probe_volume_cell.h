@@ -8,6 +8,7 @@
 #pragma once
 
 #include "../../include/hrt.h"
+#include "hrt_probe_depth_oct.h"
 
 #include <cmath>
 #include <cstdint>
@@ -145,6 +146,60 @@ HRT_PV_HD bool cell(const Grid &g, const float P[3], const float N[3], uint32_t 
         const float W = total(weight);
         for (int m = 0; m < 8; ++m) weight[m] = weight[m] / W;
     }
+    return true;
+}
+
+// ---- The visible look-up (include/hrt.h "Probe visibility"): step 3 with the visibility factor.  The pieces again, so that the
+// device may hand the corners to different lanes, and cell_visible() that composes them for the host.
+
+// Pb = P + b * Nn.  false when b is not finite: the point is degenerate.
+HRT_PV_HD bool biased(const float P[3], const float Nn[3], float b, float Pb[3]) {
+#pragma clang fp contract(off)
+    for (int a = 0; a < 3; ++a) Pb[a] = P[a] + b * Nn[a];
+    return finite(b);
+}
+
+// Step 3 (b) up to the load, for corner m: l = |Pb - C_m| and, where l > 0, the texel of the corner's depth map that looks at Pb
+// (0 otherwise: it is not read).
+HRT_PV_HD float toward(const Grid &g, const Axes &ax, const float Pb[3], uint32_t m, uint32_t &texel) {
+#pragma clang fp contract(off)
+    const uint32_t c[3] = {(m & 1u) ? ax.i1[0] : ax.i0[0], (m & 2u) ? ax.i1[1] : ax.i0[1], (m & 4u) ? ax.i1[2] : ax.i0[2]};
+    float v[3];
+    for (int a = 0; a < 3; ++a) {
+        const float centre = g.lo[a] + (((float)c[a] + .5f) / (float)g.n[a]) * (g.hi[a] - g.lo[a]);
+        v[a] = Pb[a] - centre;
+    }
+    const float l = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    texel = l > 0.f ? probedepth::texel(v) : 0u;
+    return l;
+}
+
+// Steps 1-3 of the visible look-up for the record {P, N, b}; `moments` holds HRT_PROBE_DEPTH_TEXELS pairs {m1, m2} per probe.
+// false for a degenerate point, as cell().
+HRT_PV_HD bool cell_visible(const Grid &g, const float P[3], const float N[3], float b, uint32_t flags, const float *moments, uint32_t index[8],
+                            float weight[8], float Nn[3]) {
+#pragma clang fp contract(off)
+    for (int m = 0; m < 8; ++m) {
+        index[m] = 0u;
+        weight[m] = 0.f;
+    }
+    float Pb[3];
+    if (!normal(P, N, Nn)) return false;
+    if (!biased(P, Nn, b, Pb)) {
+        Nn[0] = Nn[1] = Nn[2] = 0.f;
+        return false;
+    }
+    Axes ax;
+    axes(g, P, ax);
+    for (uint32_t m = 0; m < 8u; ++m) {
+        weight[m] = corner(g, ax, P, Nn, flags, m, index[m]);
+        uint32_t texel;
+        const float l = toward(g, ax, Pb, m, texel);
+        const float *mm = moments + 2u * ((size_t)index[m] * HRT_PROBE_DEPTH_TEXELS + texel);
+        weight[m] = weight[m] * probedepth::visibility(l, mm[0], mm[1]);
+    }
+    const float W = total(weight);
+    for (int m = 0; m < 8; ++m) weight[m] = weight[m] / W;
     return true;
 }
 

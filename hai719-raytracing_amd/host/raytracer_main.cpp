@@ -44,6 +44,10 @@
 //                                                  loaded into a probe volume and evaluated at the --w x --h texel centres of
 //                                                  quad INDEX (hrt_bake_quad_points, bias 0; --probe-facing weights the probes
 //                                                  by how far they face the surface); written as --bake-quad writes its own
+//             [--probe-visible [--probe-rmax R]]   with --probe-quad: the depth of the same grid is traced too (hrt_probe_depth,
+//                                                  the same seed and samples, depths cut at R; default 1.5 x the diagonal of a
+//                                                  grid cell) and the lightmap is that of the look-up with visibility
+//                                                  (hrt_probe_eval_visible): probes behind a wall are weighted out
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -83,6 +87,8 @@ static bool probe_grid_given = false, probe_box_given = false;  // --probe-grid 
 static uint32_t probe_n[3] = {0u, 0u, 0u};
 static float probe_box[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 static bool probe_quad_given = false, probe_side_given = false, probe_facing = false;  // --probe-quad: hrt_probe_eval over the texels of that quad
+static bool probe_visible = false, probe_rmax_given = false;  // --probe-visible: hrt_probe_depth + hrt_probe_eval_visible
+static float probe_rmax = 0.f;
 static long probe_quad = -1;
 static int32_t probe_side = 1;
 static hrt_temporal_params temporal_params = {0.02f, 64.f, 0.05f, 0.1f, 0.05f};  // the Python TemporalParams()
@@ -263,7 +269,21 @@ static int light_probes(const hrt_scene_desc &desc) {
         hrt_probe_volume *volume = nullptr;
         rc = hrt_probe_volume_create(probe_box, probe_box + 3, probe_n[0], probe_n[1], probe_n[2], &volume);
         if (rc == HRT_OK) rc = hrt_probe_volume_update(volume, sh.data());
-        if (rc == HRT_OK) rc = hrt_probe_eval(volume, points.data(), w * h, probe_facing ? HRT_PROBE_EVAL_FACING : 0u, map.data(), &st);
+        if (rc == HRT_OK && probe_visible) {
+            float r_max = probe_rmax;
+            if (!probe_rmax_given) {  // 1.5 x the diagonal of a grid cell, in fp32
+                float e[3];
+                for (int a = 0; a < 3; ++a) e[a] = (probe_box[3 + a] - probe_box[a]) / (float)probe_n[a];
+                r_max = 1.5f * std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+            }
+            std::cout << "Tracing the depth of the probes (r_max " << r_max << ")" << std::endl;
+            std::vector<float> sums(n * HRT_PROBE_DEPTH_FLOATS, 0.f);
+            rc = hrt_probe_depth(device_scene, probes.data(), nullptr, (uint32_t)n, nsamples, seed, r_max, 0u, sums.data(), &st);
+            if (rc == HRT_OK) rc = hrt_probe_volume_update_depth(volume, sums.data());
+            if (rc == HRT_OK) rc = hrt_probe_eval_visible(volume, points.data(), w * h, probe_facing ? HRT_PROBE_EVAL_FACING : 0u, map.data(), &st);
+        } else if (rc == HRT_OK) {
+            rc = hrt_probe_eval(volume, points.data(), w * h, probe_facing ? HRT_PROBE_EVAL_FACING : 0u, map.data(), &st);
+        }
         hrt_probe_volume_destroy(volume);
         if (rc != HRT_OK) {
             std::cout << "the probe volume failed: " << hrt_last_error() << std::endl;
@@ -338,8 +358,8 @@ int main(int argc, char **argv) {
     std::vector<int> devices;
     for (int i = 1; i < argc; i += 2) {
         const std::string k = argv[i];
-        if (k == "--probe-facing") {  // the one option without a value
-            probe_facing = true;
+        if (k == "--probe-facing" || k == "--probe-visible") {  // the options without a value
+            (k == "--probe-facing" ? probe_facing : probe_visible) = true;
             --i;
             continue;
         }
@@ -399,6 +419,7 @@ int main(int argc, char **argv) {
             probe_box_given = true;
         }
         else if (k == "--probe-quad") { probe_quad = strtol(v.c_str(), nullptr, 10); probe_quad_given = true; }
+        else if (k == "--probe-rmax") { probe_rmax = (float)atof(v.c_str()); probe_rmax_given = true; }
         else if (k == "--probe-side") { probe_side = (int32_t)strtol(v.c_str(), nullptr, 10); probe_side_given = true; }
         else if (k == "--gpus") { devices.clear(); for (int d = 0; d < atoi(v.c_str()); ++d) devices.push_back(d); }
         else if (k == "--devices") {
@@ -471,6 +492,18 @@ int main(int argc, char **argv) {
     }
     if (!probe_quad_given && (probe_side_given || probe_facing)) {
         std::cerr << (probe_side_given ? "--probe-side" : "--probe-facing") << " describes the look-up of a probe grid over a quad: give --probe-quad INDEX" << std::endl;
+        return 2;
+    }
+    if (!probe_quad_given && (probe_visible || probe_rmax_given)) {
+        std::cerr << (probe_visible ? "--probe-visible" : "--probe-rmax") << " describes the look-up of a probe grid over a quad: give --probe-quad INDEX" << std::endl;
+        return 2;
+    }
+    if (probe_rmax_given && !probe_visible) {
+        std::cerr << "--probe-rmax cuts the depths of --probe-visible: give --probe-visible" << std::endl;
+        return 2;
+    }
+    if (probe_rmax_given && !(std::isfinite(probe_rmax) && probe_rmax > 0.f)) {
+        std::cerr << "--probe-rmax takes a finite positive distance (got " << probe_rmax << ")" << std::endl;
         return 2;
     }
     if (probe_side != 1 && probe_side != -1) {

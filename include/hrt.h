@@ -968,8 +968,8 @@ HRT_API int hrt_bake_mesh_points(const float *positions, uint32_t n_vertices, co
  * at index (k*ny + j)*nx + i, per axis at lo + ((i + .5f)/nx) * (hi - lo); lo > hi on an axis runs it backwards.  It refuses
  * (HRT_ERR_INVALID, by name) NULL pointers, a zero count, nx*ny*nz > 2^31 - 1 and a lo, hi or time that is not finite.
  * OUT OF SCOPE (DESIGN.md section 5 "Light probes"): higher SH orders, stratified or low-discrepancy directions, probes that move,
- * visibility or depth moments per probe, the streaming kernel, multi-GPU (a caller splits the probes; the keys keep every probe's
- * random numbers).  The irradiance evaluator is "Probe volumes" below. */
+ * the streaming kernel, multi-GPU (a caller splits the probes; the keys keep every probe's random numbers).  The irradiance
+ * evaluator is "Probe volumes" below; depth moments per probe are "Probe visibility". */
 #define HRT_PROBE_FLOATS 4
 #define HRT_PROBE_COEFFS 9
 #ifndef HRT_PROBE_BLOCK
@@ -1037,8 +1037,8 @@ HRT_API int hrt_probe_grid_points(const float *lo, const float *hi, uint32_t nx,
  * An update must not overlap an evaluation of the same volume; on one stream they are ordered.  The volume needs no scene: it
  * belongs to the device that was current at create (one hrt_init has prepared), every call on it makes that device current, and
  * its buffer is counted by hrt_debug_live_resources until hrt_probe_volume_destroy, which waits for the launches that read it.
- * OUT OF SCOPE (DESIGN.md section 5 "Probe volumes"): visibility or depth moments per probe (Chebyshev leak tests), probes that
- * move, higher SH orders, a probe-lit frame mode of the renderer, multi-GPU. */
+ * OUT OF SCOPE (DESIGN.md section 5 "Probe volumes"): probes that move, higher SH orders, a probe-lit frame mode of the renderer,
+ * multi-GPU.  Visibility (Chebyshev leak tests on depth moments per probe) is "Probe visibility" below. */
 typedef struct hrt_probe_volume hrt_probe_volume;
 #define HRT_PROBE_VOLUME_MAX (1u << 24)   /* probes: the packed copy stays at or below 2 GiB */
 #define HRT_PROBE_RECORD_FLOATS 32        /* packed record: 27 coefficients + 5 zeros, 128 bytes, 128-byte aligned */
@@ -1053,6 +1053,84 @@ HRT_API int hrt_probe_eval(const hrt_probe_volume *volume, const float *points, 
                            hrt_stats *stats /* may be NULL */);
 HRT_API int hrt_probe_volume_weights(const float *lo, const float *hi, uint32_t nx, uint32_t ny, uint32_t nz, const float *point, uint32_t flags,
                                      uint32_t index[8], float weight[8]);
+
+/* ---- Probe visibility: depth moments per probe and a look-up that does not leak through walls.  A plain look-up interpolates
+ * between the eight probes round a point whether or not they can see it; here every probe also gets a small map of the mean
+ * distance and the mean squared distance to the scene per direction, and the look-up turns the two moments into a Chebyshev
+ * visibility weight per corner (the variance shadow-map test of dynamic diffuse global illumination, Majercik et al. 2019).
+ * THE RULE (tests/probe_depth_ref.py states it again in NumPy).  All arithmetic is fp32 without fused multiply-add, in the order
+ * written; it uses only + - * /, sqrtf, floorf, fabsf, fminf and fmaxf; sg(v) = v >= 0.f ? 1.f : -1.f.
+ * DEPTH MAP: HRT_PROBE_DEPTH_RES x HRT_PROBE_DEPTH_RES = HRT_PROBE_DEPTH_TEXELS texels per probe in octahedral parametrisation,
+ * texel e = 8 j + i.
+ *   Centre direction c_e: px = ((float)i + .5f) * .25f - 1.f, py likewise from j; z = (1.f - fabsf(px)) - fabsf(py); if z < 0.f:
+ *     (px, py) = ((1.f - fabsf(py)) * sg(px), (1.f - fabsf(px)) * sg(py)), computed from the old pair; c_e = normalize((px, py, z)),
+ *     the trace path's own normalize (divide by the length).
+ *   Texel of a vector v != 0, which need not be unit: s = (fabsf(v.x) + fabsf(v.y)) + fabsf(v.z); px = v.x / s, py = v.y / s; if
+ *     v.z < 0.f the same fold; i = (uint32_t)fminf(fmaxf(floorf((px * .5f + .5f) * 8.f), 0.f), 7.f), j likewise from py.
+ *   Both are csrc/hrt_probe_depth_oct.h, shared by the kernels, the host and a sanitized stand-alone program; hrt_probe_depth_texel
+ *   and hrt_probe_depth_direction (host only: no device, no hrt_init) expose them and refuse NULL pointers and a texel >=
+ *   HRT_PROBE_DEPTH_TEXELS.
+ * DEPTH SAMPLE: sample s of probe i uses the direction d of "Light probes" -- probe_dir(seed, key, s), unchanged, so the depth map
+ * sees the directions the SH coefficients saw.  r(s) = fminf(t, r_max), t being what hrt_trace_rays(HRT_QUERY_CLOSEST) returns
+ * for the record hrt_probe_rays writes for that sample under the same trace flags (its per-ray margin and far-origin rule
+ * included); a miss gives r_max; a degenerate sample adds nothing.  r_max is the caller's, finite and > 0.
+ * THE SUM.  Its order is fixed.  With j = s - first_sample, sample j belongs to block j / 64.  Block value of texel e: W = A = B =
+ * 0.f, then for the block's non-degenerate samples in ascending j:
+ *     w = fmaxf(0.f, (c_e.x*d.x + c_e.y*d.y) + c_e.z*d.z); w = w*w, five times (the 32nd power);
+ *     W = W + w; A = A + w * r; B = B + w * (r * r).
+ *   total: t = 0.f, then t = t + block_b for b ascending.
+ *   output: HRT_PROBE_DEPTH_FLOATS = 192 floats per probe, d_out[192 i + 3 e + {0, 1, 2}] = {W, A, B}: sums, not means; with
+ *   HRT_RADIANCE_ACCUMULATE d_out (on entry) + t.
+ * hrt_probe_depth_device: asynchronous on `stream`; one wave of the device works on one (probe, block) pair, a lane is one sample
+ * and then one texel; a second small launch on the same stream adds the block values.  hrt_probe_depth: the same from and into
+ * HOST buffers (4-byte aligned), blocking, samples [0, spp); stats as hrt_probes; HRT_RADIANCE_ACCUMULATE is refused there.
+ * CONTRACT A: bit-identical to the sum above over the per-sample outputs of hrt_probe_rays(s) and hrt_trace_rays(HRT_QUERY_CLOSEST)
+ * -- for every scene and flag set.
+ * Flags of a depth launch: HRT_FLAG_EXACT_ONLY, HRT_FLAG_MESH_BRUTE (with EXACT_ONLY), HRT_FLAG_NO_LDS_TREE,
+ * HRT_RADIANCE_ACCUMULATE; every other bit is refused by name.
+ * LIMIT: n * ceil(n_samples / 64) <= HRT_PROBE_DEPTH_MAX_BLOCKS: the block values stay at or below 805 MB.
+ * Checked in this order before the scene and the library state, HRT_ERR_INVALID with hrt_last_error() naming the entry point and
+ * the culprit: flags; (n == 0 returns HRT_OK here and launches nothing;) the probe records NULL or misaligned (16 bytes on the
+ * device, 4 on the host), the keys not 4-byte aligned; n > 2^31 - 1, n_samples == 0, first_sample + n_samples > 2^32, the limit;
+ * r_max not finite or not positive; the output NULL or not 4-byte aligned; then a NULL scene.
+ * CONCURRENCY: the block values are a grow-only scratch buffer of the scene's own, allocated by its first depth call and freed
+ * with the scene, so depth launches of ONE scene must not overlap each other; they may overlap anything else.
+ * MOMENTS: hrt_probe_volume_update_depth* takes the sums of the volume's nx*ny*nz probes (192 floats each) and keeps one pair per
+ * texel (hrt_probe_depth_pack_kernel): W > 0.f ? {A / W, B / W} : {+inf, 0.f} -- a texel nobody looked through hides nothing.
+ * 512 bytes per probe in a second buffer of the volume's, allocated by the first depth update, counted by
+ * hrt_debug_live_resources and freed with the volume.  Depth needs nx*ny*nz <= HRT_PROBE_DEPTH_VOLUME_MAX.  The updates refuse, in
+ * this order: the volume NULL, the sums NULL or not 4-byte aligned, a volume of more probes than that; then the library state.
+ * LOOK-UP WITH VISIBILITY (hrt_probe_eval_visible*): steps 1, 2, 4, 5 and 6 of "Probe volumes" word for word; step 3 becomes
+ *   (a) with HRT_PROBE_EVAL_FACING the facing factor exactly as there, without its normalisation;
+ *   (b) always the visibility factor, for corner m with centre C_m: Pb = P + b * Nn, b the record's `bias` float (which the plain
+ *       look-up ignores; a b that is not finite makes the point degenerate); v = Pb - C_m;
+ *       l = sqrtf((v.x*v.x + v.y*v.y) + v.z*v.z); if l > 0.f: {m1, m2} is corner m's texel of v; vis = 1.f when l <= m1, otherwise
+ *       var = fmaxf(m2 - m1*m1, 0.f), q = l - m1, c = var / (var + q*q), vis = fmaxf((c*c)*c, .001f); l == 0.f gives vis = 1.f;
+ *       w_m = w_m * vis;
+ *   (c) always W = ((((((w_0 + w_1) + w_2) + w_3) + w_4) + w_5) + w_6) + w_7 and w_m = w_m / W.  The floor of .001 keeps W > 0.
+ * Flags: HRT_PROBE_EVAL_RADIANCE and HRT_PROBE_EVAL_FACING; every other bit is refused by name.  Checked in the order of
+ * hrt_probe_eval: flags; (n == 0 returns HRT_OK;) the volume NULL; a volume without coefficients ("has no coefficients yet"); a
+ * volume without depth ("has no depth moments yet"); the points; n; the output; then the library state.  An evaluation only reads
+ * the volume; a depth update must not overlap an evaluation of the same volume.
+ * OUT OF SCOPE (DESIGN.md section 5 "Probe visibility"): bilinear texel look-up, DDGI's weight crush, a view-dependent bias,
+ * probes that move. */
+#define HRT_PROBE_DEPTH_RES 8u
+#define HRT_PROBE_DEPTH_TEXELS 64u               /* RES x RES */
+#define HRT_PROBE_DEPTH_FLOATS 192u              /* per probe: {W, A, B} per texel */
+#define HRT_PROBE_DEPTH_MAX_BLOCKS (1u << 20)
+#define HRT_PROBE_DEPTH_VOLUME_MAX (1u << 22)    /* probes of a volume with depth: the moments stay at or below 2 GiB */
+HRT_API int hrt_probe_depth_device(hrt_scene *scene, const float *d_probes, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
+                                   uint32_t n_samples, uint64_t seed, float r_max, uint32_t flags, float *d_out, void *stream);
+HRT_API int hrt_probe_depth(hrt_scene *scene, const float *probes, const uint32_t *keys, uint32_t n, uint32_t spp, uint64_t seed, float r_max,
+                            uint32_t flags, float *out, hrt_stats *stats /* may be NULL */);
+HRT_API int hrt_probe_volume_update_depth_device(hrt_probe_volume *volume, const float *d_sums, void *stream);
+HRT_API int hrt_probe_volume_update_depth(hrt_probe_volume *volume, const float *sums);
+HRT_API int hrt_probe_eval_visible_device(const hrt_probe_volume *volume, const float *d_points, uint32_t n, uint32_t flags, float *d_out,
+                                          void *stream);
+HRT_API int hrt_probe_eval_visible(const hrt_probe_volume *volume, const float *points, uint32_t n, uint32_t flags, float *out,
+                                   hrt_stats *stats /* may be NULL */);
+HRT_API int hrt_probe_depth_texel(const float v[3], uint32_t *texel);
+HRT_API int hrt_probe_depth_direction(uint32_t texel, float out[3]);
 
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
