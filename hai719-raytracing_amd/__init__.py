@@ -185,6 +185,7 @@ PROBE_DEPTH_TEXELS = 64             # HRT_PROBE_DEPTH_TEXELS
 PROBE_DEPTH_FLOATS = 192            # HRT_PROBE_DEPTH_FLOATS: the sums {W, A, B} per texel
 PROBE_DEPTH_MAX_BLOCKS = 1 << 20    # HRT_PROBE_DEPTH_MAX_BLOCKS: (probe, block of 64 samples) pairs per depth launch
 PROBE_DEPTH_VOLUME_MAX = 1 << 22    # HRT_PROBE_DEPTH_VOLUME_MAX: probes of a volume with depth
+LIT_VISIBLE = 4                     # HRT_LIT_VISIBLE: eval_flags of trace_lit / probes_lit: the look-up of "Probe visibility"
 
 
 class DenoiseParams(C.Structure):
@@ -385,6 +386,13 @@ def device_lib() -> C.CDLL:
         lib.hrt_probe_eval_visible.argtypes = lib.hrt_probe_eval.argtypes
         lib.hrt_probe_depth_texel.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         lib.hrt_probe_depth_direction.argtypes = [C.c_uint32, C.c_void_p]
+        lib.hrt_trace_lit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
+                                      C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]
+        lib.hrt_probes_lit_device.argtypes = lib.hrt_trace_lit.argtypes
+        lib.hrt_probes_lit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
+                                       C.c_float, C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_probe_volume_blend_device.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        lib.hrt_probe_volume_blend.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
         lib.hrt_debug_pick_kernel.argtypes = [C.POINTER(PickInput), C.c_char_p, C.c_size_t]
         lib.hrt_debug_last_kernel.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         lib.hrt_debug_live_resources.argtypes = [C.POINTER(C.c_uint64 * 4)]
@@ -774,14 +782,17 @@ class DeviceScene:
                                            out, accumulate, flags, None)
 
     def _radiance_batch(self, who: str, noun: str, device_fn: str, blocking_fn: Optional[str], batch, spp, first_sample, seed, keys, out, accumulate, flags, stats,
-                        rows=None, cell: tuple = (3,), extra: tuple = ()):
+                        rows=None, cell: tuple = (3,), extra: tuple = (), volume=None, after: tuple = ()):
         """What trace_radiance, bake and probes share: ``batch`` ((n, RAY_FLOATS) float32, the ``noun`` of the messages -- or what
         ``rows(who, noun, batch)`` accepts in place of ``_ray_batch``), ``keys`` and ``out`` ((n,) + ``cell``)
         checked as torch tensors on one GPU or as NumPy -- before ``self`` is touched -- then the entry point ``device_fn``
         (hrt_trace_radiance's signature) on the current torch stream; a NumPy batch is uploaded, and its result copied back.
         ``blocking_fn`` (hrt_bake's signature), if given, takes a NumPy batch of samples [0, spp) without ``out`` instead, and fills
-        ``stats``.  ``extra``: the arguments an entry point takes between the seed and the flags (hrt_probe_depth*: r_max)."""
+        ``stats``.  ``extra``: the arguments an entry point takes between the seed and the flags (hrt_probe_depth*: r_max).
+        ``volume`` (hrt_trace_lit, hrt_probes_lit*): the ProbeVolume whose handle follows the scene's; ``after``: the arguments
+        between the flags and the output (eval_flags, bias)."""
         import torch
+        head = (lambda: (self._h,)) if volume is None else (lambda: (self._h, volume._h))
         is_torch = isinstance(batch, torch.Tensor)
         batch = (rows or _ray_batch)(who, noun, batch)
         n = _row_count(who, noun, batch)
@@ -804,8 +815,8 @@ class DeviceScene:
                 raise ValueError(f"{who}: out must be {shown} float32 (got {o.shape} {o.dtype})")
         if blocking_fn is not None and not is_torch and out is None and not accumulate and first_sample == 0:
             r = np.empty(shape, dtype=np.float32)
-            self._check(getattr(self._lib, blocking_fn)(self._h, batch.ctypes.data, None if keys is None else keys.ctypes.data, n, spp, seed, *extra, flags,
-                                                        r.ctypes.data, _ref(stats)))
+            self._check(getattr(self._lib, blocking_fn)(*head(), batch.ctypes.data, None if keys is None else keys.ctypes.data, n, spp, seed, *extra, flags,
+                                                        *after, r.ctypes.data, _ref(stats)))
             return r
         if is_torch:
             d_batch, d_keys, d_out = batch, keys, out
@@ -815,7 +826,7 @@ class DeviceScene:
             d_out = None if out is None else torch.from_numpy(np.ascontiguousarray(o)).to(d_batch.device)
         if d_out is None:
             d_out = torch.zeros(shape, dtype=torch.float32, device=d_batch.device)
-        self._check(getattr(self._lib, device_fn)(self._h, _ptr(d_batch), _ptr(d_keys), n, first_sample, spp, seed, *extra, flags, _ptr(d_out),
+        self._check(getattr(self._lib, device_fn)(*head(), _ptr(d_batch), _ptr(d_keys), n, first_sample, spp, seed, *extra, flags, *after, _ptr(d_out),
                                                   _stream(d_batch.device)))
         if is_torch:
             return d_out
@@ -872,6 +883,32 @@ class DeviceScene:
         flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
         return DeviceScene._radiance_batch(self, "probe_depth", "points", "hrt_probe_depth_device", "hrt_probe_depth", points, spp, first_sample, seed,
                                            keys, out, accumulate, flags, stats, rows=_probe_batch, cell=(PROBE_DEPTH_TEXELS, 3), extra=(float(r_max),))
+
+    def trace_lit(self, rays, volume: "ProbeVolume", spp: int = 1, first_sample: int = 0, seed: int = 1, keys=None, eval_flags: int = 0,
+                  bias: float = 0.0, out=None, accumulate: bool = False, flags: int = 0, normalize: bool = False):
+        """hrt_trace_lit: the colour of caller rays whose paths END in ``volume`` at their first hit -- the hit shaded as
+        ``trace_radiance`` shades it (emission, direct light), everything beyond it the volume's irradiance about the hit's normal
+        times the albedo; mirror and glass get no tail (include/hrt.h "Lit rays").  Rays, samples, keys, ``out``, ``accumulate`` and
+        the torch / NumPy forms as ``trace_radiance``.  ``eval_flags``: PROBE_EVAL_FACING, LIT_VISIBLE (the look-up of
+        ``ProbeVolume.eval_visible``; needs ``update_depth``); ``bias``: that look-up's offset along the normal.  Returns (n, 3)
+        float32.  The call only reads the volume: order an ``update`` or ``blend`` after it."""
+        flags = int(flags) | (RAYS_NORMALIZE if normalize else 0) | (RADIANCE_ACCUMULATE if accumulate else 0)
+        eval_flags, bias = _lit_args("trace_lit", volume, eval_flags, bias)
+        return DeviceScene._radiance_batch(self, "trace_lit", "rays", "hrt_trace_lit", None, rays, spp, first_sample, seed, keys, out, accumulate,
+                                           flags, None, volume=volume, after=(eval_flags, bias))
+
+    def probes_lit(self, points, volume: "ProbeVolume", spp: int = 1, first_sample: int = 0, seed: int = 1, keys=None, eval_flags: int = 0,
+                   bias: float = 0.0, out=None, accumulate: bool = False, flags: int = 0, stats: Optional[Stats] = None):
+        """hrt_probes_lit*: ``probes`` with every sample a lit ray of ``trace_lit`` -- one segment, then ``volume`` -- in one fused
+        launch: the SH9 coefficients of the light arriving at the points with one more bounce than the volume holds.  Probe records,
+        samples, keys, ``out``, ``accumulate``, ``stats`` and the torch / NumPy forms as ``probes``; ``eval_flags`` and ``bias`` as
+        ``trace_lit``.  Returns (n, PROBE_COEFFS, 3) float32 for ``ProbeVolume.update`` or ``.blend``.  Lit probe calls of one scene
+        must not overlap each other.  ``flags``: FLAG_EXACT_ONLY, FLAG_MESH_BRUTE, FLAG_NO_LDS_TREE."""
+        flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
+        eval_flags, bias = _lit_args("probes_lit", volume, eval_flags, bias)
+        return DeviceScene._radiance_batch(self, "probes_lit", "points", "hrt_probes_lit_device", "hrt_probes_lit", points, spp, first_sample, seed,
+                                           keys, out, accumulate, flags, stats, rows=_probe_batch, cell=(PROBE_COEFFS, 3), volume=volume,
+                                           after=(eval_flags, bias))
 
     def render_views(self, cams, w: int, h: int, spp: int, seeds=None, flags: int = 0, out=None, stats: Optional[Stats] = None):
         """hrt_render_views: every camera of ``cams`` as a w x h frame of ``spp`` samples, in one launch -> (n, h, w, 3) float32;
@@ -1017,6 +1054,20 @@ class History:
             pass
 
 
+def _lit_args(who: str, volume, eval_flags, bias):
+    """(eval_flags, bias) of a lit call, refused as include/hrt.h "Lit rays" refuses them -- before any library is touched."""
+    if not isinstance(volume, ProbeVolume):
+        raise ValueError(f"{who}: volume must be a ProbeVolume (got {type(volume).__name__})")
+    eval_flags, bias = int(eval_flags), float(bias)
+    if eval_flags & PROBE_EVAL_RADIANCE:
+        raise ValueError(f"{who}: eval_flags: PROBE_EVAL_RADIANCE: the tail of a lit ray is the irradiance about the hit's normal")
+    if eval_flags & ~(PROBE_EVAL_FACING | LIT_VISIBLE):
+        raise ValueError(f"{who}: eval_flags: unknown bits {eval_flags & ~(PROBE_EVAL_FACING | LIT_VISIBLE)}")
+    if not np.isfinite(bias):
+        raise ValueError(f"{who}: bias must be finite (got {bias})")
+    return eval_flags, bias
+
+
 def _box(who: str, lo, hi):
     """``lo`` and ``hi`` of a probe grid as (3,) float32 arrays."""
     lo3, hi3 = (np.ascontiguousarray(v, dtype=np.float32) for v in (lo, hi))
@@ -1035,6 +1086,8 @@ class ProbeVolume:
         self._lib = device_lib()
         self.shape = (int(nx), int(ny), int(nz))
         self.count = self.shape[0] * self.shape[1] * self.shape[2]
+        self.lo, self.hi = tuple(float(x) for x in lo3), tuple(float(x) for x in hi3)
+        self.loaded = False  # an update has been enqueued (relight starts a volume without one from zeros)
         _call("hrt_probe_volume_create", lo3.ctypes.data, hi3.ctypes.data, nx, ny, nz, C.byref(self._h))
 
     def update(self, coeffs):
@@ -1057,6 +1110,7 @@ class ProbeVolume:
                 _call("hrt_probe_volume_update_device", self._h, _ptr(coeffs), _stream(coeffs.device))
         else:
             _call("hrt_probe_volume_update", self._h, coeffs.ctypes.data)
+        self.loaded = True
         return self
 
     def update_depth(self, sums):
@@ -1079,6 +1133,63 @@ class ProbeVolume:
                 _call("hrt_probe_volume_update_depth_device", self._h, _ptr(sums), _stream(sums.device))
         else:
             _call("hrt_probe_volume_update_depth", self._h, sums.ctypes.data)
+        return self
+
+    def blend(self, coeffs, keep: float):
+        """hrt_probe_volume_blend*: the hysteresis update of a volume that has coefficients: every coefficient becomes
+        keep x old + (1 - keep) x new, ``keep`` in [0, 1).  ``coeffs`` and the torch / NumPy forms as ``update``."""
+        import torch
+        who = "ProbeVolume.blend"
+        keep = float(keep)
+        if not (0.0 <= keep < 1.0):
+            raise ValueError(f"{who}: keep must be in [0, 1) (got {keep})")
+        is_torch = isinstance(coeffs, torch.Tensor)
+        if is_torch:
+            _check_tensor(who, "a torch tensor", coeffs, (None, PROBE_COEFFS, 3), shown=f"(n, {PROBE_COEFFS}, 3)")
+        else:
+            coeffs = np.ascontiguousarray(coeffs, dtype=np.float32)
+            if coeffs.ndim != 3 or coeffs.shape[1:] != (PROBE_COEFFS, 3):
+                raise ValueError(f"{who}: coeffs must have shape (n, {PROBE_COEFFS}, 3) (got {coeffs.shape})")
+        if coeffs.shape[0] != self.count:
+            raise ValueError(f"{who}: the volume has {self.count} probes (got coefficients of {coeffs.shape[0]})")
+        if is_torch:
+            with torch.cuda.device(coeffs.device):
+                _call("hrt_probe_volume_blend_device", self._h, _ptr(coeffs), keep, _stream(coeffs.device))
+        else:
+            _call("hrt_probe_volume_blend", self._h, coeffs.ctypes.data, keep)
+        return self
+
+    def relight(self, scene: "DeviceScene", spp: int, rounds: int, keep: float = 0.0, seed: int = 1, eval_flags: int = 0, bias: float = 0.0,
+                depth_rmax: Optional[float] = None, time: float = 0.0, flags: int = 0):
+        """The relighting loop: ``rounds`` times, ``scene.probes_lit`` at the volume's own grid points against the volume as it
+        stands -- round r takes samples [r x spp, (r + 1) x spp) -- then ``update`` (``blend`` when ``keep`` > 0), all on the
+        current torch stream, without synchronising.  Every round adds one bounce.  A volume that has never been updated starts from
+        zero coefficients (round 0 then gathers emission and direct light alone).  With ``depth_rmax`` the depth of ``spp`` samples
+        is traced and installed once before round 0 (for LIT_VISIBLE).  ``time`` is the probes' time; ``flags`` are the trace flags
+        of ``probes_lit``."""
+        import torch
+        who = "ProbeVolume.relight"
+        spp, rounds, keep = int(spp), int(rounds), float(keep)
+        if spp <= 0 or rounds < 0:
+            raise ValueError(f"{who}: spp must be positive and rounds non-negative (got {spp} and {rounds})")
+        if not (0.0 <= keep < 1.0):
+            raise ValueError(f"{who}: keep must be in [0, 1) (got {keep})")
+        if (rounds * spp) > 2 ** 32:
+            raise ValueError(f"{who}: rounds x spp must be at most 2^32 (got {rounds * spp})")
+        eval_flags, bias = _lit_args(who, self, eval_flags, bias)
+        if depth_rmax is not None and not (np.isfinite(depth_rmax) and depth_rmax > 0):
+            raise ValueError(f"{who}: depth_rmax must be finite and positive (got {depth_rmax})")
+        points = torch.from_numpy(probe_grid(self.lo, self.hi, *self.shape, time)).to("cuda")
+        if depth_rmax is not None:
+            self.update_depth(scene.probe_depth(points, spp, seed=seed, r_max=float(depth_rmax), flags=flags))
+        if not self.loaded:
+            self.update(torch.zeros((self.count, PROBE_COEFFS, 3), dtype=torch.float32, device=points.device))
+        for r in range(rounds):
+            c = scene.probes_lit(points, self, spp, first_sample=r * spp, seed=seed, eval_flags=eval_flags, bias=bias, flags=flags)
+            if keep > 0.0:
+                self.blend(c, keep)
+            else:
+                self.update(c)
         return self
 
     def eval_visible(self, points, radiance: bool = False, facing: bool = False, out=None, stats: Optional[Stats] = None):

@@ -434,6 +434,9 @@ struct hrt_scene {
     // Probe depth (hrt_probe_depth.hip): the block values of the launch in hand, allocated by the first depth call.  Nothing of
     // the trace launches.
     Scratch pd_blocks;
+    // Lit probes (hrt_probe_lit.hip): the block values of the launch in hand, allocated by the first hrt_probes_lit* call.  Nothing
+    // of the trace launches.
+    Scratch pl_blocks;
 };
 
 namespace {
@@ -1132,6 +1135,7 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 #include "hrt_probes.hip"
 #include "hrt_probe_depth.hip"
 #include "hrt_probe_volume.hip"
+#include "hrt_probe_lit.hip"
 #include "hrt_lens_adaptive.hip"
 #include "hrt_views.hip"
 

@@ -48,6 +48,15 @@
 //                                                  the same seed and samples, depths cut at R; default 1.5 x the diagonal of a
 //                                                  grid cell) and the lightmap is that of the look-up with visibility
 //                                                  (hrt_probe_eval_visible): probes behind a wall are weighted out
+//             [--probe-bounces K [--probe-keep H]] with --probe-quad or --probe-lit: the grid is not path-traced but RELIT: from zero
+//                                                  coefficients, K rounds of hrt_probes_lit_device against the volume as it stands
+//                                                  (round r takes samples [r x spp, (r + 1) x spp); --probe-facing and
+//                                                  --probe-visible apply to the rounds' look-ups too, the depth being traced before
+//                                                  round 0), each written back with hrt_probe_volume_update_device, or with
+//                                                  --probe-keep H in [0, 1) blended in (hrt_probe_volume_blend_device)
+//             [--probe-lit]                        with --probe-grid and --probe-box, instead of --probe-quad: a --w x --h camera
+//                                                  frame lit by the volume: per sample hrt_camera_rays, then hrt_trace_lit into
+//                                                  running sums; means and gamma by hrt_finalize_tiles, written as a render is
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -56,6 +65,8 @@
 #include <iostream>
 #include <string>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>  // --probe-bounces and --probe-lit drive the device forms: buffers of this program's own
 
 #include "../../include/hrt.h"
 #include "scene.h"
@@ -91,6 +102,9 @@ static bool probe_visible = false, probe_rmax_given = false;  // --probe-visible
 static float probe_rmax = 0.f;
 static long probe_quad = -1;
 static int32_t probe_side = 1;
+static bool probe_bounces_given = false, probe_keep_given = false, probe_lit = false;  // --probe-bounces: hrt_probes_lit_device rounds; --probe-lit: hrt_trace_lit
+static long probe_bounces = 0;
+static float probe_keep = 0.f;
 static hrt_temporal_params temporal_params = {0.02f, 64.f, 0.05f, 0.1f, 0.05f};  // the Python TemporalParams()
 
 // Drop-in for ray_trace_from_camera(): same inputs (current scene, nsamples, window size, camera),
@@ -237,7 +251,85 @@ static int bake_lightmap(const hrt_scene_desc &desc) {
     return rc;
 }
 
-// --probe-grid: the SH coefficients of a grid of light probes, as text -- or with --probe-quad the lightmap they give on a quad
+// A device buffer of this program's own, freed on every way out.
+struct DeviceBuffer {
+    void *p = nullptr;
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer &) = delete;
+    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
+    ~DeviceBuffer() { if (p) (void)hipFree(p); }
+    template <class T> T *as() const { return (T *)p; }
+    bool alloc(size_t bytes) { return hipMalloc(&p, bytes) == hipSuccess; }
+};
+
+static int device_failed(const char *what) {
+    std::cout << what << " failed: " << hipGetErrorString(hipGetLastError()) << std::endl;
+    return HRT_ERR_DEVICE;
+}
+
+// The eval_flags of the lit launches: what --probe-facing and --probe-visible say of the look-up.
+static uint32_t lit_eval_flags() { return (probe_facing ? HRT_PROBE_EVAL_FACING : 0u) | (probe_visible ? HRT_LIT_VISIBLE : 0u); }
+
+// --probe-bounces: from zero coefficients, K rounds of gather-and-write-back on the null stream; `sh` receives the last round's
+// coefficients.
+static int relight_probes(hrt_probe_volume *volume, const std::vector<float> &probes, size_t n, std::vector<float> &sh) {
+    std::cout << "Relighting the probes over " << probe_bounces << " rounds of " << nsamples << " samples per probe (keep " << probe_keep << ")" << std::endl;
+    int rc = hrt_probe_volume_update(volume, sh.data());  // zeros
+    if (rc != HRT_OK) return rc;
+    DeviceBuffer d_probes, d_sh;
+    if (!d_probes.alloc(probes.size() * sizeof(float)) || !d_sh.alloc(sh.size() * sizeof(float))) return device_failed("hipMalloc");
+    if (hipMemcpy(d_probes.p, probes.data(), probes.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return device_failed("hipMemcpy");
+    for (long r = 0; rc == HRT_OK && r < probe_bounces; ++r) {
+        rc = hrt_probes_lit_device(device_scene, volume, d_probes.as<float>(), nullptr, (uint32_t)n, (uint32_t)((uint64_t)r * nsamples), nsamples, seed, 0u,
+                                   lit_eval_flags(), 0.f, d_sh.as<float>(), nullptr);
+        if (rc == HRT_OK)
+            rc = probe_keep > 0.f ? hrt_probe_volume_blend_device(volume, d_sh.as<float>(), probe_keep, nullptr)
+                                  : hrt_probe_volume_update_device(volume, d_sh.as<float>(), nullptr);
+    }
+    if (rc != HRT_OK) return rc;
+    if (hipMemcpy(sh.data(), d_sh.p, sh.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return device_failed("hipMemcpy");
+    return HRT_OK;
+}
+
+// --probe-lit: the camera frame whose paths end in the volume, sample by sample into running sums, then the render's output stage.
+static int probe_lit_frame(hrt_probe_volume *volume) {
+    const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
+    const uint32_t npix = w * h, n_tiles = (npix + 63u) / 64u;  // the sums padded to whole tiles of 64 pixels for hrt_finalize_tiles
+    const hrt_camera cam = default_camera((float)w / (float)h);
+    std::cout << "Ray tracing a " << w << " x " << h << " image lit by the probes on the GPU using " << nsamples << " samples per pixel" << std::endl;
+    DeviceBuffer d_rays, d_sum;
+    const size_t sum_bytes = (size_t)n_tiles * 64u * 3u * sizeof(float);
+    if (!d_rays.alloc((size_t)npix * HRT_RAY_FLOATS * sizeof(float)) || !d_sum.alloc(sum_bytes)) return device_failed("hipMalloc");
+    if (hipMemset(d_sum.p, 0, sum_bytes) != hipSuccess) return device_failed("hipMemset");
+    int rc = HRT_OK;
+    for (uint32_t s = 0; rc == HRT_OK && s < nsamples; ++s) {
+        rc = hrt_camera_rays(&cam, w, h, s, seed, d_rays.as<float>(), nullptr);
+        if (rc == HRT_OK)
+            rc = hrt_trace_lit(device_scene, volume, d_rays.as<float>(), nullptr, npix, s, 1u, seed, HRT_RADIANCE_ACCUMULATE, lit_eval_flags(), 0.f,
+                               d_sum.as<float>(), nullptr);
+    }
+    if (rc == HRT_OK) rc = hrt_finalize_tiles(d_sum.as<float>(), n_tiles, nsamples, HRT_FLAG_GAMMA, d_sum.as<float>(), nullptr);
+    if (rc != HRT_OK) {
+        std::cout << "the probe-lit frame failed: " << hrt_last_error() << std::endl;
+        return rc;
+    }
+    std::vector<float> image((size_t)npix * 3u, 0.f);
+    if (hipMemcpy(image.data(), d_sum.p, image.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return device_failed("hipMemcpy");
+    rc = hrt_write_ppm(out_path.c_str(), image.data(), w, h);
+    if (rc != HRT_OK) std::cout << hrt_last_error() << std::endl;
+    return rc;
+}
+
+// The r_max of --probe-visible: --probe-rmax, or 1.5 x the diagonal of a grid cell, in fp32.
+static float probe_depth_rmax() {
+    if (probe_rmax_given) return probe_rmax;
+    float e[3];
+    for (int a = 0; a < 3; ++a) e[a] = (probe_box[3 + a] - probe_box[a]) / (float)probe_n[a];
+    return 1.5f * std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+}
+
+// --probe-grid: the SH coefficients of a grid of light probes, as text -- or with --probe-quad the lightmap they give on a quad, or
+// with --probe-lit the camera frame they light; with --probe-bounces the coefficients are relit instead of path-traced
 static int light_probes(const hrt_scene_desc &desc) {
     const size_t n = (size_t)probe_n[0] * probe_n[1] * probe_n[2];
     std::vector<float> probes(n * HRT_PROBE_FLOATS), sh(n * 3u * HRT_PROBE_COEFFS, 0.f);
@@ -246,54 +338,61 @@ static int light_probes(const hrt_scene_desc &desc) {
         std::cout << "hrt_probe_grid_points failed: " << hrt_last_error() << std::endl;
         return rc;
     }
-    std::cout << "Tracing " << probe_n[0] << " x " << probe_n[1] << " x " << probe_n[2] << " light probes on the GPU using " << nsamples
-              << " samples per probe" << std::endl;
     hrt_stats st;
-    rc = hrt_probes(device_scene, probes.data(), nullptr, (uint32_t)n, nsamples, seed, 0u, sh.data(), &st);
-    if (rc != HRT_OK) {
-        std::cout << "hrt_probes failed: " << hrt_last_error() << std::endl;
-        return rc;
+    hrt_probe_volume *volume = nullptr;
+    const bool needs_volume = probe_quad_given || probe_lit || probe_bounces_given;
+    auto leave = [&](int code, const char *what) {
+        if (code != HRT_OK && what) std::cout << what << " failed: " << hrt_last_error() << std::endl;
+        hrt_probe_volume_destroy(volume);
+        return code;
+    };
+    auto trace_depth = [&]() {  // the depth of the grid, the same seed and samples, into the volume
+        const float r_max = probe_depth_rmax();
+        std::cout << "Tracing the depth of the probes (r_max " << r_max << ")" << std::endl;
+        std::vector<float> sums(n * HRT_PROBE_DEPTH_FLOATS, 0.f);
+        int drc = hrt_probe_depth(device_scene, probes.data(), nullptr, (uint32_t)n, nsamples, seed, r_max, 0u, sums.data(), &st);
+        if (drc == HRT_OK) drc = hrt_probe_volume_update_depth(volume, sums.data());
+        return drc;
+    };
+    if (probe_bounces_given) {
+        rc = hrt_probe_volume_create(probe_box, probe_box + 3, probe_n[0], probe_n[1], probe_n[2], &volume);
+        if (rc == HRT_OK && probe_visible) rc = trace_depth();
+        if (rc == HRT_OK) rc = relight_probes(volume, probes, n, sh);
+        if (rc != HRT_OK) return leave(rc, "relighting the probe volume");
+    } else {
+        std::cout << "Tracing " << probe_n[0] << " x " << probe_n[1] << " x " << probe_n[2] << " light probes on the GPU using " << nsamples
+                  << " samples per probe" << std::endl;
+        rc = hrt_probes(device_scene, probes.data(), nullptr, (uint32_t)n, nsamples, seed, 0u, sh.data(), &st);
+        if (rc != HRT_OK) {
+            std::cout << "hrt_probes failed: " << hrt_last_error() << std::endl;
+            return rc;
+        }
+        std::cout << "  Done in " << st.total_ms / 1000.0 << " seconds (kernel " << st.kernel_ms << " ms, " << (double)st.samples / st.kernel_ms / 1e3
+                  << " Msamples/s)" << std::endl;
+        if (needs_volume) {
+            rc = hrt_probe_volume_create(probe_box, probe_box + 3, probe_n[0], probe_n[1], probe_n[2], &volume);
+            if (rc == HRT_OK) rc = hrt_probe_volume_update(volume, sh.data());
+            if (rc == HRT_OK && probe_visible) rc = trace_depth();
+            if (rc != HRT_OK) return leave(rc, "the probe volume");
+        }
     }
-    std::cout << "  Done in " << st.total_ms / 1000.0 << " seconds (kernel " << st.kernel_ms << " ms, " << (double)st.samples / st.kernel_ms / 1e3
-              << " Msamples/s)" << std::endl;
+    if (probe_lit) return leave(probe_lit_frame(volume), nullptr);
     if (probe_quad_given) {
         const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
         std::vector<float> points((size_t)w * h * HRT_RAY_FLOATS), map((size_t)w * h * 3, 0.f);
         rc = hrt_bake_quad_points(&desc.quads[probe_quad], w, h, probe_side, 0.f, 0.f, points.data());
-        if (rc != HRT_OK) {
-            std::cout << "hrt_bake_quad_points failed: " << hrt_last_error() << std::endl;
-            return rc;
-        }
+        if (rc != HRT_OK) return leave(rc, "hrt_bake_quad_points");
         std::cout << "Evaluating the probes over a " << w << " x " << h << " lightmap of quad " << probe_quad << " (side " << probe_side
                   << (probe_facing ? ", facing weights" : "") << ")" << std::endl;
-        hrt_probe_volume *volume = nullptr;
-        rc = hrt_probe_volume_create(probe_box, probe_box + 3, probe_n[0], probe_n[1], probe_n[2], &volume);
-        if (rc == HRT_OK) rc = hrt_probe_volume_update(volume, sh.data());
-        if (rc == HRT_OK && probe_visible) {
-            float r_max = probe_rmax;
-            if (!probe_rmax_given) {  // 1.5 x the diagonal of a grid cell, in fp32
-                float e[3];
-                for (int a = 0; a < 3; ++a) e[a] = (probe_box[3 + a] - probe_box[a]) / (float)probe_n[a];
-                r_max = 1.5f * std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-            }
-            std::cout << "Tracing the depth of the probes (r_max " << r_max << ")" << std::endl;
-            std::vector<float> sums(n * HRT_PROBE_DEPTH_FLOATS, 0.f);
-            rc = hrt_probe_depth(device_scene, probes.data(), nullptr, (uint32_t)n, nsamples, seed, r_max, 0u, sums.data(), &st);
-            if (rc == HRT_OK) rc = hrt_probe_volume_update_depth(volume, sums.data());
-            if (rc == HRT_OK) rc = hrt_probe_eval_visible(volume, points.data(), w * h, probe_facing ? HRT_PROBE_EVAL_FACING : 0u, map.data(), &st);
-        } else if (rc == HRT_OK) {
-            rc = hrt_probe_eval(volume, points.data(), w * h, probe_facing ? HRT_PROBE_EVAL_FACING : 0u, map.data(), &st);
-        }
-        hrt_probe_volume_destroy(volume);
-        if (rc != HRT_OK) {
-            std::cout << "the probe volume failed: " << hrt_last_error() << std::endl;
-            return rc;
-        }
+        rc = probe_visible ? hrt_probe_eval_visible(volume, points.data(), w * h, probe_facing ? HRT_PROBE_EVAL_FACING : 0u, map.data(), &st)
+                           : hrt_probe_eval(volume, points.data(), w * h, probe_facing ? HRT_PROBE_EVAL_FACING : 0u, map.data(), &st);
+        if (rc != HRT_OK) return leave(rc, "the probe volume");
         std::cout << "  Done (kernel " << st.kernel_ms << " ms)" << std::endl;
         rc = hrt_write_ppm(out_path.c_str(), map.data(), w, h);
         if (rc != HRT_OK) std::cout << hrt_last_error() << std::endl;
-        return rc;
+        return leave(rc, nullptr);
     }
+    hrt_probe_volume_destroy(volume);
     FILE *f = std::fopen(out_path.c_str(), "w");
     if (!f) {
         std::cout << "cannot write " << out_path << std::endl;
@@ -358,8 +457,8 @@ int main(int argc, char **argv) {
     std::vector<int> devices;
     for (int i = 1; i < argc; i += 2) {
         const std::string k = argv[i];
-        if (k == "--probe-facing" || k == "--probe-visible") {  // the options without a value
-            (k == "--probe-facing" ? probe_facing : probe_visible) = true;
+        if (k == "--probe-facing" || k == "--probe-visible" || k == "--probe-lit") {  // the options without a value
+            (k == "--probe-facing" ? probe_facing : k == "--probe-visible" ? probe_visible : probe_lit) = true;
             --i;
             continue;
         }
@@ -419,6 +518,24 @@ int main(int argc, char **argv) {
             probe_box_given = true;
         }
         else if (k == "--probe-quad") { probe_quad = strtol(v.c_str(), nullptr, 10); probe_quad_given = true; }
+        else if (k == "--probe-bounces") {
+            char *end = nullptr;
+            probe_bounces = strtol(v.c_str(), &end, 10);
+            if (end == v.c_str() || *end != '\0' || probe_bounces <= 0 || probe_bounces > 1000000) {
+                std::cerr << "--probe-bounces takes a positive number of rounds (got " << v << ")" << std::endl;
+                return 2;
+            }
+            probe_bounces_given = true;
+        }
+        else if (k == "--probe-keep") {
+            char *end = nullptr;
+            probe_keep = std::strtof(v.c_str(), &end);
+            if (end == v.c_str() || *end != '\0' || !(probe_keep >= 0.f && probe_keep < 1.f)) {
+                std::cerr << "--probe-keep takes a fraction in [0, 1) (got " << v << ")" << std::endl;
+                return 2;
+            }
+            probe_keep_given = true;
+        }
         else if (k == "--probe-rmax") { probe_rmax = (float)atof(v.c_str()); probe_rmax_given = true; }
         else if (k == "--probe-side") { probe_side = (int32_t)strtol(v.c_str(), nullptr, 10); probe_side_given = true; }
         else if (k == "--gpus") { devices.clear(); for (int d = 0; d < atoi(v.c_str()); ++d) devices.push_back(d); }
@@ -490,11 +607,31 @@ int main(int argc, char **argv) {
         std::cerr << "--probe-quad looks a probe grid up over a quad: give --probe-grid NX,NY,NZ and --probe-box x0,y0,z0,x1,y1,z1" << std::endl;
         return 2;
     }
-    if (!probe_quad_given && (probe_side_given || probe_facing)) {
+    if (probe_lit && !probe_grid_given) {
+        std::cerr << "--probe-lit lights a camera frame from a probe grid: give --probe-grid NX,NY,NZ and --probe-box x0,y0,z0,x1,y1,z1" << std::endl;
+        return 2;
+    }
+    if (probe_lit && probe_quad_given) {
+        std::cerr << "--probe-lit writes a camera frame, --probe-quad a lightmap: give one of them" << std::endl;
+        return 2;
+    }
+    if (probe_keep_given && !probe_bounces_given) {
+        std::cerr << "--probe-keep blends the rounds of --probe-bounces: give --probe-bounces K" << std::endl;
+        return 2;
+    }
+    if (probe_bounces_given && !probe_quad_given && !probe_lit) {
+        std::cerr << "--probe-bounces relights the probe grid of a lightmap or a frame: give --probe-quad INDEX or --probe-lit" << std::endl;
+        return 2;
+    }
+    if (probe_bounces_given && (uint64_t)probe_bounces * nsamples > 0x100000000ull) {
+        std::cerr << "--probe-bounces x --spp must be at most 2^32 (sample indices do not wrap)" << std::endl;
+        return 2;
+    }
+    if (!probe_quad_given && (probe_side_given || (probe_facing && !probe_lit))) {
         std::cerr << (probe_side_given ? "--probe-side" : "--probe-facing") << " describes the look-up of a probe grid over a quad: give --probe-quad INDEX" << std::endl;
         return 2;
     }
-    if (!probe_quad_given && (probe_visible || probe_rmax_given)) {
+    if (!probe_quad_given && !probe_lit && (probe_visible || probe_rmax_given)) {
         std::cerr << (probe_visible ? "--probe-visible" : "--probe-rmax") << " describes the look-up of a probe grid over a quad: give --probe-quad INDEX" << std::endl;
         return 2;
     }

@@ -1037,8 +1037,9 @@ HRT_API int hrt_probe_grid_points(const float *lo, const float *hi, uint32_t nx,
  * An update must not overlap an evaluation of the same volume; on one stream they are ordered.  The volume needs no scene: it
  * belongs to the device that was current at create (one hrt_init has prepared), every call on it makes that device current, and
  * its buffer is counted by hrt_debug_live_resources until hrt_probe_volume_destroy, which waits for the launches that read it.
- * OUT OF SCOPE (DESIGN.md section 5 "Probe volumes"): probes that move, higher SH orders, a probe-lit frame mode of the renderer,
- * multi-GPU.  Visibility (Chebyshev leak tests on depth moments per probe) is "Probe visibility" below. */
+ * OUT OF SCOPE (DESIGN.md section 5 "Probe volumes"): probes that move, higher SH orders, multi-GPU.  Visibility (Chebyshev leak
+ * tests on depth moments per probe) is "Probe visibility" below; the probe-lit frame and a volume that relights itself are "Lit
+ * rays". */
 typedef struct hrt_probe_volume hrt_probe_volume;
 #define HRT_PROBE_VOLUME_MAX (1u << 24)   /* probes: the packed copy stays at or below 2 GiB */
 #define HRT_PROBE_RECORD_FLOATS 32        /* packed record: 27 coefficients + 5 zeros, 128 bytes, 128-byte aligned */
@@ -1131,6 +1132,72 @@ HRT_API int hrt_probe_eval_visible(const hrt_probe_volume *volume, const float *
                                    hrt_stats *stats /* may be NULL */);
 HRT_API int hrt_probe_depth_texel(const float v[3], uint32_t *texel);
 HRT_API int hrt_probe_depth_direction(uint32_t texel, float out[3]);
+
+/* ---- Lit rays: the radiance of a ray whose path ENDS in a probe volume at its first hit -- one closest hit, the hit shaded as the
+ * integrator shades it, and everything beyond the hit taken from the volume as it stands.  It has two shapes: a ray query
+ * (hrt_trace_lit: the probe-lit frame, noise-free at one sample but for the direct light), and a fused probe update
+ * (hrt_probes_lit*), whose output goes back into the volume: each round of trace, look up, write back adds one bounce (the update of
+ * dynamic diffuse global illumination, Majercik et al. 2019).
+ * THE RULE (tests/probe_lit_ref.py states it again in NumPy).  All arithmetic is fp32 without fused multiply-add, in the order
+ * written.  For a ray {o, time, d, tmax} (tmax is not read, as in hrt_trace_radiance), key k and sample s:
+ *   1. RNG: stream (seed, k, s) with the draw index set to 3 -- the state of a path of hrt_trace_radiance at its first segment.  The
+ *      filter margin and the far-origin rule are those of that first segment (DESIGN.md section 5 "Ray queries").  A ray is
+ *      DEGENERATE exactly when hrt_trace_radiance calls it so (HRT_RAYS_NORMALIZE included); it adds nothing: 0 in mean mode, its
+ *      sums left as they are under HRT_RADIANCE_ACCUMULATE.
+ *   2. h = the closest hit of the ray, meshes included.
+ *   3. a miss: rad = 0 + 1 * sky(d, 6), as the integrator writes it; value = rad / 6.f per channel -- the bits of a one-sample
+ *      hrt_trace_radiance of a ray that misses.
+ *   4. a hit: sf = the shaded surface; direct = the direct light at sf with the sample's stream (scenes with lights; 0 otherwise);
+ *      rad = 0 + 1 * (direct + sf.emission); thr = 1 * sf.albedo -- the integrator's own expressions and device functions.
+ *   5. the tail: for a diffuse surface G = the look-up of the point record {sf.p, time, sf.n, bias} -- sf.p = o + t * d, sf.n the
+ *      shaded normal (NOT flipped towards the ray: the normal the integrator would scatter about) -- by THE RULE of "Probe volumes",
+ *      steps 1-6 in irradiance form, or with HRT_LIT_VISIBLE by that of "Probe visibility"; HRT_PROBE_EVAL_FACING is passed through.
+ *      A degenerate point record gives G = 0.  For mirror and glass G = 0: the chain is not followed.
+ *      value = (rad / 6.f) + thr * G per channel.
+ *   6. samples in ascending order: sum = 0.f (or d_out on entry, under HRT_RADIANCE_ACCUMULATE), sum = sum + value; the output is
+ *      sum / (float)n_samples, or the running sum.
+ * hrt_trace_lit: n ray records (device, HRT_RAY_FLOATS floats each, 16-byte aligned), 3 floats per ray at d_out[3i .. 3i+2]; ray i
+ * has the key d_keys ? d_keys[i] : i.  One lane of the device per ray.  `flags` are hrt_trace_radiance's: HRT_FLAG_EXACT_ONLY,
+ * HRT_FLAG_MESH_BRUTE (with EXACT_ONLY), HRT_FLAG_NO_LDS_TREE, HRT_RAYS_NORMALIZE, HRT_RADIANCE_ACCUMULATE.  `eval_flags`:
+ * HRT_PROBE_EVAL_FACING and HRT_LIT_VISIBLE; HRT_PROBE_EVAL_RADIANCE is refused by name.  Asynchronous on `stream`; touches no
+ * per-launch state of the scene.  Where no ray can continue past its first hit (a one-sided emitter under a dark sky) and the
+ * volume holds zeros, the output is hrt_trace_radiance's bit for bit.
+ * hrt_probes_lit_device: the same for the samples of probes -- records {P, time} as "Light probes", sample s of a probe the ray
+ * {P, time, d(s), +inf} of hrt_probe_rays -- summed by the sum of "Light probes" with v(s) = 0.f + value(s): n x 27 coefficients in
+ * the layout of hrt_probes*, the same blocks, lanes, halving and second launch.  One wave of the device works on one (probe, block)
+ * pair; a sample is one segment, so the kernel has a body of its own without the integrator's stages.  `flags` are a probe launch's.
+ * CONTRACT A: bit-identical to that sum over the per-sample outputs of hrt_probe_rays(s) and hrt_trace_lit(first_sample = s,
+ * n_samples = 1, the same d_keys, eval_flags and bias) -- for every scene, volume and flag set.
+ * hrt_probes_lit: the same from and into HOST buffers (4-byte aligned), blocking, samples [0, spp); stats as hrt_probes;
+ * HRT_RADIANCE_ACCUMULATE is refused there.  LIMIT: that of hrt_probes*.
+ * hrt_probe_volume_blend_device / hrt_probe_volume_blend: the hysteresis update on the packed records of a volume that has been
+ * updated before: for each of the 27 coefficients p = (keep * p) + ((1.f - keep) * c); the five padding floats of a record stay 0.
+ * keep = 0 gives hrt_probe_volume_update's bits for finite p.  They refuse, in this order: the volume NULL, the coefficients NULL or
+ * not 4-byte aligned, a keep outside [0, 1) (NaN included), a volume never updated; then the library state.
+ * Checked in this order, HRT_ERR_INVALID with hrt_last_error() naming the entry point and the culprit: flags; eval_flags
+ * (HRT_PROBE_EVAL_RADIANCE by name, then unknown bits); the volume NULL; a volume never updated ("has no coefficients yet");
+ * HRT_LIT_VISIBLE on a volume without depth ("has no depth moments yet"); a bias that is not finite; (n == 0 returns HRT_OK here and
+ * launches nothing;) the rays or probe records NULL or misaligned, the keys not 4-byte aligned; for hrt_trace_lit the output NULL or
+ * misaligned, then n > 2^31 - 1, n_samples == 0 and first_sample + n_samples > 2^32; for hrt_probes_lit* n, n_samples, first_sample,
+ * the limit and the output in the order of hrt_probes*; then a NULL scene, a volume that lives on another device than the scene,
+ * and the library state.
+ * CONCURRENCY: a call only READS the volume, so lit launches may overlap look-ups of the same volume; an update or a blend of the
+ * volume must be ordered after the lit launches that read it by the caller (on one stream they are).  The block values of
+ * hrt_probes_lit* are a grow-only scratch buffer of the scene's own, allocated by its first such call and freed with the scene, so
+ * lit probe launches of ONE scene must not overlap each other; they may overlap anything else.
+ * OUT OF SCOPE (DESIGN.md section 5 "Lit rays and probe relighting"): following mirror and glass to the first diffuse hit, more than
+ * one segment before the tail, a cooperative (eight lanes to a hit) look-up inside the kernels, probes that move, multi-GPU. */
+#define HRT_LIT_VISIBLE 4u                /* eval_flags of a lit launch: the look-up of "Probe visibility" */
+HRT_API int hrt_trace_lit(hrt_scene *scene, const hrt_probe_volume *volume, const float *d_rays, const uint32_t *d_keys, uint32_t n,
+                          uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias,
+                          float *d_out, void *stream);
+HRT_API int hrt_probes_lit_device(hrt_scene *scene, const hrt_probe_volume *volume, const float *d_probes, const uint32_t *d_keys, uint32_t n,
+                                  uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias,
+                                  float *d_out, void *stream);
+HRT_API int hrt_probes_lit(hrt_scene *scene, const hrt_probe_volume *volume, const float *probes, const uint32_t *keys, uint32_t n, uint32_t spp,
+                           uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, float *out, hrt_stats *stats /* may be NULL */);
+HRT_API int hrt_probe_volume_blend_device(hrt_probe_volume *volume, const float *d_coeffs, float keep, void *stream);
+HRT_API int hrt_probe_volume_blend(hrt_probe_volume *volume, const float *coeffs, float keep);
 
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
