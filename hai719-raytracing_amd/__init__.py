@@ -186,6 +186,11 @@ PROBE_DEPTH_FLOATS = 192            # HRT_PROBE_DEPTH_FLOATS: the sums {W, A, B}
 PROBE_DEPTH_MAX_BLOCKS = 1 << 20    # HRT_PROBE_DEPTH_MAX_BLOCKS: (probe, block of 64 samples) pairs per depth launch
 PROBE_DEPTH_VOLUME_MAX = 1 << 22    # HRT_PROBE_DEPTH_VOLUME_MAX: probes of a volume with depth
 LIT_VISIBLE = 4                     # HRT_LIT_VISIBLE: eval_flags of trace_lit / probes_lit: the look-up of "Probe visibility"
+# Lit paths (include/hrt.h "Lit paths").  A tail record is TAIL_FLOATS float32: {p, time, n, bias}, thr, the word, rad / 6, 0.
+TAIL_FLOATS = 16                    # HRT_TAIL_FLOATS
+TAIL_WORD = 11                      # the column of the uint32 word: bits 0..7 the segments traced, TAIL_REACHED
+TAIL_REACHED = 0x80000000           # HRT_TAIL_REACHED
+MAXBOUNCES = 6                      # HRT_MAXBOUNCES: the largest tail_after
 
 
 class DenoiseParams(C.Structure):
@@ -391,6 +396,13 @@ def device_lib() -> C.CDLL:
         lib.hrt_probes_lit_device.argtypes = lib.hrt_trace_lit.argtypes
         lib.hrt_probes_lit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
                                        C.c_float, C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_trace_lit_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
+                                            C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.hrt_probes_lit_paths_device.argtypes = lib.hrt_trace_lit_paths.argtypes
+        lib.hrt_probes_lit_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
+                                             C.c_float, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_path_tails.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_float, C.c_uint32,
+                                       C.c_void_p, C.c_void_p]
         lib.hrt_probe_volume_blend_device.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         lib.hrt_probe_volume_blend.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
         lib.hrt_debug_pick_kernel.argtypes = [C.POINTER(PickInput), C.c_char_p, C.c_size_t]
@@ -885,30 +897,78 @@ class DeviceScene:
                                            keys, out, accumulate, flags, stats, rows=_probe_batch, cell=(PROBE_DEPTH_TEXELS, 3), extra=(float(r_max),))
 
     def trace_lit(self, rays, volume: "ProbeVolume", spp: int = 1, first_sample: int = 0, seed: int = 1, keys=None, eval_flags: int = 0,
-                  bias: float = 0.0, out=None, accumulate: bool = False, flags: int = 0, normalize: bool = False):
+                  bias: float = 0.0, out=None, accumulate: bool = False, flags: int = 0, normalize: bool = False, tail_after: Optional[int] = None):
         """hrt_trace_lit: the colour of caller rays whose paths END in ``volume`` at their first hit -- the hit shaded as
         ``trace_radiance`` shades it (emission, direct light), everything beyond it the volume's irradiance about the hit's normal
         times the albedo; mirror and glass get no tail (include/hrt.h "Lit rays").  Rays, samples, keys, ``out``, ``accumulate`` and
         the torch / NumPy forms as ``trace_radiance``.  ``eval_flags``: PROBE_EVAL_FACING, LIT_VISIBLE (the look-up of
         ``ProbeVolume.eval_visible``; needs ``update_depth``); ``bias``: that look-up's offset along the normal.  Returns (n, 3)
-        float32.  The call only reads the volume: order an ``update`` or ``blend`` after it."""
+        float32.  The call only reads the volume: order an ``update`` or ``blend`` after it.
+        ``tail_after`` = K in 1 .. MAXBOUNCES (hrt_trace_lit_paths, "Lit paths"): the path is the integrator's -- mirror and glass
+        followed, K - 1 diffuse bounces traced -- and ends in the volume at its K-th diffuse hit; None: the one segment above."""
         flags = int(flags) | (RAYS_NORMALIZE if normalize else 0) | (RADIANCE_ACCUMULATE if accumulate else 0)
         eval_flags, bias = _lit_args("trace_lit", volume, eval_flags, bias)
-        return DeviceScene._radiance_batch(self, "trace_lit", "rays", "hrt_trace_lit", None, rays, spp, first_sample, seed, keys, out, accumulate,
-                                           flags, None, volume=volume, after=(eval_flags, bias))
+        entry, tail = _tail_args("trace_lit", "hrt_trace_lit", tail_after)
+        return DeviceScene._radiance_batch(self, "trace_lit", "rays", entry, None, rays, spp, first_sample, seed, keys, out, accumulate,
+                                           flags, None, volume=volume, after=(eval_flags, bias) + tail)
+
+    def path_tails(self, rays, tail_after: int, sample: int = 0, seed: int = 1, keys=None, bias: float = 0.0, out=None, flags: int = 0,
+                   normalize: bool = False):
+        """hrt_path_tails: where the paths of ``trace_lit(..., tail_after=K)`` end, for ONE sample of stream (seed, key, sample) --
+        (n, TAIL_FLOATS) float32 rows: [0:8] the point record {p, time, n, bias} that ``ProbeVolume.eval`` / ``eval_visible`` accept,
+        [8:11] the throughput at the tail, [TAIL_WORD] a uint32 word (bits 0..7 the segments traced, TAIL_REACHED set when the path
+        reached its K-th diffuse hit), [12:15] the radiance gathered so far over 6, [15] 0.  A path that ends earlier has p = n =
+        thr = 0; a degenerate ray gives 16 zeros.  The value of that sample of ``trace_lit`` is [12:15] + [8:11] x the look-up of
+        [0:8], bit for bit.  Rays, keys, ``flags``, ``normalize`` and the torch / NumPy forms as ``trace_radiance``; ``out``, if given,
+        a tensor or array of the result's shape."""
+        import torch
+        who = "path_tails"
+        flags, bias = int(flags) | (RAYS_NORMALIZE if normalize else 0), float(bias)
+        _, tail = _tail_args(who, "hrt_path_tails", int(tail_after) if tail_after is not None else 0)
+        if not np.isfinite(bias):
+            raise ValueError(f"{who}: bias must be finite (got {bias})")
+        is_torch = isinstance(rays, torch.Tensor)
+        rays = _ray_batch(who, "rays", rays)
+        n = _row_count(who, "rays", rays)
+        if keys is not None:
+            if is_torch:
+                _check_tensor(who, "keys", keys, (n,), "int32", rays.device, "rays", "(n,)")
+            else:
+                keys = np.ascontiguousarray(keys)
+                if keys.shape != (n,) or keys.dtype not in (np.uint32, np.int32):
+                    raise ValueError(f"{who}: keys must be (n,) uint32 (got {keys.shape} {keys.dtype})")
+        if out is not None:
+            if is_torch:
+                _check_tensor(who, "out", out, (n, TAIL_FLOATS), "float32", rays.device, "rays", f"(n, {TAIL_FLOATS})")
+            elif np.asarray(out).shape != (n, TAIL_FLOATS) or np.asarray(out).dtype != np.float32:
+                raise ValueError(f"{who}: out must be (n, {TAIL_FLOATS}) float32 (got {np.asarray(out).shape} {np.asarray(out).dtype})")
+        d_rays = rays if is_torch else torch.from_numpy(rays).to("cuda")
+        d_keys = keys if is_torch or keys is None else torch.from_numpy(keys.view(np.int32)).to(d_rays.device)
+        d_out = out if is_torch and out is not None else torch.empty((n, TAIL_FLOATS), dtype=torch.float32, device=d_rays.device)
+        self._check(self._lib.hrt_path_tails(self._h, _ptr(d_rays), _ptr(d_keys), n, sample, seed, flags, bias, *tail, _ptr(d_out), _stream(d_rays.device)))
+        if is_torch:
+            return d_out
+        r = d_out.cpu().numpy()
+        if out is not None:
+            out[...] = r
+            return out
+        return r
 
     def probes_lit(self, points, volume: "ProbeVolume", spp: int = 1, first_sample: int = 0, seed: int = 1, keys=None, eval_flags: int = 0,
-                   bias: float = 0.0, out=None, accumulate: bool = False, flags: int = 0, stats: Optional[Stats] = None):
+                   bias: float = 0.0, out=None, accumulate: bool = False, flags: int = 0, stats: Optional[Stats] = None,
+                   tail_after: Optional[int] = None):
         """hrt_probes_lit*: ``probes`` with every sample a lit ray of ``trace_lit`` -- one segment, then ``volume`` -- in one fused
         launch: the SH9 coefficients of the light arriving at the points with one more bounce than the volume holds.  Probe records,
         samples, keys, ``out``, ``accumulate``, ``stats`` and the torch / NumPy forms as ``probes``; ``eval_flags`` and ``bias`` as
         ``trace_lit``.  Returns (n, PROBE_COEFFS, 3) float32 for ``ProbeVolume.update`` or ``.blend``.  Lit probe calls of one scene
-        must not overlap each other.  ``flags``: FLAG_EXACT_ONLY, FLAG_MESH_BRUTE, FLAG_NO_LDS_TREE."""
+        must not overlap each other.  ``flags``: FLAG_EXACT_ONLY, FLAG_MESH_BRUTE, FLAG_NO_LDS_TREE.  ``tail_after`` as ``trace_lit``
+        (hrt_probes_lit_paths*): every sample a path that ends in the volume at its K-th diffuse hit; None: one segment."""
         flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
         eval_flags, bias = _lit_args("probes_lit", volume, eval_flags, bias)
-        return DeviceScene._radiance_batch(self, "probes_lit", "points", "hrt_probes_lit_device", "hrt_probes_lit", points, spp, first_sample, seed,
+        entry, tail = _tail_args("probes_lit", "hrt_probes_lit", tail_after)
+        return DeviceScene._radiance_batch(self, "probes_lit", "points", entry + "_device", entry, points, spp, first_sample, seed,
                                            keys, out, accumulate, flags, stats, rows=_probe_batch, cell=(PROBE_COEFFS, 3), volume=volume,
-                                           after=(eval_flags, bias))
+                                           after=(eval_flags, bias) + tail)
 
     def render_views(self, cams, w: int, h: int, spp: int, seeds=None, flags: int = 0, out=None, stats: Optional[Stats] = None):
         """hrt_render_views: every camera of ``cams`` as a w x h frame of ``spp`` samples, in one launch -> (n, h, w, 3) float32;
@@ -1068,6 +1128,17 @@ def _lit_args(who: str, volume, eval_flags, bias):
     return eval_flags, bias
 
 
+def _tail_args(who: str, entry: str, tail_after):
+    """(the entry point, the arguments it takes after the bias) of a lit call: ``entry`` and nothing for ``tail_after`` None, its
+    "_paths" form and K otherwise -- K refused as include/hrt.h "Lit paths" refuses it, before any library is touched."""
+    if tail_after is None:
+        return entry, ()
+    k = int(tail_after)
+    if not 1 <= k <= MAXBOUNCES:
+        raise ValueError(f"{who}: tail_after must be in 1 .. {MAXBOUNCES} (got {tail_after})")
+    return (entry if entry == "hrt_path_tails" else entry + "_paths"), (k,)
+
+
 def _box(who: str, lo, hi):
     """``lo`` and ``hi`` of a probe grid as (3,) float32 arrays."""
     lo3, hi3 = (np.ascontiguousarray(v, dtype=np.float32) for v in (lo, hi))
@@ -1160,13 +1231,13 @@ class ProbeVolume:
         return self
 
     def relight(self, scene: "DeviceScene", spp: int, rounds: int, keep: float = 0.0, seed: int = 1, eval_flags: int = 0, bias: float = 0.0,
-                depth_rmax: Optional[float] = None, time: float = 0.0, flags: int = 0):
+                depth_rmax: Optional[float] = None, time: float = 0.0, flags: int = 0, tail_after: Optional[int] = None):
         """The relighting loop: ``rounds`` times, ``scene.probes_lit`` at the volume's own grid points against the volume as it
         stands -- round r takes samples [r x spp, (r + 1) x spp) -- then ``update`` (``blend`` when ``keep`` > 0), all on the
         current torch stream, without synchronising.  Every round adds one bounce.  A volume that has never been updated starts from
         zero coefficients (round 0 then gathers emission and direct light alone).  With ``depth_rmax`` the depth of ``spp`` samples
         is traced and installed once before round 0 (for LIT_VISIBLE).  ``time`` is the probes' time; ``flags`` are the trace flags
-        of ``probes_lit``."""
+        of ``probes_lit``, ``tail_after`` its argument of that name (None: one segment a sample)."""
         import torch
         who = "ProbeVolume.relight"
         spp, rounds, keep = int(spp), int(rounds), float(keep)
@@ -1177,6 +1248,7 @@ class ProbeVolume:
         if (rounds * spp) > 2 ** 32:
             raise ValueError(f"{who}: rounds x spp must be at most 2^32 (got {rounds * spp})")
         eval_flags, bias = _lit_args(who, self, eval_flags, bias)
+        _tail_args(who, "hrt_probes_lit", tail_after)
         if depth_rmax is not None and not (np.isfinite(depth_rmax) and depth_rmax > 0):
             raise ValueError(f"{who}: depth_rmax must be finite and positive (got {depth_rmax})")
         points = torch.from_numpy(probe_grid(self.lo, self.hi, *self.shape, time)).to("cuda")
@@ -1185,7 +1257,7 @@ class ProbeVolume:
         if not self.loaded:
             self.update(torch.zeros((self.count, PROBE_COEFFS, 3), dtype=torch.float32, device=points.device))
         for r in range(rounds):
-            c = scene.probes_lit(points, self, spp, first_sample=r * spp, seed=seed, eval_flags=eval_flags, bias=bias, flags=flags)
+            c = scene.probes_lit(points, self, spp, first_sample=r * spp, seed=seed, eval_flags=eval_flags, bias=bias, flags=flags, tail_after=tail_after)
             if keep > 0.0:
                 self.blend(c, keep)
             else:

@@ -206,13 +206,22 @@ static DLitVolume lit_volume(const hrt_probe_volume *v, uint32_t eval_flags, flo
     return V;
 }
 
-int hrt_trace_lit(hrt_scene *s, const hrt_probe_volume *v, const float *d_rays, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
-                  uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, float *d_out, void *stream) {
-    const std::string who = "hrt_trace_lit";
+// "Lit paths" (hrt_lit_paths.hip, which comes after this file): the same entry points with a tail after `tail_after` diffuse hits.
+// Here tail_after == 0 stands for the one-segment forms of this file; theirs check it right after the flags.
+static int lit_tail_check(const std::string &who, uint32_t tail_after);
+static int lit_paths_launch(hrt_scene *s, const DLitVolume &vol, const float *d_rays, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
+                            uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t tail_after, float *d_out, void *stream);
+static int probes_lit_paths_trace(hrt_scene *s, const DProbeLit &Q0, uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags,
+                                  uint32_t tail_after, uint32_t items, hipStream_t stream);
+
+static int lit_trace(const std::string &who, bool paths, hrt_scene *s, const hrt_probe_volume *v, const float *d_rays, const uint32_t *d_keys, uint32_t n,
+                     uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, uint32_t tail_after,
+                     float *d_out, void *stream) {
     {  // the flags alone first (query_check with an empty batch), then the volume, then the rest of query_check
         const int frc = query_check(who, flags, HRT_RADIANCE_ACCUMULATE, nullptr, nullptr, nullptr, 4u, 0u);
         if (frc != HRT_OK) return frc;
     }
+    if (paths) { const int trc = lit_tail_check(who, tail_after); if (trc != HRT_OK) return trc; }
     int rc = lit_volume_check(who, v, eval_flags, bias);
     if (rc != HRT_OK || n == 0u) return rc;
     if ((rc = query_check(who, flags, HRT_RADIANCE_ACCUMULATE, d_rays, d_keys, d_out, 4u, n)) != HRT_OK) return rc;
@@ -220,11 +229,17 @@ int hrt_trace_lit(hrt_scene *s, const hrt_probe_volume *v, const float *d_rays, 
     if ((uint64_t)first_sample + n_samples > 0x100000000ull)
         return fail(HRT_ERR_INVALID, who + ": first_sample + n_samples must be at most 2^32 (sample indices do not wrap)");
     if ((rc = lit_enter(who, s, v)) != HRT_OK) return rc;
+    if (paths) return lit_paths_launch(s, lit_volume(v, eval_flags, bias), d_rays, d_keys, n, first_sample, n_samples, seed, flags, tail_after, d_out, stream);
     DLit Q;
     Q.rays = (const float4 *)d_rays;
     Q.keys = d_keys;
     Q.vol = lit_volume(v, eval_flags, bias);
     return radiance_launch(hrt_lit_kernel_builds, Q, s, first_sample, n_samples, seed, flags, d_out, n, stream);
+}
+
+int hrt_trace_lit(hrt_scene *s, const hrt_probe_volume *v, const float *d_rays, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
+                  uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, float *d_out, void *stream) {
+    return lit_trace("hrt_trace_lit", false, s, v, d_rays, d_keys, n, first_sample, n_samples, seed, flags, eval_flags, bias, 0u, d_out, stream);
 }
 
 // The flags of a lit probe launch: a probe launch's.
@@ -236,7 +251,8 @@ static int probes_lit_flags_check(const std::string &who, uint32_t flags) {
 // The fused launch into d_out on `stream` (the scene entered, the limit checked): the trace launch into the scene's block values,
 // then hrt_probe_fold_kernel, also when a probe has one block.
 static int probes_lit_launch(hrt_scene *s, const hrt_probe_volume *v, const float *d_probes, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
-                             uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, float *d_out, hipStream_t stream) {
+                             uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, uint32_t tail_after, float *d_out,
+                             hipStream_t stream) {
     const uint32_t nblocks = (uint32_t)(((uint64_t)n_samples + HRT_PROBE_BLOCK - 1u) / HRT_PROBE_BLOCK);
     const uint32_t items = n * nblocks;  // <= HRT_PROBE_MAX_BLOCKS
     if (const int rc = s->pl_blocks.grow((size_t)items * HRT_PROBE_SUMS * sizeof(float))) return rc;
@@ -245,7 +261,9 @@ static int probes_lit_launch(hrt_scene *s, const hrt_probe_volume *v, const floa
     Q.keys = d_keys;
     Q.nblocks = nblocks;
     Q.vol = lit_volume(v, eval_flags, bias);
-    if (const int rc = radiance_launch(hrt_probes_lit_kernel_builds, Q, s, first_sample, n_samples, seed, flags, s->pl_blocks.as<float>(), items * 64u, stream))
+    if (const int rc = tail_after ? probes_lit_paths_trace(s, Q, first_sample, n_samples, seed, flags, tail_after, items, stream)
+                                  : radiance_launch(hrt_probes_lit_kernel_builds, Q, s, first_sample, n_samples, seed, flags, s->pl_blocks.as<float>(),
+                                                    items * 64u, stream))
         return rc;
     const uint32_t n_sums = n * HRT_PROBE_SUMS;
     hipLaunchKernelGGL(hrt_probe_fold_kernel, dim3((n_sums + 255u) / 256u), dim3(256), 0, stream, s->pl_blocks.as<float>(), n_sums, nblocks, n_samples,
@@ -254,25 +272,32 @@ static int probes_lit_launch(hrt_scene *s, const hrt_probe_volume *v, const floa
     return HRT_OK;
 }
 
-int hrt_probes_lit_device(hrt_scene *s, const hrt_probe_volume *v, const float *d_probes, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
-                          uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, float *d_out, void *stream) {
-    const std::string who = "hrt_probes_lit_device";
+static int probes_lit_device(const std::string &who, bool paths, hrt_scene *s, const hrt_probe_volume *v, const float *d_probes, const uint32_t *d_keys,
+                             uint32_t n, uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias,
+                             uint32_t tail_after, float *d_out, void *stream) {
     int rc = probes_lit_flags_check(who, flags);
+    if (rc == HRT_OK && paths) rc = lit_tail_check(who, tail_after);
     if (rc == HRT_OK) rc = lit_volume_check(who, v, eval_flags, bias);
     if (rc != HRT_OK || n == 0u) return rc;
     if ((rc = probe_records_check(who, d_probes, d_keys, n, true)) != HRT_OK) return rc;
     if ((rc = probe_samples_out_check(who, n, first_sample, n_samples, d_out, "d_out")) != HRT_OK) return rc;
     if ((rc = lit_enter(who, s, v)) != HRT_OK) return rc;
-    return probes_lit_launch(s, v, d_probes, d_keys, n, first_sample, n_samples, seed, flags, eval_flags, bias, d_out, (hipStream_t)stream);
+    return probes_lit_launch(s, v, d_probes, d_keys, n, first_sample, n_samples, seed, flags, eval_flags, bias, tail_after, d_out, (hipStream_t)stream);
+}
+
+int hrt_probes_lit_device(hrt_scene *s, const hrt_probe_volume *v, const float *d_probes, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
+                          uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, float *d_out, void *stream) {
+    return probes_lit_device("hrt_probes_lit_device", false, s, v, d_probes, d_keys, n, first_sample, n_samples, seed, flags, eval_flags, bias, 0u, d_out,
+                             stream);
 }
 
 // Blocking, from and into host memory (BlockingCall; the probes and keys are device buffers of the call's, too).
-int hrt_probes_lit(hrt_scene *s, const hrt_probe_volume *v, const float *probes, const uint32_t *keys, uint32_t n, uint32_t spp, uint64_t seed,
-                   uint32_t flags, uint32_t eval_flags, float bias, float *out, hrt_stats *stats) {
-    const std::string who = "hrt_probes_lit";
+static int probes_lit_host(const std::string &who, bool paths, hrt_scene *s, const hrt_probe_volume *v, const float *probes, const uint32_t *keys, uint32_t n,
+                           uint32_t spp, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, uint32_t tail_after, float *out, hrt_stats *stats) {
     if (flags & HRT_RADIANCE_ACCUMULATE)
-        return fail(HRT_ERR_INVALID, who + ": flags: HRT_RADIANCE_ACCUMULATE needs the running sums on the device (hrt_probes_lit_device)");
+        return fail(HRT_ERR_INVALID, who + ": flags: HRT_RADIANCE_ACCUMULATE needs the running sums on the device (" + who + "_device)");
     int rc = probes_lit_flags_check(who, flags);
+    if (rc == HRT_OK && paths) rc = lit_tail_check(who, tail_after);
     if (rc == HRT_OK) rc = lit_volume_check(who, v, eval_flags, bias);
     if (rc != HRT_OK) return rc;
     if (n == 0u) {
@@ -287,8 +312,13 @@ int hrt_probes_lit(hrt_scene *s, const hrt_probe_volume *v, const float *probes,
     if ((rc = d_probes.from_host(probes, (size_t)n * HRT_PROBE_FLOATS * sizeof(float))) != HRT_OK) return rc;
     if (keys && (rc = d_keys.from_host(keys, (size_t)n * sizeof(uint32_t))) != HRT_OK) return rc;
     return call.run(s, (size_t)n * HRT_PROBE_SUMS * sizeof(float), out, (uint64_t)n * spp, stats, [&](float *d_out) {
-        return probes_lit_launch(s, v, d_probes.as<float>(), d_keys.as<uint32_t>(), n, 0u, spp, seed, flags, eval_flags, bias, d_out, nullptr);
+        return probes_lit_launch(s, v, d_probes.as<float>(), d_keys.as<uint32_t>(), n, 0u, spp, seed, flags, eval_flags, bias, tail_after, d_out, nullptr);
     });
+}
+
+int hrt_probes_lit(hrt_scene *s, const hrt_probe_volume *v, const float *probes, const uint32_t *keys, uint32_t n, uint32_t spp, uint64_t seed,
+                   uint32_t flags, uint32_t eval_flags, float bias, float *out, hrt_stats *stats) {
+    return probes_lit_host("hrt_probes_lit", false, s, v, probes, keys, n, spp, seed, flags, eval_flags, bias, 0u, out, stats);
 }
 
 // ---- The hysteresis update of a volume's packed records.

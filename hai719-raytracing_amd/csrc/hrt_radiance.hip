@@ -58,14 +58,23 @@ struct src_wave_items { static constexpr bool value = false; };
 template <class SRC>
 struct src_wave_items<SRC, std::enable_if_t<SRC::wave_items>> { static constexpr bool value = true; };
 
-template <bool LIGHTS, bool EXACT, class SRC = RecordRays, class QT = DRadiance>
+// Where a path ends before its bounces run out (radiance_body's TAIL).  NoTail: nowhere -- every family but those of
+// hrt_lit_paths.hip, whose policies end a path at its Q.tail_after-th diffuse hit WITHOUT scattering there: kind 1 gathers there
+// (TAIL::gather: the look-up of a probe volume), kind 2 writes the path's end out instead of its colour (TAIL::reached /
+// ::unreached / ::degenerate: 16 floats per ray where the others store 3).  A path with a tail is not pruned.  Every other family
+// is untouched by this: all of it is behind `if constexpr`.
+struct NoTail {
+    static constexpr int kind = 0;
+};
+
+template <bool LIGHTS, bool EXACT, class SRC = RecordRays, class QT = DRadiance, class TAIL = NoTail>
 __device__ __forceinline__ void radiance_body(const QT &Q) {
     constexpr bool WAVE = src_wave_items<SRC>::value;
     CtxT<EXACT, false, false, true> cx;
     unsigned long long stamps_local[17] = {0};
     query_context(cx, Q.scene, Q.lds_units, Q.flags, stamps_local);
     const bool has_mesh = cx.S->n_meshes != 0u;
-    const bool prune = !EXACT && cx.S->prune_ok != 0u;  // as trace_body
+    const bool prune = TAIL::kind == 0 && !EXACT && cx.S->prune_ok != 0u;  // as trace_body
     const bool sky_is_zero = cx.S->skybox_image < 0 && cx.S->dark_sky != 0;
     const bool accumulate = (Q.flags & HRT_RADIANCE_ACCUMULATE) != 0u;
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -78,6 +87,7 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
     uint32_t s = 0;          // next sample of this lane's ray
     [[maybe_unused]] uint32_t count = 0;  // a wave_items source: where the samples of the wave's item end (s runs in steps of 64)
     int remaining = 0;       // bounces left on the current path; 0 = needs a new path
+    [[maybe_unused]] uint32_t diffuse = 0;  // a TAIL: the diffuse hits of the current path so far
     Ray ray;
     ray.o = mk(0.f, 0.f, 0.f); ray.d = mk(0.f, 0.f, 1.f); ray.time = 0.f;
     f3 thr = mk(1.f, 1.f, 1.f), rad = mk(0.f, 0.f, 0.f);
@@ -113,7 +123,9 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
                     live = true;
                     break;
                 }
-                if (!accumulate) { float *o_ = Q.out + (size_t)i * 3u; o_[0] = 0.f; o_[1] = 0.f; o_[2] = 0.f; }
+                if constexpr (TAIL::kind == 2) {
+                    TAIL::degenerate(Q, i);
+                } else if (!accumulate) { float *o_ = Q.out + (size_t)i * 3u; o_[0] = 0.f; o_[1] = 0.f; o_[2] = 0.f; }
             }
         }
         if (live) {
@@ -167,6 +179,7 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
                 thr = mk(1.f, 1.f, 1.f);
                 rad = mk(0.f, 0.f, 0.f);
                 remaining = 6;  // MAXBOUNCES
+                if constexpr (TAIL::kind != 0) diffuse = 0u;
             }
             if (SRC::per_sample && !traced) {
                 h.kind = 0u; parked = 0u; stage = 4u;  // ends below
@@ -201,6 +214,9 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
         // ---- stage C: shade, scatter, end of path; end of ray
         if (live && stage >= 2u) {
             bool ended;
+            [[maybe_unused]] bool fired = false;            // a TAIL: this hit is the path's tail
+            [[maybe_unused]] f3 G = mk(0.f, 0.f, 0.f);      // TAIL kind 1: what it gathers there
+            [[maybe_unused]] const uint32_t segment = 7u - (uint32_t)remaining;  // TAIL kind 2: the segments traced so far, this one included
             if (stage == 3u || (SRC::per_sample && stage == 4u)) {
                 ended = true;  // pruned on its last segment (stage A), or not traced: nothing is added
             } else if (h.kind == 0u) {
@@ -212,25 +228,45 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
                 if (LIGHTS) direct = direct_light(cx, sf, ray, rng);
                 rad = rad + thr * (direct + sf.emission);
                 thr = thr * sf.albedo;
-                scatter(sf, ray, rng);
-                cx.flags = Q.flags;  // bounce segments are walked
-                --remaining;
-                ended = (remaining == 0) || (prune && thr.x == 0.f && thr.y == 0.f && thr.z == 0.f);
+                if constexpr (TAIL::kind != 0) fired = sf.type == 0u && ++diffuse == Q.tail_after;
+                if constexpr (TAIL::kind == 1) { if (fired) G = TAIL::gather(Q, sf.p, sf.n); }
+                if constexpr (TAIL::kind == 2) { if (fired) TAIL::reached(Q, i, sf.p, ray.time, sf.n, thr, segment, rad); }
+                if (fired) {
+                    ended = true;  // without scattering
+                } else {
+                    scatter(sf, ray, rng);
+                    cx.flags = Q.flags;  // bounce segments are walked
+                    --remaining;
+                    ended = (remaining == 0) || (prune && thr.x == 0.f && thr.y == 0.f && thr.z == 0.f);
+                }
             }
             if (ended) {
+                if constexpr (TAIL::kind == 2) { if (!fired) TAIL::unreached(Q, i, segment, rad); }
                 if constexpr (WAVE) {  // the sink is the source's: it gets what a one-sample query stores, 0 + rad / 6
-                    if (stage != 4u) SRC::add(Q, i, Q.first_sample + s, mk(0.f, 0.f, 0.f) + mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f));
+                    if constexpr (TAIL::kind == 1) {  // (rad / 6) + thr * G where the tail was reached
+                        if (stage != 4u)
+                            SRC::add(Q, i, Q.first_sample + s,
+                                     mk(0.f, 0.f, 0.f) + (fired ? mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f) + thr * G : mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f)));
+                    } else {
+                        if (stage != 4u) SRC::add(Q, i, Q.first_sample + s, mk(0.f, 0.f, 0.f) + mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f));
+                    }
                 } else if (!(SRC::per_sample && stage == 4u)) {
-                    sum = sum + mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f);  // Scene.h:348
+                    if constexpr (TAIL::kind == 1) {
+                        sum = sum + (fired ? mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f) + thr * G : mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f));
+                    } else {
+                        sum = sum + mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f);  // Scene.h:348
+                    }
                 }
                 remaining = 0;
                 if constexpr (WAVE) {
                     if (count - s <= 64u) live = false;  // out of samples: idle until the wave meets in more()
                     else s += 64u;
                 } else if (++s == Q.n_samples) {  // the ray is done: its mean (or running sum), then the lane's next ray
-                    const float ns = accumulate ? 1.f : (float)Q.n_samples;  // x / 1.f is exact
-                    float *o = Q.out + (size_t)i * 3u;
-                    o[0] = sum.x / ns; o[1] = sum.y / ns; o[2] = sum.z / ns;
+                    if constexpr (TAIL::kind != 2) {  // kind 2 has written its record
+                        const float ns = accumulate ? 1.f : (float)Q.n_samples;  // x / 1.f is exact
+                        float *o = Q.out + (size_t)i * 3u;
+                        o[0] = sum.x / ns; o[1] = sum.y / ns; o[2] = sum.z / ns;
+                    }
                     i += stride;
                     next_ray();
                 }

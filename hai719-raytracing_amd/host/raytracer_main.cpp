@@ -57,6 +57,9 @@
 //             [--probe-lit]                        with --probe-grid and --probe-box, instead of --probe-quad: a --w x --h camera
 //                                                  frame lit by the volume: per sample hrt_camera_rays, then hrt_trace_lit into
 //                                                  running sums; means and gamma by hrt_finalize_tiles, written as a render is
+//             [--probe-tail K]                     with --probe-lit or --probe-bounces, K in 1 .. 6: their paths follow mirror and glass
+//                                                  and end in the volume at their K-th diffuse hit (hrt_trace_lit_paths,
+//                                                  hrt_probes_lit_paths_device) instead of at their first hit of any kind
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -104,6 +107,7 @@ static long probe_quad = -1;
 static int32_t probe_side = 1;
 static bool probe_bounces_given = false, probe_keep_given = false, probe_lit = false;  // --probe-bounces: hrt_probes_lit_device rounds; --probe-lit: hrt_trace_lit
 static long probe_bounces = 0;
+static long probe_tail = 0;  // --probe-tail K: the lit launches are "Lit paths" with tail_after = K; 0: not given, one segment
 static float probe_keep = 0.f;
 static hrt_temporal_params temporal_params = {0.02f, 64.f, 0.05f, 0.1f, 0.05f};  // the Python TemporalParams()
 
@@ -280,8 +284,11 @@ static int relight_probes(hrt_probe_volume *volume, const std::vector<float> &pr
     if (!d_probes.alloc(probes.size() * sizeof(float)) || !d_sh.alloc(sh.size() * sizeof(float))) return device_failed("hipMalloc");
     if (hipMemcpy(d_probes.p, probes.data(), probes.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return device_failed("hipMemcpy");
     for (long r = 0; rc == HRT_OK && r < probe_bounces; ++r) {
-        rc = hrt_probes_lit_device(device_scene, volume, d_probes.as<float>(), nullptr, (uint32_t)n, (uint32_t)((uint64_t)r * nsamples), nsamples, seed, 0u,
-                                   lit_eval_flags(), 0.f, d_sh.as<float>(), nullptr);
+        const uint32_t first = (uint32_t)((uint64_t)r * nsamples);
+        rc = probe_tail ? hrt_probes_lit_paths_device(device_scene, volume, d_probes.as<float>(), nullptr, (uint32_t)n, first, nsamples, seed, 0u,
+                                                      lit_eval_flags(), 0.f, (uint32_t)probe_tail, d_sh.as<float>(), nullptr)
+                        : hrt_probes_lit_device(device_scene, volume, d_probes.as<float>(), nullptr, (uint32_t)n, first, nsamples, seed, 0u,
+                                                lit_eval_flags(), 0.f, d_sh.as<float>(), nullptr);
         if (rc == HRT_OK)
             rc = probe_keep > 0.f ? hrt_probe_volume_blend_device(volume, d_sh.as<float>(), probe_keep, nullptr)
                                   : hrt_probe_volume_update_device(volume, d_sh.as<float>(), nullptr);
@@ -305,8 +312,10 @@ static int probe_lit_frame(hrt_probe_volume *volume) {
     for (uint32_t s = 0; rc == HRT_OK && s < nsamples; ++s) {
         rc = hrt_camera_rays(&cam, w, h, s, seed, d_rays.as<float>(), nullptr);
         if (rc == HRT_OK)
-            rc = hrt_trace_lit(device_scene, volume, d_rays.as<float>(), nullptr, npix, s, 1u, seed, HRT_RADIANCE_ACCUMULATE, lit_eval_flags(), 0.f,
-                               d_sum.as<float>(), nullptr);
+            rc = probe_tail ? hrt_trace_lit_paths(device_scene, volume, d_rays.as<float>(), nullptr, npix, s, 1u, seed, HRT_RADIANCE_ACCUMULATE,
+                                                  lit_eval_flags(), 0.f, (uint32_t)probe_tail, d_sum.as<float>(), nullptr)
+                            : hrt_trace_lit(device_scene, volume, d_rays.as<float>(), nullptr, npix, s, 1u, seed, HRT_RADIANCE_ACCUMULATE, lit_eval_flags(),
+                                            0.f, d_sum.as<float>(), nullptr);
     }
     if (rc == HRT_OK) rc = hrt_finalize_tiles(d_sum.as<float>(), n_tiles, nsamples, HRT_FLAG_GAMMA, d_sum.as<float>(), nullptr);
     if (rc != HRT_OK) {
@@ -527,6 +536,14 @@ int main(int argc, char **argv) {
             }
             probe_bounces_given = true;
         }
+        else if (k == "--probe-tail") {
+            char *end = nullptr;
+            probe_tail = strtol(v.c_str(), &end, 10);
+            if (end == v.c_str() || *end != '\0' || probe_tail < 1 || probe_tail > (long)HRT_MAXBOUNCES) {
+                std::cerr << "--probe-tail takes a number of diffuse hits in 1 .. " << HRT_MAXBOUNCES << " (got " << v << ")" << std::endl;
+                return 2;
+            }
+        }
         else if (k == "--probe-keep") {
             char *end = nullptr;
             probe_keep = std::strtof(v.c_str(), &end);
@@ -613,6 +630,10 @@ int main(int argc, char **argv) {
     }
     if (probe_lit && probe_quad_given) {
         std::cerr << "--probe-lit writes a camera frame, --probe-quad a lightmap: give one of them" << std::endl;
+        return 2;
+    }
+    if (probe_tail && !probe_bounces_given && !probe_lit) {
+        std::cerr << "--probe-tail says where the paths of --probe-lit and --probe-bounces end: give one of them" << std::endl;
         return 2;
     }
     if (probe_keep_given && !probe_bounces_given) {

@@ -1185,8 +1185,9 @@ HRT_API int hrt_probe_depth_direction(uint32_t texel, float out[3]);
  * volume must be ordered after the lit launches that read it by the caller (on one stream they are).  The block values of
  * hrt_probes_lit* are a grow-only scratch buffer of the scene's own, allocated by its first such call and freed with the scene, so
  * lit probe launches of ONE scene must not overlap each other; they may overlap anything else.
- * OUT OF SCOPE (DESIGN.md section 5 "Lit rays and probe relighting"): following mirror and glass to the first diffuse hit, more than
- * one segment before the tail, a cooperative (eight lanes to a hit) look-up inside the kernels, probes that move, multi-GPU. */
+ * OUT OF SCOPE (DESIGN.md section 5 "Lit rays and probe relighting"): a cooperative (eight lanes to a hit) look-up inside the kernels,
+ * probes that move, multi-GPU.  Following mirror and glass to the first diffuse hit, and more than one segment before the tail, are
+ * "Lit paths" below: these entry points keep their one segment and their bits. */
 #define HRT_LIT_VISIBLE 4u                /* eval_flags of a lit launch: the look-up of "Probe visibility" */
 HRT_API int hrt_trace_lit(hrt_scene *scene, const hrt_probe_volume *volume, const float *d_rays, const uint32_t *d_keys, uint32_t n,
                           uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias,
@@ -1198,6 +1199,67 @@ HRT_API int hrt_probes_lit(hrt_scene *scene, const hrt_probe_volume *volume, con
                            uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, float *out, hrt_stats *stats /* may be NULL */);
 HRT_API int hrt_probe_volume_blend_device(hrt_probe_volume *volume, const float *d_coeffs, float keep, void *stream);
 HRT_API int hrt_probe_volume_blend(hrt_probe_volume *volume, const float *coeffs, float keep);
+
+/* ---- Lit paths: a path of the integrator that ENDS in a probe volume at its K-th diffuse hit.  It is hrt_trace_radiance's path --
+ * bounce loop, meshes, direct light, sky -- with one hook: at the K-th diffuse surface the path does not scatter but gathers from the
+ * volume, as a lit ray does at its first hit.  Mirror and glass are followed (they cost a bounce and do not count towards K), so
+ * K = 1 is "Lit rays" with specular chains followed, and K = 2 or 3 is final gathering: K - 1 real diffuse bounces, then the volume.
+ * The same hook can write the path's end out instead of gathering there (hrt_path_tails): vertex, throughput and radiance so far.
+ * THE RULE (tests/lit_paths_ref.py states it again in NumPy).  All arithmetic is fp32 without fused multiply-add, in the order
+ * written.  For a ray {o, time, d, tmax} (tmax is not read), key k, sample s and tail_after = K in 1 .. HRT_MAXBOUNCES:
+ *   1. the path starts as a path of hrt_trace_radiance starts: stream (seed, k, s) with the draw index set to 3, the filter margin
+ *      and far-origin rule of a first segment, the same DEGENERATE rays (which add nothing); thr = 1, rad = 0, remaining = 6, and a
+ *      counter diffuse = 0.
+ *   2. per segment: h = the closest hit, meshes included.  A miss: rad = rad + thr * sky(d, remaining); the path ends with
+ *      value = rad / 6.f per channel and NO TAIL.
+ *   3. a hit: sf = the shaded surface; direct = the direct light at sf with the sample's stream (scenes with lights; 0 otherwise);
+ *      rad = rad + thr * (direct + sf.emission); thr = thr * sf.albedo -- the integrator's own expressions and device functions.
+ *   4. if sf is diffuse and ++diffuse == K the path ends in THE TAIL, without scattering: G = the look-up of the point record
+ *      {sf.p, time, sf.n, bias} (sf.n the shaded normal, not flipped) by THE RULE of "Probe volumes", steps 1-6 in irradiance form, or
+ *      with HRT_LIT_VISIBLE by that of "Probe visibility"; HRT_PROBE_EVAL_FACING is passed through; a degenerate point record gives
+ *      G = 0.  value = (rad / 6.f) + thr * G per channel.
+ *   5. otherwise the path scatters as the integrator does (the bounce segment's flags are the launch's) and remaining decreases;
+ *      at 0 the path ends with value = rad / 6.f and no tail.
+ *   6. samples in ascending order: sum = 0.f (or d_out on entry, under HRT_RADIANCE_ACCUMULATE), sum = sum + value; the output is
+ *      sum / (float)n_samples, or the running sum.
+ * PRUNING: hrt_trace_radiance drops work that cannot change a bit of its result (a last segment that cannot reach an emitter, a
+ * path whose throughput is zero).  The kernels here drop nothing: the first would lose a hit at which the tail fires, and a tail
+ * record counts its segments by the rule as written.
+ * hrt_trace_lit_paths: hrt_trace_lit with tail_after -- the same records, keys, flags, eval_flags, bias, output and stream; one lane
+ * of the device per ray.  On a ray whose first hit is diffuse, or that misses, tail_after = 1 gives hrt_trace_lit's bits.
+ * hrt_path_tails: ONE sample per call (as hrt_camera_rays and hrt_probe_rays are per sample) and no volume: the end of the path of
+ * every ray as a TAIL RECORD of HRT_TAIL_FLOATS = 16 floats at d_out[16i .. 16i+15] (device, 16-byte aligned):
+ *     [0..7]   the point record {p, time, n, bias} of step 4, exactly what hrt_probe_eval* accepts;
+ *     [8..10]  thr at the tail;
+ *     [11]     a uint32 word: bits 0..7 the segments traced (1 .. 6), bit 31 set when the tail was reached;
+ *     [12..14] a = rad / 6.f;
+ *     [15]     0.
+ *   A path that ends without a tail writes p = 0, n = 0, thr = 0 (a degenerate point record: its look-up gives 0); a degenerate
+ *   ray writes 16 zeros.  CONTRACT B: for every K, the value of step 4 or 5 is a where bit 31 is clear and a + thr * G elsewhere,
+ *   with G = hrt_probe_eval* (or _visible) of [0..7] -- hrt_trace_lit_paths gives exactly those bits.  `flags`: HRT_FLAG_EXACT_ONLY,
+ *   HRT_FLAG_MESH_BRUTE (with EXACT_ONLY), HRT_FLAG_NO_LDS_TREE, HRT_RAYS_NORMALIZE.
+ * hrt_probes_lit_paths_device / hrt_probes_lit_paths: hrt_probes_lit_device / hrt_probes_lit with tail_after: one wave of the device
+ * per (probe, block of HRT_PROBE_BLOCK samples), the sum, the second launch, the scratch buffer, the LIMIT and the CONCURRENCY note
+ * of "Lit rays".  CONTRACT A holds with hrt_trace_lit_paths (the same tail_after) in place of hrt_trace_lit.
+ * Checked in this order, HRT_ERR_INVALID with hrt_last_error() naming the entry point and the culprit: flags; tail_after outside
+ * 1 .. HRT_MAXBOUNCES; then for the three entry points with a volume everything "Lit rays" checks after the flags, in its order; for
+ * hrt_path_tails a bias that is not finite; (n == 0 returns HRT_OK here and launches nothing;) d_rays NULL or not 16-byte aligned,
+ * d_keys not 4-byte aligned, d_out NULL or not 16-byte aligned, n > 2^31 - 1; then a NULL scene and the library state.
+ * OUT OF SCOPE (DESIGN.md section 5 "Lit paths"): lens-camera sources with a tail (the fused lit frame), the cooperative look-up,
+ * parking the lanes whose tail fires, probes that move, multi-GPU. */
+#define HRT_TAIL_FLOATS 16u               /* floats of a tail record */
+#define HRT_TAIL_REACHED 0x80000000u      /* word [11] of a tail record: the tail was reached */
+HRT_API int hrt_trace_lit_paths(hrt_scene *scene, const hrt_probe_volume *volume, const float *d_rays, const uint32_t *d_keys, uint32_t n,
+                                uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias,
+                                uint32_t tail_after, float *d_out, void *stream);
+HRT_API int hrt_path_tails(hrt_scene *scene, const float *d_rays, const uint32_t *d_keys, uint32_t n, uint32_t sample, uint64_t seed,
+                           uint32_t flags, float bias, uint32_t tail_after, float *d_out, void *stream);
+HRT_API int hrt_probes_lit_paths_device(hrt_scene *scene, const hrt_probe_volume *volume, const float *d_probes, const uint32_t *d_keys, uint32_t n,
+                                        uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias,
+                                        uint32_t tail_after, float *d_out, void *stream);
+HRT_API int hrt_probes_lit_paths(hrt_scene *scene, const hrt_probe_volume *volume, const float *probes, const uint32_t *keys, uint32_t n,
+                                 uint32_t spp, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, uint32_t tail_after, float *out,
+                                 hrt_stats *stats /* may be NULL */);
 
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
