@@ -152,19 +152,22 @@ def contract_points(hrt, name):
     to), so the points exist without a GPU; tests/test_gpu_bake.py checks them against the device's own SHADE records."""
     if name not in _contract:
         host = hrt.HostScene().setup(name, W / H, 1)
-        desc = host.flatten()
-        cam = hrt.default_camera(W / H)
-        y, x = np.mgrid[0:H, 0:W]
-        uv = np.stack([(x.ravel().astype(F32) + F32(0.5)) / F32(W), (y.ravel().astype(F32) + F32(0.5)) / F32(H)], axis=1)
-        cr = oracle_lib.camera_rays(cam, uv)
-        aov = oracle_lib.OracleScene(desc).aov(cam, W, H)
-        shade = np.zeros((W * H, 16), F32)
-        shade[:, 0] = aov["hit"].reshape(-1, 3)[:, 0]
-        shade[:, 4:7] = aov["normal"].reshape(-1, 3)
-        rays = np.empty((W * H, 8), F32)
-        rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7] = cr[:, 0:3], 0.0, cr[:, 3:6], np.inf
-        _contract[name] = np.concatenate([hit_points(rays, shade), degenerate_records()])
+        _contract[name] = frame_points(host.flatten(), hrt.default_camera(W / H))
     return _contract[name].copy()
+
+
+def frame_points(desc, cam):
+    """contract_points' construction for any flattened description and the camera of its W x H frame."""
+    y, x = np.mgrid[0:H, 0:W]
+    uv = np.stack([(x.ravel().astype(F32) + F32(0.5)) / F32(W), (y.ravel().astype(F32) + F32(0.5)) / F32(H)], axis=1)
+    cr = oracle_lib.camera_rays(cam, uv)
+    aov = oracle_lib.OracleScene(desc).aov(cam, W, H)
+    shade = np.zeros((W * H, 16), F32)
+    shade[:, 0] = aov["hit"].reshape(-1, 3)[:, 0]
+    shade[:, 4:7] = aov["normal"].reshape(-1, 3)
+    rays = np.empty((W * H, 8), F32)
+    rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7] = cr[:, 0:3], 0.0, cr[:, 3:6], np.inf
+    return np.concatenate([hit_points(rays, shade), degenerate_records()])
 
 
 def rule_points():

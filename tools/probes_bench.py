@@ -8,8 +8,9 @@ The median (and the spread) of --reps timings after two warm-up runs, the two al
 per (scene, grid, spp, what); a table at the end; --out writes the rows as a JSON file (profiles/probes_bench.json).
 
 A/B of the block size: for every library named by --variants (A/B builds of the same ABI with another -DHRT_PROBE_BLOCK,
-  make -C hai719-raytracing_amd libhrt_var_probe256.so VARIANT=libhrt_var_probe256.so VARIANT_FLAGS=-DHRT_PROBE_BLOCK=256u
-and likewise 1024u) the script starts itself once more with HRT_LIBNAME set and --fused-only, and adds that process's fused rows
+  make -C hai719-raytracing_amd libhrt_var_probe256.so          (part of `make all`: tests/test_gpu_probe_cases.py loads it)
+  make -C hai719-raytracing_amd libhrt_var_probe1024.so VARIANT=libhrt_var_probe1024.so VARIANT_FLAGS=-DHRT_PROBE_BLOCK=1024u
+) the script starts itself once more with HRT_LIBNAME set and --fused-only, and adds that process's fused rows
 tagged with the library.  The shipped library (libhrt.so) has the header's HRT_PROBE_BLOCK.
 
   python tools/probes_bench.py [--scenes cornell_mesh backrooms_pool random_spheres] [--reps 10] [--out profiles/probes_bench.json]
