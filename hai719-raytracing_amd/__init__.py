@@ -403,6 +403,14 @@ def device_lib() -> C.CDLL:
                                              C.c_float, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
         lib.hrt_path_tails.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_float, C.c_uint32,
                                        C.c_void_p, C.c_void_p]
+        lib.hrt_render_lit_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Lens), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                              C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.hrt_render_lit.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Lens), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
+                                       C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_render_lit_views_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(LensView), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                    C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.hrt_render_lit_views.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(LensView), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
         lib.hrt_probe_volume_blend_device.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         lib.hrt_probe_volume_blend.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
         lib.hrt_debug_pick_kernel.argtypes = [C.POINTER(PickInput), C.c_char_p, C.c_size_t]
@@ -1072,6 +1080,34 @@ class DeviceScene:
         flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
         return DeviceScene._frames(self, "render_lens_views", (n, h, w, 3), ("hrt_render_lens_views_device", (views, n, w, h, first_sample, spp, flags)),
                                    ("hrt_render_lens_views", (views, n, w, h, spp, flags)), first_sample, out, accumulate, stats)
+
+    def render_lit(self, lens: Lens, volume: "ProbeVolume", w: int, h: int, spp: int, seed: int = 1, flags: int = 0, first_sample: int = 0,
+                   out=None, accumulate: bool = False, stats: Optional[Stats] = None, eval_flags: int = 0, bias: float = 0.0,
+                   tail_after: Optional[int] = None):
+        """hrt_render_lit*: the frame of ``lens`` whose paths END in ``volume`` (include/hrt.h "Lit frames") -> (h, w, 3) float32:
+        sample s of a pixel is ``trace_lit`` of that pixel's record of ``lens_rays(lens, w, h, s, seed)``, in one launch for all
+        samples and without the ray buffer.  ``tail_after`` None: one segment, the volume at the first hit; K in 1 .. MAXBOUNCES:
+        mirror and glass followed, the volume at the K-th diffuse hit.  ``eval_flags`` and ``bias`` as ``trace_lit``; everything
+        else -- samples, ``out``, ``accumulate``, ``stats``, ``flags`` and the torch / NumPy forms -- as ``render_lens``.  The call
+        only reads the volume: order an ``update`` or ``blend`` after it."""
+        flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
+        after = _lit_args("render_lit", volume, eval_flags, bias) + (0 if tail_after is None else _tail_args("render_lit", "", tail_after)[1][0],)
+        return DeviceScene._frames(self, "render_lit", (h, w, 3),
+                                   ("hrt_render_lit_device", (volume._h, C.byref(lens), w, h, first_sample, spp, seed, flags) + after),
+                                   ("hrt_render_lit", (volume._h, C.byref(lens), w, h, spp, seed, flags) + after), first_sample, out, accumulate, stats)
+
+    def render_lit_views(self, lenses, volume: "ProbeVolume", w: int, h: int, spp: int, seeds=None, flags: int = 0, first_sample: int = 0,
+                         out=None, accumulate: bool = False, stats: Optional[Stats] = None, eval_flags: int = 0, bias: float = 0.0,
+                         tail_after: Optional[int] = None):
+        """hrt_render_lit_views*: every lens of ``lenses`` as a w x h lit frame, in one launch -> (n, h, w, 3) float32; frame v has
+        the bits of ``render_lit(lenses[v], volume, w, h, spp, seeds[v], ...)``.  ``seeds`` and the forms as ``render_lens_views``;
+        ``eval_flags``, ``bias`` and ``tail_after`` as ``render_lit``."""
+        views, n = _view_table("render_lit_views", "lenses", LensView, lenses, seeds)
+        flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
+        after = _lit_args("render_lit_views", volume, eval_flags, bias) + (0 if tail_after is None else _tail_args("render_lit_views", "", tail_after)[1][0],)
+        return DeviceScene._frames(self, "render_lit_views", (n, h, w, 3),
+                                   ("hrt_render_lit_views_device", (volume._h, views, n, w, h, first_sample, spp, flags) + after),
+                                   ("hrt_render_lit_views", (volume._h, views, n, w, h, spp, flags) + after), first_sample, out, accumulate, stats)
 
     def render_lens_views_features(self, lenses, w: int, h: int, first_sample: int, n_samples: int, seeds=None) -> np.ndarray:
         """hrt_render_lens_views_features: ``render_lens_features`` of every lens of ``lenses`` with its seed, in one launch ->

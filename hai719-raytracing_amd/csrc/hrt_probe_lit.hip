@@ -86,8 +86,11 @@ __device__ __forceinline__ f3 lit_sample(const CX &cx, const DLitVolume &V, cons
 }
 
 // One lane per ray by grid stride; hrt_trace_radiance's handling of a degenerate ray, of the keys and of the running sums.
-template <bool LIGHTS, bool EXACT>
-__device__ __forceinline__ void lit_body(const DLit &Q) {
+// SRC is radiance_body's source policy: RecordRays reads record i once, with Q.keys and the launch's seed; a per-sample source
+// (LensRays, LensViewRays: the lit frames of hrt_lit_frames.hip) makes the ray, the margin, the key and the seed of every sample,
+// and a sample it does not trace adds nothing.
+template <bool LIGHTS, bool EXACT, class SRC = RecordRays, class QT = DLit>
+__device__ __forceinline__ void lit_body(const QT &Q) {
     CtxT<EXACT, false, false, true> cx;
     unsigned long long stamps_local[17] = {0};
     query_context(cx, Q.scene, Q.lds_units, Q.flags, stamps_local);
@@ -97,18 +100,30 @@ __device__ __forceinline__ void lit_body(const DLit &Q) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < Q.n; i += stride) {
         float *o = Q.out + (size_t)i * 3u;
         Ray ray;
-        float tmax;  // not read: a path's first segment has no far end
-        if (!query_ray(Q, i, ray, tmax)) {  // adds nothing
-            if (!accumulate) { o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; }
-            continue;
+        [[maybe_unused]] float tmax;  // not read: a path's first segment has no far end
+        if constexpr (!SRC::per_sample) {
+            if (!query_ray(Q, i, ray, tmax)) {  // adds nothing
+                if (!accumulate) { o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; }
+                continue;
+            }
         }
-        const uint32_t key = Q.keys ? Q.keys[i] : i;
-        query_margin(ray, Q.bound, far, Q.flags, cx.err_abs, cx.flags);
+        uint32_t key;
+        if constexpr (SRC::per_sample) key = SRC::key(Q, i);
+        else key = Q.keys ? Q.keys[i] : i;
+        if constexpr (!SRC::per_sample) query_margin(ray, Q.bound, far, Q.flags, cx.err_abs, cx.flags);
         f3 sum = mk(0.f, 0.f, 0.f);
         if (accumulate) sum = mk(o[0], o[1], o[2]);
         for (uint32_t s = 0; s < Q.n_samples; ++s) {
             Rng rng;
-            rng.start(Q.seed_lo, Q.seed_hi, key, Q.first_sample + s);
+            if constexpr (SRC::per_sample) {  // this sample's own ray, and the margin and far-origin flag of that ray
+                if (!SRC::sample(Q, i, Q.first_sample + s, ray)) continue;  // a degenerate sample adds nothing
+                query_margin(ray, Q.bound, far, Q.flags, cx.err_abs, cx.flags);
+                uint32_t seed_lo, seed_hi;
+                SRC::seed(Q, i, seed_lo, seed_hi);
+                rng.start(seed_lo, seed_hi, key, Q.first_sample + s);
+            } else {
+                rng.start(Q.seed_lo, Q.seed_hi, key, Q.first_sample + s);
+            }
             rng.i = 3u;  // draws 0..2 are the camera's u, v, time
             sum = sum + lit_sample<LIGHTS>(cx, Q.vol, ray, rng);
         }

@@ -55,8 +55,11 @@
 //                                                  round 0), each written back with hrt_probe_volume_update_device, or with
 //                                                  --probe-keep H in [0, 1) blended in (hrt_probe_volume_blend_device)
 //             [--probe-lit]                        with --probe-grid and --probe-box, instead of --probe-quad: a --w x --h camera
-//                                                  frame lit by the volume: per sample hrt_camera_rays, then hrt_trace_lit into
-//                                                  running sums; means and gamma by hrt_finalize_tiles, written as a render is
+//                                                  frame lit by the volume: all samples in ONE fused launch into running sums
+//                                                  (hrt_render_lit_device); means and gamma by hrt_finalize_tiles, written as a
+//                                                  render is.  With --lens ... the frame of that lens (a pinhole without); with
+//                                                  --views N [--orbit DEGREES] N lit frames in one launch
+//                                                  (hrt_render_lit_views_device), cameras, seeds and files as --views has them
 //             [--probe-tail K]                     with --probe-lit or --probe-bounces, K in 1 .. 6: their paths follow mirror and glass
 //                                                  and end in the volume at their K-th diffuse hit (hrt_trace_lit_paths,
 //                                                  hrt_probes_lit_paths_device) instead of at their first hit of any kind
@@ -161,6 +164,16 @@ static int ray_trace_frames() {
     return rc;
 }
 
+// The file of view k of --views: NAME_kkk.ppm for --out NAME.ppm.
+static std::string view_path(uint32_t k) {
+    const size_t dot = out_path.rfind('.'), slash = out_path.rfind('/');
+    const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+    const std::string stem = has_ext ? out_path.substr(0, dot) : out_path, ext = has_ext ? out_path.substr(dot) : std::string(".ppm");
+    char num[16];
+    std::snprintf(num, sizeof(num), "_%03u", k);
+    return stem + num + ext;
+}
+
 // --views: N cameras in one launch.  View k has seed + k and the camera turned by k * orbit; frame k goes to NAME_kkk.ppm.
 // With --lens every view is that lens behind its camera (hrt_render_lens_views).
 static int ray_trace_views() {
@@ -191,14 +204,7 @@ static int ray_trace_views() {
     }
     std::cout << "  Done in " << st.total_ms / 1000.0 << " seconds (kernel " << st.kernel_ms << " ms, " << (double)st.samples / st.kernel_ms / 1e3
               << " Msamples/s)" << std::endl;
-    const size_t dot = out_path.rfind('.'), slash = out_path.rfind('/');
-    const bool has_ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
-    const std::string stem = has_ext ? out_path.substr(0, dot) : out_path, ext = has_ext ? out_path.substr(dot) : std::string(".ppm");
-    for (uint32_t k = 0; rc == HRT_OK && k < n_views; ++k) {
-        char num[16];
-        std::snprintf(num, sizeof(num), "_%03u", k);
-        rc = hrt_write_ppm((stem + num + ext).c_str(), images.data() + frame * k, w, h);
-    }
+    for (uint32_t k = 0; rc == HRT_OK && k < n_views; ++k) rc = hrt_write_ppm(view_path(k).c_str(), images.data() + frame * k, w, h);
     if (rc != HRT_OK) std::cout << hrt_last_error() << std::endl;
     return rc;
 }
@@ -298,33 +304,42 @@ static int relight_probes(hrt_probe_volume *volume, const std::vector<float> &pr
     return HRT_OK;
 }
 
-// --probe-lit: the camera frame whose paths end in the volume, sample by sample into running sums, then the render's output stage.
+// --probe-lit: the frame whose paths end in the volume -- ONE fused launch of all samples into running sums (hrt_render_lit_device;
+// with --views the batch, hrt_render_lit_views_device, cameras, seeds and files as --views has them), then the render's output stage.
 static int probe_lit_frame(hrt_probe_volume *volume) {
     const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
-    const uint32_t npix = w * h, n_tiles = (npix + 63u) / 64u;  // the sums padded to whole tiles of 64 pixels for hrt_finalize_tiles
-    const hrt_camera cam = default_camera((float)w / (float)h);
-    std::cout << "Ray tracing a " << w << " x " << h << " image lit by the probes on the GPU using " << nsamples << " samples per pixel" << std::endl;
-    DeviceBuffer d_rays, d_sum;
-    const size_t sum_bytes = (size_t)n_tiles * 64u * 3u * sizeof(float);
-    if (!d_rays.alloc((size_t)npix * HRT_RAY_FLOATS * sizeof(float)) || !d_sum.alloc(sum_bytes)) return device_failed("hipMalloc");
-    if (hipMemset(d_sum.p, 0, sum_bytes) != hipSuccess) return device_failed("hipMemset");
-    int rc = HRT_OK;
-    for (uint32_t s = 0; rc == HRT_OK && s < nsamples; ++s) {
-        rc = hrt_camera_rays(&cam, w, h, s, seed, d_rays.as<float>(), nullptr);
-        if (rc == HRT_OK)
-            rc = probe_tail ? hrt_trace_lit_paths(device_scene, volume, d_rays.as<float>(), nullptr, npix, s, 1u, seed, HRT_RADIANCE_ACCUMULATE,
-                                                  lit_eval_flags(), 0.f, (uint32_t)probe_tail, d_sum.as<float>(), nullptr)
-                            : hrt_trace_lit(device_scene, volume, d_rays.as<float>(), nullptr, npix, s, 1u, seed, HRT_RADIANCE_ACCUMULATE, lit_eval_flags(),
-                                            0.f, d_sum.as<float>(), nullptr);
+    const uint32_t frames = n_views ? n_views : 1u;
+    const uint32_t npix = w * h, n_tiles = (uint32_t)(((uint64_t)frames * npix + 63u) / 64u);  // the sums padded to whole tiles of 64 pixels for hrt_finalize_tiles
+    const hrt_camera cam0 = default_camera((float)w / (float)h);
+    std::vector<hrt_lens_view> views(frames);
+    for (uint32_t k = 0; k < frames; ++k) {
+        views[k].lens = lens_params;  // without --lens the pinhole
+        views[k].lens.cam = n_views ? orbited(cam0, orbit_degrees * (double)k) : cam0;
+        views[k].seed = seed + k;
     }
+    if (n_views) std::cout << "Ray tracing " << n_views << " views of " << w << " x " << h << " pixels, " << orbit_degrees << " degrees apart,";
+    else std::cout << "Ray tracing a " << w << " x " << h << " image";
+    std::cout << " lit by the probes on the GPU using " << nsamples << " samples per pixel" << std::endl;
+    DeviceBuffer d_sum;
+    const size_t sum_bytes = (size_t)n_tiles * 64u * 3u * sizeof(float);
+    if (!d_sum.alloc(sum_bytes)) return device_failed("hipMalloc");
+    if (hipMemset(d_sum.p, 0, sum_bytes) != hipSuccess) return device_failed("hipMemset");
+    int rc = n_views ? hrt_render_lit_views_device(device_scene, volume, views.data(), n_views, w, h, 0u, nsamples, HRT_RADIANCE_ACCUMULATE, lit_eval_flags(),
+                                                   0.f, (uint32_t)probe_tail, d_sum.as<float>(), nullptr)
+                     : hrt_render_lit_device(device_scene, volume, &views[0].lens, w, h, 0u, nsamples, seed, HRT_RADIANCE_ACCUMULATE, lit_eval_flags(), 0.f,
+                                             (uint32_t)probe_tail, d_sum.as<float>(), nullptr);
     if (rc == HRT_OK) rc = hrt_finalize_tiles(d_sum.as<float>(), n_tiles, nsamples, HRT_FLAG_GAMMA, d_sum.as<float>(), nullptr);
     if (rc != HRT_OK) {
         std::cout << "the probe-lit frame failed: " << hrt_last_error() << std::endl;
         return rc;
     }
-    std::vector<float> image((size_t)npix * 3u, 0.f);
-    if (hipMemcpy(image.data(), d_sum.p, image.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return device_failed("hipMemcpy");
-    rc = hrt_write_ppm(out_path.c_str(), image.data(), w, h);
+    std::vector<float> images((size_t)frames * npix * 3u, 0.f);
+    if (hipMemcpy(images.data(), d_sum.p, images.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return device_failed("hipMemcpy");
+    if (!n_views) {
+        rc = hrt_write_ppm(out_path.c_str(), images.data(), w, h);
+    } else {
+        for (uint32_t k = 0; rc == HRT_OK && k < n_views; ++k) rc = hrt_write_ppm(view_path(k).c_str(), images.data() + (size_t)npix * 3u * k, w, h);
+    }
     if (rc != HRT_OK) std::cout << hrt_last_error() << std::endl;
     return rc;
 }
@@ -670,7 +685,7 @@ int main(int argc, char **argv) {
     }
     const bool probes = probe_grid_given;
     if (probes) {
-        const char *other = use_lens ? "--lens" : bake_quad != -1 ? "--bake-quad" : n_views != 0u ? "--views" : adaptive ? "--adaptive" : denoise ? "--denoise"
+        const char *other = use_lens && !probe_lit ? "--lens" : bake_quad != -1 ? "--bake-quad" : n_views != 0u && !probe_lit ? "--views" : adaptive ? "--adaptive" : denoise ? "--denoise"
                             : denoise_var ? "--denoise-var" : temporal ? "--temporal" : !devices.empty() ? "--gpus / --devices" : nullptr;
         if (other) {
             std::cerr << "--probe-grid traces light probes on one GPU: it cannot be combined with " << other << std::endl;

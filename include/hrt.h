@@ -1245,8 +1245,8 @@ HRT_API int hrt_probe_volume_blend(hrt_probe_volume *volume, const float *coeffs
  * 1 .. HRT_MAXBOUNCES; then for the three entry points with a volume everything "Lit rays" checks after the flags, in its order; for
  * hrt_path_tails a bias that is not finite; (n == 0 returns HRT_OK here and launches nothing;) d_rays NULL or not 16-byte aligned,
  * d_keys not 4-byte aligned, d_out NULL or not 16-byte aligned, n > 2^31 - 1; then a NULL scene and the library state.
- * OUT OF SCOPE (DESIGN.md section 5 "Lit paths"): lens-camera sources with a tail (the fused lit frame), the cooperative look-up,
- * parking the lanes whose tail fires, probes that move, multi-GPU. */
+ * OUT OF SCOPE (DESIGN.md section 5 "Lit paths"): the cooperative look-up, parking the lanes whose tail fires, probes that move,
+ * multi-GPU; lens-camera sources with a tail are not in this section but in "Lit frames" below. */
 #define HRT_TAIL_FLOATS 16u               /* floats of a tail record */
 #define HRT_TAIL_REACHED 0x80000000u      /* word [11] of a tail record: the tail was reached */
 HRT_API int hrt_trace_lit_paths(hrt_scene *scene, const hrt_probe_volume *volume, const float *d_rays, const uint32_t *d_keys, uint32_t n,
@@ -1260,6 +1260,49 @@ HRT_API int hrt_probes_lit_paths_device(hrt_scene *scene, const hrt_probe_volume
 HRT_API int hrt_probes_lit_paths(hrt_scene *scene, const hrt_probe_volume *volume, const float *probes, const uint32_t *keys, uint32_t n,
                                  uint32_t spp, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, uint32_t tail_after, float *out,
                                  hrt_stats *stats /* may be NULL */);
+
+/* ---- Lit frames: the frame of a lens camera whose paths END in a probe volume -- "Lens cameras" in front of "Lit rays" or "Lit
+ * paths", fused: one launch for all samples of a frame, no w*h*32-byte ray buffer, any projection, and a batch form.
+ * THE RULE.  Sample s of pixel p = y*w + x is the value that hrt_trace_lit (tail_after == 0) or hrt_trace_lit_paths (tail_after in
+ * 1 .. HRT_MAXBOUNCES) gives for record p of hrt_lens_rays(lens, w, h, s, seed), called with d_keys = NULL (key p), first_sample = s,
+ * n_samples = 1 and the same seed, flags, eval_flags and bias.  The frame is the sum of those values in ascending sample order,
+ * sum = 0.f (or d_frame on entry, under HRT_RADIANCE_ACCUMULATE), sum = sum + value, divided by (float)n_samples -- or the running
+ * sums.  HRT_FLAG_GAMMA is applied after the division, as in lens frames.  A DEGENERATE sample (a fisheye pixel outside the circle,
+ * a thin lens with c <= 0: see "Lens cameras") adds nothing and still counts in the divisor.  All arithmetic is fp32 without fused
+ * multiply-add; every bit is the composition's.
+ * hrt_render_lit_device: d_frame (device, h*w*3 floats, row-major) receives the means over samples [first_sample, first_sample +
+ * n_samples), or with HRT_RADIANCE_ACCUMULATE the running sums.  Asynchronous on `stream`; touches none of the scene's per-launch
+ * state and only READS the volume (the CONCURRENCY note of "Lit rays").  `flags` are hrt_render_lens_device's, refused by the same
+ * names and texts: HRT_FLAG_EXACT_ONLY, HRT_FLAG_MESH_BRUTE (with EXACT_ONLY), HRT_FLAG_NO_LDS_TREE, HRT_RADIANCE_ACCUMULATE,
+ * HRT_FLAG_GAMMA (not with ACCUMULATE).  `eval_flags` and `bias` are hrt_trace_lit's: HRT_PROBE_EVAL_FACING, HRT_LIT_VISIBLE (the
+ * volume needs its depth moments).  With PERSPECTIVE and aperture_radius == 0 the frame is hrt_camera_rays + hrt_trace_lit[_paths]
+ * per sample, bit for bit.
+ * hrt_render_lit: the same into a HOST buffer, blocking, samples [0, spp); stats as hrt_render_lens (samples = w*h*spp).
+ * HRT_RADIANCE_ACCUMULATE is refused (the sums live on the device).
+ * hrt_render_lit_views_device / hrt_render_lit_views: the batch, laid out, keyed and staged as "Batched lens views" (its
+ * CONCURRENCY note and LIMIT hold; `views` is hrt_lens_view, unchanged).  CONTRACT: frame v is bit-identical to
+ * hrt_render_lit_device(scene, volume, &views[v].lens, w, h, first_sample, n_samples, views[v].seed, ...).  Stats count n_views * w *
+ * h * spp samples; n_views == 0 zeroes them.
+ * Checked in this order, HRT_ERR_INVALID with hrt_last_error() naming the entry point and the culprit: (the blocking forms:
+ * HRT_RADIANCE_ACCUMULATE;) flags; the lens, as hrt_lens_rays checks it -- for a batch (an empty one skips to tail_after) views
+ * NULL, then every lens, the message prefixed "views[<index>].lens"; the frame; n_samples == 0; first_sample + n_samples > 2^32; the
+ * output NULL or not 4-byte aligned; for a batch the limit; tail_after > HRT_MAXBOUNCES; (n_views == 0 returns HRT_OK here and
+ * launches nothing;) eval_flags, the volume and the bias in the order of "Lit rays"; then a NULL scene, a volume that lives on
+ * another device than the scene, and the library state.
+ * OUT OF SCOPE (DESIGN.md section 5 "Lit frames"): adaptive lit frames (the tile-list source), lit feature buffers, the cooperative
+ * or parked look-up, probes that move, the streaming kernel, multi-GPU. */
+HRT_API int hrt_render_lit_device(hrt_scene *scene, const hrt_probe_volume *volume, const hrt_lens *lens, uint32_t w, uint32_t h,
+                                  uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias,
+                                  uint32_t tail_after, float *d_frame, void *stream);
+HRT_API int hrt_render_lit(hrt_scene *scene, const hrt_probe_volume *volume, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t spp,
+                           uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, uint32_t tail_after, float *out_rgb,
+                           hrt_stats *stats /* may be NULL */);
+HRT_API int hrt_render_lit_views_device(hrt_scene *scene, const hrt_probe_volume *volume, const hrt_lens_view *views, uint32_t n_views,
+                                        uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples, uint32_t flags, uint32_t eval_flags,
+                                        float bias, uint32_t tail_after, float *d_frames, void *stream);
+HRT_API int hrt_render_lit_views(hrt_scene *scene, const hrt_probe_volume *volume, const hrt_lens_view *views, uint32_t n_views, uint32_t w,
+                                 uint32_t h, uint32_t spp, uint32_t flags, uint32_t eval_flags, float bias, uint32_t tail_after,
+                                 float *out_rgb, hrt_stats *stats /* may be NULL */);
 
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
