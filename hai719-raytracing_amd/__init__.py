@@ -411,6 +411,12 @@ def device_lib() -> C.CDLL:
                                                     C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.hrt_render_lit_views.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(LensView), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                              C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_bake_lit_device.argtypes = lib.hrt_trace_lit_paths.argtypes
+        lib.hrt_bake_lit.argtypes = lib.hrt_probes_lit_paths.argtypes
+        lib.hrt_render_lit_adaptive_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Lens), C.c_uint32, C.c_uint32, C.POINTER(Adaptive), C.c_uint64,
+                                                       C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.hrt_render_lit_adaptive.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Lens), C.c_uint32, C.c_uint32, C.POINTER(Adaptive), C.c_uint64,
+                                                C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         lib.hrt_probe_volume_blend_device.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         lib.hrt_probe_volume_blend.argtypes = [C.c_void_p, C.c_void_p, C.c_float]
         lib.hrt_debug_pick_kernel.argtypes = [C.POINTER(PickInput), C.c_char_p, C.c_size_t]
@@ -871,6 +877,23 @@ class DeviceScene:
         return DeviceScene._radiance_batch(self, "bake", "points", "hrt_bake_device", "hrt_bake", points, spp, first_sample, seed, keys, out,
                                            accumulate, flags, stats)
 
+    def bake_lit(self, points, volume: "ProbeVolume", spp: int = 1, first_sample: int = 0, seed: int = 1, keys=None, out=None,
+                 accumulate: bool = False, flags: int = 0, stats: Optional[Stats] = None, eval_flags: int = 0, bias: float = 0.0,
+                 tail_after: Optional[int] = None):
+        """hrt_bake_lit*: the final gather -- ``bake`` whose paths END in ``volume`` (include/hrt.h "Lit bakes") -> (n, 3) float32 in
+        the units of ``bake``: sample s of a point is ``trace_lit`` of that point's record of ``bake_rays(points, s, seed, keys)``,
+        in one launch for all samples and without the ray buffer.  ``tail_after`` None: one segment, the hit shaded with its own
+        direct light and emission and the volume behind it; K in 1 .. MAXBOUNCES: mirror and glass followed, the volume at the K-th
+        diffuse hit.  ``eval_flags`` as ``trace_lit``.  ``bias`` is the LOOK-UP's offset along the normal at the hit, as
+        ``trace_lit``'s; it is not the point record's own bias float (column 7 of ``points``), which moves the ray's origin off the
+        baked surface -- the two are independent.  A non-finite ``bias`` is refused here.  Everything else -- points, samples, keys,
+        ``out``, ``accumulate``, ``stats``, ``flags`` and the torch (asynchronous on the current torch stream) / NumPy (blocking)
+        forms -- as ``bake``.  The call only reads the volume: order an ``update`` or ``blend`` after it."""
+        flags = int(flags) | (RADIANCE_ACCUMULATE if accumulate else 0)
+        after = _lit_args("bake_lit", volume, eval_flags, bias) + (0 if tail_after is None else _tail_args("bake_lit", "", tail_after)[1][0],)
+        return DeviceScene._radiance_batch(self, "bake_lit", "points", "hrt_bake_lit_device", "hrt_bake_lit", points, spp, first_sample, seed, keys,
+                                           out, accumulate, flags, stats, volume=volume, after=after)
+
     def probes(self, points, spp: int = 1, first_sample: int = 0, seed: int = 1, keys=None, out=None, accumulate: bool = False,
                flags: int = 0, stats: Optional[Stats] = None):
         """hrt_probes*: the radiance arriving at points in space from every direction, (n, PROBE_FLOATS) float32 rows {P, time},
@@ -1095,6 +1118,33 @@ class DeviceScene:
         return DeviceScene._frames(self, "render_lit", (h, w, 3),
                                    ("hrt_render_lit_device", (volume._h, C.byref(lens), w, h, first_sample, spp, seed, flags) + after),
                                    ("hrt_render_lit", (volume._h, C.byref(lens), w, h, spp, seed, flags) + after), first_sample, out, accumulate, stats)
+
+    def render_lit_adaptive(self, lens: Lens, volume: "ProbeVolume", w: int, h: int, min_spp: int, max_spp: int, threshold: float, seed: int = 1,
+                            flags: int = 0, out=None, stats: Optional[Stats] = None, eval_flags: int = 0, bias: float = 0.0,
+                            tail_after: Optional[int] = None):
+        """hrt_render_lit_adaptive*: ``render_lens_adaptive`` with the sums of ``render_lit`` (include/hrt.h "Adaptive lit frames") ->
+        (frame (h, w, 3) float32, tile_spp (tiles_y, tiles_x) uint32).  Every tile of the frame is bit-identical to the same tile
+        of ``render_lit`` at that tile's count.  ``eval_flags``, ``bias`` and ``tail_after`` as ``render_lit``; ``out``, ``stats``,
+        ``flags`` and the torch / NumPy forms as ``render_lens_adaptive``.  The call shares the round scratch with the other
+        adaptive calls of the scene (no overlap with them) and only reads the volume."""
+        who = "render_lit_adaptive"
+        p = Adaptive(min_spp, max_spp, threshold)
+        ty, tx = (h + TILE - 1) // TILE, (w + TILE - 1) // TILE
+        after = _lit_args(who, volume, eval_flags, bias) + (0 if tail_after is None else _tail_args(who, "", tail_after)[1][0],)
+        if out is not None:
+            import torch
+            _check_tensor(who, "out", out, (h, w, 3))
+            if stats is not None:
+                raise ValueError(f"{who}: stats are the blocking form's (no `out`)")
+            counts = torch.empty((ty, tx), dtype=torch.int32, device=out.device)
+            self._check(self._lib.hrt_render_lit_adaptive_device(self._h, volume._h, C.byref(lens), w, h, C.byref(p), seed, int(flags), *after,
+                                                                 _ptr(out), _ptr(counts), _stream(out.device)))
+            return out, counts
+        frame = np.empty((h, w, 3), dtype=np.float32)
+        spp = np.empty((ty, tx), dtype=np.uint32)
+        self._check(self._lib.hrt_render_lit_adaptive(self._h, volume._h, C.byref(lens), w, h, C.byref(p), seed, int(flags), *after,
+                                                      frame.ctypes.data, spp.ctypes.data, _ref(stats)))
+        return frame, spp
 
     def render_lit_views(self, lenses, volume: "ProbeVolume", w: int, h: int, spp: int, seeds=None, flags: int = 0, first_sample: int = 0,
                          out=None, accumulate: bool = False, stats: Optional[Stats] = None, eval_flags: int = 0, bias: float = 0.0,

@@ -1138,7 +1138,9 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 #include "hrt_probe_lit.hip"
 #include "hrt_lit_paths.hip"
 #include "hrt_lit_frames.hip"
+#include "hrt_bake_lit.hip"
 #include "hrt_lens_adaptive.hip"
+#include "hrt_lit_adaptive.hip"
 #include "hrt_views.hip"
 
 int hrt_kd_build_gpu(const hrt_kd_build_input *in, hrt_kd_build_output *out, void *user) {

@@ -11,6 +11,10 @@
 // The lens travels as a kernel argument, the lists and keep words are ad_compact / ad_words (shared with hrt_render_adaptive: the
 // two may not overlap on one scene), the sums are la_tiles; the work-queue head, the path pool, the camera blocks and the trace
 // launches' events are not touched.
+//
+// The host side of the rounds -- lens_adaptive_run, lens_adaptive_frame, lens_adaptive_host -- takes the launch of the tile-list
+// kernel as a callable: lens_tiles_launch here, the lit launch of hrt_lit_adaptive.hip (hrt_render_lit_adaptive*), which shares
+// everything else with this file.
 
 // One launch of the tile-list lens kernel (the scene entered): samples [first, first + add) of the n_active tiles of `list` (NULL:
 // every tile) onto the running sums at `sums`, between events e0 and e1 on `stream`.
@@ -32,13 +36,17 @@ static int lens_tiles_launch(hrt_scene *s, const DLens &L, uint32_t w, uint32_t 
     return HRT_OK;
 }
 
-// The rounds (adaptive_rounds, hrt_adaptive.hip) over all tiles of the frame with the lens kernel: d_sums (tile-major, every
-// tile) ends with the means, d_counts with each tile's count (NULL: the scene's own count map).  ev: two pairs of timing events,
-// the call's own: pair 0 around round 0's launch, pair 1 around every later one.  The stream is synchronised once per round from
-// round 1 on, and the times are read after it; a fault of a round's kernels ends the call there, before the length of the next
-// list is believed.
-static int lens_adaptive_run(hrt_scene *s, const DLens &L, uint32_t w, uint32_t h, const hrt_adaptive *p, uint64_t seed, uint32_t flags,
-                             float *d_sums, uint32_t *d_counts, hipStream_t stream, const Event ev[4], double *kernel_ms) {
+// The rounds (adaptive_rounds, hrt_adaptive.hip) over all tiles of the frame with a tile-list kernel: d_sums (tile-major, every
+// tile) ends with the means, d_counts with each tile's count (NULL: the scene's own count map).
+//   launch(list, n, first, add, sums, e0, e1)   one launch of the tile-list kernel between the events: lens_tiles_launch here, the
+//                                               lit one in hrt_lit_adaptive.hip -- the one thing the two clients do not share
+// ev: two pairs of timing events, the call's own: pair 0 around round 0's launch, pair 1 around every later one.  The stream is
+// synchronised once per round from round 1 on, and the times are read after it; a fault of a round's kernels ends the call there,
+// before the length of the next list is believed.
+extern "C++" {
+template <class Launch>
+static int lens_adaptive_run(hrt_scene *s, uint32_t w, uint32_t h, const hrt_adaptive *p, uint32_t flags, float *d_sums, uint32_t *d_counts,
+                             hipStream_t stream, const Event ev[4], double *kernel_ms, Launch launch) {
     *kernel_ms = 0.0;
     auto add_time = [&](hipEvent_t e0, hipEvent_t e1) -> int {  // after the synchronisation that covers e1
         float f = 0.f;
@@ -50,13 +58,14 @@ static int lens_adaptive_run(hrt_scene *s, const DLens &L, uint32_t w, uint32_t 
         s, AdFrame{w, h, (w + HRT_TILE - 1u) / HRT_TILE, hrt_tiles_total(w, h), 0u, 1u}, p, (flags & HRT_FLAG_GAMMA) != 0u, d_sums, d_counts, stream,
         [&](const uint32_t *list, uint32_t n, uint32_t first, uint32_t add, float *sums, uint32_t round) -> int {
             const Event *const e = ev + (round == 0u ? 0 : 2);
-            return lens_tiles_launch(s, L, w, h, list, n, first, add, seed, flags, sums, stream, e[0], e[1]);
+            return launch(list, n, first, add, sums, (hipEvent_t)e[0], (hipEvent_t)e[1]);
         },
         [&](uint32_t round) -> int {
             const int rc = round == 1u ? add_time(ev[0], ev[1]) : HRT_OK;
             return rc != HRT_OK ? rc : add_time(ev[2], ev[3]);
         });
 }
+}  // extern "C++"
 
 // The checks of both entry points, in the header's order (all before the scene and the library state); fills L.
 static int lens_adaptive_check(const std::string &who, const hrt_lens *lens, uint32_t w, uint32_t h, const hrt_adaptive *p, uint32_t flags,
@@ -78,8 +87,10 @@ static int lens_adaptive_check(const std::string &who, const hrt_lens *lens, uin
 
 // The rounds into la_tiles on `stream`, then the row-major frame into d_frame (the scene entered).  The sums buffer is read by the
 // previous call's assemble launch: one on another stream is waited for on `stream`.
-static int lens_adaptive_frame(hrt_scene *s, const DLens &L, uint32_t w, uint32_t h, const hrt_adaptive *p, uint64_t seed, uint32_t flags,
-                               float *d_frame, uint32_t *d_counts, hipStream_t stream, double *kernel_ms) {
+extern "C++" {
+template <class Launch>
+static int lens_adaptive_frame(hrt_scene *s, uint32_t w, uint32_t h, const hrt_adaptive *p, uint32_t flags, float *d_frame, uint32_t *d_counts,
+                               hipStream_t stream, double *kernel_ms, Launch launch) {
     const uint32_t tiles = hrt_tiles_total(w, h);
     const size_t tile_bytes = (size_t)tiles * 192u * sizeof(float);
     int rc = s->la_tiles.cap < tile_bytes ? s->la_reader.sync() : HRT_OK;  // the old sums are freed: their last reader is done
@@ -89,35 +100,22 @@ static int lens_adaptive_frame(hrt_scene *s, const DLens &L, uint32_t w, uint32_
     Event ev[4];
     for (Event &e : ev)
         if ((rc = e.ready()) != HRT_OK) return rc;
-    if ((rc = lens_adaptive_run(s, L, w, h, p, seed, flags, s->la_tiles.as<float>(), d_counts, stream, ev, kernel_ms)) != HRT_OK) return rc;
+    if ((rc = lens_adaptive_run(s, w, h, p, flags, s->la_tiles.as<float>(), d_counts, stream, ev, kernel_ms, launch)) != HRT_OK) return rc;
     if ((rc = hrt_assemble_frame(s->la_tiles.as<float>(), tiles, w, h, 1, d_frame, stream)) != HRT_OK) return rc;
     return s->la_reader.mark(stream);
 }
 
-int hrt_render_lens_adaptive_device(hrt_scene *s, const hrt_lens *lens, uint32_t w, uint32_t h, const hrt_adaptive *params, uint64_t seed,
-                                    uint32_t flags, float *d_frame, uint32_t *d_tile_spp, void *stream) {
-    const std::string who = "hrt_render_lens_adaptive_device";
-    DLens L;
-    int rc = lens_adaptive_check(who, lens, w, h, params, flags, d_frame, "d_frame", d_tile_spp, "d_tile_spp", L);
-    if (rc == HRT_OK) rc = enter_scene(who, s);
-    if (rc != HRT_OK) return rc;
-    double ms = 0.0;
-    return lens_adaptive_frame(s, L, w, h, params, seed, flags, d_frame, d_tile_spp, (hipStream_t)stream, &ms);
-}
-
-// Blocking, into host memory, on the null stream.  The count map is the scene's (ad_words), as hrt_render_adaptive's.
-int hrt_render_lens_adaptive(hrt_scene *s, const hrt_lens *lens, uint32_t w, uint32_t h, const hrt_adaptive *params, uint64_t seed,
-                             uint32_t flags, float *out_rgb, uint32_t *out_tile_spp, hrt_stats *stats) {
-    const std::string who = "hrt_render_lens_adaptive";
-    DLens L;
-    int rc = lens_adaptive_check(who, lens, w, h, params, flags, out_rgb, "out_rgb", out_tile_spp, "out_tile_spp", L);
-    if (rc == HRT_OK) rc = enter_scene(who, s);
-    if (rc != HRT_OK) return rc;
+// The blocking form (the scene entered), into host memory on the null stream.  The count map is the scene's (ad_words), as
+// hrt_render_adaptive's.
+template <class Launch>
+static int lens_adaptive_host(hrt_scene *s, uint32_t w, uint32_t h, const hrt_adaptive *p, uint32_t flags, float *out_rgb, uint32_t *out_tile_spp,
+                              hrt_stats *stats, Launch launch) {
     const auto t0 = std::chrono::steady_clock::now();
     const size_t frame_bytes = (size_t)w * h * 3u * sizeof(float);
+    int rc;
     if ((rc = s->la_frame.grow(frame_bytes)) != HRT_OK) return rc;
     double ms = 0.0;
-    if ((rc = lens_adaptive_frame(s, L, w, h, params, seed, flags, s->la_frame.as<float>(), nullptr, nullptr, &ms)) != HRT_OK) return rc;
+    if ((rc = lens_adaptive_frame(s, w, h, p, flags, s->la_frame.as<float>(), nullptr, nullptr, &ms, launch)) != HRT_OK) return rc;
     HIP_TRY(hipMemcpy(out_rgb, s->la_frame.p, frame_bytes, hipMemcpyDeviceToHost));
     uint64_t samples = 0;  // degenerate samples count: every in-image pixel has its tile's count
     if ((rc = adaptive_counts_to_host(s, w, h, out_tile_spp, stats ? &samples : nullptr)) != HRT_OK) return rc;
@@ -127,4 +125,33 @@ int hrt_render_lens_adaptive(hrt_scene *s, const hrt_lens *lens, uint32_t w, uin
         stats->waves_launched = 0u;
     }
     return HRT_OK;
+}
+}  // extern "C++"
+
+int hrt_render_lens_adaptive_device(hrt_scene *s, const hrt_lens *lens, uint32_t w, uint32_t h, const hrt_adaptive *params, uint64_t seed,
+                                    uint32_t flags, float *d_frame, uint32_t *d_tile_spp, void *stream) {
+    const std::string who = "hrt_render_lens_adaptive_device";
+    DLens L;
+    int rc = lens_adaptive_check(who, lens, w, h, params, flags, d_frame, "d_frame", d_tile_spp, "d_tile_spp", L);
+    if (rc == HRT_OK) rc = enter_scene(who, s);
+    if (rc != HRT_OK) return rc;
+    double ms = 0.0;
+    return lens_adaptive_frame(s, w, h, params, flags, d_frame, d_tile_spp, (hipStream_t)stream, &ms,
+                               [&](const uint32_t *list, uint32_t n, uint32_t first, uint32_t add, float *sums, hipEvent_t e0, hipEvent_t e1) -> int {
+                                   return lens_tiles_launch(s, L, w, h, list, n, first, add, seed, flags, sums, (hipStream_t)stream, e0, e1);
+                               });
+}
+
+// Blocking, into host memory, on the null stream.
+int hrt_render_lens_adaptive(hrt_scene *s, const hrt_lens *lens, uint32_t w, uint32_t h, const hrt_adaptive *params, uint64_t seed,
+                             uint32_t flags, float *out_rgb, uint32_t *out_tile_spp, hrt_stats *stats) {
+    const std::string who = "hrt_render_lens_adaptive";
+    DLens L;
+    int rc = lens_adaptive_check(who, lens, w, h, params, flags, out_rgb, "out_rgb", out_tile_spp, "out_tile_spp", L);
+    if (rc == HRT_OK) rc = enter_scene(who, s);
+    if (rc != HRT_OK) return rc;
+    return lens_adaptive_host(s, w, h, params, flags, out_rgb, out_tile_spp, stats,
+                              [&](const uint32_t *list, uint32_t n, uint32_t first, uint32_t add, float *sums, hipEvent_t e0, hipEvent_t e1) -> int {
+                                  return lens_tiles_launch(s, L, w, h, list, n, first, add, seed, flags, sums, nullptr, e0, e1);
+                              });
 }

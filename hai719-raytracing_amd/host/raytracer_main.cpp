@@ -63,6 +63,14 @@
 //             [--probe-tail K]                     with --probe-lit or --probe-bounces, K in 1 .. 6: their paths follow mirror and glass
 //                                                  and end in the volume at their K-th diffuse hit (hrt_trace_lit_paths,
 //                                                  hrt_probes_lit_paths_device) instead of at their first hit of any kind
+//             [--bake-lit]                         with --bake-quad INDEX, --probe-grid and --probe-box: the FINAL GATHER -- the grid
+//                                                  is path-traced (or relit with --probe-bounces K [--probe-keep H]) and the
+//                                                  lightmap of quad INDEX is written by ONE hrt_bake_lit_device call instead of
+//                                                  hrt_bake: every sample's path ends in the volume at its first hit, or with
+//                                                  --probe-tail K at its K-th diffuse hit; --probe-facing and --probe-visible
+//                                                  describe the look-up there; --bake-side and --bake-bias the points, as ever
+//             --probe-lit --adaptive THRESHOLD [--spp-min N]  the lit frame with per-tile counts (hrt_render_lit_adaptive), --lens
+//                                                  honoured; prints the mean spp, as --lens --adaptive does (not with --views)
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -110,6 +118,7 @@ static long probe_quad = -1;
 static int32_t probe_side = 1;
 static bool probe_bounces_given = false, probe_keep_given = false, probe_lit = false;  // --probe-bounces: hrt_probes_lit_device rounds; --probe-lit: hrt_trace_lit
 static long probe_bounces = 0;
+static bool bake_lit = false;  // --bake-lit: the lightmap of --bake-quad by hrt_bake_lit_device against the grid's volume
 static long probe_tail = 0;  // --probe-tail K: the lit launches are "Lit paths" with tail_after = K; 0: not given, one segment
 static float probe_keep = 0.f;
 static hrt_temporal_params temporal_params = {0.02f, 64.f, 0.05f, 0.1f, 0.05f};  // the Python TemporalParams()
@@ -308,6 +317,26 @@ static int relight_probes(hrt_probe_volume *volume, const std::vector<float> &pr
 // with --views the batch, hrt_render_lit_views_device, cameras, seeds and files as --views has them), then the render's output stage.
 static int probe_lit_frame(hrt_probe_volume *volume) {
     const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
+    if (adaptive) {  // per-tile counts from --spp-min up to --spp (hrt_render_lit_adaptive; never with --views)
+        hrt_lens lens = lens_params;  // without --lens the pinhole
+        lens.cam = default_camera((float)w / (float)h);
+        std::vector<float> image((size_t)w * h * 3, 0.f);
+        std::cout << "Ray tracing a " << w << " x " << h << " image lit by the probes on the GPU using " << adaptive_params.min_spp << " to " << nsamples
+                  << " samples per pixel (adaptive, threshold " << adaptive_params.threshold << ")" << std::endl;
+        hrt_stats st;
+        adaptive_params.max_spp = nsamples;
+        int arc = hrt_render_lit_adaptive(device_scene, volume, &lens, w, h, &adaptive_params, seed, HRT_FLAG_GAMMA, lit_eval_flags(), 0.f,
+                                          (uint32_t)probe_tail, image.data(), nullptr, &st);
+        if (arc != HRT_OK) {
+            std::cout << "hrt_render_lit_adaptive failed: " << hrt_last_error() << std::endl;
+            return arc;
+        }
+        std::cout << "  Done in " << st.total_ms / 1000.0 << " seconds (kernel " << st.kernel_ms << " ms, " << (double)st.samples / st.kernel_ms / 1e3
+                  << " Msamples/s, mean " << (double)st.samples / ((double)w * h) << " spp)" << std::endl;
+        arc = hrt_write_ppm(out_path.c_str(), image.data(), w, h);
+        if (arc != HRT_OK) std::cout << hrt_last_error() << std::endl;
+        return arc;
+    }
     const uint32_t frames = n_views ? n_views : 1u;
     const uint32_t npix = w * h, n_tiles = (uint32_t)(((uint64_t)frames * npix + 63u) / 64u);  // the sums padded to whole tiles of 64 pixels for hrt_finalize_tiles
     const hrt_camera cam0 = default_camera((float)w / (float)h);
@@ -344,6 +373,33 @@ static int probe_lit_frame(hrt_probe_volume *volume) {
     return rc;
 }
 
+// --bake-lit: the lightmap of --bake-quad whose paths end in the volume -- ONE fused launch of all samples (hrt_bake_lit_device),
+// written as --bake-quad writes its own.
+static int bake_lit_lightmap(const hrt_scene_desc &desc, hrt_probe_volume *volume) {
+    const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
+    std::vector<float> points((size_t)w * h * HRT_RAY_FLOATS), map((size_t)w * h * 3, 0.f);
+    int rc = hrt_bake_quad_points(&desc.quads[bake_quad], w, h, bake_side, 0.f, bake_bias, points.data());
+    if (rc != HRT_OK) {
+        std::cout << "hrt_bake_quad_points failed: " << hrt_last_error() << std::endl;
+        return rc;
+    }
+    std::cout << "Baking a " << w << " x " << h << " lightmap of quad " << bake_quad << " (side " << bake_side << ", bias " << bake_bias
+              << ") lit by the probes on the GPU using " << nsamples << " samples per texel" << std::endl;
+    DeviceBuffer d_points, d_map;
+    if (!d_points.alloc(points.size() * sizeof(float)) || !d_map.alloc(map.size() * sizeof(float))) return device_failed("hipMalloc");
+    if (hipMemcpy(d_points.p, points.data(), points.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return device_failed("hipMemcpy");
+    rc = hrt_bake_lit_device(device_scene, volume, d_points.as<float>(), nullptr, w * h, 0u, nsamples, seed, 0u, lit_eval_flags(), 0.f,
+                             (uint32_t)probe_tail, d_map.as<float>(), nullptr);
+    if (rc != HRT_OK) {
+        std::cout << "hrt_bake_lit_device failed: " << hrt_last_error() << std::endl;
+        return rc;
+    }
+    if (hipMemcpy(map.data(), d_map.p, map.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return device_failed("hipMemcpy");
+    rc = hrt_write_ppm(out_path.c_str(), map.data(), w, h);
+    if (rc != HRT_OK) std::cout << hrt_last_error() << std::endl;
+    return rc;
+}
+
 // The r_max of --probe-visible: --probe-rmax, or 1.5 x the diagonal of a grid cell, in fp32.
 static float probe_depth_rmax() {
     if (probe_rmax_given) return probe_rmax;
@@ -364,7 +420,7 @@ static int light_probes(const hrt_scene_desc &desc) {
     }
     hrt_stats st;
     hrt_probe_volume *volume = nullptr;
-    const bool needs_volume = probe_quad_given || probe_lit || probe_bounces_given;
+    const bool needs_volume = probe_quad_given || probe_lit || probe_bounces_given || bake_lit;
     auto leave = [&](int code, const char *what) {
         if (code != HRT_OK && what) std::cout << what << " failed: " << hrt_last_error() << std::endl;
         hrt_probe_volume_destroy(volume);
@@ -401,6 +457,7 @@ static int light_probes(const hrt_scene_desc &desc) {
         }
     }
     if (probe_lit) return leave(probe_lit_frame(volume), nullptr);
+    if (bake_lit) return leave(bake_lit_lightmap(desc, volume), nullptr);
     if (probe_quad_given) {
         const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
         std::vector<float> points((size_t)w * h * HRT_RAY_FLOATS), map((size_t)w * h * 3, 0.f);
@@ -481,8 +538,8 @@ int main(int argc, char **argv) {
     std::vector<int> devices;
     for (int i = 1; i < argc; i += 2) {
         const std::string k = argv[i];
-        if (k == "--probe-facing" || k == "--probe-visible" || k == "--probe-lit") {  // the options without a value
-            (k == "--probe-facing" ? probe_facing : k == "--probe-visible" ? probe_visible : probe_lit) = true;
+        if (k == "--probe-facing" || k == "--probe-visible" || k == "--probe-lit" || k == "--bake-lit") {  // the options without a value
+            (k == "--probe-facing" ? probe_facing : k == "--probe-visible" ? probe_visible : k == "--probe-lit" ? probe_lit : bake_lit) = true;
             --i;
             continue;
         }
@@ -647,7 +704,15 @@ int main(int argc, char **argv) {
         std::cerr << "--probe-lit writes a camera frame, --probe-quad a lightmap: give one of them" << std::endl;
         return 2;
     }
-    if (probe_tail && !probe_bounces_given && !probe_lit) {
+    if (bake_lit && (bake_quad == -1 || !probe_grid_given)) {
+        std::cerr << "--bake-lit bakes a lightmap whose paths end in a probe grid: give --bake-quad INDEX, --probe-grid NX,NY,NZ and --probe-box x0,y0,z0,x1,y1,z1" << std::endl;
+        return 2;
+    }
+    if (bake_lit && (probe_lit || probe_quad_given)) {
+        std::cerr << "--bake-lit writes a gathered lightmap, --probe-lit a camera frame, --probe-quad a looked-up lightmap: give one of them" << std::endl;
+        return 2;
+    }
+    if (probe_tail && !probe_bounces_given && !probe_lit && !bake_lit) {
         std::cerr << "--probe-tail says where the paths of --probe-lit and --probe-bounces end: give one of them" << std::endl;
         return 2;
     }
@@ -655,7 +720,7 @@ int main(int argc, char **argv) {
         std::cerr << "--probe-keep blends the rounds of --probe-bounces: give --probe-bounces K" << std::endl;
         return 2;
     }
-    if (probe_bounces_given && !probe_quad_given && !probe_lit) {
+    if (probe_bounces_given && !probe_quad_given && !probe_lit && !bake_lit) {
         std::cerr << "--probe-bounces relights the probe grid of a lightmap or a frame: give --probe-quad INDEX or --probe-lit" << std::endl;
         return 2;
     }
@@ -663,11 +728,11 @@ int main(int argc, char **argv) {
         std::cerr << "--probe-bounces x --spp must be at most 2^32 (sample indices do not wrap)" << std::endl;
         return 2;
     }
-    if (!probe_quad_given && (probe_side_given || (probe_facing && !probe_lit))) {
+    if (!probe_quad_given && (probe_side_given || (probe_facing && !probe_lit && !bake_lit))) {
         std::cerr << (probe_side_given ? "--probe-side" : "--probe-facing") << " describes the look-up of a probe grid over a quad: give --probe-quad INDEX" << std::endl;
         return 2;
     }
-    if (!probe_quad_given && !probe_lit && (probe_visible || probe_rmax_given)) {
+    if (!probe_quad_given && !probe_lit && !bake_lit && (probe_visible || probe_rmax_given)) {
         std::cerr << (probe_visible ? "--probe-visible" : "--probe-rmax") << " describes the look-up of a probe grid over a quad: give --probe-quad INDEX" << std::endl;
         return 2;
     }
@@ -685,7 +750,7 @@ int main(int argc, char **argv) {
     }
     const bool probes = probe_grid_given;
     if (probes) {
-        const char *other = use_lens && !probe_lit ? "--lens" : bake_quad != -1 ? "--bake-quad" : n_views != 0u && !probe_lit ? "--views" : adaptive ? "--adaptive" : denoise ? "--denoise"
+        const char *other = use_lens && !probe_lit ? "--lens" : bake_quad != -1 && !bake_lit ? "--bake-quad" : n_views != 0u && !probe_lit ? "--views" : adaptive && !probe_lit ? "--adaptive" : denoise ? "--denoise"
                             : denoise_var ? "--denoise-var" : temporal ? "--temporal" : !devices.empty() ? "--gpus / --devices" : nullptr;
         if (other) {
             std::cerr << "--probe-grid traces light probes on one GPU: it cannot be combined with " << other << std::endl;

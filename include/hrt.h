@@ -1304,6 +1304,79 @@ HRT_API int hrt_render_lit_views(hrt_scene *scene, const hrt_probe_volume *volum
                                  uint32_t h, uint32_t spp, uint32_t flags, uint32_t eval_flags, float bias, uint32_t tail_after,
                                  float *out_rgb, hrt_stats *stats /* may be NULL */);
 
+/* ---- Lit bakes: the FINAL GATHER of a baked-lighting pipeline -- "Baking" in front of "Lit rays" or "Lit paths", fused: the
+ * cosine-weighted rays of bake points whose paths END in a probe volume, one launch for all samples, no n*32-byte ray buffer.  The
+ * texel keeps its own contact shadows and direct light; everything beyond the hit (or the K-th diffuse hit) is read from the volume.
+ * THE RULE.  Sample s of point i is the value that hrt_trace_lit (tail_after == 0) or hrt_trace_lit_paths (tail_after in
+ * 1 .. HRT_MAXBOUNCES) gives for record i of hrt_bake_rays(d_points, d_keys, n, s, seed), called with the same d_keys, first_sample = s,
+ * n_samples = 1 and the same seed, flags, eval_flags and bias.  The output is the sum of those values in ascending sample order,
+ * sum = 0.f (or d_out on entry, under HRT_RADIANCE_ACCUMULATE), sum = sum + value, divided by (float)n_samples -- or the running
+ * sums.  A DEGENERATE sample (what "Baking" calls degenerate: its bake ray record has direction 0) adds nothing and still counts in
+ * the divisor: a degenerate point gives 0 in mean mode and leaves its sums as they are under HRT_RADIANCE_ACCUMULATE.  All
+ * arithmetic is fp32 without fused multiply-add; every bit is the composition's.
+ * BIAS: `bias` is the look-up's bias of "Lit rays", applied at the HIT where the path ends in the volume.  It is NOT the point
+ * record's own bias float (record[7]), which the rule of "Baking" adds to the ray's ORIGIN along the point's normal; the two are
+ * independent and neither replaces the other.
+ * UNITS: hrt_bake's (the mean over samples of radiance / 6; the irradiance at the point is pi times the mean radiance; NO factor
+ * is applied), so the result is directly comparable with hrt_bake and with hrt_probe_eval (irradiance form) on the same records.
+ * hrt_bake_lit_device: 3 floats per point at d_out[3i .. 3i+2], the means over samples [first_sample, first_sample + n_samples), or
+ * with HRT_RADIANCE_ACCUMULATE the running sums.  Asynchronous on `stream`; touches none of the scene's per-launch state and only
+ * READS the volume (the CONCURRENCY note of "Lit rays").  `flags` are hrt_bake_device's, refused by the same names and texts:
+ * HRT_FLAG_EXACT_ONLY, HRT_FLAG_MESH_BRUTE (with EXACT_ONLY), HRT_FLAG_NO_LDS_TREE, HRT_RADIANCE_ACCUMULATE.  `eval_flags` are
+ * hrt_trace_lit's: HRT_PROBE_EVAL_FACING, HRT_LIT_VISIBLE (the volume needs its depth moments).
+ * hrt_bake_lit: the same from and into HOST buffers (`points`, `keys`, `out`; 4-byte aligned), blocking, samples [0, spp); stats as
+ * hrt_bake (samples = n * spp; n == 0 zeroes them).  HRT_RADIANCE_ACCUMULATE is refused (the sums live on the device).
+ * Checked in this order, HRT_ERR_INVALID with hrt_last_error() naming the entry point and the culprit: (the blocking form:
+ * HRT_RADIANCE_ACCUMULATE;) flags; (n == 0 returns HRT_OK here and launches nothing;) the points NULL or misaligned (device 16
+ * bytes, host 4); the keys not 4-byte aligned; n > 2^31 - 1; n_samples == 0; first_sample + n_samples > 2^32; the output NULL or
+ * not 4-byte aligned; tail_after > HRT_MAXBOUNCES; eval_flags, the volume and the bias in the order of "Lit rays"; then a NULL
+ * scene, a volume that lives on another device than the scene, and the library state.
+ * OUT OF SCOPE (DESIGN.md section 5 "Lit bakes"): the cooperative or parked look-up, batched point sets over several volumes,
+ * multi-GPU. */
+HRT_API int hrt_bake_lit_device(hrt_scene *scene, const hrt_probe_volume *volume, const float *d_points, const uint32_t *d_keys, uint32_t n,
+                                uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias,
+                                uint32_t tail_after, float *d_out, void *stream);
+HRT_API int hrt_bake_lit(hrt_scene *scene, const hrt_probe_volume *volume, const float *points, const uint32_t *keys, uint32_t n, uint32_t spp,
+                         uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, uint32_t tail_after, float *out,
+                         hrt_stats *stats /* may be NULL */);
+
+/* ---- Adaptive lit frames: the per-tile sample counts of hrt_render_adaptive for a lit frame -- "Adaptive lens frames" with the
+ * sums of "Lit frames".  A lit frame is noise-free but for direct-light penumbrae, lens blur and edges: most tiles stop at min_spp.
+ * The rounds, the estimate and the counts are EXACTLY the rule stated at hrt_render_adaptive, with the sums of hrt_render_lit in
+ * place of hrt_render's: round 0 adds samples [0, min_spp/2) to every HRT_TILE x HRT_TILE tile, round 1 adds [min_spp/2, min_spp) and
+ * judges every tile, every later round adds min(n, max_spp - n) samples to the tiles still active and judges them, until none is
+ * active.  Every round is one launch of a fused lit kernel over the list of active tiles (one lane per pixel of a listed tile),
+ * adding its samples in sample order onto the stored sums.  A DEGENERATE sample (see "Lit frames") adds nothing and counts in the
+ * divisor; a tile of a fisheye frame wholly outside the image circle has tile_err 0, stops at min_spp and is all zeros.
+ * CONTRACT A: every tile of the result is bit-identical to the same tile of hrt_render_lit(volume, lens, w, h, count of that tile,
+ * seed, flags, eval_flags, bias, tail_after), for every projection, both tail rules (tail_after == 0 and 1 .. HRT_MAXBOUNCES), every
+ * look-up (HRT_PROBE_EVAL_FACING, HRT_LIT_VISIBLE) and every permitted flag set, HRT_FLAG_GAMMA included.
+ * hrt_render_lit_adaptive_device: d_frame (device, h*w*3 floats, ROW-MAJOR) receives the means (gamma-corrected with
+ * HRT_FLAG_GAMMA), d_tile_spp (device, may be NULL) tiles_y * tiles_x uint32 counts, row-major.  Runs on `stream` and synchronises
+ * it once per round from round 1 on, as hrt_render_lens_adaptive_device does; a fault while a round runs ends the call with
+ * HRT_ERR_DEVICE at that round's synchronisation.
+ * hrt_render_lit_adaptive: the same into HOST buffers out_rgb[h*w*3] and out_tile_spp (may be NULL), blocking.  stats (may be NULL)
+ * as hrt_render_lens_adaptive: kernel_ms = the lit kernels' time summed over all rounds, samples = sum over in-image pixels of their
+ * tile's count (degenerate samples count).
+ * FLAGS: hrt_render_lens_adaptive's, refused by the same names and texts.  `eval_flags`, `bias` and `tail_after` are hrt_render_lit's.
+ * Checked in this order, HRT_ERR_INVALID with hrt_last_error() naming the entry point and the culprit: everything
+ * hrt_render_lens_adaptive checks before the scene, in its order (flags; params; the lens; the frame; the LIMIT; the output
+ * pointers); tail_after > HRT_MAXBOUNCES; eval_flags, the volume and the bias in the order of "Lit rays"; then a NULL scene, a
+ * volume that lives on another device than the scene, and the library state.
+ * CONCURRENCY: the call shares the tile-major sums and the round scratch with hrt_render_adaptive and hrt_render_lens_adaptive: it
+ * may NOT overlap another adaptive call of the same scene, lit, lens or pinhole.  Nothing of the trace launches' state is touched:
+ * it may overlap a plain render or a query of the same scene on another stream.  It only READS the volume (the CONCURRENCY note of
+ * "Lit rays").
+ * OUT OF SCOPE (DESIGN.md section 5 "Adaptive lit frames"): batched views (hrt_render_lit_views stays uniform), rank
+ * partitions, denoising of adaptive frames, the streaming kernel, multi-GPU. */
+HRT_API int hrt_render_lit_adaptive_device(hrt_scene *scene, const hrt_probe_volume *volume, const hrt_lens *lens, uint32_t w, uint32_t h,
+                                           const hrt_adaptive *params, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias,
+                                           uint32_t tail_after, float *d_frame, uint32_t *d_tile_spp /* may be NULL */, void *stream);
+HRT_API int hrt_render_lit_adaptive(hrt_scene *scene, const hrt_probe_volume *volume, const hrt_lens *lens, uint32_t w, uint32_t h,
+                                    const hrt_adaptive *params, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias,
+                                    uint32_t tail_after, float *out_rgb, uint32_t *out_tile_spp /* may be NULL */,
+                                    hrt_stats *stats /* may be NULL */);
+
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
  * format 6: the same integers as bytes (binary PPM; negative values, which P3 prints with a sign, clamp to 0).
