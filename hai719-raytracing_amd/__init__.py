@@ -508,6 +508,52 @@ def _row_count(who: str, noun: str, batch) -> int:
     return n
 
 
+def _batch_checked(who: str, noun: str, batch, keys, out, cell: tuple, rows=None):
+    """The checks every batched entry point makes before anything is touched: ``batch`` by ``rows`` (default ``_ray_batch``),
+    ``keys`` ((n,) uint32 / int32) and ``out`` ((n,) + ``cell`` float32), if given, as torch tensors on the batch's GPU or as NumPy
+    -> (is the batch a torch tensor, the batch, n, the keys, the result's shape)."""
+    import torch
+    is_torch = isinstance(batch, torch.Tensor)
+    batch = (rows or _ray_batch)(who, noun, batch)
+    n = _row_count(who, noun, batch)
+    shape, shown = (n,) + tuple(cell), "(n, " + ", ".join(str(c) for c in cell) + ")"
+    if keys is not None:
+        if is_torch:
+            _check_tensor(who, "keys", keys, (n,), "int32", batch.device, noun, "(n,)")
+        else:
+            keys = np.ascontiguousarray(keys)
+            if keys.shape != (n,) or keys.dtype not in (np.uint32, np.int32):
+                raise ValueError(f"{who}: keys must be (n,) uint32 (got {keys.shape} {keys.dtype})")
+    if out is not None:
+        if is_torch:
+            _check_tensor(who, "out", out, shape, "float32", batch.device, noun, shown)
+        else:
+            o = np.asarray(out)
+            if o.shape != shape or o.dtype != np.float32:
+                raise ValueError(f"{who}: out must be {shown} float32 (got {o.shape} {o.dtype})")
+    return is_torch, batch, n, keys, shape
+
+
+def _batch_on_device(is_torch: bool, batch, keys):
+    """(batch, keys) as they are for torch tensors, a NumPy batch and its keys uploaded."""
+    import torch
+    if is_torch:
+        return batch, keys
+    d_batch = torch.from_numpy(batch).to("cuda")
+    return d_batch, None if keys is None else torch.from_numpy(keys.view(np.int32)).to(d_batch.device)
+
+
+def _batch_result(is_torch: bool, d_out, out):
+    """The device result as the caller gets it: the tensor itself, or NumPy -- into ``out``, if given."""
+    if is_torch:
+        return d_out
+    r = d_out.cpu().numpy()
+    if out is not None:
+        out[...] = r
+        return out
+    return r
+
+
 def _view_table(who: str, noun: str, view_type, items, seeds):
     """(the ``view_type`` table -- View or LensView -- of ``items`` with their ``seeds`` (default 1 each), its length)."""
     items = list(items)
@@ -819,48 +865,24 @@ class DeviceScene:
         between the flags and the output (eval_flags, bias)."""
         import torch
         head = (lambda: (self._h,)) if volume is None else (lambda: (self._h, volume._h))
-        is_torch = isinstance(batch, torch.Tensor)
-        batch = (rows or _ray_batch)(who, noun, batch)
-        n = _row_count(who, noun, batch)
-        shape, shown = (n,) + tuple(cell), "(n, " + ", ".join(str(c) for c in cell) + ")"
-        if keys is not None:
-            if is_torch:
-                _check_tensor(who, "keys", keys, (n,), "int32", batch.device, noun, "(n,)")
-            else:
-                keys = np.ascontiguousarray(keys)
-                if keys.shape != (n,) or keys.dtype not in (np.uint32, np.int32):
-                    raise ValueError(f"{who}: keys must be (n,) uint32 (got {keys.shape} {keys.dtype})")
-        if out is None:
-            if accumulate and first_sample != 0:
-                raise ValueError(f"{who}: accumulate after sample 0 needs the running sums in `out`")
-        elif is_torch:
-            _check_tensor(who, "out", out, shape, "float32", batch.device, noun, shown)
-        else:
-            o = np.asarray(out)
-            if o.shape != shape or o.dtype != np.float32:
-                raise ValueError(f"{who}: out must be {shown} float32 (got {o.shape} {o.dtype})")
+        is_torch, batch, n, keys, shape = _batch_checked(who, noun, batch, keys, out, cell, rows)
+        if out is None and accumulate and first_sample != 0:
+            raise ValueError(f"{who}: accumulate after sample 0 needs the running sums in `out`")
         if blocking_fn is not None and not is_torch and out is None and not accumulate and first_sample == 0:
             r = np.empty(shape, dtype=np.float32)
             self._check(getattr(self._lib, blocking_fn)(*head(), batch.ctypes.data, None if keys is None else keys.ctypes.data, n, spp, seed, *extra, flags,
                                                         *after, r.ctypes.data, _ref(stats)))
             return r
+        d_batch, d_keys = _batch_on_device(is_torch, batch, keys)
         if is_torch:
-            d_batch, d_keys, d_out = batch, keys, out
+            d_out = out
         else:
-            d_batch = torch.from_numpy(batch).to("cuda")
-            d_keys = None if keys is None else torch.from_numpy(keys.view(np.int32)).to(d_batch.device)
-            d_out = None if out is None else torch.from_numpy(np.ascontiguousarray(o)).to(d_batch.device)
+            d_out = None if out is None else torch.from_numpy(np.ascontiguousarray(np.asarray(out))).to(d_batch.device)
         if d_out is None:
             d_out = torch.zeros(shape, dtype=torch.float32, device=d_batch.device)
         self._check(getattr(self._lib, device_fn)(*head(), _ptr(d_batch), _ptr(d_keys), n, first_sample, spp, seed, *extra, flags, *after, _ptr(d_out),
                                                   _stream(d_batch.device)))
-        if is_torch:
-            return d_out
-        r = d_out.cpu().numpy()
-        if out is not None:
-            out[...] = r
-            return out
-        return r
+        return _batch_result(is_torch, d_out, out)
 
     def bake(self, points, spp: int = 1, first_sample: int = 0, seed: int = 1, keys=None, out=None, accumulate: bool = False,
              flags: int = 0, stats: Optional[Stats] = None):
@@ -958,32 +980,11 @@ class DeviceScene:
         _, tail = _tail_args(who, "hrt_path_tails", int(tail_after) if tail_after is not None else 0)
         if not np.isfinite(bias):
             raise ValueError(f"{who}: bias must be finite (got {bias})")
-        is_torch = isinstance(rays, torch.Tensor)
-        rays = _ray_batch(who, "rays", rays)
-        n = _row_count(who, "rays", rays)
-        if keys is not None:
-            if is_torch:
-                _check_tensor(who, "keys", keys, (n,), "int32", rays.device, "rays", "(n,)")
-            else:
-                keys = np.ascontiguousarray(keys)
-                if keys.shape != (n,) or keys.dtype not in (np.uint32, np.int32):
-                    raise ValueError(f"{who}: keys must be (n,) uint32 (got {keys.shape} {keys.dtype})")
-        if out is not None:
-            if is_torch:
-                _check_tensor(who, "out", out, (n, TAIL_FLOATS), "float32", rays.device, "rays", f"(n, {TAIL_FLOATS})")
-            elif np.asarray(out).shape != (n, TAIL_FLOATS) or np.asarray(out).dtype != np.float32:
-                raise ValueError(f"{who}: out must be (n, {TAIL_FLOATS}) float32 (got {np.asarray(out).shape} {np.asarray(out).dtype})")
-        d_rays = rays if is_torch else torch.from_numpy(rays).to("cuda")
-        d_keys = keys if is_torch or keys is None else torch.from_numpy(keys.view(np.int32)).to(d_rays.device)
-        d_out = out if is_torch and out is not None else torch.empty((n, TAIL_FLOATS), dtype=torch.float32, device=d_rays.device)
+        is_torch, rays, n, keys, shape = _batch_checked(who, "rays", rays, keys, out, (TAIL_FLOATS,))
+        d_rays, d_keys = _batch_on_device(is_torch, rays, keys)
+        d_out = out if is_torch and out is not None else torch.empty(shape, dtype=torch.float32, device=d_rays.device)
         self._check(self._lib.hrt_path_tails(self._h, _ptr(d_rays), _ptr(d_keys), n, sample, seed, flags, bias, *tail, _ptr(d_out), _stream(d_rays.device)))
-        if is_torch:
-            return d_out
-        r = d_out.cpu().numpy()
-        if out is not None:
-            out[...] = r
-            return out
-        return r
+        return _batch_result(is_torch, d_out, out)
 
     def probes_lit(self, points, volume: "ProbeVolume", spp: int = 1, first_sample: int = 0, seed: int = 1, keys=None, eval_flags: int = 0,
                    bias: float = 0.0, out=None, accumulate: bool = False, flags: int = 0, stats: Optional[Stats] = None,

@@ -124,47 +124,55 @@ int hrt_bake_rays(const float *d_points, const uint32_t *d_keys, uint32_t n, uin
     return HRT_OK;
 }
 
-// The fused launch into d_out on `stream` (the scene entered).
-static int bake_launch(hrt_scene *s, const float *d_points, const uint32_t *d_keys, uint32_t n, uint32_t first_sample, uint32_t n_samples,
-                       uint64_t seed, uint32_t flags, float *d_out, hipStream_t stream) {
-    DBake Q;
+// The fused launch into d_out on `stream` (the scene entered).  Q and its builds: DBake and hrt_bake_kernel_builds, or the record
+// and a table of a lit bake (hrt_bake_lit.hip) with the rule filled in.
+extern "C++" {
+template <class QT>
+static int bake_launch(void (*const *builds)(const QT), QT &Q, hrt_scene *s, const float *d_points, const uint32_t *d_keys, uint32_t n,
+                       uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags, float *d_out, hipStream_t stream) {
     Q.points = (const float4 *)d_points;
     Q.keys = d_keys;
-    return radiance_launch(hrt_bake_kernel_builds, Q, s, first_sample, n_samples, seed, flags, d_out, n, stream);
+    return radiance_launch(builds, Q, s, first_sample, n_samples, seed, flags, d_out, n, stream);
+}
+
+// Both forms of a bake, plain (NoRule) or lit (LitRule), checked in the header's order: the flags, (an empty batch,) the points,
+// the samples and the output, the rule's, then the scene.  launch(d_points, d_keys, d_out, stream) is the fused launch; the blocking
+// form runs it on device copies of the points and keys (BlockingCall::run_batch).
+template <class Rule, class Launch>
+static int bake_call(const std::string &who, bool dev, hrt_scene *s, const Rule &R, const float *points, const uint32_t *keys, uint32_t n,
+                     uint32_t first_sample, uint32_t n_samples, uint32_t flags, float *out, void *stream, hrt_stats *stats, Launch launch) {
+    int rc = dev ? HRT_OK : blocking_accumulate_check(who, flags);
+    if (rc == HRT_OK) rc = bake_flags_check(who, flags);
+    if (rc != HRT_OK) return rc;
+    if (n == 0u) return empty_batch(stats);
+    if ((rc = bake_points_check(who, points, keys, n, dev)) != HRT_OK) return rc;
+    if ((rc = samples_out_check(who, first_sample, n_samples, out, dev ? "d_out" : "out")) != HRT_OK) return rc;
+    if ((rc = R.check(who)) != HRT_OK) return rc;
+    if ((rc = R.enter(who, s)) != HRT_OK) return rc;
+    if (dev) return launch(points, keys, out, (hipStream_t)stream);
+    BlockingCall call;
+    return call.run_batch(s, points, HRT_RAY_FLOATS * sizeof(float), keys, n, (size_t)n * 3u * sizeof(float), out, (uint64_t)n * n_samples, stats, launch);
+}
+}  // extern "C++"
+
+static int bake_entry(const std::string &who, bool dev, hrt_scene *s, const float *points, const uint32_t *keys, uint32_t n, uint32_t first_sample,
+                      uint32_t n_samples, uint64_t seed, uint32_t flags, float *out, void *stream, hrt_stats *stats) {
+    return bake_call(who, dev, s, NoRule{}, points, keys, n, first_sample, n_samples, flags, out, stream, stats,
+                     [&](const float *d_points, const uint32_t *d_keys, float *d_out, hipStream_t st) {
+                         DBake Q;
+                         return bake_launch(hrt_bake_kernel_builds, Q, s, d_points, d_keys, n, first_sample, n_samples, seed, flags, d_out, st);
+                     });
 }
 
 int hrt_bake_device(hrt_scene *s, const float *d_points, const uint32_t *d_keys, uint32_t n, uint32_t first_sample, uint32_t n_samples,
                     uint64_t seed, uint32_t flags, float *d_out, void *stream) {
-    const std::string who = "hrt_bake_device";
-    int rc = bake_flags_check(who, flags);
-    if (rc != HRT_OK || n == 0u) return rc;
-    if ((rc = bake_points_check(who, d_points, d_keys, n, true)) != HRT_OK) return rc;
-    if ((rc = samples_out_check(who, first_sample, n_samples, d_out, "d_out")) != HRT_OK) return rc;
-    if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
-    return bake_launch(s, d_points, d_keys, n, first_sample, n_samples, seed, flags, d_out, (hipStream_t)stream);
+    return bake_entry("hrt_bake_device", true, s, d_points, d_keys, n, first_sample, n_samples, seed, flags, d_out, stream, nullptr);
 }
 
-// Blocking, from and into host memory (BlockingCall; the points and keys are device buffers of the call's, too).
+// Blocking, from and into host memory.
 int hrt_bake(hrt_scene *s, const float *points, const uint32_t *keys, uint32_t n, uint32_t spp, uint64_t seed, uint32_t flags, float *out,
              hrt_stats *stats) {
-    const std::string who = "hrt_bake";
-    if (flags & HRT_RADIANCE_ACCUMULATE) return fail(HRT_ERR_INVALID, who + ": flags: HRT_RADIANCE_ACCUMULATE needs the running sums on the device (hrt_bake_device)");
-    int rc = bake_flags_check(who, flags);
-    if (rc != HRT_OK) return rc;
-    if (n == 0u) {
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        return HRT_OK;
-    }
-    if ((rc = bake_points_check(who, points, keys, n, false)) != HRT_OK) return rc;
-    if ((rc = samples_out_check(who, 0u, spp, out, "out")) != HRT_OK) return rc;
-    if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
-    BlockingCall call;
-    Scratch d_points, d_keys;
-    if ((rc = d_points.from_host(points, (size_t)n * HRT_RAY_FLOATS * sizeof(float))) != HRT_OK) return rc;
-    if (keys && (rc = d_keys.from_host(keys, (size_t)n * sizeof(uint32_t))) != HRT_OK) return rc;
-    return call.run(s, (size_t)n * 3u * sizeof(float), out, (uint64_t)n * spp, stats, [&](float *d_out) {
-        return bake_launch(s, d_points.as<float>(), d_keys.as<uint32_t>(), n, 0u, spp, seed, flags, d_out, nullptr);
-    });
+    return bake_entry("hrt_bake", false, s, points, keys, n, 0u, spp, seed, flags, out, nullptr, stats);
 }
 
 int hrt_bake_quad_points(const hrt_quad *quad, uint32_t tw, uint32_t th, int32_t side, float time, float bias, float *out_points) {

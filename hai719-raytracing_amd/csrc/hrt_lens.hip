@@ -393,40 +393,56 @@ static int lens_gamma(float *d_frame, uint64_t total, hipStream_t stream) {
     return HRT_OK;
 }
 
-// The fused launch into d_frame on `stream` (the scene entered), then the gamma.
-static int lens_launch(hrt_scene *s, const DLens &L, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples, uint64_t seed,
-                       uint32_t flags, float *d_frame, hipStream_t stream) {
-    DLensRadiance Q;
+// The fused launch into d_frame on `stream` (the scene entered), then the gamma.  Q and its builds: DLensRadiance and
+// hrt_lens_kernel_builds, or the record and a table of a lit frame (hrt_lit_frames.hip) with the rule filled in.
+extern "C++" {
+template <class QT>
+static int lens_launch(void (*const *builds)(const QT), QT &Q, hrt_scene *s, const DLens &L, uint32_t w, uint32_t h, uint32_t first_sample,
+                       uint32_t n_samples, uint64_t seed, uint32_t flags, float *d_frame, hipStream_t stream) {
     Q.w = w;
     Q.h = h;
     Q.lens = L;
-    const int rc = radiance_launch(hrt_lens_kernel_builds, Q, s, first_sample, n_samples, seed, flags & ~(uint32_t)HRT_FLAG_GAMMA, d_frame, w * h, stream);
+    const int rc = radiance_launch(builds, Q, s, first_sample, n_samples, seed, flags & ~(uint32_t)HRT_FLAG_GAMMA, d_frame, w * h, stream);
     if (rc != HRT_OK || !(flags & HRT_FLAG_GAMMA)) return rc;
     return lens_gamma(d_frame, (uint64_t)Q.n * 3u, stream);
 }
 
-int hrt_render_lens_device(hrt_scene *s, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples, uint64_t seed,
-                           uint32_t flags, float *d_frame, void *stream) {
-    const std::string who = "hrt_render_lens_device";
+// Both forms of a lens frame, plain (NoRule) or lit (LitRule), checked in the header's order: lens_render_check's, the rule's,
+// then the scene.  launch(L, d_frame, stream) is the fused launch; the blocking form runs it into a buffer of its own (BlockingCall).
+template <class Rule, class Launch>
+static int lens_frame_call(const std::string &who, bool dev, hrt_scene *s, const Rule &R, const hrt_lens *lens, uint32_t w, uint32_t h,
+                           uint32_t first_sample, uint32_t n_samples, uint32_t flags, float *out, void *stream, hrt_stats *stats, Launch launch) {
     DLens L;
-    int rc = lens_render_check(who, lens, w, h, first_sample, n_samples, flags, d_frame, "d_frame", L);
-    if (rc == HRT_OK) rc = enter_scene(who, s);
+    int rc = dev ? HRT_OK : blocking_accumulate_check(who, flags);
+    if (rc == HRT_OK) rc = lens_render_check(who, lens, w, h, first_sample, n_samples, flags, out, dev ? "d_frame" : "out_rgb", L);
+    if (rc == HRT_OK) rc = R.check(who);
+    if (rc == HRT_OK) rc = R.enter(who, s);
     if (rc != HRT_OK) return rc;
-    return lens_launch(s, L, w, h, first_sample, n_samples, seed, flags, d_frame, (hipStream_t)stream);
+    if (dev) return launch(L, out, (hipStream_t)stream);
+    BlockingCall call;
+    return call.run(s, (size_t)w * h * 3u * sizeof(float), out, (uint64_t)w * h * n_samples, stats,
+                    [&](float *d_frame) { return launch(L, d_frame, nullptr); });
+}
+}  // extern "C++"
+
+static int lens_frame_entry(const std::string &who, bool dev, hrt_scene *s, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t first_sample,
+                            uint32_t n_samples, uint64_t seed, uint32_t flags, float *out, void *stream, hrt_stats *stats) {
+    return lens_frame_call(who, dev, s, NoRule{}, lens, w, h, first_sample, n_samples, flags, out, stream, stats,
+                           [&](const DLens &L, float *d_frame, hipStream_t st) {
+                               DLensRadiance Q;
+                               return lens_launch(hrt_lens_kernel_builds, Q, s, L, w, h, first_sample, n_samples, seed, flags, d_frame, st);
+                           });
 }
 
-// Blocking, into host memory (BlockingCall).
+int hrt_render_lens_device(hrt_scene *s, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples, uint64_t seed,
+                           uint32_t flags, float *d_frame, void *stream) {
+    return lens_frame_entry("hrt_render_lens_device", true, s, lens, w, h, first_sample, n_samples, seed, flags, d_frame, stream, nullptr);
+}
+
+// Blocking, into host memory.
 int hrt_render_lens(hrt_scene *s, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed, uint32_t flags, float *out_rgb,
                     hrt_stats *stats) {
-    const std::string who = "hrt_render_lens";
-    DLens L;
-    if (flags & HRT_RADIANCE_ACCUMULATE) return fail(HRT_ERR_INVALID, who + ": flags: HRT_RADIANCE_ACCUMULATE needs the running sums on the device (hrt_render_lens_device)");
-    int rc = lens_render_check(who, lens, w, h, 0u, spp, flags, out_rgb, "out_rgb", L);
-    if (rc == HRT_OK) rc = enter_scene(who, s);
-    if (rc != HRT_OK) return rc;
-    BlockingCall call;
-    return call.run(s, (size_t)w * h * 3u * sizeof(float), out_rgb, (uint64_t)w * h * spp, stats,
-                    [&](float *d_frame) { return lens_launch(s, L, w, h, 0u, spp, seed, flags, d_frame, nullptr); });
+    return lens_frame_entry("hrt_render_lens", false, s, lens, w, h, 0u, spp, seed, flags, out_rgb, nullptr, stats);
 }
 
 int hrt_render_lens_features(hrt_scene *s, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples, uint64_t seed,
@@ -498,47 +514,63 @@ static int lens_views_stage(hrt_scene *s, std::vector<DLensView> &blocks, hipStr
     return s->lens_views.stage(blocks, stream, table);
 }
 
-// The fused launch over all views into d_frames on `stream` (the scene entered), then the gamma over all frames.
-static int lens_views_launch(hrt_scene *s, std::vector<DLensView> &blocks, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples,
-                             uint32_t flags, float *d_frames, hipStream_t stream) {
-    DLensViewsRadiance Q;
+// The fused launch over all views into d_frames on `stream` (the scene entered), then the gamma over all frames.  Q and its
+// builds: DLensViewsRadiance and hrt_lens_views_kernel_builds, or those of a lit batch (hrt_lit_frames.hip).
+extern "C++" {
+template <class QT>
+static int lens_views_launch(void (*const *builds)(const QT), QT &Q, hrt_scene *s, std::vector<DLensView> &blocks, uint32_t w, uint32_t h,
+                             uint32_t first_sample, uint32_t n_samples, uint32_t flags, float *d_frames, hipStream_t stream) {
     { const int src = lens_views_stage(s, blocks, stream, &Q.views); if (src != HRT_OK) return src; }
     Q.w = w;
     Q.h = h;
     Q.npix = w * h;
-    int rc = radiance_launch(hrt_lens_views_kernel_builds, Q, s, first_sample, n_samples, 0u, flags & ~(uint32_t)HRT_FLAG_GAMMA, d_frames,
+    int rc = radiance_launch(builds, Q, s, first_sample, n_samples, 0u, flags & ~(uint32_t)HRT_FLAG_GAMMA, d_frames,
                              (uint32_t)blocks.size() * Q.npix, stream);  // no launch seed: every view has its own
     if (rc == HRT_OK) rc = s->lens_views.staged(stream);
     if (rc != HRT_OK || !(flags & HRT_FLAG_GAMMA)) return rc;
     return lens_gamma(d_frames, (uint64_t)Q.n * 3u, stream);
 }
 
-int hrt_render_lens_views_device(hrt_scene *s, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h, uint32_t first_sample,
-                                 uint32_t n_samples, uint32_t flags, float *d_frames, void *stream) {
-    const std::string who = "hrt_render_lens_views_device";
+// Both forms of a batch of lens views, plain (NoRule) or lit (LitRule), checked in the header's order: lens_views_check's (an empty
+// batch skips all but the flags), the rule's tail_after, (an empty batch returns,) the rule's volume, then the scene.
+// launch(blocks, d_frames, stream) is the fused launch.
+template <class Rule, class Launch>
+static int lens_views_call(const std::string &who, bool dev, hrt_scene *s, const Rule &R, const hrt_lens_view *views, uint32_t n_views, uint32_t w,
+                           uint32_t h, uint32_t first_sample, uint32_t n_samples, uint32_t flags, float *out, void *stream, hrt_stats *stats,
+                           Launch launch) {
     std::vector<DLensView> blocks;
-    int rc = lens_views_check(who, views, n_views, w, h, first_sample, n_samples, flags, d_frames, "d_frames", blocks);
-    if (rc != HRT_OK || n_views == 0u) return rc;
-    if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
-    return lens_views_launch(s, blocks, w, h, first_sample, n_samples, flags, d_frames, (hipStream_t)stream);
+    int rc = dev ? HRT_OK : blocking_accumulate_check(who, flags);
+    if (rc == HRT_OK) rc = lens_views_check(who, views, n_views, w, h, first_sample, n_samples, flags, out, dev ? "d_frames" : "out_rgb", blocks);
+    if (rc == HRT_OK) rc = R.check_tail(who);
+    if (rc != HRT_OK) return rc;
+    if (n_views == 0u) return empty_batch(stats);
+    if ((rc = R.check_volume(who)) != HRT_OK) return rc;
+    if ((rc = R.enter(who, s)) != HRT_OK) return rc;
+    if (dev) return launch(blocks, out, (hipStream_t)stream);
+    BlockingCall call;
+    return call.run(s, (size_t)n_views * w * h * 3u * sizeof(float), out, (uint64_t)n_views * w * h * n_samples, stats,
+                    [&](float *d_frames) { return launch(blocks, d_frames, nullptr); });
+}
+}  // extern "C++"
+
+static int lens_views_entry(const std::string &who, bool dev, hrt_scene *s, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h,
+                            uint32_t first_sample, uint32_t n_samples, uint32_t flags, float *out, void *stream, hrt_stats *stats) {
+    return lens_views_call(who, dev, s, NoRule{}, views, n_views, w, h, first_sample, n_samples, flags, out, stream, stats,
+                           [&](std::vector<DLensView> &blocks, float *d_frames, hipStream_t st) {
+                               DLensViewsRadiance Q;
+                               return lens_views_launch(hrt_lens_views_kernel_builds, Q, s, blocks, w, h, first_sample, n_samples, flags, d_frames, st);
+                           });
 }
 
-// Blocking, into host memory (BlockingCall).
+int hrt_render_lens_views_device(hrt_scene *s, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h, uint32_t first_sample,
+                                 uint32_t n_samples, uint32_t flags, float *d_frames, void *stream) {
+    return lens_views_entry("hrt_render_lens_views_device", true, s, views, n_views, w, h, first_sample, n_samples, flags, d_frames, stream, nullptr);
+}
+
+// Blocking, into host memory.
 int hrt_render_lens_views(hrt_scene *s, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h, uint32_t spp, uint32_t flags,
                           float *out_rgb, hrt_stats *stats) {
-    const std::string who = "hrt_render_lens_views";
-    std::vector<DLensView> blocks;
-    if (flags & HRT_RADIANCE_ACCUMULATE) return fail(HRT_ERR_INVALID, who + ": flags: HRT_RADIANCE_ACCUMULATE needs the running sums on the device (hrt_render_lens_views_device)");
-    int rc = lens_views_check(who, views, n_views, w, h, 0u, spp, flags, out_rgb, "out_rgb", blocks);
-    if (rc != HRT_OK) return rc;
-    if (n_views == 0u) {
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        return HRT_OK;
-    }
-    if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
-    BlockingCall call;
-    return call.run(s, (size_t)n_views * w * h * 3u * sizeof(float), out_rgb, (uint64_t)n_views * w * h * spp, stats,
-                    [&](float *d_frames) { return lens_views_launch(s, blocks, w, h, 0u, spp, flags, d_frames, nullptr); });
+    return lens_views_entry("hrt_render_lens_views", false, s, views, n_views, w, h, 0u, spp, flags, out_rgb, nullptr, stats);
 }
 
 int hrt_render_lens_views_features(hrt_scene *s, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h, uint32_t first_sample,

@@ -13,14 +13,17 @@
 // launches' events are not touched.
 //
 // The host side of the rounds -- lens_adaptive_run, lens_adaptive_frame, lens_adaptive_host -- takes the launch of the tile-list
-// kernel as a callable: lens_tiles_launch here, the lit launch of hrt_lit_adaptive.hip (hrt_render_lit_adaptive*), which shares
-// everything else with this file.
+// kernel as a callable: lens_tiles_launch with the plain record and table here, with the lit ones in hrt_lit_adaptive.hip
+// (hrt_render_lit_adaptive*), which shares everything else with this file.
 
-// One launch of the tile-list lens kernel (the scene entered): samples [first, first + add) of the n_active tiles of `list` (NULL:
-// every tile) onto the running sums at `sums`, between events e0 and e1 on `stream`.
-static int lens_tiles_launch(hrt_scene *s, const DLens &L, uint32_t w, uint32_t h, const uint32_t *list, uint32_t n_active, uint32_t first,
-                             uint32_t add, uint64_t seed, uint32_t flags, float *sums, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
-    DLensTilesRadiance Q;
+// One launch of a tile-list lens kernel (the scene entered): samples [first, first + add) of the n_active tiles of `list` (NULL:
+// every tile) onto the running sums at `sums`, between events e0 and e1 on `stream`.  Q and its builds: DLensTilesRadiance and
+// hrt_lens_tiles_kernel_builds, or the record and a table of an adaptive lit frame (hrt_lit_adaptive.hip) with the rule filled in.
+extern "C++" {
+template <class QT>
+static int lens_tiles_launch(void (*const *builds)(const QT), QT &Q, hrt_scene *s, const DLens &L, uint32_t w, uint32_t h, const uint32_t *list,
+                             uint32_t n_active, uint32_t first, uint32_t add, uint64_t seed, uint32_t flags, float *sums, hipStream_t stream,
+                             hipEvent_t e0, hipEvent_t e1) {
     Q.w = w;
     Q.h = h;
     Q.tiles_x = (w + HRT_TILE - 1u) / HRT_TILE;
@@ -28,18 +31,19 @@ static int lens_tiles_launch(hrt_scene *s, const DLens &L, uint32_t w, uint32_t 
     Q.lens = L;
     HIP_TRY(hipEventRecord(e0, stream));
     // n_active <= the frame's tiles, which the entry points hold to (2^31 - 1) / 64
-    const int rc = radiance_launch(hrt_lens_tiles_kernel_builds, Q, s, first, add, seed,
+    const int rc = radiance_launch(builds, Q, s, first, add, seed,
                                    (flags & (HRT_FLAG_EXACT_ONLY | HRT_FLAG_MESH_BRUTE | HRT_FLAG_NO_LDS_TREE)) | HRT_RADIANCE_ACCUMULATE, sums,
                                    n_active * 64u, stream);  // refuses a launch HIP refused
     if (rc != HRT_OK) return rc;
     HIP_TRY(hipEventRecord(e1, stream));
     return HRT_OK;
 }
+}  // extern "C++"
 
 // The rounds (adaptive_rounds, hrt_adaptive.hip) over all tiles of the frame with a tile-list kernel: d_sums (tile-major, every
 // tile) ends with the means, d_counts with each tile's count (NULL: the scene's own count map).
-//   launch(list, n, first, add, sums, e0, e1)   one launch of the tile-list kernel between the events: lens_tiles_launch here, the
-//                                               lit one in hrt_lit_adaptive.hip -- the one thing the two clients do not share
+//   launch(list, n, first, add, sums, e0, e1)   one launch of the tile-list kernel between the events: lens_tiles_launch with the
+//                                               client's record and table -- the one thing the two clients do not share
 // ev: two pairs of timing events, the call's own: pair 0 around round 0's launch, pair 1 around every later one.  The stream is
 // synchronised once per round from round 1 on, and the times are read after it; a fault of a round's kernels ends the call there,
 // before the length of the next list is believed.
@@ -138,7 +142,9 @@ int hrt_render_lens_adaptive_device(hrt_scene *s, const hrt_lens *lens, uint32_t
     double ms = 0.0;
     return lens_adaptive_frame(s, w, h, params, flags, d_frame, d_tile_spp, (hipStream_t)stream, &ms,
                                [&](const uint32_t *list, uint32_t n, uint32_t first, uint32_t add, float *sums, hipEvent_t e0, hipEvent_t e1) -> int {
-                                   return lens_tiles_launch(s, L, w, h, list, n, first, add, seed, flags, sums, (hipStream_t)stream, e0, e1);
+                                   DLensTilesRadiance Q;
+                                   return lens_tiles_launch(hrt_lens_tiles_kernel_builds, Q, s, L, w, h, list, n, first, add, seed, flags, sums,
+                                                            (hipStream_t)stream, e0, e1);
                                });
 }
 
@@ -152,6 +158,8 @@ int hrt_render_lens_adaptive(hrt_scene *s, const hrt_lens *lens, uint32_t w, uin
     if (rc != HRT_OK) return rc;
     return lens_adaptive_host(s, w, h, params, flags, out_rgb, out_tile_spp, stats,
                               [&](const uint32_t *list, uint32_t n, uint32_t first, uint32_t add, float *sums, hipEvent_t e0, hipEvent_t e1) -> int {
-                                  return lens_tiles_launch(s, L, w, h, list, n, first, add, seed, flags, sums, nullptr, e0, e1);
+                                  DLensTilesRadiance Q;
+                                  return lens_tiles_launch(hrt_lens_tiles_kernel_builds, Q, s, L, w, h, list, n, first, add, seed, flags, sums, nullptr, e0,
+                                                           e1);
                               });
 }

@@ -1,7 +1,8 @@
 // Lit paths (include/hrt.h "Lit paths": hrt_trace_lit_paths, hrt_path_tails, hrt_probes_lit_paths_device, hrt_probes_lit_paths): a
 // path of the integrator that ENDS in a probe volume at its K-th diffuse hit -- mirror and glass are followed, and K - 1 real diffuse
-// bounces are traced before the volume takes over.  Included by hrt_api.hip inside its extern "C" block, after hrt_probe_lit.hip
-// (DLit, DProbeLit, lit_lookup and the host checks, which carry tail_after for the entry points here).
+// bounces are traced before the volume takes over -- and, since each shares one body with its "Lit paths" form, the entry points of
+// "Lit rays" (hrt_trace_lit, hrt_probes_lit_device, hrt_probes_lit).  Included by hrt_api.hip inside its extern "C" block, after
+// hrt_probe_lit.hip (Lit<Base>, lit_lookup, the one-segment kernels and LitRule) and hrt_probes.hip (probe_call, probe_launch).
 //
 // There is no path loop in this file: the kernels are radiance_body (hrt_radiance.hip) with a TAIL policy -- bounce loop, mesh
 // parking, direct light and sky are the integrator's own, and the policy is the one hook in stage C, between `thr = thr * albedo`
@@ -14,13 +15,7 @@
 //
 // All of it is fp32 without fused multiply-add (the library is built with -ffp-contract=off), in the order the header writes.
 
-// The launch records: those of the one-segment forms with K, and DRadiance with K and the bias a tail record carries.
-struct DLitPaths : DLit {
-    uint32_t tail_after;
-};
-struct DProbeLitPaths : DProbeLit {
-    uint32_t tail_after;
-};
+// The launch record of a tail record's kernel: DRadiance with K and the bias the record carries (no volume: not a Lit<Base>).
 struct DPathTails : DRadiance {  // out: HRT_TAIL_FLOATS floats per ray
     uint32_t tail_after;
     float bias;
@@ -66,12 +61,8 @@ struct RecordTail {
 // kernels' bound) nothing spills, and it is the slowest form.  Measured on MI355X, cornell_mesh (DESIGN.md section 5 "Lit paths";
 // -DHRT_LIT_PATHS_MIN_WAVES / -DHRT_PROBES_LIT_PATHS_MIN_WAVES: the A/B builds), 2 / 3 / 4 / 5 waves: a 16^3 x 1024 probe update
 // with tail_after = 1 takes 2.32 / 2.10 / 1.84 / 1.80 ms, a 1080p sample of the lit frame 0.387 / 0.326 / 0.373 / 0.350 ms.
-#define HRT_TAIL_FAMILY(base, SRC, QT, TAIL, WAVES)                                                                                                   \
-    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, WAVES) base(const QT Q) { radiance_body<false, false, SRC, QT, TAIL>(Q); }          \
-    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, WAVES) base##_lights(const QT Q) { radiance_body<true, false, SRC, QT, TAIL>(Q); }  \
-    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) base##_exact(const QT Q) { radiance_body<false, true, SRC, QT, TAIL>(Q); }       \
-    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) base##_lights_exact(const QT Q) { radiance_body<true, true, SRC, QT, TAIL>(Q); } \
-    static void (*const base##_builds[4])(const QT) = {base, base##_lights, base##_exact, base##_lights_exact};
+#define HRT_TAIL_FAMILY(base, SRC, QT, TAIL, WAVES) \
+    HRT_KERNEL_FAMILY(base, QT, (HRT_RADIANCE_WG, WAVES), (HRT_RADIANCE_WG, 2), radiance_body, SRC, QT, TAIL)
 
 #ifndef HRT_LIT_PATHS_MIN_WAVES
 #define HRT_LIT_PATHS_MIN_WAVES 3
@@ -79,51 +70,82 @@ struct RecordTail {
 #ifndef HRT_PROBES_LIT_PATHS_MIN_WAVES
 #define HRT_PROBES_LIT_PATHS_MIN_WAVES 5
 #endif
-HRT_TAIL_FAMILY(hrt_lit_paths_kernel, RecordRays, DLitPaths, VolumeTail, HRT_LIT_PATHS_MIN_WAVES)
+HRT_TAIL_FAMILY(hrt_lit_paths_kernel, RecordRays, DLit, VolumeTail, HRT_LIT_PATHS_MIN_WAVES)
 HRT_TAIL_FAMILY(hrt_path_tails_kernel, RecordRays, DPathTails, RecordTail, HRT_RADIANCE_MIN_WAVES)
-HRT_TAIL_FAMILY(hrt_probes_lit_paths_kernel, ProbeRays, DProbeLitPaths, VolumeTail, HRT_PROBES_LIT_PATHS_MIN_WAVES)
+HRT_TAIL_FAMILY(hrt_probes_lit_paths_kernel, ProbeRays, DProbeLit, VolumeTail, HRT_PROBES_LIT_PATHS_MIN_WAVES)
 
-static int lit_tail_check(const std::string &who, uint32_t tail_after) {
-    if (tail_after < 1u || tail_after > HRT_MAXBOUNCES)
-        return fail(HRT_ERR_INVALID, who + ": tail_after must be in 1 .. HRT_MAXBOUNCES = " + std::to_string(HRT_MAXBOUNCES) + " (got " + std::to_string(tail_after) + ")");
-    return HRT_OK;
-}
-
-static int lit_paths_launch(hrt_scene *s, const DLitVolume &vol, const float *d_rays, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
-                            uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t tail_after, float *d_out, void *stream) {
-    DLitPaths Q;
+// hrt_trace_lit and hrt_trace_lit_paths, checked in the header's order.
+static int lit_trace(const std::string &who, hrt_scene *s, const LitRule &R, const float *d_rays, const uint32_t *d_keys, uint32_t n,
+                     uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags, float *d_out, void *stream) {
+    {  // the flags alone first (query_check with an empty batch), then the rule, then the rest of query_check
+        const int frc = query_check(who, flags, HRT_RADIANCE_ACCUMULATE, nullptr, nullptr, nullptr, 4u, 0u);
+        if (frc != HRT_OK) return frc;
+    }
+    int rc = R.check(who);
+    if (rc != HRT_OK || n == 0u) return rc;
+    if ((rc = query_check(who, flags, HRT_RADIANCE_ACCUMULATE, d_rays, d_keys, d_out, 4u, n)) != HRT_OK) return rc;
+    if (n_samples == 0u) return fail(HRT_ERR_INVALID, who + ": n_samples must be positive");
+    if ((uint64_t)first_sample + n_samples > 0x100000000ull)
+        return fail(HRT_ERR_INVALID, who + ": first_sample + n_samples must be at most 2^32 (sample indices do not wrap)");
+    if ((rc = R.enter(who, s)) != HRT_OK) return rc;
+    DLit Q;
     Q.rays = (const float4 *)d_rays;
     Q.keys = d_keys;
-    Q.vol = vol;
-    Q.tail_after = tail_after;
-    return radiance_launch(hrt_lit_paths_kernel_builds, Q, s, first_sample, n_samples, seed, flags, d_out, n, stream);
+    R.fill(Q);
+    if (R.tail_after) return radiance_launch(hrt_lit_paths_kernel_builds, Q, s, first_sample, n_samples, seed, flags, d_out, n, stream);
+    return radiance_launch(hrt_lit_kernel_builds, static_cast<LitOne<DRadiance> &>(Q), s, first_sample, n_samples, seed, flags, d_out, n, stream);
 }
 
-// The trace launch of a fused update with a tail: Q0 is the record probes_lit_launch has filled for the one-segment kernel.
-static int probes_lit_paths_trace(hrt_scene *s, const DProbeLit &Q0, uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags,
-                                  uint32_t tail_after, uint32_t items, hipStream_t stream) {
-    DProbeLitPaths Q;
-    static_cast<DProbeLit &>(Q) = Q0;
-    Q.tail_after = tail_after;
-    return radiance_launch(hrt_probes_lit_paths_kernel_builds, Q, s, first_sample, n_samples, seed, flags, s->pl_blocks.as<float>(), items * 64u, stream);
+int hrt_trace_lit(hrt_scene *s, const hrt_probe_volume *v, const float *d_rays, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
+                  uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, float *d_out, void *stream) {
+    return lit_trace("hrt_trace_lit", s, LitRule{v, eval_flags, bias, 0u}, d_rays, d_keys, n, first_sample, n_samples, seed, flags, d_out, stream);
 }
 
 int hrt_trace_lit_paths(hrt_scene *s, const hrt_probe_volume *v, const float *d_rays, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
                         uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, uint32_t tail_after, float *d_out,
                         void *stream) {
-    return lit_trace("hrt_trace_lit_paths", true, s, v, d_rays, d_keys, n, first_sample, n_samples, seed, flags, eval_flags, bias, tail_after, d_out, stream);
+    return lit_trace("hrt_trace_lit_paths", s, LitRule{v, eval_flags, bias, tail_after, 1u}, d_rays, d_keys, n, first_sample, n_samples, seed, flags, d_out,
+                     stream);
+}
+
+// The four lit probe entry points: probe_call with the rule, probe_launch with the lit record (all of it, or its one-segment head),
+// the table tail_after chooses and block values of their own (pl_blocks: a lit probe launch may overlap a plain one).
+static int probes_lit(const std::string &who, bool dev, hrt_scene *s, const LitRule &R, const float *probes, const uint32_t *keys,
+                      uint32_t n, uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags, float *out, void *stream, hrt_stats *stats) {
+    return probe_call(who, dev, s, R, "a lit probe launch has one kernel form", probes, keys, n, first_sample, n_samples, flags, out, stream, stats,
+                      [&](const float *d_probes, const uint32_t *d_keys, float *d_out, hipStream_t st) {
+                          DProbeLit Q;
+                          R.fill(Q);
+                          if (R.tail_after)
+                              return probe_launch(hrt_probes_lit_paths_kernel_builds, Q, s, s->pl_blocks, d_probes, d_keys, n, first_sample, n_samples, seed,
+                                                  flags, d_out, st);
+                          return probe_launch(hrt_probes_lit_kernel_builds, static_cast<LitOne<DProbe> &>(Q), s, s->pl_blocks, d_probes, d_keys, n,
+                                              first_sample, n_samples, seed, flags, d_out, st);
+                      });
+}
+
+int hrt_probes_lit_device(hrt_scene *s, const hrt_probe_volume *v, const float *d_probes, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
+                          uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, float *d_out, void *stream) {
+    return probes_lit("hrt_probes_lit_device", true, s, LitRule{v, eval_flags, bias, 0u}, d_probes, d_keys, n, first_sample, n_samples, seed, flags,
+                      d_out, stream, nullptr);
+}
+
+int hrt_probes_lit(hrt_scene *s, const hrt_probe_volume *v, const float *probes, const uint32_t *keys, uint32_t n, uint32_t spp, uint64_t seed,
+                   uint32_t flags, uint32_t eval_flags, float bias, float *out, hrt_stats *stats) {
+    return probes_lit("hrt_probes_lit", false, s, LitRule{v, eval_flags, bias, 0u}, probes, keys, n, 0u, spp, seed, flags, out, nullptr, stats);
 }
 
 int hrt_probes_lit_paths_device(hrt_scene *s, const hrt_probe_volume *v, const float *d_probes, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
                                 uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, uint32_t tail_after, float *d_out,
                                 void *stream) {
-    return probes_lit_device("hrt_probes_lit_paths_device", true, s, v, d_probes, d_keys, n, first_sample, n_samples, seed, flags, eval_flags, bias,
-                             tail_after, d_out, stream);
+    return probes_lit("hrt_probes_lit_paths_device", true, s, LitRule{v, eval_flags, bias, tail_after, 1u}, d_probes, d_keys, n, first_sample, n_samples,
+                      seed, flags, d_out, stream, nullptr);
 }
 
 int hrt_probes_lit_paths(hrt_scene *s, const hrt_probe_volume *v, const float *probes, const uint32_t *keys, uint32_t n, uint32_t spp, uint64_t seed,
                          uint32_t flags, uint32_t eval_flags, float bias, uint32_t tail_after, float *out, hrt_stats *stats) {
-    return probes_lit_host("hrt_probes_lit_paths", true, s, v, probes, keys, n, spp, seed, flags, eval_flags, bias, tail_after, out, stats);
+    return probes_lit("hrt_probes_lit_paths", false, s, LitRule{v, eval_flags, bias, tail_after, 1u}, probes, keys, n, 0u, spp, seed, flags, out, nullptr,
+                      stats);
 }
 
 // Checked in the header's order: flags, tail_after, bias, (an empty batch,) the pointers, n, then the scene and the library state.
@@ -131,7 +153,7 @@ int hrt_path_tails(hrt_scene *s, const float *d_rays, const uint32_t *d_keys, ui
                    uint32_t tail_after, float *d_out, void *stream) {
     const std::string who = "hrt_path_tails";
     int rc = query_check(who, flags, 0u, nullptr, nullptr, nullptr, 16u, 0u);
-    if (rc == HRT_OK) rc = lit_tail_check(who, tail_after);
+    if (rc == HRT_OK) rc = lit_tail_check(who, tail_after, 1u);
     if (rc != HRT_OK) return rc;
     if (!std::isfinite(bias)) return fail(HRT_ERR_INVALID, who + ": bias must be finite (got " + std::to_string(bias) + ")");
     if (n == 0u) return HRT_OK;

@@ -164,38 +164,35 @@ static int probe_depth_launch(hrt_scene *s, const float *d_probes, const uint32_
     return HRT_OK;
 }
 
-int hrt_probe_depth_device(hrt_scene *s, const float *d_probes, const uint32_t *d_keys, uint32_t n, uint32_t first_sample, uint32_t n_samples,
-                           uint64_t seed, float r_max, uint32_t flags, float *d_out, void *stream) {
-    const std::string who = "hrt_probe_depth_device";
-    int rc = probe_depth_flags_check(who, flags);
-    if (rc != HRT_OK || n == 0u) return rc;
-    if ((rc = probe_records_check(who, d_probes, d_keys, n, true)) != HRT_OK) return rc;
-    if ((rc = probe_depth_counts_out_check(who, n, first_sample, n_samples, r_max, d_out, "d_out")) != HRT_OK) return rc;
+// Both forms, checked in the header's order; the blocking one runs the launch on device copies of the probes and keys.
+static int probe_depth_entry(const std::string &who, bool dev, hrt_scene *s, const float *probes, const uint32_t *keys, uint32_t n,
+                             uint32_t first_sample, uint32_t n_samples, uint64_t seed, float r_max, uint32_t flags, float *out, void *stream,
+                             hrt_stats *stats) {
+    int rc = dev ? HRT_OK : blocking_accumulate_check(who, flags);
+    if (rc == HRT_OK) rc = probe_depth_flags_check(who, flags);
+    if (rc != HRT_OK) return rc;
+    if (n == 0u) return empty_batch(stats);
+    if ((rc = probe_records_check(who, probes, keys, n, dev)) != HRT_OK) return rc;
+    if ((rc = probe_depth_counts_out_check(who, n, first_sample, n_samples, r_max, out, dev ? "d_out" : "out")) != HRT_OK) return rc;
     if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
-    return probe_depth_launch(s, d_probes, d_keys, n, first_sample, n_samples, seed, r_max, flags, d_out, (hipStream_t)stream);
+    const auto launch = [&](const float *d_probes, const uint32_t *d_keys, float *d_out, hipStream_t st) {
+        return probe_depth_launch(s, d_probes, d_keys, n, first_sample, n_samples, seed, r_max, flags, d_out, st);
+    };
+    if (dev) return launch(probes, keys, out, (hipStream_t)stream);
+    BlockingCall call;
+    return call.run_batch(s, probes, HRT_PROBE_FLOATS * sizeof(float), keys, n, (size_t)n * HRT_PROBE_DEPTH_FLOATS * sizeof(float), out,
+                          (uint64_t)n * n_samples, stats, launch);
 }
 
-// Blocking, from and into host memory (BlockingCall; the probes and keys are device buffers of the call's, too).
+int hrt_probe_depth_device(hrt_scene *s, const float *d_probes, const uint32_t *d_keys, uint32_t n, uint32_t first_sample, uint32_t n_samples,
+                           uint64_t seed, float r_max, uint32_t flags, float *d_out, void *stream) {
+    return probe_depth_entry("hrt_probe_depth_device", true, s, d_probes, d_keys, n, first_sample, n_samples, seed, r_max, flags, d_out, stream, nullptr);
+}
+
+// Blocking, from and into host memory.
 int hrt_probe_depth(hrt_scene *s, const float *probes, const uint32_t *keys, uint32_t n, uint32_t spp, uint64_t seed, float r_max, uint32_t flags,
                     float *out, hrt_stats *stats) {
-    const std::string who = "hrt_probe_depth";
-    if (flags & HRT_RADIANCE_ACCUMULATE) return fail(HRT_ERR_INVALID, who + ": flags: HRT_RADIANCE_ACCUMULATE needs the running sums on the device (hrt_probe_depth_device)");
-    int rc = probe_depth_flags_check(who, flags);
-    if (rc != HRT_OK) return rc;
-    if (n == 0u) {
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        return HRT_OK;
-    }
-    if ((rc = probe_records_check(who, probes, keys, n, false)) != HRT_OK) return rc;
-    if ((rc = probe_depth_counts_out_check(who, n, 0u, spp, r_max, out, "out")) != HRT_OK) return rc;
-    if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
-    BlockingCall call;
-    Scratch d_probes, d_keys;
-    if ((rc = d_probes.from_host(probes, (size_t)n * HRT_PROBE_FLOATS * sizeof(float))) != HRT_OK) return rc;
-    if (keys && (rc = d_keys.from_host(keys, (size_t)n * sizeof(uint32_t))) != HRT_OK) return rc;
-    return call.run(s, (size_t)n * HRT_PROBE_DEPTH_FLOATS * sizeof(float), out, (uint64_t)n * spp, stats, [&](float *d_out) {
-        return probe_depth_launch(s, d_probes.as<float>(), d_keys.as<uint32_t>(), n, 0u, spp, seed, r_max, flags, d_out, nullptr);
-    });
+    return probe_depth_entry("hrt_probe_depth", false, s, probes, keys, n, 0u, spp, seed, r_max, flags, out, nullptr, stats);
 }
 
 int hrt_probe_depth_texel(const float v[3], uint32_t *texel) {

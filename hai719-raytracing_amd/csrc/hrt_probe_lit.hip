@@ -1,8 +1,12 @@
-// Lit rays and probe relighting (include/hrt.h "Lit rays": hrt_trace_lit, hrt_probes_lit_device, hrt_probes_lit and the hysteresis
-// update hrt_probe_volume_blend*): the radiance of a ray whose path ENDS in a probe volume at its first hit -- one closest hit, the
-// hit shaded with the integrator's own device functions, and everything beyond it taken from the volume as it stands.  Included by
-// hrt_api.hip inside its extern "C" block, after hrt_probes.hip (probe_sample, ProbeRays' sum, the record checks), hrt_rays.hip
-// (query_context, query_margin, query_ray) and hrt_probe_volume.hip (the volume, pv_fold_corner, pv_basis, pv_channel).
+// Lit rays and probe relighting (include/hrt.h "Lit rays" and the hysteresis update hrt_probe_volume_blend*): the radiance of a ray
+// whose path ENDS in a probe volume at its first hit -- one closest hit, the hit shaded with the integrator's own device functions,
+// and everything beyond it taken from the volume as it stands.  Included by hrt_api.hip inside its extern "C" block, after
+// hrt_probes.hip (probe_sample, ProbeRays' sum), hrt_rays.hip (query_context, query_margin, query_ray) and hrt_probe_volume.hip
+// (the volume, pv_fold_corner, pv_basis, pv_channel).
+//
+// This file states the rule "a path ends in the volume" ONCE for every lit source: on the device DLitVolume, the record template
+// Lit<Base> and lit_lookup; on the host LitRule, the value an entry point makes of its four rule parameters, with the rule's
+// checks and the record's filling.  The entry points of "Lit rays" are in hrt_lit_paths.hip, next to their "Lit paths" forms.
 //
 // Two shapes of one per-sample body (lit_sample):
 //   hrt_lit_kernel builds: one lane per ray by grid stride, the samples of a ray in ascending order -- the probe-lit frame;
@@ -26,13 +30,23 @@ struct DLitVolume {
     float bias;
 };
 
-// The launch records: DRadiance and DProbe (query_launch and radiance_launch reach their fields by name) with the volume.
-struct DLit : DRadiance {
+// The launch record of a lit source: its plain sibling's (query_launch, radiance_launch and the sibling's own launch reach their
+// fields by name) with the volume and K = tail_after.  The one-segment kernels do not read tail_after; those over record rays and
+// probes (hrt_lit_kernel, hrt_probes_lit_kernel) take the record WITHOUT that word, LitOne<Base>, the head of a Lit<Base>.  With
+// the word their kernel arguments would grow by eight bytes, the hidden arguments behind them would move, and one s_add_u32 in
+// each of the eight kernels would change: they are kept instruction for instruction instead.
+extern "C++" {
+template <class Base>
+struct LitOne : Base {
     DLitVolume vol;
 };
-struct DProbeLit : DProbe {
-    DLitVolume vol;
+template <class Base>
+struct Lit : LitOne<Base> {
+    uint32_t tail_after;  // 0: one segment
 };
+}
+using DLit = Lit<DRadiance>;
+using DProbeLit = Lit<DProbe>;
 
 extern "C++" {
 namespace hrtk {
@@ -89,7 +103,7 @@ __device__ __forceinline__ f3 lit_sample(const CX &cx, const DLitVolume &V, cons
 // SRC is radiance_body's source policy: RecordRays reads record i once, with Q.keys and the launch's seed; a per-sample source
 // (LensRays, LensViewRays: the lit frames of hrt_lit_frames.hip) makes the ray, the margin, the key and the seed of every sample,
 // and a sample it does not trace adds nothing.
-template <bool LIGHTS, bool EXACT, class SRC = RecordRays, class QT = DLit>
+template <bool LIGHTS, bool EXACT, class SRC, class QT>
 __device__ __forceinline__ void lit_body(const QT &Q) {
     CtxT<EXACT, false, false, true> cx;
     unsigned long long stamps_local[17] = {0};
@@ -135,8 +149,8 @@ __device__ __forceinline__ void lit_body(const QT &Q) {
 // One wave per (probe, block) item by a wave-granular grid stride: Q.n counts lanes, 64 per item, and is a multiple of 64, as is
 // the stride, so a whole wave takes an item or none.  ProbeRays keeps the item's four words and the lanes' partial sums in LDS; a
 // wave touches only its own columns and words, so nothing here needs a barrier.
-template <bool LIGHTS, bool EXACT>
-__device__ __forceinline__ void probes_lit_body(const DProbeLit &Q) {
+template <bool LIGHTS, bool EXACT, class QT>
+__device__ __forceinline__ void probes_lit_body(const QT &Q) {
     CtxT<EXACT, false, false, true> cx;
     unsigned long long stamps_local[17] = {0};
     query_context(cx, Q.scene, Q.lds_units, Q.flags, stamps_local);
@@ -162,17 +176,12 @@ __device__ __forceinline__ void probes_lit_body(const DProbeLit &Q) {
 }  // namespace hrtk
 }  // extern "C++"
 
-// The four builds of a lit body -- plain, lights, and the two proof builds of HRT_FLAG_EXACT_ONLY -- and their table, indexed
-// lights | exact << 1 as radiance_launch indexes it.
-#define HRT_LIT_FAMILY(base, body, QT)                                                                                     \
-    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG) base(const QT Q) { body<false, false>(Q); }              \
-    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG) base##_lights(const QT Q) { body<true, false>(Q); }      \
-    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG) base##_exact(const QT Q) { body<false, true>(Q); }       \
-    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG) base##_lights_exact(const QT Q) { body<true, true>(Q); } \
-    static void (*const base##_builds[4])(const QT) = {base, base##_lights, base##_exact, base##_lights_exact};
+// The families of the two bodies over record rays and probes, without a register bound; over a per-sample source (the lit
+// frames and bakes of the later files) a family of lit_body names the waves per SIMD of its plain and lights builds.
+#define HRT_LIT_FAMILY(base, SRC, QT, WAVES) HRT_KERNEL_FAMILY(base, QT, (HRT_RADIANCE_WG, WAVES), (HRT_RADIANCE_WG, 2), lit_body, SRC, QT)
 
-HRT_LIT_FAMILY(hrt_lit_kernel, lit_body, DLit)
-HRT_LIT_FAMILY(hrt_probes_lit_kernel, probes_lit_body, DProbeLit)
+HRT_KERNEL_FAMILY(hrt_lit_kernel, LitOne<DRadiance>, (HRT_RADIANCE_WG), (HRT_RADIANCE_WG), lit_body, RecordRays, LitOne<DRadiance>)
+HRT_KERNEL_FAMILY(hrt_probes_lit_kernel, LitOne<DProbe>, (HRT_RADIANCE_WG), (HRT_RADIANCE_WG), probes_lit_body, LitOne<DProbe>)
 
 // One lane per 16-byte piece of a packed record: p = (keep * p) + ((1.f - keep) * c) for the probe's 27 floats, zeros past them.
 extern "C" __global__ void __launch_bounds__(HRT_PV_WG) hrt_probe_blend_kernel(const float *__restrict__ coeffs, uint32_t n_pieces, float keep,
@@ -189,152 +198,63 @@ extern "C" __global__ void __launch_bounds__(HRT_PV_WG) hrt_probe_blend_kernel(c
     packed[i] = make_float4(v[0], v[1], v[2], v[3]);
 }
 
-// Checks 2..6 of the header's order: eval_flags, the volume, bias.
-static int lit_volume_check(const std::string &who, const hrt_probe_volume *v, uint32_t eval_flags, float bias) {
-    if (eval_flags & HRT_PROBE_EVAL_RADIANCE)
-        return fail(HRT_ERR_INVALID, who + ": eval_flags: HRT_PROBE_EVAL_RADIANCE: the tail of a lit ray is the irradiance about the hit's normal");
-    const uint32_t known = HRT_PROBE_EVAL_FACING | HRT_LIT_VISIBLE;
-    if (eval_flags & ~known) return fail(HRT_ERR_INVALID, who + ": eval_flags: unknown bits " + std::to_string(eval_flags & ~known));
-    if (!v) return fail(HRT_ERR_INVALID, who + ": volume is NULL");
-    if (!v->loaded) return fail(HRT_ERR_INVALID, who + ": the volume has no coefficients yet (hrt_probe_volume_update)");
-    if ((eval_flags & HRT_LIT_VISIBLE) && !v->has_depth)
-        return fail(HRT_ERR_INVALID, who + ": eval_flags: HRT_LIT_VISIBLE: the volume has no depth moments yet (hrt_probe_volume_update_depth)");
-    if (!std::isfinite(bias)) return fail(HRT_ERR_INVALID, who + ": bias must be finite (got " + std::to_string(bias) + ")");
+// tail_after: 0 is the one-segment rule where the entry point accepts it (least == 0), else 1 .. HRT_MAXBOUNCES (hrt_path_tails has
+// a tail_after and no volume, so no LitRule).
+static int lit_tail_check(const std::string &who, uint32_t tail_after, uint32_t least) {
+    if (tail_after < least || tail_after > HRT_MAXBOUNCES)
+        return fail(HRT_ERR_INVALID, who + ": tail_after must be in 1 .. HRT_MAXBOUNCES = " + std::to_string(HRT_MAXBOUNCES) + " (got " + std::to_string(tail_after) + ")");
     return HRT_OK;
 }
 
-// The last checks: the scene, a volume of another device than the scene's, then the library state.
-static int lit_enter(const std::string &who, hrt_scene *s, const hrt_probe_volume *v) {
-    if (!s) return fail(HRT_ERR_INVALID, who + ": scene is NULL");
-    if (v->device != s->device)
-        return fail(HRT_ERR_INVALID, who + ": the volume lives on device " + std::to_string(v->device) + ", the scene on device " + std::to_string(s->device));
-    return enter_scene(who, s);
-}
+// THE RULE on the host: what an entry point makes of (volume, eval_flags, bias, tail_after), once, and passes on as one value.  A
+// one-segment entry point of "Lit rays" has tail_after 0, a *_paths entry point the least tail_after 1.  A plain entry point has
+// NoRule (hrt_radiance.hip) in its place.
+extern "C++" {
+struct LitRule {
+    const hrt_probe_volume *v;
+    uint32_t eval_flags;
+    float bias;
+    uint32_t tail_after;
+    uint32_t least = 0u;  // the smallest tail_after the entry point accepts: 1 for the *_paths entry points
 
-static DLitVolume lit_volume(const hrt_probe_volume *v, uint32_t eval_flags, float bias) {
-    DLitVolume V;
-    V.grid = v->grid;
-    V.packed = v->packed.as<float4>();
-    V.moments = (eval_flags & HRT_LIT_VISIBLE) ? v->depth.as<float2>() : nullptr;
-    V.eval_flags = eval_flags & HRT_PROBE_EVAL_FACING;
-    V.bias = bias;
-    return V;
-}
-
-// "Lit paths" (hrt_lit_paths.hip, which comes after this file): the same entry points with a tail after `tail_after` diffuse hits.
-// Here tail_after == 0 stands for the one-segment forms of this file; theirs check it right after the flags.
-static int lit_tail_check(const std::string &who, uint32_t tail_after);
-static int lit_paths_launch(hrt_scene *s, const DLitVolume &vol, const float *d_rays, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
-                            uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t tail_after, float *d_out, void *stream);
-static int probes_lit_paths_trace(hrt_scene *s, const DProbeLit &Q0, uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags,
-                                  uint32_t tail_after, uint32_t items, hipStream_t stream);
-
-static int lit_trace(const std::string &who, bool paths, hrt_scene *s, const hrt_probe_volume *v, const float *d_rays, const uint32_t *d_keys, uint32_t n,
-                     uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, uint32_t tail_after,
-                     float *d_out, void *stream) {
-    {  // the flags alone first (query_check with an empty batch), then the volume, then the rest of query_check
-        const int frc = query_check(who, flags, HRT_RADIANCE_ACCUMULATE, nullptr, nullptr, nullptr, 4u, 0u);
-        if (frc != HRT_OK) return frc;
-    }
-    if (paths) { const int trc = lit_tail_check(who, tail_after); if (trc != HRT_OK) return trc; }
-    int rc = lit_volume_check(who, v, eval_flags, bias);
-    if (rc != HRT_OK || n == 0u) return rc;
-    if ((rc = query_check(who, flags, HRT_RADIANCE_ACCUMULATE, d_rays, d_keys, d_out, 4u, n)) != HRT_OK) return rc;
-    if (n_samples == 0u) return fail(HRT_ERR_INVALID, who + ": n_samples must be positive");
-    if ((uint64_t)first_sample + n_samples > 0x100000000ull)
-        return fail(HRT_ERR_INVALID, who + ": first_sample + n_samples must be at most 2^32 (sample indices do not wrap)");
-    if ((rc = lit_enter(who, s, v)) != HRT_OK) return rc;
-    if (paths) return lit_paths_launch(s, lit_volume(v, eval_flags, bias), d_rays, d_keys, n, first_sample, n_samples, seed, flags, tail_after, d_out, stream);
-    DLit Q;
-    Q.rays = (const float4 *)d_rays;
-    Q.keys = d_keys;
-    Q.vol = lit_volume(v, eval_flags, bias);
-    return radiance_launch(hrt_lit_kernel_builds, Q, s, first_sample, n_samples, seed, flags, d_out, n, stream);
-}
-
-int hrt_trace_lit(hrt_scene *s, const hrt_probe_volume *v, const float *d_rays, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
-                  uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, float *d_out, void *stream) {
-    return lit_trace("hrt_trace_lit", false, s, v, d_rays, d_keys, n, first_sample, n_samples, seed, flags, eval_flags, bias, 0u, d_out, stream);
-}
-
-// The flags of a lit probe launch: a probe launch's.
-static int probes_lit_flags_check(const std::string &who, uint32_t flags) {
-    return fused_flags_check(who, flags, "a lit probe launch has one kernel form", "a probe has no direction to normalise",
-                             "probes are linear radiance, not a frame");
-}
-
-// The fused launch into d_out on `stream` (the scene entered, the limit checked): the trace launch into the scene's block values,
-// then hrt_probe_fold_kernel, also when a probe has one block.
-static int probes_lit_launch(hrt_scene *s, const hrt_probe_volume *v, const float *d_probes, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
-                             uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, uint32_t tail_after, float *d_out,
-                             hipStream_t stream) {
-    const uint32_t nblocks = (uint32_t)(((uint64_t)n_samples + HRT_PROBE_BLOCK - 1u) / HRT_PROBE_BLOCK);
-    const uint32_t items = n * nblocks;  // <= HRT_PROBE_MAX_BLOCKS
-    if (const int rc = s->pl_blocks.grow((size_t)items * HRT_PROBE_SUMS * sizeof(float))) return rc;
-    DProbeLit Q;
-    Q.probes = (const float4 *)d_probes;
-    Q.keys = d_keys;
-    Q.nblocks = nblocks;
-    Q.vol = lit_volume(v, eval_flags, bias);
-    if (const int rc = tail_after ? probes_lit_paths_trace(s, Q, first_sample, n_samples, seed, flags, tail_after, items, stream)
-                                  : radiance_launch(hrt_probes_lit_kernel_builds, Q, s, first_sample, n_samples, seed, flags, s->pl_blocks.as<float>(),
-                                                    items * 64u, stream))
-        return rc;
-    const uint32_t n_sums = n * HRT_PROBE_SUMS;
-    hipLaunchKernelGGL(hrt_probe_fold_kernel, dim3((n_sums + 255u) / 256u), dim3(256), 0, stream, s->pl_blocks.as<float>(), n_sums, nblocks, n_samples,
-                       (flags & HRT_RADIANCE_ACCUMULATE) ? 1u : 0u, d_out);
-    HIP_TRY(hipGetLastError());
-    return HRT_OK;
-}
-
-static int probes_lit_device(const std::string &who, bool paths, hrt_scene *s, const hrt_probe_volume *v, const float *d_probes, const uint32_t *d_keys,
-                             uint32_t n, uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias,
-                             uint32_t tail_after, float *d_out, void *stream) {
-    int rc = probes_lit_flags_check(who, flags);
-    if (rc == HRT_OK && paths) rc = lit_tail_check(who, tail_after);
-    if (rc == HRT_OK) rc = lit_volume_check(who, v, eval_flags, bias);
-    if (rc != HRT_OK || n == 0u) return rc;
-    if ((rc = probe_records_check(who, d_probes, d_keys, n, true)) != HRT_OK) return rc;
-    if ((rc = probe_samples_out_check(who, n, first_sample, n_samples, d_out, "d_out")) != HRT_OK) return rc;
-    if ((rc = lit_enter(who, s, v)) != HRT_OK) return rc;
-    return probes_lit_launch(s, v, d_probes, d_keys, n, first_sample, n_samples, seed, flags, eval_flags, bias, tail_after, d_out, (hipStream_t)stream);
-}
-
-int hrt_probes_lit_device(hrt_scene *s, const hrt_probe_volume *v, const float *d_probes, const uint32_t *d_keys, uint32_t n, uint32_t first_sample,
-                          uint32_t n_samples, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, float *d_out, void *stream) {
-    return probes_lit_device("hrt_probes_lit_device", false, s, v, d_probes, d_keys, n, first_sample, n_samples, seed, flags, eval_flags, bias, 0u, d_out,
-                             stream);
-}
-
-// Blocking, from and into host memory (BlockingCall; the probes and keys are device buffers of the call's, too).
-static int probes_lit_host(const std::string &who, bool paths, hrt_scene *s, const hrt_probe_volume *v, const float *probes, const uint32_t *keys, uint32_t n,
-                           uint32_t spp, uint64_t seed, uint32_t flags, uint32_t eval_flags, float bias, uint32_t tail_after, float *out, hrt_stats *stats) {
-    if (flags & HRT_RADIANCE_ACCUMULATE)
-        return fail(HRT_ERR_INVALID, who + ": flags: HRT_RADIANCE_ACCUMULATE needs the running sums on the device (" + who + "_device)");
-    int rc = probes_lit_flags_check(who, flags);
-    if (rc == HRT_OK && paths) rc = lit_tail_check(who, tail_after);
-    if (rc == HRT_OK) rc = lit_volume_check(who, v, eval_flags, bias);
-    if (rc != HRT_OK) return rc;
-    if (n == 0u) {
-        if (stats) std::memset(stats, 0, sizeof(*stats));
+    int check_tail(const std::string &who) const { return lit_tail_check(who, tail_after, least); }
+    // "Lit rays"' checks 2..6 of the header's order: eval_flags, the volume, bias.
+    int check_volume(const std::string &who) const {
+        if (eval_flags & HRT_PROBE_EVAL_RADIANCE)
+            return fail(HRT_ERR_INVALID, who + ": eval_flags: HRT_PROBE_EVAL_RADIANCE: the tail of a lit ray is the irradiance about the hit's normal");
+        const uint32_t known = HRT_PROBE_EVAL_FACING | HRT_LIT_VISIBLE;
+        if (eval_flags & ~known) return fail(HRT_ERR_INVALID, who + ": eval_flags: unknown bits " + std::to_string(eval_flags & ~known));
+        if (!v) return fail(HRT_ERR_INVALID, who + ": volume is NULL");
+        if (!v->loaded) return fail(HRT_ERR_INVALID, who + ": the volume has no coefficients yet (hrt_probe_volume_update)");
+        if ((eval_flags & HRT_LIT_VISIBLE) && !v->has_depth)
+            return fail(HRT_ERR_INVALID, who + ": eval_flags: HRT_LIT_VISIBLE: the volume has no depth moments yet (hrt_probe_volume_update_depth)");
+        if (!std::isfinite(bias)) return fail(HRT_ERR_INVALID, who + ": bias must be finite (got " + std::to_string(bias) + ")");
         return HRT_OK;
     }
-    if ((rc = probe_records_check(who, probes, keys, n, false)) != HRT_OK) return rc;
-    if ((rc = probe_samples_out_check(who, n, 0u, spp, out, "out")) != HRT_OK) return rc;
-    if ((rc = lit_enter(who, s, v)) != HRT_OK) return rc;
-    BlockingCall call;
-    Scratch d_probes, d_keys;
-    if ((rc = d_probes.from_host(probes, (size_t)n * HRT_PROBE_FLOATS * sizeof(float))) != HRT_OK) return rc;
-    if (keys && (rc = d_keys.from_host(keys, (size_t)n * sizeof(uint32_t))) != HRT_OK) return rc;
-    return call.run(s, (size_t)n * HRT_PROBE_SUMS * sizeof(float), out, (uint64_t)n * spp, stats, [&](float *d_out) {
-        return probes_lit_launch(s, v, d_probes.as<float>(), d_keys.as<uint32_t>(), n, 0u, spp, seed, flags, eval_flags, bias, tail_after, d_out, nullptr);
-    });
-}
-
-int hrt_probes_lit(hrt_scene *s, const hrt_probe_volume *v, const float *probes, const uint32_t *keys, uint32_t n, uint32_t spp, uint64_t seed,
-                   uint32_t flags, uint32_t eval_flags, float bias, float *out, hrt_stats *stats) {
-    return probes_lit_host("hrt_probes_lit", false, s, v, probes, keys, n, spp, seed, flags, eval_flags, bias, 0u, out, stats);
-}
+    // Both, where nothing comes between them (a batch of views returns for no views there).
+    int check(const std::string &who) const {
+        const int rc = check_tail(who);
+        return rc != HRT_OK ? rc : check_volume(who);
+    }
+    // The last checks: the scene, a volume of another device than the scene's, then the library state.
+    int enter(const std::string &who, hrt_scene *s) const {
+        if (!s) return fail(HRT_ERR_INVALID, who + ": scene is NULL");
+        if (v->device != s->device)
+            return fail(HRT_ERR_INVALID, who + ": the volume lives on device " + std::to_string(v->device) + ", the scene on device " + std::to_string(s->device));
+        return enter_scene(who, s);
+    }
+    // The rule's part of a launch record (the checks passed).
+    template <class Base>
+    void fill(Lit<Base> &Q) const {
+        Q.vol.grid = v->grid;
+        Q.vol.packed = v->packed.as<float4>();
+        Q.vol.moments = (eval_flags & HRT_LIT_VISIBLE) ? v->depth.as<float2>() : nullptr;
+        Q.vol.eval_flags = eval_flags & HRT_PROBE_EVAL_FACING;
+        Q.vol.bias = bias;
+        Q.tail_after = tail_after;
+    }
+};
+}  // extern "C++"
 
 // ---- The hysteresis update of a volume's packed records.
 

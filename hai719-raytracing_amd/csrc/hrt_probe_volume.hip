@@ -345,10 +345,7 @@ int hrt_probe_eval(const hrt_probe_volume *v, const float *points, uint32_t n, u
     const std::string who = "hrt_probe_eval";
     int rc = pv_flags_check(who, flags);
     if (rc != HRT_OK) return rc;
-    if (n == 0u) {
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        return HRT_OK;
-    }
+    if (n == 0u) return empty_batch(stats);
     if ((rc = pv_eval_check(who, v, points, n, out, false)) != HRT_OK) return rc;
     if ((rc = pv_enter(who, v)) != HRT_OK) return rc;
     BlockingCall call;
@@ -430,10 +427,7 @@ int hrt_probe_eval_visible(const hrt_probe_volume *v, const float *points, uint3
     const std::string who = "hrt_probe_eval_visible";
     int rc = pv_flags_check(who, flags);
     if (rc != HRT_OK) return rc;
-    if (n == 0u) {
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        return HRT_OK;
-    }
+    if (n == 0u) return empty_batch(stats);
     if ((rc = pv_eval_check(who, v, points, n, out, false, true)) != HRT_OK) return rc;
     if ((rc = pv_enter(who, v)) != HRT_OK) return rc;
     BlockingCall call;

@@ -163,10 +163,9 @@ extern "C" __global__ void __launch_bounds__(256) hrt_probe_fold_kernel(const fl
     out[i] = accumulate ? out[i] + t : t / (float)n_samples;
 }
 
-// The flags of a probe launch.
-static int probe_flags_check(const std::string &who, uint32_t flags) {
-    return fused_flags_check(who, flags, "a probe launch has one kernel form", "a probe has no direction to normalise",
-                             "probes are linear radiance, not a frame");
+// The flags of a probe launch; one_form: why the kernel-form flags are refused, which names the plain or the lit launch.
+static int probe_flags_check(const std::string &who, uint32_t flags, const char *one_form) {
+    return fused_flags_check(who, flags, one_form, "a probe has no direction to normalise", "probes are linear radiance, not a frame");
 }
 
 // Checks 3..5 of the header's order: the probe records, the keys, the count.  `dev`: device pointers (d_ names, 16-byte records).
@@ -206,58 +205,67 @@ int hrt_probe_rays(const float *d_probes, const uint32_t *d_keys, uint32_t n, ui
     return HRT_OK;
 }
 
-// The fused launch into d_out on `stream` (the scene entered, the limit checked): the trace launch into the scene's block values,
-// then the fold, also when a probe has one block.
-static int probe_launch(hrt_scene *s, const float *d_probes, const uint32_t *d_keys, uint32_t n, uint32_t first_sample, uint32_t n_samples,
-                        uint64_t seed, uint32_t flags, float *d_out, hipStream_t stream) {
+// The fused launch into d_out on `stream` (the scene entered, the limit checked): the trace launch into `blocks`, a scratch buffer
+// of the scene's that this family alone uses, then the fold, also when a probe has one block.  Q, its builds and its blocks: DProbe,
+// hrt_probe_kernel_builds and pr_blocks, or those of a lit probe launch (hrt_lit_paths.hip) with the rule filled in and pl_blocks.
+extern "C++" {
+template <class QT>
+static int probe_launch(void (*const *builds)(const QT), QT &Q, hrt_scene *s, Scratch &blocks, const float *d_probes, const uint32_t *d_keys,
+                        uint32_t n, uint32_t first_sample, uint32_t n_samples, uint64_t seed, uint32_t flags, float *d_out, hipStream_t stream) {
     const uint32_t nblocks = (uint32_t)(((uint64_t)n_samples + HRT_PROBE_BLOCK - 1u) / HRT_PROBE_BLOCK);
     const uint32_t items = n * nblocks;  // <= HRT_PROBE_MAX_BLOCKS
-    if (const int rc = s->pr_blocks.grow((size_t)items * HRT_PROBE_SUMS * sizeof(float))) return rc;
-    DProbe Q;
+    if (const int rc = blocks.grow((size_t)items * HRT_PROBE_SUMS * sizeof(float))) return rc;
     Q.probes = (const float4 *)d_probes;
     Q.keys = d_keys;
     Q.nblocks = nblocks;
-    if (const int rc = radiance_launch(hrt_probe_kernel_builds, Q, s, first_sample, n_samples, seed, flags, s->pr_blocks.as<float>(), items * 64u, stream))
-        return rc;
+    if (const int rc = radiance_launch(builds, Q, s, first_sample, n_samples, seed, flags, blocks.as<float>(), items * 64u, stream)) return rc;
     const uint32_t n_sums = n * HRT_PROBE_SUMS;
-    hipLaunchKernelGGL(hrt_probe_fold_kernel, dim3((n_sums + 255u) / 256u), dim3(256), 0, stream, s->pr_blocks.as<float>(), n_sums, nblocks, n_samples,
+    hipLaunchKernelGGL(hrt_probe_fold_kernel, dim3((n_sums + 255u) / 256u), dim3(256), 0, stream, blocks.as<float>(), n_sums, nblocks, n_samples,
                        (flags & HRT_RADIANCE_ACCUMULATE) ? 1u : 0u, d_out);
     HIP_TRY(hipGetLastError());
     return HRT_OK;
 }
 
-int hrt_probes_device(hrt_scene *s, const float *d_probes, const uint32_t *d_keys, uint32_t n, uint32_t first_sample, uint32_t n_samples,
-                      uint64_t seed, uint32_t flags, float *d_out, void *stream) {
-    const std::string who = "hrt_probes_device";
-    int rc = probe_flags_check(who, flags);
-    if (rc != HRT_OK || n == 0u) return rc;
-    if ((rc = probe_records_check(who, d_probes, d_keys, n, true)) != HRT_OK) return rc;
-    if ((rc = probe_samples_out_check(who, n, first_sample, n_samples, d_out, "d_out")) != HRT_OK) return rc;
-    if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
-    return probe_launch(s, d_probes, d_keys, n, first_sample, n_samples, seed, flags, d_out, (hipStream_t)stream);
+// Both forms of a probe launch, plain (NoRule) or lit (LitRule), checked in the header's
+// order: the flags, the rule's, (an empty batch,) the records, the samples and the output, then the scene.
+// launch(d_probes, d_keys, d_out, stream) is the fused launch; the blocking form runs it on device copies of the probes and keys.
+template <class Rule, class Launch>
+static int probe_call(const std::string &who, bool dev, hrt_scene *s, const Rule &R, const char *one_form, const float *probes,
+                      const uint32_t *keys, uint32_t n, uint32_t first_sample, uint32_t n_samples, uint32_t flags, float *out, void *stream,
+                      hrt_stats *stats, Launch launch) {
+    int rc = dev ? HRT_OK : blocking_accumulate_check(who, flags);
+    if (rc == HRT_OK) rc = probe_flags_check(who, flags, one_form);
+    if (rc == HRT_OK) rc = R.check(who);
+    if (rc != HRT_OK) return rc;
+    if (n == 0u) return empty_batch(stats);
+    if ((rc = probe_records_check(who, probes, keys, n, dev)) != HRT_OK) return rc;
+    if ((rc = probe_samples_out_check(who, n, first_sample, n_samples, out, dev ? "d_out" : "out")) != HRT_OK) return rc;
+    if ((rc = R.enter(who, s)) != HRT_OK) return rc;
+    if (dev) return launch(probes, keys, out, (hipStream_t)stream);
+    BlockingCall call;
+    return call.run_batch(s, probes, HRT_PROBE_FLOATS * sizeof(float), keys, n, (size_t)n * HRT_PROBE_SUMS * sizeof(float), out,
+                          (uint64_t)n * n_samples, stats, launch);
+}
+}  // extern "C++"
+
+static int probes_entry(const std::string &who, bool dev, hrt_scene *s, const float *probes, const uint32_t *keys, uint32_t n, uint32_t first_sample,
+                        uint32_t n_samples, uint64_t seed, uint32_t flags, float *out, void *stream, hrt_stats *stats) {
+    return probe_call(who, dev, s, NoRule{}, "a probe launch has one kernel form", probes, keys, n, first_sample, n_samples, flags, out, stream, stats,
+                      [&](const float *d_probes, const uint32_t *d_keys, float *d_out, hipStream_t st) {
+                          DProbe Q;
+                          return probe_launch(hrt_probe_kernel_builds, Q, s, s->pr_blocks, d_probes, d_keys, n, first_sample, n_samples, seed, flags, d_out, st);
+                      });
 }
 
-// Blocking, from and into host memory (BlockingCall; the probes and keys are device buffers of the call's, too).
+int hrt_probes_device(hrt_scene *s, const float *d_probes, const uint32_t *d_keys, uint32_t n, uint32_t first_sample, uint32_t n_samples,
+                      uint64_t seed, uint32_t flags, float *d_out, void *stream) {
+    return probes_entry("hrt_probes_device", true, s, d_probes, d_keys, n, first_sample, n_samples, seed, flags, d_out, stream, nullptr);
+}
+
+// Blocking, from and into host memory.
 int hrt_probes(hrt_scene *s, const float *probes, const uint32_t *keys, uint32_t n, uint32_t spp, uint64_t seed, uint32_t flags, float *out,
                hrt_stats *stats) {
-    const std::string who = "hrt_probes";
-    if (flags & HRT_RADIANCE_ACCUMULATE) return fail(HRT_ERR_INVALID, who + ": flags: HRT_RADIANCE_ACCUMULATE needs the running sums on the device (hrt_probes_device)");
-    int rc = probe_flags_check(who, flags);
-    if (rc != HRT_OK) return rc;
-    if (n == 0u) {
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        return HRT_OK;
-    }
-    if ((rc = probe_records_check(who, probes, keys, n, false)) != HRT_OK) return rc;
-    if ((rc = probe_samples_out_check(who, n, 0u, spp, out, "out")) != HRT_OK) return rc;
-    if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
-    BlockingCall call;
-    Scratch d_probes, d_keys;
-    if ((rc = d_probes.from_host(probes, (size_t)n * HRT_PROBE_FLOATS * sizeof(float))) != HRT_OK) return rc;
-    if (keys && (rc = d_keys.from_host(keys, (size_t)n * sizeof(uint32_t))) != HRT_OK) return rc;
-    return call.run(s, (size_t)n * HRT_PROBE_SUMS * sizeof(float), out, (uint64_t)n * spp, stats, [&](float *d_out) {
-        return probe_launch(s, d_probes.as<float>(), d_keys.as<uint32_t>(), n, 0u, spp, seed, flags, d_out, nullptr);
-    });
+    return probes_entry("hrt_probes", false, s, probes, keys, n, 0u, spp, seed, flags, out, nullptr, stats);
 }
 
 int hrt_probe_grid_points(const float *lo, const float *hi, uint32_t nx, uint32_t ny, uint32_t nz, float time, float *out_probes) {

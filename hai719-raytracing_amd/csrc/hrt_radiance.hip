@@ -290,26 +290,32 @@ extern "C" __global__ void __launch_bounds__(256) hrt_camera_rays_kernel(const D
     out[2u * pixel + 1u] = make_float4(r.d.x, r.d.y, r.d.z, __builtin_inff());
 }
 
-// A family of radiance_body kernels: the four builds of source SRC over launch record QT -- plain, lights, and the two proof builds
-// of HRT_FLAG_EXACT_ONLY (no filters, no v_rcp_f32; see CtxT; not tuned: 2 waves per SIMD, as trace_body's) -- and their table,
-// indexed lights | exact << 1 (radiance_launch).
-#define HRT_RADIANCE_FAMILY(base, SRC, QT)                                                                                                                           \
-    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) base(const QT Q) { radiance_body<false, false, SRC>(Q); }                  \
-    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES) base##_lights(const QT Q) { radiance_body<true, false, SRC>(Q); }          \
-    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) base##_exact(const QT Q) { radiance_body<false, true, SRC>(Q); }                                \
-    extern "C" __global__ void __launch_bounds__(HRT_RADIANCE_WG, 2) base##_lights_exact(const QT Q) { radiance_body<true, true, SRC>(Q); }                          \
+// A family of kernels: the four builds of one body over launch record QT -- plain, lights, and the two proof builds of
+// HRT_FLAG_EXACT_ONLY (no filters, no v_rcp_f32; see CtxT) -- and their table, indexed lights | exact << 1 (radiance_launch).
+// BOUNDS and PROOF_BOUNDS are the parenthesised __launch_bounds__ of the first and the last two; BODY<lights, exact, ...>(Q) is the
+// body, the variadic arguments its template arguments after the two flags.
+#define HRT_KERNEL_FAMILY(base, QT, BOUNDS, PROOF_BOUNDS, BODY, ...)                                                                    \
+    extern "C" __global__ void __launch_bounds__ BOUNDS base(const QT Q) { BODY<false, false, __VA_ARGS__>(Q); }                       \
+    extern "C" __global__ void __launch_bounds__ BOUNDS base##_lights(const QT Q) { BODY<true, false, __VA_ARGS__>(Q); }               \
+    extern "C" __global__ void __launch_bounds__ PROOF_BOUNDS base##_exact(const QT Q) { BODY<false, true, __VA_ARGS__>(Q); }          \
+    extern "C" __global__ void __launch_bounds__ PROOF_BOUNDS base##_lights_exact(const QT Q) { BODY<true, true, __VA_ARGS__>(Q); }    \
     static void (*const base##_builds[4])(const QT) = {base, base##_lights, base##_exact, base##_lights_exact};
+
+// A family of radiance_body kernels over source SRC (the proof builds are not tuned: 2 waves per SIMD, as trace_body's).
+#define HRT_RADIANCE_FAMILY(base, SRC, QT) \
+    HRT_KERNEL_FAMILY(base, QT, (HRT_RADIANCE_WG, HRT_RADIANCE_MIN_WAVES), (HRT_RADIANCE_WG, 2), radiance_body, SRC)
 
 HRT_RADIANCE_FAMILY(hrt_radiance_kernel, RecordRays, DRadiance)
 
-struct DLensViewsRadiance;  // hrt_lens.hip: the one record without a launch seed (every view has its own)
+struct DLensViewsRadiance;  // hrt_lens.hip: the one record without a launch seed (every view has its own), and what derives from it
 
 extern "C++" {
-static void radiance_seed(DLensViewsRadiance &, uint64_t) {}
 template <class QT>
 static void radiance_seed(QT &Q, uint64_t seed) {
-    Q.seed_lo = (uint32_t)seed;
-    Q.seed_hi = (uint32_t)(seed >> 32);
+    if constexpr (!std::is_base_of_v<DLensViewsRadiance, QT>) {
+        Q.seed_lo = (uint32_t)seed;
+        Q.seed_hi = (uint32_t)(seed >> 32);
+    }
 }
 
 // THE launch of a radiance_body family (the scene entered): fills what every record has -- the caller has set its family's own
@@ -355,8 +361,42 @@ struct BlockingCall {
         }
         return HRT_OK;
     }
+    // The same for a batch in host memory: its n records of `record_bytes` and its keys (NULL: none) are device buffers of the
+    // call's, too -- launch(d_records, d_keys, d_out, the null stream).
+    template <class F>
+    int run_batch(const hrt_scene *s, const float *records, size_t record_bytes, const uint32_t *keys, uint32_t n, size_t bytes, float *out,
+                  uint64_t samples, hrt_stats *stats, F launch) {
+        Scratch d_records, d_keys;
+        if (const int rc = d_records.from_host(records, (size_t)n * record_bytes)) return rc;
+        if (keys)
+            if (const int rc = d_keys.from_host(keys, (size_t)n * sizeof(uint32_t))) return rc;
+        return run(s, bytes, out, samples, stats,
+                   [&](float *d_out) { return launch(d_records.as<float>(), d_keys.as<uint32_t>(), d_out, nullptr); });
+    }
 };
 }  // extern "C++"
+
+// The two forms of an entry point share one body with the form as a parameter (`dev`: the device form -- d_ names, a stream, no
+// stats).  What only the blocking form has, first of all its checks: running sums would have to be on the device.
+static int blocking_accumulate_check(const std::string &who, uint32_t flags) {
+    if (flags & HRT_RADIANCE_ACCUMULATE)
+        return fail(HRT_ERR_INVALID, who + ": flags: HRT_RADIANCE_ACCUMULATE needs the running sums on the device (" + who + "_device)");
+    return HRT_OK;
+}
+
+// An empty batch, of either form (the device form has no stats): nothing is launched, the stats are zeroed.
+static int empty_batch(hrt_stats *stats) {
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    return HRT_OK;
+}
+
+// What a plain entry point has where its lit sibling has a LitRule (hrt_probe_lit.hip): nothing to check, and the scene to enter.
+struct NoRule {
+    int check_tail(const std::string &) const { return HRT_OK; }
+    int check_volume(const std::string &) const { return HRT_OK; }
+    int check(const std::string &) const { return HRT_OK; }
+    int enter(const std::string &who, hrt_scene *s) const { return enter_scene(who, s); }
+};
 
 // The flags of a fused launch (lens frames, bakes).  one_form: why the kernel-form flags are refused; no_normalize: why
 // HRT_RAYS_NORMALIZE is; no_gamma: why HRT_FLAG_GAMMA is, NULL where it is accepted.

@@ -90,10 +90,7 @@ int hrt_render_views(hrt_scene *s, const hrt_view *views, uint32_t n_views, uint
     std::vector<DView> blocks;
     int rc = views_check(who, views, n_views, w, h, spp, flags, out_rgb, "out_rgb", blocks);
     if (rc != HRT_OK) return rc;
-    if (n_views == 0u) {
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        return HRT_OK;
-    }
+    if (n_views == 0u) return empty_batch(stats);
     if ((rc = enter_scene(who, s)) != HRT_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     const size_t bytes = (size_t)n_views * w * h * 3u * sizeof(float);

@@ -4,9 +4,9 @@ entry point and the culprit, in the header's order -- (the blocking form: HRT_RA
 the points, keys and n as hrt_bake* checks them, the samples and the output, tail_after, then the volume checks of "Lit rays".  A
 volume cannot be created without a device, so "the volume is NULL" is the last refusal reachable here through the C ABI: what comes
 after it is in tests/test_gpu_bake_lit.py, and the non-finite bias is refused here where a caller meets it first, in the Python
-wrapper.  The entry points add no host logic of their own -- they compose bake_flags_check, bake_points_check, samples_out_check,
-lit_frame_tail_check, lit_volume_check and lit_enter -- so there is no sanitized stand-alone program for them.  The pointers
-below are never dereferenced: every call fails validation first."""
+wrapper.  The entry points add no host logic of their own -- they are hrt_bake*'s body (bake_call: bake_flags_check,
+bake_points_check, samples_out_check) with a LitRule (check, enter) -- so there is no sanitized stand-alone program for them.  The
+pointers below are never dereferenced: every call fails validation first."""
 import ctypes as C
 import re
 import subprocess

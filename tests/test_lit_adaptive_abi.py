@@ -5,7 +5,7 @@ hrt_render_lens_adaptive checks before the scene, in its order (flags, params, t
 then tail_after, then the volume checks of "Lit rays".  A volume cannot be created without a device, so "the volume is NULL" is the
 last refusal reachable here through the C ABI: what comes after it is in tests/test_gpu_lit_adaptive.py, and the non-finite bias is
 refused here where a caller meets it first, in the Python wrapper.  The entry points add no host logic of their own -- they compose
-lens_adaptive_check, lit_frame_tail_check, lit_volume_check and lit_enter -- so there is no sanitized stand-alone program for them.
+lens_adaptive_check and a LitRule's check and enter -- so there is no sanitized stand-alone program for them.
 The pointers below are never dereferenced: every call fails validation first."""
 import ctypes as C
 import re

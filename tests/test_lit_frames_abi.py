@@ -5,7 +5,7 @@ hrt_render_lens*, then tail_after, then the volume checks of "Lit rays", then th
 cannot be created without a device, so "the volume is NULL" is the last refusal reachable here through the C ABI: what comes after
 it (HRT_LIT_VISIBLE without depth, a non-finite bias at the ABI, a closed volume, the scene) is in tests/test_gpu_lit_frames.py, and
 the non-finite bias is refused here where a caller meets it first, in the Python wrapper.  The entry points add no host logic of
-their own -- they compose lens_render_check / lens_views_check, lit_tail_check, lit_volume_check and lit_enter -- so there is no
+their own -- they are hrt_render_lens*'s bodies (lens_render_check / lens_views_check) with a LitRule (check, enter) -- so there is no
 sanitized stand-alone program for them.  The device pointers below are never dereferenced: every call fails validation first."""
 import ctypes as C
 import re
