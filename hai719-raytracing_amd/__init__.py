@@ -191,6 +191,16 @@ TAIL_FLOATS = 16                    # HRT_TAIL_FLOATS
 TAIL_WORD = 11                      # the column of the uint32 word: bits 0..7 the segments traced, TAIL_REACHED
 TAIL_REACHED = 0x80000000           # HRT_TAIL_REACHED
 MAXBOUNCES = 6                      # HRT_MAXBOUNCES: the largest tail_after
+GUIDES_FIRST_HIT = 0                # HRT_GUIDES_FIRST_HIT: denoiser guides from render_features
+GUIDES_FIRST_DIFFUSE = 1            # HRT_GUIDES_FIRST_DIFFUSE: denoiser guides from render_path_features ("Path features")
+_GUIDES = {"first": GUIDES_FIRST_HIT, "diffuse": GUIDES_FIRST_DIFFUSE}
+
+
+def _guides_arg(who: str, guides) -> int:
+    """The ``guides`` keyword of the guided renders: "first" or "diffuse" -> HRT_GUIDES_*."""
+    if guides not in _GUIDES:
+        raise ValueError(f"{who}: guides must be \"first\" or \"diffuse\" (got {guides!r})")
+    return _GUIDES[guides]
 
 
 class DenoiseParams(C.Structure):
@@ -403,6 +413,15 @@ def device_lib() -> C.CDLL:
                                              C.c_float, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
         lib.hrt_path_tails.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_float, C.c_uint32,
                                        C.c_void_p, C.c_void_p]
+        lib.hrt_path_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.hrt_render_path_features.argtypes = lib.hrt_render_features.argtypes
+        lib.hrt_render_lens_path_features.argtypes = lib.hrt_render_lens_features.argtypes
+        lib.hrt_render_lens_views_path_features.argtypes = lib.hrt_render_lens_views_features.argtypes
+        lib.hrt_render_denoised_guides.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                                   C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(Stats)]
+        lib.hrt_render_denoised_var_guides.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                                       C.c_uint32, C.c_uint32, C.POINTER(DenoiseVarParams), C.c_void_p, C.c_void_p,
+                                                       C.POINTER(Stats)]
         lib.hrt_render_lit_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Lens), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                               C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.hrt_render_lit.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Lens), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32,
@@ -765,6 +784,12 @@ class DeviceScene:
         -> (h, w, FEATURE_FLOATS) float32.  The device buffer is a torch tensor on the scene's device; the call waits for it."""
         return DeviceScene._features(self, "hrt_render_features", (h, w), C.byref(cam), w, h, first_sample, n_samples, seed)
 
+    def render_path_features(self, cam: Camera, w: int, h: int, first_sample: int, n_samples: int, seed: int = 1) -> np.ndarray:
+        """hrt_render_path_features: the features of ``render_features`` taken at the FIRST DIFFUSE hit of every sample's path --
+        mirror and glass followed, albedo = the throughput there, depth = the length of the chain, coverage = the fraction of
+        samples that reached one (include/hrt.h "Path features") -> (h, w, FEATURE_FLOATS) float32.  ``n_samples`` >= 1."""
+        return DeviceScene._features(self, "hrt_render_path_features", (h, w), C.byref(cam), w, h, first_sample, n_samples, seed)
+
     def _features(self, entry: str, frames: tuple, *args) -> np.ndarray:
         """What the three feature wrappers share: ``entry`` on ``args``, a fresh ``frames`` + (FEATURE_FLOATS,) device tensor and the
         current torch stream; waits, and returns the tensor as NumPy."""
@@ -776,26 +801,40 @@ class DeviceScene:
         return d.cpu().numpy()
 
     def render_denoised(self, cam: Camera, w: int, h: int, spp: int, feature_spp: int, seed: int = 1, flags: int = 0,
-                        params: Optional[DenoiseParams] = None, stats: Optional[Stats] = None) -> np.ndarray:
+                        params: Optional[DenoiseParams] = None, stats: Optional[Stats] = None, guides: str = "first") -> np.ndarray:
         """hrt_render_denoised: render, features over samples [0, feature_spp), denoise -> (h, w, 3) float32.  ``params``: a
-        DenoiseParams (default values when None); ``stats``: a Stats to fill, if wanted."""
+        DenoiseParams (default values when None); ``stats``: a Stats to fill, if wanted.  ``guides``: "first", the first-hit
+        features of ``render_features``, or "diffuse" (hrt_render_denoised_guides), those of ``render_path_features``, which follow
+        mirror and glass to the first diffuse hit and need ``feature_spp`` >= 1."""
+        g = _guides_arg("render_denoised", guides)
         out = np.empty((h, w, 3), dtype=np.float32)
         p = DenoiseParams() if params is None else params
-        self._check(self._lib.hrt_render_denoised(self._h, C.byref(cam), w, h, spp, feature_spp, seed, flags, C.byref(p), out.ctypes.data,
-                                                  _ref(stats)))
+        if g == GUIDES_FIRST_HIT:
+            self._check(self._lib.hrt_render_denoised(self._h, C.byref(cam), w, h, spp, feature_spp, seed, flags, C.byref(p), out.ctypes.data,
+                                                      _ref(stats)))
+        else:
+            self._check(self._lib.hrt_render_denoised_guides(self._h, C.byref(cam), w, h, spp, feature_spp, seed, flags, g, C.byref(p),
+                                                             out.ctypes.data, _ref(stats)))
         return out
 
     def render_denoised_var(self, cam: Camera, w: int, h: int, spp: int, feature_spp: int, seed: int = 1, flags: int = 0,
-                            params: Optional[DenoiseVarParams] = None, stats: Optional[Stats] = None, variance: bool = False):
+                            params: Optional[DenoiseVarParams] = None, stats: Optional[Stats] = None, variance: bool = False,
+                            guides: str = "first"):
         """hrt_render_denoised_var: render ``spp`` samples (even) keeping the first half's means, features over samples
         [0, feature_spp), the variance-guided filter -> (h, w, 3) float32; with ``variance`` the pair (frame, (h, w) float32 map of
-        the result's estimated variance, in demodulated units).  ``params``: a DenoiseVarParams (default values when None)."""
+        the result's estimated variance, in demodulated units).  ``params``: a DenoiseVarParams (default values when None).
+        ``guides``: "first" or "diffuse" (hrt_render_denoised_var_guides), as ``render_denoised``."""
+        g = _guides_arg("render_denoised_var", guides)
         out = np.empty((h, w, 3), dtype=np.float32)
         var = np.empty((h, w), dtype=np.float32) if variance else None
         p = DenoiseVarParams() if params is None else params
-        self._check(self._lib.hrt_render_denoised_var(self._h, C.byref(cam), w, h, spp, feature_spp, seed, flags, C.byref(p),
-                                                      out.ctypes.data, None if var is None else var.ctypes.data,
-                                                      _ref(stats)))
+        d_var = None if var is None else var.ctypes.data
+        if g == GUIDES_FIRST_HIT:
+            self._check(self._lib.hrt_render_denoised_var(self._h, C.byref(cam), w, h, spp, feature_spp, seed, flags, C.byref(p),
+                                                          out.ctypes.data, d_var, _ref(stats)))
+        else:
+            self._check(self._lib.hrt_render_denoised_var_guides(self._h, C.byref(cam), w, h, spp, feature_spp, seed, flags, g, C.byref(p),
+                                                                 out.ctypes.data, d_var, _ref(stats)))
         return (out, var) if variance else out
 
     def render_temporal(self, history: "History", cam: Camera, w: int, h: int, spp: int, feature_spp: int, seed: int = 1, flags: int = 0,
@@ -986,6 +1025,22 @@ class DeviceScene:
         self._check(self._lib.hrt_path_tails(self._h, _ptr(d_rays), _ptr(d_keys), n, sample, seed, flags, bias, *tail, _ptr(d_out), _stream(d_rays.device)))
         return _batch_result(is_torch, d_out, out)
 
+    def path_features(self, rays, sample: int = 0, seed: int = 1, keys=None, out=None, flags: int = 0, normalize: bool = False):
+        """hrt_path_features: the path-feature record of ONE sample of stream (seed, key, sample) for every caller ray -- (n,
+        FEATURE_FLOATS) float32 rows in the layout of ``render_features``: [0:3] the throughput at the path's first diffuse hit,
+        [3:6] that surface's shading normal, [6:9] the emission met on the way, [9] the summed hit distances, [10] 1 where a diffuse
+        hit was reached, else 0 (then [0:6] and [9] are 0 and [6:9] stays), [11] 0.  A degenerate ray gives 12 zeros.  It is
+        ``path_tails(rays, 1)`` with a feature record (include/hrt.h "Path features").  Rays, keys, ``flags``, ``normalize`` and the
+        torch / NumPy forms as ``trace_radiance``; ``out``, if given, a tensor or array of the result's shape."""
+        import torch
+        who = "path_features"
+        flags = int(flags) | (RAYS_NORMALIZE if normalize else 0)
+        is_torch, rays, n, keys, shape = _batch_checked(who, "rays", rays, keys, out, (FEATURE_FLOATS,))
+        d_rays, d_keys = _batch_on_device(is_torch, rays, keys)
+        d_out = out if is_torch and out is not None else torch.empty(shape, dtype=torch.float32, device=d_rays.device)
+        self._check(self._lib.hrt_path_features(self._h, _ptr(d_rays), _ptr(d_keys), n, sample, seed, flags, _ptr(d_out), _stream(d_rays.device)))
+        return _batch_result(is_torch, d_out, out)
+
     def probes_lit(self, points, volume: "ProbeVolume", spp: int = 1, first_sample: int = 0, seed: int = 1, keys=None, eval_flags: int = 0,
                    bias: float = 0.0, out=None, accumulate: bool = False, flags: int = 0, stats: Optional[Stats] = None,
                    tail_after: Optional[int] = None):
@@ -1091,6 +1146,10 @@ class DeviceScene:
         torch tensor on the scene's device; the call waits for it."""
         return DeviceScene._features(self, "hrt_render_lens_features", (h, w), C.byref(lens), w, h, first_sample, n_samples, seed)
 
+    def render_lens_path_features(self, lens: Lens, w: int, h: int, first_sample: int, n_samples: int, seed: int = 1) -> np.ndarray:
+        """hrt_render_lens_path_features: ``render_path_features`` through ``lens`` -> (h, w, FEATURE_FLOATS) float32."""
+        return DeviceScene._features(self, "hrt_render_lens_path_features", (h, w), C.byref(lens), w, h, first_sample, n_samples, seed)
+
     def render_lens_views(self, lenses, w: int, h: int, spp: int, seeds=None, flags: int = 0, first_sample: int = 0, out=None,
                           accumulate: bool = False, stats: Optional[Stats] = None):
         """hrt_render_lens_views*: every lens of ``lenses`` as a w x h frame, in one launch -> (n, h, w, 3) float32; frame v has the
@@ -1165,6 +1224,12 @@ class DeviceScene:
         (n, h, w, FEATURE_FLOATS) float32.  The device buffer is a torch tensor on the scene's device; the call waits for it."""
         views, n = _view_table("render_lens_views_features", "lenses", LensView, lenses, seeds)
         return DeviceScene._features(self, "hrt_render_lens_views_features", (n, h, w), views, n, w, h, first_sample, n_samples)
+
+    def render_lens_views_path_features(self, lenses, w: int, h: int, first_sample: int, n_samples: int, seeds=None) -> np.ndarray:
+        """hrt_render_lens_views_path_features: ``render_lens_path_features`` of every lens of ``lenses`` with its seed, in one launch
+        -> (n, h, w, FEATURE_FLOATS) float32."""
+        views, n = _view_table("render_lens_views_path_features", "lenses", LensView, lenses, seeds)
+        return DeviceScene._features(self, "hrt_render_lens_views_path_features", (n, h, w), views, n, w, h, first_sample, n_samples)
 
     def check_last_launch(self):
         """hrt_check_last_launch: waits for the last launch; raises if the trace kernel gave up (incomplete tiles)."""

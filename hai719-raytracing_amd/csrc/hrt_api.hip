@@ -1137,6 +1137,7 @@ int hrt_write_ppm(const char *path, const float *rgb, uint32_t w, uint32_t h) {
 #include "hrt_probe_volume.hip"
 #include "hrt_probe_lit.hip"
 #include "hrt_lit_paths.hip"
+#include "hrt_path_features.hip"
 #include "hrt_lit_frames.hip"
 #include "hrt_bake_lit.hip"
 #include "hrt_lens_adaptive.hip"

@@ -395,10 +395,19 @@ static int dn_render_pair(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint3
     return rc;
 }
 
-// hrt_render_denoised and hrt_render_denoised_var after their checks of the parameters, the frame size and spp.  The frame is
-// hrt_render's at spp samples, linear; F.var: with the first half's frame beside it (dn_render_pair).
+// The feature launch of HRT_GUIDES_FIRST_DIFFUSE (hrt_path_features.hip, which comes after the lens sources it is made of).
+static int path_features_frame(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples, uint64_t seed,
+                               float *d_features, hipStream_t stream);
+
+// hrt_render_denoised, hrt_render_denoised_var and their _guides forms after their checks of the parameters, the frame size and
+// spp.  The frame is hrt_render's at spp samples, linear; F.var: with the first half's frame beside it (dn_render_pair).  guides:
+// where the features come from, HRT_GUIDES_FIRST_HIT (the existing entry points) or HRT_GUIDES_FIRST_DIFFUSE.
 static int dn_render(const std::string &who, hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp,
-                     uint64_t seed, uint32_t flags, const DnFilter &F, float *out_rgb, float *out_variance, hrt_stats *stats) {
+                     uint64_t seed, uint32_t flags, uint32_t guides, const DnFilter &F, float *out_rgb, float *out_variance, hrt_stats *stats) {
+    if (guides > HRT_GUIDES_FIRST_DIFFUSE)
+        return fail(HRT_ERR_INVALID, who + ": guides must be HRT_GUIDES_FIRST_HIT or HRT_GUIDES_FIRST_DIFFUSE (got " + std::to_string(guides) + ")");
+    if (guides == HRT_GUIDES_FIRST_DIFFUSE && feature_spp == 0u)
+        return fail(HRT_ERR_INVALID, who + ": feature_spp must be at least 1 with HRT_GUIDES_FIRST_DIFFUSE (a pixel-centre path has no stream)");
     if (feature_spp > spp) return fail(HRT_ERR_INVALID, who + ": feature_spp must be at most spp (got " + std::to_string(feature_spp) + " > " + std::to_string(spp) + ")");
     if (!cam) return fail(HRT_ERR_INVALID, who + ": camera is NULL");
     if (!out_rgb) return fail(HRT_ERR_INVALID, who + ": out_rgb is NULL");
@@ -423,7 +432,9 @@ static int dn_render(const std::string &who, hrt_scene *s, const hrt_camera *cam
         if (rc == HRT_OK) rc = hrt_assemble_frame(d_tiles, tiles, w, h, 1, s->dn_frame.as<float>(), nullptr);
         if (rc == HRT_OK) rc = hrt_check_last_launch(s);  // never denoise a frame the kernel did not finish
     }
-    if (rc == HRT_OK) rc = features_launch(s, cam, w, h, 0, feature_spp, seed, s->dn_feat.as<float>(), nullptr);
+    if (rc == HRT_OK)
+        rc = guides == HRT_GUIDES_FIRST_DIFFUSE ? path_features_frame(s, cam, w, h, 0, feature_spp, seed, s->dn_feat.as<float>(), nullptr)
+                                                : features_launch(s, cam, w, h, 0, feature_spp, seed, s->dn_feat.as<float>(), nullptr);
     if (rc == HRT_OK) rc = dn_run(s->dn_frame.as<float>(), s->dnv_frame_half.as<float>(), s->dn_feat.as<float>(), w, h, F, flags & HRT_FLAG_GAMMA,
                                   s->dn_scratch.p, s->dn_out.as<float>(), out_variance ? s->dnv_var.as<float>() : nullptr, nullptr);
     if (rc != HRT_OK) return rc;
@@ -438,24 +449,44 @@ static int dn_render(const std::string &who, hrt_scene *s, const hrt_camera *cam
     return HRT_OK;
 }
 
-int hrt_render_denoised(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp, uint64_t seed,
-                        uint32_t flags, const hrt_denoise_params *p, float *out_rgb, hrt_stats *stats) {
-    const std::string who = "hrt_render_denoised";
+static int dn_render_fixed(const std::string &who, hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp,
+                           uint64_t seed, uint32_t flags, uint32_t guides, const hrt_denoise_params *p, float *out_rgb, hrt_stats *stats) {
     DnFilter F;
     int rc = dn_check_params(who, p, F);
     if (rc == HRT_OK) rc = check_frame(who, w, h, k_max_records);
     if (rc != HRT_OK) return rc;
     if (!spp) return fail(HRT_ERR_INVALID, who + ": spp must be positive");
-    return dn_render(who, s, cam, w, h, spp, feature_spp, seed, flags, F, out_rgb, nullptr, stats);
+    return dn_render(who, s, cam, w, h, spp, feature_spp, seed, flags, guides, F, out_rgb, nullptr, stats);
 }
 
-int hrt_render_denoised_var(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp, uint64_t seed,
-                            uint32_t flags, const hrt_denoise_var_params *p, float *out_rgb, float *out_variance, hrt_stats *stats) {
-    const std::string who = "hrt_render_denoised_var";
+int hrt_render_denoised(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp, uint64_t seed,
+                        uint32_t flags, const hrt_denoise_params *p, float *out_rgb, hrt_stats *stats) {
+    return dn_render_fixed("hrt_render_denoised", s, cam, w, h, spp, feature_spp, seed, flags, HRT_GUIDES_FIRST_HIT, p, out_rgb, stats);
+}
+
+int hrt_render_denoised_guides(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp, uint64_t seed,
+                               uint32_t flags, uint32_t guides, const hrt_denoise_params *p, float *out_rgb, hrt_stats *stats) {
+    return dn_render_fixed("hrt_render_denoised_guides", s, cam, w, h, spp, feature_spp, seed, flags, guides, p, out_rgb, stats);
+}
+
+static int dn_render_var(const std::string &who, hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp,
+                         uint64_t seed, uint32_t flags, uint32_t guides, const hrt_denoise_var_params *p, float *out_rgb, float *out_variance,
+                         hrt_stats *stats) {
     DnFilter F;
     int rc = dn_check_params(who, p, F);
     if (rc == HRT_OK) rc = check_frame(who, w, h, k_max_records);
     if (rc != HRT_OK) return rc;
     if (spp < 2u || (spp & 1u)) return fail(HRT_ERR_INVALID, who + ": spp must be even and at least 2 (got " + std::to_string(spp) + ")");
-    return dn_render(who, s, cam, w, h, spp, feature_spp, seed, flags, F, out_rgb, out_variance, stats);
+    return dn_render(who, s, cam, w, h, spp, feature_spp, seed, flags, guides, F, out_rgb, out_variance, stats);
+}
+
+int hrt_render_denoised_var(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp, uint64_t seed,
+                            uint32_t flags, const hrt_denoise_var_params *p, float *out_rgb, float *out_variance, hrt_stats *stats) {
+    return dn_render_var("hrt_render_denoised_var", s, cam, w, h, spp, feature_spp, seed, flags, HRT_GUIDES_FIRST_HIT, p, out_rgb, out_variance, stats);
+}
+
+int hrt_render_denoised_var_guides(hrt_scene *s, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp, uint64_t seed,
+                                   uint32_t flags, uint32_t guides, const hrt_denoise_var_params *p, float *out_rgb, float *out_variance,
+                                   hrt_stats *stats) {
+    return dn_render_var("hrt_render_denoised_var_guides", s, cam, w, h, spp, feature_spp, seed, flags, guides, p, out_rgb, out_variance, stats);
 }

@@ -61,8 +61,11 @@ struct src_wave_items<SRC, std::enable_if_t<SRC::wave_items>> { static constexpr
 // Where a path ends before its bounces run out (radiance_body's TAIL).  NoTail: nowhere -- every family but those of
 // hrt_lit_paths.hip, whose policies end a path at its Q.tail_after-th diffuse hit WITHOUT scattering there: kind 1 gathers there
 // (TAIL::gather: the look-up of a probe volume), kind 2 writes the path's end out instead of its colour (TAIL::reached /
-// ::unreached / ::degenerate: 16 floats per ray where the others store 3).  A path with a tail is not pruned.  Every other family
-// is untouched by this: all of it is behind `if constexpr`.
+// ::unreached / ::degenerate: 16 floats per ray where the others store 3).  Kind 3 (hrt_path_features.hip) is kind 2 with K = 1 and a
+// feature record for a tail record: it keeps the emission seen on the way in `rad` (no direct light, no sky) and the summed hit
+// distances in `depth`, and where the source makes the ray of every sample it folds the records of an item's samples in the item's
+// output (TAIL::begin / ::finish).  A path with a tail is not pruned.  Every other family is untouched by this: all of it is behind
+// `if constexpr`.
 struct NoTail {
     static constexpr int kind = 0;
 };
@@ -88,6 +91,7 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
     [[maybe_unused]] uint32_t count = 0;  // a wave_items source: where the samples of the wave's item end (s runs in steps of 64)
     int remaining = 0;       // bounces left on the current path; 0 = needs a new path
     [[maybe_unused]] uint32_t diffuse = 0;  // a TAIL: the diffuse hits of the current path so far
+    [[maybe_unused]] float depth = 0.f;     // TAIL kind 3: the hit distances of the current path so far
     Ray ray;
     ray.o = mk(0.f, 0.f, 0.f); ray.d = mk(0.f, 0.f, 1.f); ray.time = 0.f;
     f3 thr = mk(1.f, 1.f, 1.f), rad = mk(0.f, 0.f, 0.f);
@@ -123,7 +127,7 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
                     live = true;
                     break;
                 }
-                if constexpr (TAIL::kind == 2) {
+                if constexpr (TAIL::kind >= 2) {
                     TAIL::degenerate(Q, i);
                 } else if (!accumulate) { float *o_ = Q.out + (size_t)i * 3u; o_[0] = 0.f; o_[1] = 0.f; o_[2] = 0.f; }
             }
@@ -136,7 +140,11 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
                 query_margin(ray, Q.bound, far, Q.flags, cx.err_abs, first_flags);
             }
             sum = mk(0.f, 0.f, 0.f);
-            if (accumulate) { const float *a_ = Q.out + (size_t)i * 3u; sum = mk(a_[0], a_[1], a_[2]); }
+            if constexpr (TAIL::kind == 3) {
+                if constexpr (SRC::per_sample) TAIL::begin(Q, i);  // the item's sums, from +0
+            } else {
+                if (accumulate) { const float *a_ = Q.out + (size_t)i * 3u; sum = mk(a_[0], a_[1], a_[2]); }
+            }
             s = 0;
         }
     };
@@ -180,6 +188,7 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
                 rad = mk(0.f, 0.f, 0.f);
                 remaining = 6;  // MAXBOUNCES
                 if constexpr (TAIL::kind != 0) diffuse = 0u;
+                if constexpr (TAIL::kind == 3) depth = 0.f;
             }
             if (SRC::per_sample && !traced) {
                 h.kind = 0u; parked = 0u; stage = 4u;  // ends below
@@ -220,17 +229,24 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
             if (stage == 3u || (SRC::per_sample && stage == 4u)) {
                 ended = true;  // pruned on its last segment (stage A), or not traced: nothing is added
             } else if (h.kind == 0u) {
-                rad = rad + thr * sky(cx, ray.d, remaining);
+                if constexpr (TAIL::kind != 3) rad = rad + thr * sky(cx, ray.d, remaining);
                 ended = true;
             } else {
                 const Surface sf = shade(cx, ray, h);
                 f3 direct = mk(0.f, 0.f, 0.f);
                 if (LIGHTS) direct = direct_light(cx, sf, ray, rng);
-                rad = rad + thr * (direct + sf.emission);
+                if constexpr (TAIL::kind == 3) {  // the draws of `direct` move the stream; its value is not a feature
+                    rad = rad + thr * sf.emission;
+                    depth = depth + h.t;
+                } else {
+                    rad = rad + thr * (direct + sf.emission);
+                }
                 thr = thr * sf.albedo;
-                if constexpr (TAIL::kind != 0) fired = sf.type == 0u && ++diffuse == Q.tail_after;
+                if constexpr (TAIL::kind == 3) fired = sf.type == 0u;
+                else if constexpr (TAIL::kind != 0) fired = sf.type == 0u && ++diffuse == Q.tail_after;
                 if constexpr (TAIL::kind == 1) { if (fired) G = TAIL::gather(Q, sf.p, sf.n); }
                 if constexpr (TAIL::kind == 2) { if (fired) TAIL::reached(Q, i, sf.p, ray.time, sf.n, thr, segment, rad); }
+                if constexpr (TAIL::kind == 3) { if (fired) TAIL::template reached<SRC::per_sample>(Q, i, thr, sf.n, rad, depth); }
                 if (fired) {
                     ended = true;  // without scattering
                 } else {
@@ -242,6 +258,7 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
             }
             if (ended) {
                 if constexpr (TAIL::kind == 2) { if (!fired) TAIL::unreached(Q, i, segment, rad); }
+                if constexpr (TAIL::kind == 3) { if (!fired && !(SRC::per_sample && stage == 4u)) TAIL::template unreached<SRC::per_sample>(Q, i, rad); }
                 if constexpr (WAVE) {  // the sink is the source's: it gets what a one-sample query stores, 0 + rad / 6
                     if constexpr (TAIL::kind == 1) {  // (rad / 6) + thr * G where the tail was reached
                         if (stage != 4u)
@@ -251,7 +268,9 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
                         if (stage != 4u) SRC::add(Q, i, Q.first_sample + s, mk(0.f, 0.f, 0.f) + mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f));
                     }
                 } else if (!(SRC::per_sample && stage == 4u)) {
-                    if constexpr (TAIL::kind == 1) {
+                    if constexpr (TAIL::kind == 3) {
+                        // the record is in the output
+                    } else if constexpr (TAIL::kind == 1) {
                         sum = sum + (fired ? mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f) + thr * G : mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f));
                     } else {
                         sum = sum + mk(rad.x / 6.f, rad.y / 6.f, rad.z / 6.f);  // Scene.h:348
@@ -262,7 +281,9 @@ __device__ __forceinline__ void radiance_body(const QT &Q) {
                     if (count - s <= 64u) live = false;  // out of samples: idle until the wave meets in more()
                     else s += 64u;
                 } else if (++s == Q.n_samples) {  // the ray is done: its mean (or running sum), then the lane's next ray
-                    if constexpr (TAIL::kind != 2) {  // kind 2 has written its record
+                    if constexpr (TAIL::kind == 3) {  // kind 3 has written its record, or holds the item's sums there
+                        if constexpr (SRC::per_sample) TAIL::finish(Q, i);
+                    } else if constexpr (TAIL::kind != 2) {  // kind 2 has written its record
                         const float ns = accumulate ? 1.f : (float)Q.n_samples;  // x / 1.f is exact
                         float *o = Q.out + (size_t)i * 3u;
                         o[0] = sum.x / ns; o[1] = sum.y / ns; o[2] = sum.z / ns;

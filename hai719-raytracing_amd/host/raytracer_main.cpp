@@ -14,6 +14,13 @@
 //                                                  parameters and N iterations (one GPU)
 //             [--denoise-var FEATURE_SPP [--denoise-iters N]] variance-guided denoised frame (hrt_render_denoised_var): --spp samples
 //                                                  (even), the colour width of every pair of pixels set by the noise of their own means (one GPU)
+//             [--denoise-guides first|diffuse]   with --denoise or --denoise-var: where the filter's features are taken -- at the first
+//                                                  hit (the default; the same bytes as without the option) or at the first DIFFUSE
+//                                                  hit of every sample's path, mirror and glass followed (hrt_render_denoised_guides,
+//                                                  hrt_render_denoised_var_guides; FEATURE_SPP >= 1).  With --lens the frame, the
+//                                                  features and the filter of that lens (hrt_render_lens_device,
+//                                                  hrt_render_lens_features or hrt_render_lens_path_features, hrt_denoise*); not
+//                                                  with --temporal
 //             [--temporal FRAMES [--orbit DEGREES] [--denoise-var FEATURE_SPP]] FRAMES frames of --spp samples (even) with seeds seed,
 //                                                  seed + 1, ..., each accumulated onto the reprojected last one (hrt_render_temporal); the
 //                                                  camera turns about the scene's up axis by DEGREES / FRAMES per frame; with --denoise-var
@@ -25,7 +32,8 @@
 //             [--lens perspective|ortho|equirect|fisheye [--aperture R --focus D] [--lens-extent X]] a lens camera (hrt_render_lens): the
 //                                                  thin lens of radius R focused at depth D (perspective), the view volume's height X
 //                                                  (ortho), a 360 x 180 degree panorama (equirect), X degrees of equidistant fisheye
-//                                                  (one GPU; no --denoise, --denoise-var, --temporal, --gpus).  With --adaptive
+//                                                  (one GPU; no --temporal, --gpus; --denoise and --denoise-var only with
+//                                                  --denoise-guides).  With --adaptive
 //                                                  THRESHOLD [--spp-min N]: per-tile counts under the lens (hrt_render_lens_adaptive).
 //                                                  With --views N [--orbit DEGREES]: N lens frames in ONE launch
 //                                                  (hrt_render_lens_views), cameras and seeds and files as --views has them
@@ -100,6 +108,7 @@ static uint32_t feature_spp = 0;
 static hrt_denoise_params denoise_params = {4u, 8.0f, 0.05f, 0.4f, 0.05f};
 static bool denoise_var = false;  // --denoise-var: hrt_render_denoised_var with the default parameters (the Python DenoiseVarParams())
 static hrt_denoise_var_params denoise_var_params = {4u, 2u, 8.0f, 0.05f, 0.4f, 0.05f, 1e-8f};
+static int denoise_guides = -1;  // --denoise-guides: HRT_GUIDES_FIRST_HIT or HRT_GUIDES_FIRST_DIFFUSE; -1: not given (first-hit guides)
 static uint32_t temporal_frames = 0;  // --temporal: hrt_render_temporal over that many frames, the default hrt_temporal_params
 static double orbit_degrees = 0.0;    // --orbit: the camera's turn about the up axis over the whole run
 static uint32_t n_views = 0;          // --views: hrt_render_views over that many cameras, --orbit degrees apart
@@ -284,6 +293,41 @@ struct DeviceBuffer {
 static int device_failed(const char *what) {
     std::cout << what << " failed: " << hipGetErrorString(hipGetLastError()) << std::endl;
     return HRT_ERR_DEVICE;
+}
+
+// --lens with --denoise or --denoise-var and --denoise-guides: the lens frame (and, variance-guided, the frame of the first half of
+// its samples), the features the lens saw -- first-hit or first-diffuse -- and the filter, all on the null stream; the guided renders
+// of a pinhole camera do the same inside the library.
+static int ray_trace_lens_denoised() {
+    const unsigned w = SCREENWIDTH, h = SCREENHEIGHT;
+    const size_t npix = (size_t)w * h;
+    lens_params.cam = default_camera((float)w / (float)h);
+    std::cout << "Ray tracing a " << w << " x " << h << " image on the GPU using " << nsamples << " samples per pixel through a lens, denoised"
+              << (denoise_var ? " by variance" : "") << " (" << (denoise_guides == (int)HRT_GUIDES_FIRST_DIFFUSE ? "first-diffuse" : "first-hit")
+              << " features of " << feature_spp << " samples)" << std::endl;
+    DeviceBuffer d_frame, d_half, d_feat, d_scratch, d_out;
+    if (!d_frame.alloc(npix * 3 * sizeof(float)) || !d_half.alloc(npix * 3 * sizeof(float)) || !d_feat.alloc(npix * HRT_FEATURE_FLOATS * sizeof(float)) ||
+        !d_scratch.alloc(hrt_denoise_scratch_bytes(w, h)) || !d_out.alloc(npix * 3 * sizeof(float)))
+        return device_failed("hipMalloc");
+    int rc = hrt_render_lens_device(device_scene, &lens_params, w, h, 0u, nsamples, seed, 0u, d_frame.as<float>(), nullptr);
+    if (rc == HRT_OK && denoise_var) rc = hrt_render_lens_device(device_scene, &lens_params, w, h, 0u, nsamples / 2u, seed, 0u, d_half.as<float>(), nullptr);
+    if (rc == HRT_OK)
+        rc = denoise_guides == (int)HRT_GUIDES_FIRST_DIFFUSE
+                 ? hrt_render_lens_path_features(device_scene, &lens_params, w, h, 0u, feature_spp, seed, d_feat.as<float>(), nullptr)
+                 : hrt_render_lens_features(device_scene, &lens_params, w, h, 0u, feature_spp, seed, d_feat.as<float>(), nullptr);
+    if (rc == HRT_OK)
+        rc = denoise_var ? hrt_denoise_var(d_frame.as<float>(), d_half.as<float>(), d_feat.as<float>(), w, h, &denoise_var_params, HRT_FLAG_GAMMA, d_scratch.p,
+                                           d_out.as<float>(), nullptr, nullptr)
+                         : hrt_denoise(d_frame.as<float>(), d_feat.as<float>(), w, h, &denoise_params, HRT_FLAG_GAMMA, d_scratch.p, d_out.as<float>(), nullptr);
+    if (rc != HRT_OK) {
+        std::cout << "the denoised lens frame failed: " << hrt_last_error() << std::endl;
+        return rc;
+    }
+    std::vector<float> image(npix * 3, 0.f);
+    if (hipMemcpy(image.data(), d_out.p, image.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return device_failed("hipMemcpy");
+    rc = hrt_write_ppm(out_path.c_str(), image.data(), w, h);
+    if (rc != HRT_OK) std::cout << hrt_last_error() << std::endl;
+    return rc;
 }
 
 // The eval_flags of the lit launches: what --probe-facing and --probe-visible say of the look-up.
@@ -515,6 +559,10 @@ static int ray_trace_from_camera() {
     adaptive_params.max_spp = nsamples;
     int rc = multi ? hrt_multi_render(multi, &cam, w, h, nsamples, seed, HRT_FLAG_GAMMA, image.data(), &st)
              : adaptive ? hrt_render_adaptive(device_scene, &cam, w, h, &adaptive_params, seed, HRT_FLAG_GAMMA, image.data(), nullptr, &st)
+             : denoise_var && denoise_guides == (int)HRT_GUIDES_FIRST_DIFFUSE
+                 ? hrt_render_denoised_var_guides(device_scene, &cam, w, h, nsamples, feature_spp, seed, HRT_FLAG_GAMMA, HRT_GUIDES_FIRST_DIFFUSE, &denoise_var_params, image.data(), nullptr, &st)
+             : denoise && denoise_guides == (int)HRT_GUIDES_FIRST_DIFFUSE
+                 ? hrt_render_denoised_guides(device_scene, &cam, w, h, nsamples, feature_spp, seed, HRT_FLAG_GAMMA, HRT_GUIDES_FIRST_DIFFUSE, &denoise_params, image.data(), &st)
              : denoise_var ? hrt_render_denoised_var(device_scene, &cam, w, h, nsamples, feature_spp, seed, HRT_FLAG_GAMMA, &denoise_var_params, image.data(), nullptr, &st)
              : denoise  ? hrt_render_denoised(device_scene, &cam, w, h, nsamples, feature_spp, seed, HRT_FLAG_GAMMA, &denoise_params, image.data(), &st)
                         : hrt_render(device_scene, &cam, w, h, nsamples, seed, HRT_FLAG_GAMMA, image.data(), &st);
@@ -558,6 +606,11 @@ int main(int argc, char **argv) {
         else if (k == "--spp-min") adaptive_params.min_spp = (unsigned)atoi(v.c_str());
         else if (k == "--denoise") { denoise = true; feature_spp = (uint32_t)strtoul(v.c_str(), nullptr, 10); }
         else if (k == "--denoise-var") { denoise_var = true; feature_spp = (uint32_t)strtoul(v.c_str(), nullptr, 10); }
+        else if (k == "--denoise-guides") {
+            if (v == "first") denoise_guides = (int)HRT_GUIDES_FIRST_HIT;
+            else if (v == "diffuse") denoise_guides = (int)HRT_GUIDES_FIRST_DIFFUSE;
+            else { std::cerr << "--denoise-guides takes first or diffuse (got " << v << ")" << std::endl; return 2; }
+        }
         else if (k == "--denoise-iters") denoise_params.iterations = denoise_var_params.iterations = (uint32_t)strtoul(v.c_str(), nullptr, 10);
         else if (k == "--temporal") temporal_frames = (uint32_t)strtoul(v.c_str(), nullptr, 10);
         else if (k == "--views") n_views = (uint32_t)strtoul(v.c_str(), nullptr, 10);
@@ -675,8 +728,20 @@ int main(int argc, char **argv) {
         std::cerr << "--views renders plain frames on one GPU: it cannot be combined with --adaptive, --denoise, --denoise-var, --temporal or --gpus / --devices" << std::endl;
         return 2;
     }
-    if (use_lens && (denoise || denoise_var || temporal || !devices.empty())) {
-        std::cerr << "--lens renders plain or adaptive frames on one GPU: it cannot be combined with --denoise, --denoise-var, --temporal or --gpus / --devices" << std::endl;
+    if (denoise_guides != -1 && !denoise && !denoise_var) {
+        std::cerr << "--denoise-guides says where a filter's features come from: give --denoise or --denoise-var" << std::endl;
+        return 2;
+    }
+    if (denoise_guides != -1 && temporal) {
+        std::cerr << "--denoise-guides cannot be combined with --temporal: the reprojection reads the first-hit depth, which a path depth is not" << std::endl;
+        return 2;
+    }
+    if (denoise_guides == (int)HRT_GUIDES_FIRST_DIFFUSE && feature_spp == 0u) {
+        std::cerr << "--denoise-guides diffuse follows the paths of the samples: FEATURE_SPP must be at least 1 (a pixel-centre path has no stream)" << std::endl;
+        return 2;
+    }
+    if (use_lens && (((denoise || denoise_var) && denoise_guides == -1) || temporal || !devices.empty())) {
+        std::cerr << "--lens renders plain or adaptive frames on one GPU: it cannot be combined with --denoise or --denoise-var (unless --denoise-guides is given), --temporal or --gpus / --devices" << std::endl;
         return 2;
     }
     if (!use_lens && (lens_params.aperture_radius != 0.f || lens_params.focus_distance != 1.f || lens_params.extent != 0.f)) {
@@ -795,7 +860,7 @@ int main(int argc, char **argv) {
         std::cout << "Image tiles across " << devices.size() << " GPU slot(s), gather: " << hrt_multi_gather(multi)
                   << (note.empty() ? "" : " (" + note + ")") << std::endl;
     }
-    int rc = probes ? light_probes(flat->desc) : bake ? bake_lightmap(flat->desc) : n_views ? ray_trace_views() : use_lens ? ray_trace_lens() : temporal ? ray_trace_frames() : ray_trace_from_camera();  // the 'r' key, once or frame after frame
+    int rc = probes ? light_probes(flat->desc) : bake ? bake_lightmap(flat->desc) : n_views ? ray_trace_views() : use_lens ? (denoise || denoise_var ? ray_trace_lens_denoised() : ray_trace_lens()) : temporal ? ray_trace_frames() : ray_trace_from_camera();  // the 'r' key, once or frame after frame
     hrt_scene_destroy(device_scene);
     hrt_multi_destroy(multi);
     hrt_shutdown();

@@ -1377,6 +1377,82 @@ HRT_API int hrt_render_lit_adaptive(hrt_scene *scene, const hrt_probe_volume *vo
                                     uint32_t tail_after, float *out_rgb, uint32_t *out_tile_spp /* may be NULL */,
                                     hrt_stats *stats /* may be NULL */);
 
+/* ---- Path features: the denoisers' feature record taken at the FIRST DIFFUSE hit of the integrator's own path.  The features of
+ * "denoising" above are first-hit features: on a mirror or a glass sphere they carry the mirror's own flat albedo and smooth normal,
+ * so the filter sees no edge inside a reflection and blurs what the mirror shows.  Here mirror and glass are followed: the albedo is
+ * the path's throughput at its first diffuse hit (the factor by which everything beyond that hit reaches the pixel, which is what
+ * the filter demodulates by), the normal is that surface's, the emission is what the path met on the way, the depth is the length
+ * of the chain.  It is "Lit paths" with K = 1 and a feature record for a tail record: the same hook of the same kernel body.
+ * THE RULE (tests/path_features_ref.py states the fold again in NumPy).  All arithmetic is fp32 without fused multiply-add, in the
+ * order written.  A PATH-FEATURE RECORD of one sample is HRT_FEATURE_FLOATS = 12 floats in the layout of hrt_render_features.  For
+ * a ray {o, time, d, tmax} (tmax is not read), key k and sample s:
+ *   1. the path starts as a path of hrt_path_tails starts: stream (seed, k, s) with the draw index set to 3, the filter margin and
+ *      far-origin rule of a first segment, the same DEGENERATE rays, which give 12 zeros; thr = 1, E = 0, depth = 0.f, remaining = 6.
+ *   2. per segment: h = the closest hit, meshes included.  A miss ends the path UNREACHED.
+ *   3. a hit: sf = the shaded surface.  In a scene with lights the direct light at sf is drawn as the integrator draws it, because
+ *      its draws move the stream; its value is not used.  Then, in this order: E = E + thr * sf.emission; depth = depth + h.t;
+ *      thr = thr * sf.albedo.
+ *   4. if sf is diffuse the path ends REACHED, without scattering.  Otherwise it scatters as the integrator does (the bounce
+ *      segment's flags are the launch's) and remaining decreases; at 0 the path ends unreached.  Nothing is pruned.
+ *   5. the record:             [0..2]    [3..5]                           [6..8]  [9]     [10]  [11]
+ *        reached               thr       sf.n (shaded, not flipped)       E       depth   1.f   0
+ *        unreached             0, 0, 0   0, 0, 0                          E       0       0     0
+ *      An unreached path keeps E, the emitters seen on the way.  The sky is NOT added; a first-hit miss adds nothing either.
+ * THE FRAME FORM: per pixel, feature = (sum of the records of samples [first_sample, first_sample + n_samples) in ascending order,
+ * in fp32, starting from +0) / (float)n_samples.  The ray of sample s is the one hrt_lens_rays writes for it, the key is the pixel
+ * index y*w + x.  A sample the lens does not trace (outside a fisheye's circle) adds nothing and counts in the divisor.
+ * n_samples == 0 is REFUSED: hrt_render_features' pixel-centre ray has no stream to scatter with.
+ * CONTRACT A: a sample whose first segment misses, or whose first hit is diffuse, gives the first-hit values (1 * x, 0 + x and
+ * 0 + 1 * x are exact), so a pixel all of whose samples are such has the bits of hrt_render_lens_features and, for a pinhole, of
+ * hrt_render_features.
+ * CONTRACT B: the record agrees with the tail record of hrt_path_tails(tail_after = 1, bias = 0) for the same ray, key, sample, seed
+ * and flags: [3..5] = tail [4..6], [0..2] = tail [8..10], [10] = bit 31 of the tail's word (as 1.f or 0), and in a scene without
+ * lights E / 6.f = tail [12..14] on every path that does not end in a miss under a sky (there the tail record adds the sky; E
+ * does not).
+ * CONTRACT C: the frame entry points are the fold above over hrt_lens_rays and hrt_path_features, sample by sample; frame v of a
+ * batch is the single frame of views[v].lens with seed views[v].seed.
+ * hrt_path_features: ONE sample per call, as hrt_path_tails: record i at d_out[12i .. 12i+11] (device, 4-byte aligned).  One lane
+ * of the device per ray, asynchronous on `stream`; touches none of the scene's per-launch state.  `flags`: HRT_FLAG_EXACT_ONLY,
+ * HRT_FLAG_MESH_BRUTE (with EXACT_ONLY), HRT_FLAG_NO_LDS_TREE, HRT_RAYS_NORMALIZE.  Checked in this order, HRT_ERR_INVALID with
+ * hrt_last_error() naming the entry point and the culprit: flags; (n == 0 returns HRT_OK here and launches nothing;) d_rays NULL or
+ * not 16-byte aligned, d_keys not 4-byte aligned, d_out NULL or not 4-byte aligned, n > 2^31 - 1; then a NULL scene and the library
+ * state.
+ * hrt_render_lens_path_features: the frame form for a lens, d_features (device) h*w*HRT_FEATURE_FLOATS floats, row-major, one lane
+ * per pixel, no ray buffer; asynchronous on `stream`, and like hrt_render_lens_features no part of the ordering of the scene's
+ * feature launches.  Checked in the order of hrt_render_lens_features: the lens; the frame; n_samples == 0; first_sample + n_samples
+ * > 2^32 - 1; d_features NULL or not 4-byte aligned; then a NULL scene.
+ * hrt_render_path_features: the same through the pinhole lens of `cam` (PERSPECTIVE, aperture 0).  Checked in the order of
+ * hrt_render_features: cam NULL; the frame; n_samples == 0; the sample range; d_features; the scene; then the camera's values.
+ * hrt_render_lens_views_path_features: the batch, n_views * h * w * HRT_FEATURE_FLOATS floats, view-major; the table, the
+ * CONCURRENCY note and the LIMIT (2^31 / 16 items) of hrt_render_lens_views_features.  Checked in its order: (n_views == 0 returns
+ * HRT_OK and launches nothing;) views NULL; every lens; the frame; n_samples == 0; the sample range; d_features NULL or not 4-byte
+ * aligned; the limit; then a NULL scene.
+ * GUIDED RENDERS: hrt_render_denoised_guides and hrt_render_denoised_var_guides are hrt_render_denoised and
+ * hrt_render_denoised_var with one parameter more, where the features come from.  HRT_GUIDES_FIRST_HIT gives the bits of the
+ * existing functions; HRT_GUIDES_FIRST_DIFFUSE takes the features of samples [0, feature_spp) from hrt_render_path_features and
+ * requires feature_spp >= 1: the result is bit-identical to hrt_denoise / hrt_denoise_var of the same frames with
+ * hrt_render_path_features(0, feature_spp).  Checked after the parameters, the frame and spp, and before feature_spp > spp: any
+ * other value of `guides`, then feature_spp == 0 with HRT_GUIDES_FIRST_DIFFUSE, each refused by name.  Every existing entry point
+ * keeps its signature and its bits.
+ * OUT OF SCOPE (DESIGN.md section 5 "Path features"): pixel-centre paths; temporal accumulation with path guides (hrt_render_temporal
+ * reprojects with the first-hit depth, which a path depth is not); a virtual (mirrored) normal; K > 1; adaptive frames. */
+#define HRT_GUIDES_FIRST_HIT 0u           /* guides: the features of hrt_render_features */
+#define HRT_GUIDES_FIRST_DIFFUSE 1u       /* guides: the features of hrt_render_path_features */
+HRT_API int hrt_path_features(hrt_scene *scene, const float *d_rays, const uint32_t *d_keys, uint32_t n, uint32_t sample, uint64_t seed,
+                              uint32_t flags, float *d_out, void *stream);
+HRT_API int hrt_render_path_features(hrt_scene *scene, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t first_sample, uint32_t n_samples,
+                                     uint64_t seed, float *d_features, void *stream);
+HRT_API int hrt_render_lens_path_features(hrt_scene *scene, const hrt_lens *lens, uint32_t w, uint32_t h, uint32_t first_sample,
+                                          uint32_t n_samples, uint64_t seed, float *d_features, void *stream);
+HRT_API int hrt_render_lens_views_path_features(hrt_scene *scene, const hrt_lens_view *views, uint32_t n_views, uint32_t w, uint32_t h,
+                                                uint32_t first_sample, uint32_t n_samples, float *d_features, void *stream);
+HRT_API int hrt_render_denoised_guides(hrt_scene *scene, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp,
+                                       uint64_t seed, uint32_t flags, uint32_t guides, const hrt_denoise_params *p, float *out_rgb,
+                                       hrt_stats *stats /* may be NULL */);
+HRT_API int hrt_render_denoised_var_guides(hrt_scene *scene, const hrt_camera *cam, uint32_t w, uint32_t h, uint32_t spp, uint32_t feature_spp,
+                                           uint64_t seed, uint32_t flags, uint32_t guides, const hrt_denoise_var_params *p, float *out_rgb,
+                                           float *out_variance /* may be NULL */, hrt_stats *stats /* may be NULL */);
+
 /* The PPM file of main.cpp:252-262 encoded ON THE DEVICE from a row-major frame (device, h*w*3 floats).
  * format 3: the reference's ASCII file byte for byte ("P3\n<w> <h>\n255\n", then "r g b " per pixel, "\n");
  * format 6: the same integers as bytes (binary PPM; negative values, which P3 prints with a sign, clamp to 0).
