@@ -44,8 +44,20 @@
 #define HRT_DIV_UNI 1      // wave-uniform divisors (image width and height, the 6 of Scene.h:348): reciprocal taken once per launch
 #endif
 
+// The squares' filter (quad_filter, quad_filter_axis) with less scalar and bookkeeping work per square.  Each part is a switch of its
+// own for A/B builds (tools/variants.sh); 0 gives the earlier form.  DESIGN.md section 5 has the static counts and what each measured.
+#ifndef HRT_QF_SLACK
+#define HRT_QF_SLACK 1     // one signed slack per condition, combined with v_min3 / v_min / v_max and decided by ONE compare (no lane-mask algebra)
+#endif
+#ifndef HRT_QF_ROWS
+#define HRT_QF_ROWS 1      // the two SGPR row sets stay where they are: a scheduling barrier keeps a set's reload below the test that reads it
+#endif
+#ifndef HRT_QF_MASK
+#define HRT_QF_MASK 1      // the 0 / 1 of the compare shifted into ONE candidate mask (v_cndmask + v_lshl_or); err_abs in a VGPR from before the loops
+#endif
+
 #ifndef HRT_MESH_BATCH
-#define HRT_MESH_BATCH 16  // parked lanes that trigger a mesh stage (A/B on MI355X: 1 -> 45.4 ms, 16 -> 43.3, 32 -> 53.4)
+#define HRT_MESH_BATCH 16 // parked lanes that trigger a mesh stage (A/B on MI355X: 1 -> 45.4 ms, 16 -> 43.3, 32 -> 53.4)
 #endif
 #ifndef HRT_WG
 #define HRT_WG 256        // threads per workgroup of the trace kernels; the workgroup shares one LDS copy of the nodelets
@@ -109,6 +121,11 @@ typedef const v4f __attribute__((address_space(3))) *lf4;         // scene table
 typedef const DMesh __attribute__((address_space(1))) *gmesh;     // per-lane mesh records, global
 typedef const DMesh __attribute__((address_space(3))) *lmesh;     // per-lane mesh records, LDS
 __device__ __forceinline__ float4 ld(cf4 p, uint32_t i) { const v4f v = p[i]; return make_float4(v.x, v.y, v.z, v.w); }
+// wave-uniform row at a BYTE offset of 32 bits: s_load with the offset in an SGPR, no 64-bit address arithmetic
+__device__ __forceinline__ float4 ld_at(cf4 p, uint32_t off) {
+    const v4f v = *(cf4)((const char __attribute__((address_space(4))) *)p + off);
+    return make_float4(v.x, v.y, v.z, v.w);
+}
 __device__ __forceinline__ float4 ld(gf4 p, uint32_t i) { const v4f v = p[i]; return make_float4(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ uint4 ld(gu4 p, uint32_t i) { const v4u v = p[i]; return make_uint4(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ uint4 ld(lu4 p, uint32_t i) { const v4u v = p[i]; return make_uint4(v.x, v.y, v.z, v.w); }
@@ -659,25 +676,91 @@ __device__ __forceinline__ float cget(f3 v) { return A == 0 ? v.x : (A == 1 ? v.
 // and the reference's.  The rectangle bounds along I, J are those of the four corners, widened on the host by the same
 // kind of term.  Rays with |d_K| < par (= 8 (eps_n + 4e-7)) are too parallel to judge: they go to the exact arithmetic.
 // 21 VALU per square instead of the 40 of the general form below; the reciprocal is taken once per ray and axis.
+//
+// SLACK FORM (HRT_QF_SLACK).  The seven compares and the lane-mask algebra that joined them (a dozen scalar instructions per square)
+// become signed slacks, each >= 0 exactly when its condition holds:
+//   q1 = ta - 9e-6    q2 = tsure_up - ta    q3 = half_I - |xi|    q4 = half_J - |xj|       X = E + min(q1, q2, q3, q4)
+//   G = g d_K         g = -1.5 sgn, and NaN for glass: one scalar XOR of 0xbfc00000 with bits << 30 (bit 31 = the sign, bit 30 = glass)
+//   u = par - |d_K|                                        candidate  <=>  max(min(X, G), u) >= 0         (ONE compare)
+// Still a superset of what quad_t / quad_t_rcp accept, because it is a superset of the earlier form up to roundings the margins cover:
+//  - G >= 0 is sgn d_K <= 0.  The earlier `front` was sgn d_K < par; outside the unsure band (|d_K| >= par) that is sgn d_K <= -par.
+//    For glass G is NaN, which v_min drops: no condition, as before.  (The product of a NaN is a quiet NaN, and every other operand
+//    below is the result of an arithmetic instruction, never a signalling NaN, so v_min / v_max return the other operand.)
+//  - u >= 0 is |d_K| <= par, the earlier strict `unsure` with equality added.
+//  - E + q >= 0 against the earlier  ta + E >= 9e-6, ta - E <= tsure_up, |x| <= half + E:  the same real-number conditions with the
+//    roundings elsewhere: one of q (half an ulp of q, which is about -E where the decision falls: 6e-8 E) and one of the sum.  E
+//    exceeds the bound it stands for by 8 % in its first term (5 against 1.15 * 4) and by ten times in err_abs (2e-6 ext against
+//    three roundings of a coordinate, 1.8e-7 ext); the thresholds 9e-6 (against the accepted t > 1e-5) and tsure_up (2e-6 relative)
+//    carry their own.
+//  - A non-finite intermediate can only drop a condition (a NaN slack is ignored by v_min: more candidates, never fewer) or fail
+//    one (an infinite ta).  With finite inputs it needs |1 / d_K| beyond 1 / par <= 3.2e5, that is |d_K| < par: such a ray has the
+//    finite u > 0 and passes through v_max whatever the other operand is.  err_abs = +inf (a query ray of non-unit direction) gives
+//    X = +inf and leaves the sign test, as before.
+// Vector instructions per square: 8 for ta, xi, xj, E; 4 differences; v_min3 + v_min; the sum; G, v_min, u, v_max; the compare;
+// v_cndmask + v_lshl_or = 22, and three scalar ones (the shift and XOR for g, the shift for the index) besides loop and addresses.
+#if HRT_QF_ROWS
+#define HRT_QF_KEEP() __builtin_amdgcn_sched_barrier(0)  // nothing crosses: a set's reload stays below the test that last reads the set
+#else
+#define HRT_QF_KEEP() do { } while (0)
+#endif
+template <class M>
+__device__ __forceinline__ void qf_mark(M &cand, bool pass, uint32_t index) {
+#if HRT_QF_MASK
+    if constexpr (sizeof(M) == 8) {  // the bit of both words from ONE scalar shift; v_cndmask 0 / -1 and a v_and_or per word
+        const uint64_t bit = 1ull << index;
+        const uint32_t all = pass ? ~0u : 0u;
+        cand |= (uint64_t)(all & (uint32_t)bit) | ((uint64_t)(all & (uint32_t)(bit >> 32)) << 32);
+    } else {
+        cand |= (M)(pass ? 1u : 0u) << index;  // v_cndmask 0 / 1, v_lshl_or with the index in an SGPR
+    }
+#else
+    if (pass) cand |= (M)1 << index;
+#endif
+}
 template <class M, int K, class CX>
-__device__ __forceinline__ void quad_filter_axis(const CX &cx, const Ray &ray, f3 inv, cf4 rows, uint32_t n, float tsure_up, M &cand) {
+__device__ __forceinline__ void quad_filter_axis(const CX &cx, const Ray &ray, f3 inv, cf4 rows, uint32_t n, float tsure_up, float err_abs, M &cand) {
     constexpr int I = (K + 1) % 3, J = (K + 2) % 3;
     const float ok = cget<K>(ray.o), dk = cget<K>(ray.d), ik = cget<K>(inv);
     const float oi = cget<I>(ray.o), di = cget<I>(ray.d), oj = cget<J>(ray.o), dj = cget<J>(ray.d);
-    const float iek = fabsf(ik) * cx.err_abs;
+    const float iek = fabsf(ik) * err_abs;
     auto test = [&](const float4 &r0, const float4 &r1) {
         const uint32_t bits = __float_as_uint(r1.y);
         const float ta = (r0.x - ok) * ik;
         const float xi = __builtin_fmaf(ta, di, oi) - r0.y, xj = __builtin_fmaf(ta, dj, oj) - r0.z;
-        const float E = __builtin_fmaf(r1.w, iek, __builtin_fmaf(fabsf(ta), 5e-6f, cx.err_abs));
+        const float E = __builtin_fmaf(r1.w, iek, __builtin_fmaf(fabsf(ta), 5e-6f, err_abs));
+#if HRT_QF_SLACK
+        const float q = fminf(fminf(fminf(ta - 9e-6f, tsure_up - ta), r0.w - fabsf(xi)), r1.x - fabsf(xj));
+        const float G = dk * __uint_as_float(0xbfc00000u ^ (bits << 30));
+        const float r = fmaxf(fminf(E + q, G), r1.z - fabsf(dk));
+        qf_mark(cand, r >= 0.f, bits >> 8);
+#else
         const float dn = __uint_as_float(__float_as_uint(dk) ^ ((bits & 2u) << 30));  // sgn * d_K ~ d . n
         const bool glass = (bits & 1u) != 0u;
         const bool front = glass | (dn < r1.z);
         const bool unsure = fabsf(dk) < r1.z;
         const bool loose = front & (ta + E >= 9e-6f) & (ta - E <= tsure_up) & (fabsf(xi) <= r0.w + E) & (fabsf(xj) <= r1.x + E);
-        if (loose | unsure) cand |= (M)1 << (bits >> 8);
+        qf_mark(cand, loose | unsure, bits >> 8);
+#endif
     };
     float4 a0 = make_float4(0, 0, 0, 0), a1 = a0, b0 = a0, b1 = a0;  // two row sets in ping-pong (see quad_filter)
+#if HRT_QF_ROWS
+    // Pairs, the odd last square peeled; every reload is unconditional (the index clamped to the last square, whose rows are then
+    // read once more for nothing), so that a set is defined at ONE place of the loop and the registers need no copy.
+    if (n == 0u) return;
+    const uint32_t last = n - 1u;
+    a0 = ld(rows, 0); a1 = ld(rows, 1);
+    { const uint32_t k = 32u * min(1u, last); b0 = ld_at(rows, k); b1 = ld_at(rows, k + 16u); }
+    uint32_t i = 0;
+    for (; i + 1u < n; i += 2u) {
+        test(a0, a1);
+        HRT_QF_KEEP();
+        { const uint32_t k = 32u * min(i + 2u, last); a0 = ld_at(rows, k); a1 = ld_at(rows, k + 16u); }
+        test(b0, b1);
+        HRT_QF_KEEP();
+        { const uint32_t k = 32u * min(i + 3u, last); b0 = ld_at(rows, k); b1 = ld_at(rows, k + 16u); }
+    }
+    if (i < n) test(a0, a1);
+#else
     if (n > 0u) { a0 = ld(rows, 0); a1 = ld(rows, 1); }
     if (n > 1u) { b0 = ld(rows, 2); b1 = ld(rows, 3); }
     for (uint32_t i = 0; i < n; i += 2u) {
@@ -688,6 +771,7 @@ __device__ __forceinline__ void quad_filter_axis(const CX &cx, const Ray &ray, f
             if (i + 3u < n) { b0 = ld(rows, 2u * (i + 3u)); b1 = ld(rows, 2u * (i + 3u) + 1u); }
         }
     }
+#endif
 }
 
 // The no-division FILTER over the squares (wave-uniform loops, scalar rows): bit i of the result = square i can possibly
@@ -701,11 +785,17 @@ __device__ __forceinline__ M quad_filter(const CX &cx, const Ray &ray, float tsu
     cf4 qf = (cf4)S->qfilter;
     const float tsure_up = tsure * (1.f + 2e-6f);  // the approximate t may exceed the exact one by a few ulp
     const uint32_t n0 = S->qf_n[0], n1 = S->qf_n[1], n2 = S->qf_n[2], n3 = S->qf_n[3];
+    float err_abs = cx.err_abs;
+#if HRT_QF_MASK
+    // Wave-uniform where the launch has one eye, and an instruction reads ONE scalar register: beside a row or a constant the
+    // margin was moved into a VGPR again for every square.  Once, here.
+    asm("" : "+v"(err_abs));
+#endif
     if (n0 + n1 + n2 != 0u) {
         const f3 inv = ray_inv<false>(ray);
-        quad_filter_axis<M, 0>(cx, ray, inv, qf, n0, tsure_up, cand);
-        quad_filter_axis<M, 1>(cx, ray, inv, qf + 2u * n0, n1, tsure_up, cand);
-        quad_filter_axis<M, 2>(cx, ray, inv, qf + 2u * (n0 + n1), n2, tsure_up, cand);
+        quad_filter_axis<M, 0>(cx, ray, inv, qf, n0, tsure_up, err_abs, cand);
+        quad_filter_axis<M, 1>(cx, ray, inv, qf + 2u * n0, n1, tsure_up, err_abs, cand);
+        quad_filter_axis<M, 2>(cx, ray, inv, qf + 2u * (n0 + n1), n2, tsure_up, err_abs, cand);
     }
     // General squares.  Two row sets in ping-pong: while quad i is evaluated from one set, the rows of quad i + 1 are
     // already in flight into the other, and quad i + 2 is requested into the first as soon as quad i is done -- the scalar
@@ -718,34 +808,71 @@ __device__ __forceinline__ M quad_filter(const CX &cx, const Ray &ray, float tsu
         const uint32_t flags = __float_as_uint(f1.w), i = flags >> 8;
         if (flags & HRT_QUAD_FLAG_MOVING) { cand |= (M)1 << i; return; }  // uniform branch; the exact path decides
         const float dotRN = ray.d.x * f1.z + ray.d.y * f1.x + ray.d.z * f1.y;  // exact, Vec3.h:48 order: the sign tests are the reference's
-        const bool glass = (flags & HRT_QUAD_FLAG_GLASS) != 0u;
-        const bool front = (dotRN < 0.f) | (glass & (dotRN > 0.f));  // `|`, `&`: lane masks combined, no short-circuit branches
         const float num = f0.w - (ray.o.x * f1.z + ray.o.y * f1.x + ray.o.z * f1.y);  // exact numerator
         const float ta = num * __builtin_amdgcn_rcpf(dotRN);  // |ta - fl(num/dotRN)| <= 4e-7 |t|
         const float ax = __builtin_fmaf(ta, ray.d.x, ray.o.x) - f0.x, ay = __builtin_fmaf(ta, ray.d.y, ray.o.y) - f0.y,
                     az = __builtin_fmaf(ta, ray.d.z, ray.o.z) - f0.z;
         const float x1 = __builtin_fmaf(az, f3.x, __builtin_fmaf(ay, f2.z, ax * f2.x));
         const float x2 = __builtin_fmaf(az, f3.y, __builtin_fmaf(ay, f2.w, ax * f2.y));
-        const float e = __builtin_fmaf(fabsf(ta), 4e-6f, cx.err_abs);  // bound on |p' - p|, generous
-        const float m1 = f3.z * e, m2 = f3.w * e, s1 = f3.z * f3.z, s2 = f3.w * f3.w;
+        const float e = __builtin_fmaf(fabsf(ta), 4e-6f, err_abs);  // bound on |p' - p|, generous
+        const float s1 = f3.z * f3.z, s2 = f3.w * f3.w;
+#if HRT_QF_SLACK
+        // The seven compares as slacks and ONE compare (see quad_filter_axis).  ta - 9e-6 and tsure_up - ta have the sign the earlier
+        // compares asked for, exactly.  G = g dotRN with g = -1.5, and NaN for glass (flags << 30 holds the glass bit alone: a moving
+        // square left above), asks dotRN <= 0 of a plain square and nothing of glass (earlier: < 0, and != 0).  |R| e + min(x, s - x)
+        // >= 0 is x >= -m and x <= s + m with the roundings elsewhere: half an ulp of s - x, about 6e-8 m where the decision falls,
+        // against an e that is ten times the error it bounds.  A NaN (dotRN = 0) drops its condition: more candidates, never fewer.
+        const float G = dotRN * __uint_as_float(0xbfc00000u ^ (flags << 30));
+        const float y1 = __builtin_fmaf(f3.z, e, fminf(x1, s1 - x1)), y2 = __builtin_fmaf(f3.w, e, fminf(x2, s2 - x2));
+        const float r = fminf(fminf(fminf(fminf(ta - 9e-6f, tsure_up - ta), G), y1), y2);
+        qf_mark(cand, r >= 0.f, i);
+#else
+        const bool glass = (flags & HRT_QUAD_FLAG_GLASS) != 0u;
+        const bool front = (dotRN < 0.f) | (glass & (dotRN > 0.f));  // `|`, `&`: lane masks combined, no short-circuit branches
+        const float m1 = f3.z * e, m2 = f3.w * e;
         const bool loose = front & (ta >= 9e-6f) & (ta <= tsure_up) & (x1 >= -m1) & (x1 <= s1 + m1) & (x2 >= -m2) & (x2 <= s2 + m2);
-        if (loose) cand |= (M)1 << i;
+        qf_mark(cand, loose, i);
+#endif
         // (A second, strict test used to shrink `tsure` to the nearest square that is certainly hit, so that squares
         // behind it were not refined.  It cost 11 VALU per square and saved a second refinement on ~5 % of the rays:
         // dropping it is 1-4 % faster on every scene.)
     };
     float4 a0 = make_float4(0, 0, 0, 0), a1 = a0, a2 = a0, a3 = a0, b0 = a0, b1 = a0, b2 = a0, b3 = a0;
     cf4 fr = qf + 2u * (n0 + n1 + n2);
-    if (n3 > 0u) { a0 = ld(fr, 0); a1 = ld(fr, 1); a2 = ld(fr, 2); a3 = ld(fr, 3); }
-    if (n3 > 1u) { b0 = ld(fr, 4); b1 = ld(fr, 5); b2 = ld(fr, 6); b3 = ld(fr, 7); }
+    auto fetch = [&](uint32_t q, float4 &r0, float4 &r1, float4 &r2, float4 &r3) {
+#if HRT_QF_ROWS
+        r0 = ld_at(fr, 64u * q); r1 = ld_at(fr, 64u * q + 16u); r2 = ld_at(fr, 64u * q + 32u); r3 = ld_at(fr, 64u * q + 48u);
+#else
+        r0 = ld(fr, 4u * q); r1 = ld(fr, 4u * q + 1u); r2 = ld(fr, 4u * q + 2u); r3 = ld(fr, 4u * q + 3u);
+#endif
+    };
+#if HRT_QF_ROWS
+    if (n3 == 0u) return cand;  // pairs with unconditional, clamped reloads and the odd tail peeled, as in quad_filter_axis
+    const uint32_t last = n3 - 1u;
+    fetch(0u, a0, a1, a2, a3);
+    fetch(min(1u, last), b0, b1, b2, b3);
+    uint32_t i = 0;
+    for (; i + 1u < n3; i += 2u) {
+        filter(a0, a1, a2, a3);
+        HRT_QF_KEEP();
+        fetch(min(i + 2u, last), a0, a1, a2, a3);
+        filter(b0, b1, b2, b3);
+        HRT_QF_KEEP();
+        fetch(min(i + 3u, last), b0, b1, b2, b3);
+    }
+    if (i < n3) filter(a0, a1, a2, a3);
+#else
+    if (n3 > 0u) fetch(0u, a0, a1, a2, a3);
+    if (n3 > 1u) fetch(1u, b0, b1, b2, b3);
     for (uint32_t i = 0; i < n3; i += 2u) {
         filter(a0, a1, a2, a3);
-        if (i + 2u < n3) { a0 = ld(fr, 4u * (i + 2u)); a1 = ld(fr, 4u * (i + 2u) + 1u); a2 = ld(fr, 4u * (i + 2u) + 2u); a3 = ld(fr, 4u * (i + 2u) + 3u); }
+        if (i + 2u < n3) fetch(i + 2u, a0, a1, a2, a3);
         if (i + 1u < n3) {
             filter(b0, b1, b2, b3);
-            if (i + 3u < n3) { b0 = ld(fr, 4u * (i + 3u)); b1 = ld(fr, 4u * (i + 3u) + 1u); b2 = ld(fr, 4u * (i + 3u) + 2u); b3 = ld(fr, 4u * (i + 3u) + 3u); }
+            if (i + 3u < n3) fetch(i + 3u, b0, b1, b2, b3);
         }
     }
+#endif
     return cand;
 }
 

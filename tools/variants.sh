@@ -1,6 +1,9 @@
 #!/bin/bash
 # Build A/B variants of libhrt.so (same ABI, different -D flags) in the build container:
 #   tools/variants.sh build "name1:-DFLAG=1" "name2:-DFLAG=2" ...
+# e.g. the parts of the squares' filter, each alone and none (libhrt.so has all three):
+#   tools/variants.sh build "qf_none:-DHRT_QF_SLACK=0 -DHRT_QF_ROWS=0 -DHRT_QF_MASK=0" "qf_slack:-DHRT_QF_ROWS=0 -DHRT_QF_MASK=0" \
+#                           "qf_rows:-DHRT_QF_SLACK=0 -DHRT_QF_MASK=0" "qf_mask:-DHRT_QF_SLACK=0 -DHRT_QF_ROWS=0"
 # and time them on the GPU box (one process per variant):
 #   tools/variants.sh run [scene ...]
 cd "$(dirname "$0")/../hai719-raytracing_amd"
